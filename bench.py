@@ -13,7 +13,11 @@ ONE JSON line; its "extra" object carries the other draw modes (mesh = the refer
 mesh + --infill_mask + convergence = movie_2_3D.py's default), the batch-size sweep and the
 300-frame clip of BASELINE configs[2] (strong scaling: the clip's frames are split over the ranks).
 
-`--gpus N` with N > 1 and no torchrun environment re-executes itself under torch.distributed.run with
+`--dump-outputs DIR` writes what the last timed step computed to DIR/<name>.npy after the timed region
+(float32 / float64, under 64 MB: whole arrays when small, else exact per-frame sums and a seeded pixel
+sample), so that two builds can be compared output for output; the inputs depend only on the arguments.
+
+`--gpus N` with N > 1 and no torchrun environment runs itself under torch.distributed.run with
 N ranks (one per GPU); it exits non-zero if the node has fewer than N GPUs -- it never silently
 measures fewer GPUs than asked for.
 """
@@ -51,6 +55,8 @@ def parse_args():
     ap.add_argument("--remove-edges", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU-baseline sample budget")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed (side-by-side RGB + hole mask) as DIR/<name>.npy")
     ap.add_argument("--cpu-worker", type=str, default=None, help=argparse.SUPPRESS)
     return ap.parse_args()
 
@@ -213,7 +219,9 @@ def relaunch_under_torchrun(args):
         port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    os.execv(sys.executable, cmd)
+    # a child, not execv: this process has the GPU runtime initialised (device_count above)
+    import subprocess
+    sys.exit(subprocess.call(cmd))
 
 
 def timed_steps(step, steps, dev, torch, barrier=None):
@@ -253,6 +261,33 @@ def measure_variant(make_job, frames, W, H, dev, torch, budget_s=0.6, bytes_per_
     return {"frames_per_launch": frames, "launch_ms": ms, "fps": frames / (ms * 1e-3),
             "algorithmic_GBps": byts / (ms * 1e-3) / 1e9, "roofline_frac": byts / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
             "groups": len(groups), "launches_per_group": per_group}
+
+
+DUMP_FULL_BYTES = 48 << 20     # --dump-outputs: whole arrays up to this size in float32, else per-frame sums + a seeded sample
+DUMP_SAMPLE = 1 << 20          # sampled pixels (frame, row, column) when the whole arrays do not fit
+
+
+def dump_outputs(out_dir, sbs, mask, torch, prefix=""):
+    """What the timed path hands its caller -- sbs [N, H, 2W, 3] u8 and mask [N, H, 2W] u8 -- as .npy files that two builds
+    can be compared by.  Small outputs go whole (float32).  Large ones go as exact per-frame sums (float64) and the values at
+    a fixed, seeded set of pixels (float32), with the pixels' (frame, row, column) alongside; under 64 MB either way."""
+    os.makedirs(out_dir, exist_ok=True)
+    N, H, W2 = mask.shape
+    files = {}
+    if 16 * N * H * W2 <= DUMP_FULL_BYTES:
+        files["sbs"] = sbs.float().cpu().numpy()
+        files["mask"] = mask.float().cpu().numpy()
+    else:
+        files["sbs_frame_sum"] = np.stack([sbs[k].sum(dim=(0, 1), dtype=torch.int64).cpu().numpy() for k in range(N)]).astype(np.float64)
+        files["mask_frame_sum"] = np.array([mask[k].sum(dtype=torch.int64).item() for k in range(N)], dtype=np.float64)
+        flat = np.sort(np.random.default_rng(20240613).choice(N * H * W2, size=min(DUMP_SAMPLE, N * H * W2), replace=False))
+        idx = torch.from_numpy(flat).to(mask.device)
+        files["sbs_sample"] = sbs.reshape(-1, 3).index_select(0, idx).float().cpu().numpy()
+        files["mask_sample"] = mask.reshape(-1).index_select(0, idx).float().cpu().numpy()
+        files["sample_frame_row_col"] = np.stack(np.unravel_index(flat, (N, H, W2)), axis=1).astype(np.float64)
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), a)
+    sys.stderr.write(f"bench.py: wrote {', '.join(prefix + n + '.npy' for n in files)} to {out_dir}\n")
 
 
 def device_uuid(torch, index):
@@ -375,6 +410,8 @@ def main():
     wall = D.max_over_ranks(wall, device=dev)
     hole_px = float((mask[0] > 0).sum().item())
     stats = D.gather_rank_stats(n_local * args.steps, wall, hole_px, device=dev)
+    if args.dump_outputs:                       # before the extras, which reuse sbs / mask
+        dump_outputs(args.dump_outputs, sbs, mask, torch, prefix=f"rank{rank}_" if world > 1 else "")
 
     extra = {}
     if not args.no_extra:

@@ -26,7 +26,10 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PROCS, ITERS = 6, 2000
+# At most six processes may hold one GPU at a time, and the pytest process is one of them: five children share the 12 000
+# fresh contexts the stress has always rendered (it ran 6 x 2000 before).
+CROWD = 5
+PROCS, ITERS = CROWD, 2400
 
 
 def _stress(extra_env, procs=PROCS, iters=ITERS):
@@ -109,14 +112,14 @@ def test_pool_blocks_go_back_to_contexts_of_their_own_gpu_only(monkeypatch):
 
 
 def test_bank_resources_crowd(tmp_path):
-    """The crowd that found both runtime bugs, on the path the r05 fix protects: 8 processes share the GPU, each
-    makes 300 multi-frame calls that take the two-bank path (side stream + four events from the process-wide pool of
-    `bank_res_take`), a context per call, native backtraces armed.  Every process must exit 0 with every call's bytes equal to its
+    """The crowd that found both runtime bugs, on the path the r05 fix protects: CROWD processes share the GPU,
+    each makes 480 multi-frame calls (the 2 400 calls that 8 x 300 made before the six-process cap) that take the two-bank path
+    (side stream + four events from the process-wide pool of `bank_res_take`), a context per call, native backtraces armed.  Every process must exit 0 with every call's bytes equal to its
     first call's, and the first calls must agree across processes."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     import numpy as np
-    procs, calls = 8, 300
+    procs, calls = CROWD, 480
     env = {k: v for k, v in os.environ.items() if not k.startswith("MDVT_")}
     env.update(CALLS=str(calls), MDVT_SEGV_TRACE_DIR=str(tmp_path), OMP_NUM_THREADS="1")
     ps = [subprocess.Popen([sys.executable, os.path.join(REPO, "tests", "dbg_bank_crowd.py")], cwd=REPO, env=env,
