@@ -275,6 +275,25 @@ int mdvt_finish_infill_mask_stereo(mdvt_ctx* ctx, const uint8_t* d_left_seed, co
                                    size_t seed_stride, uint8_t* d_left_out, uint8_t* d_right_out, size_t out_pitch,
                                    size_t out_stride, int n_frames, int max_rounds, uint32_t* d_remaining, void* stream);
 
+/* The same completion in the order of cv2.inpaint itself (opt-in; the level order above stays the default): Telea's heap pops one
+ * pixel at a time by arrival time T, ties first in, first out, and the key-coloured pixels of the result are byte-identical to
+ * that sequential march (orc_telea_fmm on the mask key-coloured OR black, radius 3), followed by the same sr:807 merge and
+ * masked_blur.  One workgroup marches one image from start to end (mdvt_telea_heap.hip); an image stops once all its key-coloured
+ * pixels have their estimates.  No level bound: d_remaining (optional, n_images x uint32; for the stereo call 2 * n_frames, left
+ * eyes first) receives the key-coloured pixels that no known pixel reaches (they keep the seed's value, as in cv2.inpaint), or
+ * 0xFFFFFFFF if the image's march hit a loop bound (an internal error).  The calls only enqueue work: they wait for the device
+ * only when the ctx's workspace has to grow (the first call, or a larger batch than before: hipDeviceSynchronize, as the level
+ * path does).  Workspace: 44 B/px per image in flight (about 91 MB per 1920 x 1080 image), kept by the ctx; a pass takes as many
+ * images as fit both a quarter of the device's memory and the memory free at the call, at most 256 (a 128-frame stereo batch at
+ * 1080p is one launch on an idle device), and fewer if the allocation fails.  The rate grows with the images per call: a launch
+ * lasts as long as its slowest image.  d_out may not alias d_seed.
+ * Added in 0.15 without changing any earlier entry point: the ABI version stays 0.15. */
+int mdvt_finish_infill_mask_heap(mdvt_ctx* ctx, const uint8_t* d_seed, size_t seed_pitch, size_t seed_stride, uint8_t* d_out,
+                                 size_t out_pitch, size_t out_stride, int n_images, uint32_t* d_remaining, void* stream);
+int mdvt_finish_infill_mask_heap_stereo(mdvt_ctx* ctx, const uint8_t* d_left_seed, const uint8_t* d_right_seed, size_t seed_pitch,
+                                        size_t seed_stride, uint8_t* d_left_out, uint8_t* d_right_out, size_t out_pitch,
+                                        size_t out_stride, int n_frames, uint32_t* d_remaining, void* stream);
+
 /* basic_nomal_infill.normal_infill (basic_nomal_infill.py:87-119, called per eye at :186 and :226): the stereo image
  * d_img and its finished infill-mask image d_infill_mask (the output of mdvt_finish_infill_mask; both u8 RGB, the mask's
  * r, g = the direction to march in, black = not a hole) -> the image with its holes filled.  In the reference's order:

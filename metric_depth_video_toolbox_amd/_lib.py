@@ -26,7 +26,7 @@ SYMBOLS = ("mdvt_version", "mdvt_create", "mdvt_destroy", "mdvt_last_error", "md
            "mdvt_equirect_tables", "mdvt_equirect_remap", "mdvt_masked_blur", "mdvt_finish_infill_mask",
            "mdvt_finish_infill_mask_stereo", "mdvt_swap_rb", "mdvt_selftest", "mdvt_normal_infill", "mdvt_infill_using_mask_normals",
            "mdvt_edge_point_pixels", "mdvt_workspace_bytes", "mdvt_release_cached_memory", "mdvt_cached_memory", "mdvt_set_cached_memory_limit",
-           "mdvt_debug_read")
+           "mdvt_debug_read", "mdvt_finish_infill_mask_heap", "mdvt_finish_infill_mask_heap_stereo")
 
 
 class MdvtError(RuntimeError):
@@ -119,6 +119,10 @@ def load():
     L.mdvt_finish_infill_mask.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int, vp, vp]
     L.mdvt_finish_infill_mask_stereo.restype = C.c_int
     L.mdvt_finish_infill_mask_stereo.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, vp, vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int, vp, vp]
+    L.mdvt_finish_infill_mask_heap.restype = C.c_int
+    L.mdvt_finish_infill_mask_heap.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_int, vp, vp]
+    L.mdvt_finish_infill_mask_heap_stereo.restype = C.c_int
+    L.mdvt_finish_infill_mask_heap_stereo.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, vp, vp, C.c_size_t, C.c_size_t, C.c_int, vp, vp]
     L.mdvt_swap_rb.restype = C.c_int
     L.mdvt_swap_rb.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_int, vp]
     L.mdvt_normal_infill.restype = C.c_int

@@ -363,7 +363,7 @@ class VideoSink:
 
 def render_clip(depth_frames, color_frames, out_sbs, out_mask, clip: D.ClipParameters, *, lo: int = 0,
                 hi: Optional[int] = None, batch: int = 16, out_depth_rgb=None, out_infill=None, green_and_black: bool = False,
-                device: Optional[int] = None, out_base: int = 0, io_threads: int = 12, out_infilled=None):
+                device: Optional[int] = None, out_base: int = 0, io_threads: int = 12, out_infilled=None, inpaint_order: str = "levels"):
     """Render frames [lo, hi) of a clip.  depth_frames / color_frames / out_*: array-likes indexed
     [frame] (NumPy arrays or memmaps, uint8); frame t is written to out_*[t - out_base] (a rank that owns the output
     segment [lo, hi) passes out_base = lo).  out_infilled (optional, [frames, H, 2W, 3]): the stereo frames after
@@ -399,6 +399,10 @@ def render_clip(depth_frames, color_frames, out_sbs, out_mask, clip: D.ClipParam
     # without --infill_mask the key colour is black and every black pixel counts as "to fill" (sr:803-805): the front
     # then has to cross the whole frame, as the reference's own cv2.inpaint call does
     telea_rounds = 0 if (clip.mode_flags & 8) else W + H
+    if inpaint_order not in ("levels", "heap"):
+        raise ValueError(f"inpaint_order must be 'levels' or 'heap', got {inpaint_order!r}")
+    if inpaint_order == "heap":
+        telea_rounds = 0             # cv2.inpaint's own order: no level budget (mdvt_finish_infill_mask_heap), nothing to redo
     oH, oW = output_shape(clip)
     post = vr180 or touchly1                                   # the main output is a post-processed image
 
@@ -475,7 +479,10 @@ def render_clip(depth_frames, color_frames, out_sbs, out_mask, clip: D.ClipParam
         o = a - out_base
         jobs = fan(f_sbs.write_from, st["h_sbs"][:n].numpy(), o, n, 6) + fan(f_mask.write_from, st["h_mask"][:n].numpy(), o, n, 1)
         h = int(st["h_counts"][:n].sum())           # hole pixels, counted on the device (mdvt_io.hole_counts)
-        if st.get("check_rem") and int(st["h_rem"][:, :n].sum()) != 0:
+        if st.get("check_rem") and inpaint_order == "heap":
+            if bool((st["h_rem"][:, :n] == -1).any()):          # 0xFFFFFFFF: the march hit a loop bound
+                raise RuntimeError(f"heap-order infill-mask completion failed on frames {a}..{a + n - 1}")
+        elif st.get("check_rem") and int(st["h_rem"][:, :n].sum()) != 0:
             redo.append((a, n))                     # a hole deeper than the default 256 levels: finished again below
         if want_zrgb:
             jobs += fan(f_zrgb.write_from, st["h_zrgb"][:n].numpy(), o, n, 3)
@@ -507,7 +514,8 @@ def render_clip(depth_frames, color_frames, out_sbs, out_mask, clip: D.ClipParam
                 dfh.encode_depth_frame(st["d_z"][f], clip.max_depth, bgr=True, out=st["d_zrgb"][f])
         st["d_rem"] = None
         if want_seed and res is not None:              # sr:803-808: finish the normal-coloured mask on the device, per eye
-            _, st["d_rem"] = r.finish_infill_mask_sbs(res["seed"], out=st["d_infill"][:n], max_rounds=rounds, want_remaining=True)
+            _, st["d_rem"] = r.finish_infill_mask_sbs(res["seed"], out=st["d_infill"][:n], max_rounds=rounds, want_remaining=True,
+                                                      order=inpaint_order)
             if basic_infill:                           # sr:809-812: march along the normals into the holes, all frames of an eye at once
                 from .stereo_rerender import infill_using_mask_normals
                 for eye in range(2):
@@ -826,7 +834,7 @@ def pin_to_gpu_numa_node(device_index: int) -> Optional[int]:
 
 def run(depth_path: str, color_path: Optional[str], *, batch: int = 16, create_sbs_depth_video: bool = False,
         max_frames: int = -1, green_and_black_infill_mask: bool = False, backend: Optional[str] = None,
-        normal_infill: bool = False, **clip_kwargs):
+        normal_infill: bool = False, inpaint_order: str = "levels", **clip_kwargs):
     """File-level entry (what `python stereo_rerender.py --depth_video ...` is to the reference).
     Multi-process aware: under torchrun every rank renders its own contiguous frame range into its own output segment
     files (plan_outputs); rank 0 adds the index.  `backend`: torch.distributed backend (default: RCCL when a GPU is
@@ -876,7 +884,10 @@ def run(depth_path: str, color_path: Optional[str], *, batch: int = 16, create_s
     frames, secs, holes = render_clip(depth, color, outs["sbs"], outs["mask"], clip, lo=lo, hi=hi, batch=batch,
                                       out_depth_rgb=outs.get("depth"), out_infill=outs.get("infill"),
                                       green_and_black=green_and_black_infill_mask, out_base=lo, io_threads=io_threads,
-                                      out_infilled=outs.get("infilled"))
+                                      out_infilled=outs.get("infilled"),
+                                      # (the default order is not passed on: tests/test_distributed_cpu.py replaces render_clip
+                                      #  with a stand-in that predates the keyword)
+                                      **({} if inpaint_order == "levels" else {"inpaint_order": inpaint_order}))
     # (no msync: the dumps were written through the page cache, which every later reader shares; forcing 6 GB of dirty pages
     #  to the disk before the rename is what the reference's writers do not do either, and costs seconds on a container fs)
     if video:

@@ -80,6 +80,10 @@ struct mdvt_ctx {
     int telea_images = 0, telea_rounds = 0;
     mdvt::TeleaWorkspace telea{};
     uint32_t* telea_levels_host = nullptr;      // pinned: the deepest level of a pass, read back once per pass
+    // infill-mask completion in the heap order: one block of mdvt::telea_heap_image_bytes per image of a pass, + remaining
+    int heap_images = 0;
+    uint8_t* heap_ws = nullptr;
+    uint32_t* heap_remaining = nullptr;
     // normal_infill / infill_using_mask_normals: about 16 B/px per image in flight
     uint8_t* ni_ws = nullptr;
     int ni_images = 0;
@@ -658,6 +662,13 @@ static void free_telea(mdvt_ctx* c)
     c->telea_images = 0; c->telea_rounds = 0;
 }
 
+static void free_telea_heap(mdvt_ctx* c)
+{
+    if (c->heap_ws) ws_free(c, c->heap_ws);
+    if (c->heap_remaining) ws_free(c, c->heap_remaining);
+    c->heap_ws = nullptr; c->heap_remaining = nullptr; c->heap_images = 0;
+}
+
 int mdvt_destroy(mdvt_ctx* c)
 {
     if (!c) return MDVT_OK;
@@ -680,6 +691,7 @@ int mdvt_destroy(mdvt_ctx* c)
     if (c->rowcell) ws_free(c, c->rowcell);
     pool_give(c->telea_levels_host, nullptr, 64, -1);
     free_telea(c);
+    free_telea_heap(c);
     if (c->ni_ws) ws_free(c, c->ni_ws);
     delete c;
     return MDVT_OK;
@@ -1515,6 +1527,92 @@ static int finish_infill_mask(mdvt_ctx* c, const uint8_t* d_seed, const uint8_t*
         }
     }
     return MDVT_OK;
+}
+
+// The same completion in the heap order of cv2.inpaint (mdvt_telea_heap.hip): one launch per pass, no host read-back.  Images per
+// pass: below.
+static int finish_infill_mask_heap(mdvt_ctx* c, const uint8_t* d_seed, const uint8_t* d_seed_right, size_t seed_pitch, size_t seed_stride,
+                                   uint8_t* d_out, uint8_t* d_out_right, size_t out_pitch, size_t out_stride, int n_frames,
+                                   uint32_t* d_remaining, void* stream)
+{
+    if (!c) return MDVT_ERR_INVALID_ARG;
+    if (!d_seed || !d_out) return fail(c, MDVT_ERR_INVALID_ARG, "NULL buffer");
+    if ((d_seed_right == nullptr) != (d_out_right == nullptr)) return fail(c, MDVT_ERR_INVALID_ARG, "right-eye seed and output go together");
+    if (n_frames < 1) return fail(c, MDVT_ERR_INVALID_ARG, "n_images must be >= 1");
+    if (seed_pitch < (size_t)3 * c->W || out_pitch < (size_t)3 * c->W) return fail(c, MDVT_ERR_INVALID_ARG, "pitch smaller than one row");
+    if (d_seed == d_out || (d_seed_right && d_seed_right == d_out_right)) return fail(c, MDVT_ERR_INVALID_ARG, "d_out may not alias d_seed");
+    DeviceGuard g(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    const int W = c->W, H = c->H;
+    const size_t npx = (size_t)W * H;
+    if (npx >= ((size_t)1 << 29))          // activation keys 4 rank + direction and push numbers (< 2 npx) are 32-bit
+        return fail(c, MDVT_ERR_UNSUPPORTED, "frame too large for the heap-order completion (%d x %d)", W, H);
+    const size_t per_image = mdvt::telea_heap_image_bytes(W, H);
+    // images per pass: what fits a quarter of the device's memory and what is free now (the workspace this ctx already holds
+    // counts as free: it is reused or handed back first), at most kTeleaHeapMaxImages; both eyes of a frame travel together
+    size_t free_b = 0, total_b = 0;
+    MDVT_HIP(c, hipMemGetInfo(&free_b, &total_b));
+    const size_t held = (size_t)c->heap_images * per_image;
+    size_t budget = total_b / 4;
+    if (free_b + held < budget) budget = free_b + held;
+    size_t cap = budget / per_image;
+    if (cap < (size_t)c->heap_images) cap = (size_t)c->heap_images;
+    if (cap > (size_t)mdvt::kTeleaHeapMaxImages) cap = mdvt::kTeleaHeapMaxImages;
+    const int eyes = d_seed_right ? 2 : 1;
+    int fchunk = cap / eyes >= 1 ? (int)(cap / eyes) : 1;                // frames per pass
+    const int want_images = (n_frames < fchunk ? n_frames : fchunk) * eyes;
+    if (c->heap_images < want_images) {
+        MDVT_HIP(c, hipDeviceSynchronize());                 // earlier submissions may still use the old workspace
+        free_telea_heap(c);
+        // if the block does not fit after all (another process took the memory meanwhile), fewer images per pass
+        int images = want_images;
+        for (;;) {
+            const hipError_t e = ws_malloc(c, (void**)&c->heap_ws, (size_t)images * per_image, s);
+            if (e == hipSuccess) break;
+            (void)hipGetLastError();
+            if (images <= eyes)
+                return fail(c, MDVT_ERR_OOM, "heap-order completion: no room for the workspace of one %s (%zu bytes): %s",
+                            eyes == 2 ? "frame" : "image", (size_t)eyes * per_image, hipGetErrorString(e));
+            images = images / 2 / eyes * eyes;
+            if (images < eyes) images = eyes;
+        }
+        MDVT_HIP(c, ws_malloc(c, (void**)&c->heap_remaining, (size_t)images * sizeof(uint32_t), s));
+        c->heap_images = images;
+    }
+    if (fchunk > c->heap_images / eyes) fchunk = c->heap_images / eyes;
+    const uint32_t key = (uint32_t)c->cfg.key_rgb[0] | ((uint32_t)c->cfg.key_rgb[1] << 8) | ((uint32_t)c->cfg.key_rgb[2] << 16);
+    const mdvt::BlurKernel K = masked_blur_kernel();
+    for (int f0 = 0; f0 < n_frames; f0 += fchunk) {
+        const int nf = n_frames - f0 < fchunk ? n_frames - f0 : fchunk, n = nf * eyes;
+        const mdvt::ImageSet seed{const_cast<uint8_t*>(d_seed) + (size_t)f0 * seed_stride, seed_pitch, seed_stride,
+                                  d_seed_right ? d_seed_right - d_seed : 0, nf};
+        const mdvt::ImageSet out{d_out + (size_t)f0 * out_stride, out_pitch, out_stride, d_out_right ? d_out_right - d_out : 0, nf};
+        const mdvt::ImageSet work{c->heap_ws + mdvt::telea_heap_img_offset(W, H), (size_t)3 * W, per_image, 0, n};
+        MDVT_HIP(c, launch_telea_heap(seed, c->heap_ws, per_image, c->heap_remaining, n, W, H, key, s));     // sr:806, inpaintRadius = 3
+        MDVT_HIP(c, launch_masked_blur(work, &seed, out, n, W, H, K, key, s));                                // sr:807-808
+        if (d_remaining) {      // image order of the result: left eyes of all frames, then right eyes
+            for (int e = 0; e < eyes; ++e)
+                MDVT_HIP(c, hipMemcpyAsync(d_remaining + (size_t)e * n_frames + f0, c->heap_remaining + (size_t)e * nf,
+                                           (size_t)nf * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+        }
+    }
+    return MDVT_OK;
+}
+
+int mdvt_finish_infill_mask_heap(mdvt_ctx* c, const uint8_t* d_seed, size_t seed_pitch, size_t seed_stride, uint8_t* d_out,
+                                 size_t out_pitch, size_t out_stride, int n_images, uint32_t* d_remaining, void* stream)
+{
+    return finish_infill_mask_heap(c, d_seed, nullptr, seed_pitch, seed_stride, d_out, nullptr, out_pitch, out_stride, n_images,
+                                   d_remaining, stream);
+}
+
+int mdvt_finish_infill_mask_heap_stereo(mdvt_ctx* c, const uint8_t* d_left_seed, const uint8_t* d_right_seed, size_t seed_pitch,
+                                        size_t seed_stride, uint8_t* d_left_out, uint8_t* d_right_out, size_t out_pitch,
+                                        size_t out_stride, int n_frames, uint32_t* d_remaining, void* stream)
+{
+    if (c && (!d_right_seed || !d_right_out)) return fail(c, MDVT_ERR_INVALID_ARG, "NULL buffer");
+    return finish_infill_mask_heap(c, d_left_seed, d_right_seed, seed_pitch, seed_stride, d_left_out, d_right_out, out_pitch,
+                                   out_stride, n_frames, d_remaining, stream);
 }
 
 int mdvt_finish_infill_mask(mdvt_ctx* c, const uint8_t* d_seed, size_t seed_pitch, size_t seed_stride, uint8_t* d_out,

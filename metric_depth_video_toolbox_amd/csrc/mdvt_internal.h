@@ -189,6 +189,13 @@ hipError_t launch_telea_init(const ImageSet& seed, const TeleaWorkspace& ws, int
                              uint32_t* h_levels, hipStream_t s);
 hipError_t launch_telea_rounds(const TeleaWorkspace& ws, int W, int H, int levels, uint32_t key_rgb, hipStream_t s);
 hipError_t launch_swap_rb(const ImageSet& src, const ImageSet& dst, int n, int W, int H, hipStream_t s);
+// mdvt_telea_heap.hip: the same completion in the heap order of cv2.inpaint, one workgroup per image (opt-in).  Workspace: one
+// block of telea_heap_image_bytes(W, H) per image (44 B/px), the work image at telea_heap_img_offset inside it (pitch 3 W).
+constexpr int kTeleaHeapMaxImages = 256;  // images per launch at most (one workgroup each: one per CU)
+size_t telea_heap_image_bytes(int W, int H);
+size_t telea_heap_img_offset(int W, int H);
+hipError_t launch_telea_heap(const ImageSet& seed, uint8_t* ws, size_t image_bytes, uint32_t* remaining, int n, int W, int H,
+                             uint32_t key_rgb, hipStream_t s);
 struct BlurKernel { float k[36]; };      // masked_blur's 6x6 Gaussian, f32, row major (built on the host in f64)
 hipError_t launch_masked_blur(const ImageSet& img, const ImageSet* seed, const ImageSet& out, int n, int W, int H,
                               const BlurKernel& K, uint32_t key_rgb, hipStream_t s, uint32_t* list = nullptr, uint32_t* count = nullptr);

@@ -275,6 +275,11 @@ class PreparedRender:
         return self.results
 
 
+# the orders in which the infill-mask completion may inpaint: "levels" (the default, level-synchronous) or "heap" (cv2.inpaint's
+# own sequential order, byte-exact to the reference; opt-in)
+INPAINT_ORDERS = ("levels", "heap")
+
+
 class StereoRerenderer:
     """One render context for W x H frames on one GPU.
 
@@ -418,11 +423,21 @@ class StereoRerenderer:
                             want_depth=want_depth, out_depth=out_depth, want_maskbits=want_maskbits,
                             want_hole_counts=want_hole_counts, want_seed=want_seed, want_mask=want_mask).launch(stream)
 
-    def finish_infill_mask_sbs(self, seed_sbs, out=None, max_rounds: int = 0, want_remaining: bool = False, no_host_wait: bool = False):
+    @staticmethod
+    def _check_order(order, max_rounds, no_host_wait=False):
+        if order not in INPAINT_ORDERS:
+            raise ValueError(f"order must be one of {INPAINT_ORDERS}, got {order!r}")
+        if order == "heap" and (int(max_rounds) != 0 or no_host_wait):
+            raise ValueError("order='heap' has no level bound: max_rounds and no_host_wait do not apply (it never waits on the stream)")
+
+    def finish_infill_mask_sbs(self, seed_sbs, out=None, max_rounds: int = 0, want_remaining: bool = False, no_host_wait: bool = False,
+                               order: str = "levels"):
         """finish_infill_mask for side-by-side seed buffers [N,H,2W,3] (render(want_seed=True)["seed"]): both eyes of
         all frames in one pass (mdvt_finish_infill_mask_stereo).  Returns [N,H,2W,3] (and, with want_remaining, an
         int32 tensor [2,N]: left eyes, right eyes).  no_host_wait: the asynchronous form (max_rounds, default 256, levels are
-        launched without reading the deepest level back: nothing waits on the stream)."""
+        launched without reading the deepest level back: nothing waits on the stream).  order="heap": cv2.inpaint's own order
+        (mdvt_finish_infill_mask_heap_stereo; see finish_infill_mask) in one context and one pass per launch."""
+        self._check_order(order, max_rounds, no_host_wait)
         if no_host_wait:
             max_rounds = -(int(max_rounds) if max_rounds > 0 else 256)
         torch = self.torch
@@ -440,6 +455,14 @@ class StereoRerenderer:
         assert tuple(out.shape) == (N, H, 2 * W, 3) and out.stride(-1) == 1 and out.stride(-2) == 3
         rem = torch.zeros((2, N), dtype=torch.int32, device=seed_sbs.device) if want_remaining else None
         s = torch.cuda.current_stream(seed_sbs.device)
+
+        if order == "heap":
+            self.ctx.check(self._L.mdvt_finish_infill_mask_heap_stereo(
+                self.ctx.handle, seed_sbs.data_ptr(), seed_sbs.data_ptr() + 3 * W, seed_sbs.stride(1), seed_sbs.stride(0),
+                out.data_ptr(), out.data_ptr() + 3 * W, out.stride(1), out.stride(0), N, rem.data_ptr() if rem is not None else None,
+                C.c_void_p(s.cuda_stream)))
+            res = out[0] if single else out
+            return (res, rem) if want_remaining else res
 
         def one_pass(ctx, a, b, stream, r):
             sd, o = seed_sbs[a:b], out[a:b]
@@ -476,12 +499,15 @@ class StereoRerenderer:
         res = out[0] if single else out
         return (res, rem) if want_remaining else res
 
-    def finish_infill_mask(self, seed, out=None, max_rounds: int = 0, want_remaining: bool = False):
+    def finish_infill_mask(self, seed, out=None, max_rounds: int = 0, want_remaining: bool = False, order: str = "levels"):
         """sr:803-808 + 816 on the device: seed image(s) from render(want_seed=True) -> the finished infill-mask
         image(s): Telea-weighted inpaint of the key-coloured / black pixels (level by level, see include/mdvt.h),
         key-coloured pixels keep the inpainted normal, then masked_blur.  seed: uint8 CUDA [H,W,3] or [N,H,W,3],
         rows / images may be strided (e.g. one eye of the side-by-side seed buffer).  Returns the image(s)
-        (and, with want_remaining, an int32 tensor [N] of key-coloured pixels the front did not reach)."""
+        (and, with want_remaining, an int32 tensor [N] of key-coloured pixels the front did not reach).
+        order="heap": the inpaint in cv2.inpaint's own order, byte-exact to the reference's sequential heap
+        (mdvt_finish_infill_mask_heap; opt-in, much slower than the default "levels"); no max_rounds."""
+        self._check_order(order, max_rounds)
         torch = self.torch
         assert seed.is_cuda and seed.dtype == torch.uint8 and seed.dim() in (3, 4) and seed.shape[-1] == 3
         assert seed.stride(-1) == 1 and seed.stride(-2) == 3, "pixels must be packed RGB"
@@ -493,6 +519,12 @@ class StereoRerenderer:
         assert out.shape == seed.shape and out.stride(-1) == 1 and out.stride(-2) == 3
         rem = torch.zeros(N, dtype=torch.int32, device=seed.device) if want_remaining else None
         s = torch.cuda.current_stream(seed.device)
+        if order == "heap":
+            self.ctx.check(self._L.mdvt_finish_infill_mask_heap(
+                self.ctx.handle, seed.data_ptr(), seed.stride(-3), seed.stride(0) if batched else 0, out.data_ptr(),
+                out.stride(-3), out.stride(0) if batched else 0, N, rem.data_ptr() if rem is not None else None,
+                C.c_void_p(s.cuda_stream)))
+            return (out, rem) if want_remaining else out
         self.ctx.check(self._L.mdvt_finish_infill_mask(
             self.ctx.handle, seed.data_ptr(), seed.stride(-3), seed.stride(0) if batched else 0, out.data_ptr(),
             out.stride(-3), out.stride(0) if batched else 0, N, int(max_rounds), rem.data_ptr() if rem is not None else None,
@@ -592,6 +624,10 @@ def build_arg_parser():
     ap.add_argument("--normal_infill", action="store_true",
                     help="not a reference flag: also run basic_nomal_infill.py's normal_infill on every frame while it is on the device "
                          "and write <output>_infilled.npy (needs --infill_mask)")
+    ap.add_argument("--inpaint_order", choices=INPAINT_ORDERS, default="levels",
+                    help="not a reference flag: the order of the infill-mask completion's inpaint (--infill_mask). 'levels' (default) "
+                         "fills level by level; 'heap' follows cv2.inpaint's own heap order and gives the reference's bytes, "
+                         "at a far lower rate that grows with the frames per call: raise --batch (e.g. 128) with 'heap' (README)")
     for flag in ("--compressed", "--mask_video", "--save_background", "--load_background"):
         ap.add_argument(flag, nargs="?", const=True, default=None, help="reference flag outside the built hot path")
     return ap
@@ -623,7 +659,7 @@ def main(argv=None):
                             infill_mask=args.infill_mask,
                             dont_place_points_in_edges=args.dont_place_points_in_edges,
                             vr180=args.vr180, touchly0=args.touchly0, touchly1=args.touchly1,
-                            do_basic_infill=args.do_basic_infill, normal_infill=args.normal_infill,
+                            do_basic_infill=args.do_basic_infill, normal_infill=args.normal_infill, inpaint_order=args.inpaint_order,
                             touchly_max_depth=args.touchly_max_depth, touchly_min_depth=args.touchly_min_depth)
     if int(os.environ.get("RANK", "0")) == 0:
         frames, secs = float(stats[:, 0].sum()), float(stats[:, 1].max())

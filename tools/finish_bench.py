@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Timing of the infill-mask completion (mdvt_finish_infill_mask) on real seeds: N 1080p frames rendered in the
-product-default mode (mesh, --infill_mask), both eyes finished.  Prints per-stage times."""
+product-default mode (mesh, --infill_mask), both eyes finished.  Prints per-stage times.  --order heap: the completion in
+cv2.inpaint's own order (mdvt_finish_infill_mask_heap) instead of the default level order."""
 import argparse
 import sys
 import os
@@ -21,6 +22,7 @@ ap.add_argument("--config", type=int, default=3, help="synthetic scene id (bench
 ap.add_argument("--conv", type=float, default=0.0, help="convergence distance in metres (0: none)")
 ap.add_argument("--per-eye", action="store_true", help="one call per eye instead of the stereo entry point")
 ap.add_argument("--streams", type=int, default=1, help="split the frames over this many contexts, each on its own stream")
+ap.add_argument("--order", choices=sr.INPAINT_ORDERS, default="levels", help="inpaint order of the completion")
 a = ap.parse_args()
 W, H, N = a.width, a.height, a.frames
 d, c = synthetic.SyntheticScene(W, H, config_id=a.config).clip(N)
@@ -41,18 +43,19 @@ for rep in range(a.reps):
         for k in range(a.streams):
             streams[k].wait_stream(cur)
             with torch.cuda.stream(streams[k]):
-                rs[k].finish_infill_mask_sbs(seed[k * per:(k + 1) * per], out=out[k * per:(k + 1) * per], max_rounds=a.rounds)
+                rs[k].finish_infill_mask_sbs(seed[k * per:(k + 1) * per], out=out[k * per:(k + 1) * per], max_rounds=a.rounds, order=a.order)
         for k in range(a.streams):
             cur.wait_stream(streams[k])
         rem = torch.zeros(1)
     elif a.per_eye:
         for eye in range(2):
             _, rem = r.finish_infill_mask(seed[:, :, eye * W:(eye + 1) * W], out=out[:, :, eye * W:(eye + 1) * W], max_rounds=a.rounds,
-                                          want_remaining=True)
+                                          want_remaining=True, order=a.order)
     else:
-        _, rem = r.finish_infill_mask_sbs(seed, out=out, max_rounds=a.rounds, want_remaining=True)
+        _, rem = r.finish_infill_mask_sbs(seed, out=out, max_rounds=a.rounds, want_remaining=True, order=a.order)
     ev[1].record()
     torch.cuda.synchronize()
     ms = ev[0].elapsed_time(ev[1])
-    print(f"finish {2 * N} images {W}x{H}: {ms:.2f} ms  -> {ms / N:.3f} ms/frame, remaining {int(rem.sum())}, "
+    print(f"finish ({a.order}) {2 * N} images {W}x{H}: {ms:.2f} ms  -> {ms / N:.3f} ms/frame, {2000 * N / ms:.1f} images/s, "
+          f"remaining {int(rem.sum())}, "
           f"holes {int((res['mask'] > 0).sum()) / (2 * N * W * H) * 100:.1f} %")
