@@ -81,7 +81,21 @@ typedef struct mdvt_config {
                                     that the path can be held to them; other values are refused.  Applies to the mesh AND to
                                     points (a size-1 point is the unit square around the snapped vertex).  New in ABI 0.14
                                     together with reserved2: the struct grew from 40 to 48 bytes                                */
-    int32_t reserved2;           /* must be 0 */
+    /* Multisampling (took over `reserved2` of ABI 0.14 without changing the size or the version: all zero = single sample, as
+     * before).  samples: 0 or 1 = one sample at the pixel centre (the decree), 4 = 4x multisampled as a GL renders into a 4x
+     * multisampled framebuffer -- coverage and depth per sample, colour once per pixel at the centre (no centroid sampling), the
+     * nearest fragment keeps a sample (exact tie: the first drawn), resolve of the four samples with the key colour in the
+     * uncovered ones, hole = resolved colour == key colour.  Other values are refused.  sample_pattern: 0 = the Direct3D /
+     * Vulkan standard positions (6,2) (14,6) (2,10) (10,14) / 16 px, 1 = SwiftShader's (3,10) (10,13) (13,6) (6,3) / 16 (image
+     * space, y down).  sample_resolve: 0 = (s0 + s1 + s2 + s3 + 2) >> 2, 1 = SwiftShader's avg(avg(s0, s1), avg(s2, s3)) with
+     * avg = (a + b + 1) >> 1.  Mesh and points, every kind of frame, cull, remove_edges, both grids, batches and the same layouts
+     * as the single-sample path; a parity mode, 17-130x slower (profiles/r07_multisample.md).  With samples = 4 the
+     * render calls answer MDVT_ERR_UNSUPPORTED for what it does not cover: edge_points != 0, depth planes, seed images,
+     * packed mask bits and NULL byte masks (hole counts are supported).  Workspace: 64 B per pixel and frame in flight (the
+     * sample key planes of both eyes), + 3 B with remove_edges; workspace_mib bounds the frames in flight (1 ... 16). */
+    int16_t samples;
+    uint8_t sample_pattern;
+    uint8_t sample_resolve;
 } mdvt_config;
 
 /* Per-frame parameters: what sr:515-541, 563-566 and 707-721 compute before the render calls. */

@@ -38,7 +38,9 @@ class MdvtError(RuntimeError):
 class MdvtConfig(C.Structure):
     _fields_ = [("mode", C.c_int32), ("remove_edges", C.c_int32), ("edge_points", C.c_int32), ("cull", C.c_int32),
                 ("ipd_m", C.c_double), ("max_depth", C.c_double), ("key_rgb", C.c_uint8 * 4), ("workspace_mib", C.c_uint32),
-                ("subpixel_bits", C.c_int32), ("reserved2", C.c_int32)]
+                ("subpixel_bits", C.c_int32),
+                # multisampling (took over reserved2 of ABI 0.14; all zero = single sample): samples 0/1 or 4, pattern 0/1, resolve 0/1
+                ("samples", C.c_int16), ("sample_pattern", C.c_uint8), ("sample_resolve", C.c_uint8)]
 
 
 class MdvtFrameParams(C.Structure):

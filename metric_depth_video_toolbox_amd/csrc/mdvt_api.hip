@@ -100,6 +100,10 @@ struct mdvt_ctx {
     hipStream_t side = nullptr;
     uint32_t* hugeq2 = nullptr;
     hipEvent_t ev_start = nullptr, ev_join = nullptr, ev_vert[2] = {nullptr, nullptr};
+    // multisampled render (mdvt_config.samples = 4): the sample key planes of msaa_frames frames in flight, [slot][eye][H*W][4]
+    unsigned long long* msaa_keys = nullptr;
+    int msaa_frames = 0;
+    bool msaa_dirty = false;          // a submission stopped between raster and resolve: the planes are not all empty
 };
 
 namespace {
@@ -572,6 +576,83 @@ int ensure_rowcell(mdvt_ctx* c, hipStream_t s)
     return MDVT_OK;
 }
 
+// ---- 4x multisampled render (mdvt_config.samples = 4; mdvt_msaa.hip) ---------------------------------------------------------
+// What the mode does not cover is refused before anything is checked or launched, with the output named.
+int msaa_refusal(mdvt_ctx* c, const mdvt_io* io)
+{
+    const char* what = nullptr;
+    if (c->cfg.edge_points) what = "edge points (mdvt_config.edge_points != 0)";
+    else if (io->left_depth || io->right_depth) what = "depth planes (left_depth / right_depth)";
+    else if (io->left_seed || io->right_seed) what = "seed images (left_seed / right_seed)";
+    else if (io->left_maskbits || io->right_maskbits) what = "packed mask bits (left_maskbits / right_maskbits)";
+    else if (!io->left_mask || !io->right_mask) what = "a NULL byte mask (left_mask / right_mask are required)";
+    if (!what) return MDVT_OK;
+    return fail(c, MDVT_ERR_UNSUPPORTED, "multisampling (samples = 4) does not cover %s", what);
+}
+
+// Launch sets of up to 16 frames, as many as workspace_mib affords (64 B/px of sample keys, 3 B/px of edge-filter flags).
+int render_msaa(mdvt_ctx* c, int n_frames, const std::vector<FrameDev>& fd, const mdvt_io* io, hipStream_t s)
+{
+    const int W = c->W, H = c->H;
+    const size_t npx = (size_t)W * (size_t)H;
+    if (2 * npx >= (size_t)0xFFFFFFFFu)
+        return fail(c, MDVT_ERR_UNSUPPORTED, "multisampling: a %d x %d frame has more triangles than its 32-bit draw ids can name", W, H);
+    const bool rm = c->cfg.remove_edges != 0;
+    const size_t per_slot = npx * (2 * 4 * sizeof(unsigned long long) + (rm ? 3 : 0));
+    const size_t budget = (size_t)(c->cfg.workspace_mib ? c->cfg.workspace_mib : 4096u) << 20;
+    int chunk = 16;
+    if ((size_t)chunk > budget / per_slot) chunk = budget / per_slot < 1 ? 1 : (int)(budget / per_slot);
+    if (chunk > n_frames) chunk = n_frames;
+
+    const FrameDev* dfp = nullptr;
+    ParamSlot* slot = nullptr;
+    int rc = stage_params(c, fd, s, &dfp, &slot);
+    if (rc != MDVT_OK) return rc;
+    if (rm && (rc = ensure_workspace(c, chunk, false, false, true, false, s)) != MDVT_OK) return rc;
+    const size_t plane_bytes = npx * 2 * 4 * sizeof(unsigned long long);       // one slot, both eyes
+    if (c->msaa_frames < chunk) {
+        if (c->msaa_keys) { MDVT_HIP(c, hipDeviceSynchronize()); ws_free(c, c->msaa_keys); }     // (earlier submissions may still use it)
+        c->msaa_keys = nullptr; c->msaa_frames = 0;
+        MDVT_HIP(c, ws_malloc(c, (void**)&c->msaa_keys, (size_t)chunk * plane_bytes, s));
+        c->msaa_frames = chunk;
+        c->msaa_dirty = true;
+    }
+    if (c->msaa_dirty) MDVT_HIP(c, hipMemsetAsync(c->msaa_keys, 0xFF, (size_t)c->msaa_frames * plane_bytes, s));
+    c->msaa_dirty = false;
+    if (io->hole_counts) MDVT_HIP(c, hipMemsetAsync(io->hole_counts, 0, 2 * (size_t)n_frames * sizeof(uint32_t), s));
+
+    MsaaArgs a{};
+    a.depth = io->depth_rgb; a.depth_pitch = io->depth_pitch; a.depth_stride = io->depth_stride;
+    a.color = io->color_rgb; a.color_pitch = io->color_pitch; a.color_stride = io->color_stride;
+    a.rgb[0] = io->left_rgb; a.rgb[1] = io->right_rgb; a.rgb_pitch = io->rgb_pitch; a.rgb_stride = io->rgb_stride;
+    a.mask[0] = io->left_mask; a.mask[1] = io->right_mask; a.mask_pitch = io->mask_pitch; a.mask_stride = io->mask_stride;
+    a.hole_counts = io->hole_counts;
+    a.fp = dfp;
+    a.keys = c->msaa_keys;
+    a.tri_invalid = rm ? c->tri_invalid : nullptr;
+    a.unused = rm ? c->unused : nullptr;
+    a.ws_stride_px = npx;
+    a.ws_stride_tri = 2 * (size_t)(W - 1) * (H - 1);
+    a.W = W; a.H = H;
+    a.mode = c->cfg.mode; a.cull = c->cfg.cull;
+    a.pattern = c->cfg.sample_pattern; a.resolve = c->cfg.sample_resolve;
+    a.key_rgb = (uint32_t)c->cfg.key_rgb[0] | ((uint32_t)c->cfg.key_rgb[1] << 8) | ((uint32_t)c->cfg.key_rgb[2] << 16);
+    for (int f0 = 0; f0 < n_frames; f0 += chunk) {
+        const int n = n_frames - f0 < chunk ? n_frames - f0 : chunk;
+        a.frame0 = f0;
+        if (rm) {
+            MDVT_HIP(c, launch_zero_bytes(c->unused, (size_t)n * npx, s));
+            MDVT_HIP(c, launch_edge_filter(a.depth, a.depth_pitch, a.depth_stride, dfp, f0, n, W, H, c->cfg.mode == MDVT_MODE_MESH,
+                                           c->tri_invalid, a.ws_stride_tri, c->unused, npx, s));
+        }
+        c->msaa_dirty = true;
+        MDVT_HIP(c, MDVT_GRID_CALL(c, launch_msaa_render, a, n, s));
+        c->msaa_dirty = false;
+    }
+    MDVT_HIP(c, hipEventRecord(slot->done, s));
+    return MDVT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -689,6 +770,7 @@ int mdvt_destroy(mdvt_ctx* c)
     if (c->wave_counts) ws_free(c, c->wave_counts);
     if (c->divcheck) ws_free(c, c->divcheck);
     if (c->rowcell) ws_free(c, c->rowcell);
+    if (c->msaa_keys) ws_free(c, c->msaa_keys);
     pool_give(c->telea_levels_host, nullptr, 64, -1);
     free_telea(c);
     free_telea_heap(c);
@@ -709,7 +791,10 @@ int mdvt_set_config(mdvt_ctx* c, const mdvt_config* cfg)
     if (cfg->cull < 0 || cfg->cull > 2) return fail(c, MDVT_ERR_INVALID_ARG, "cull must be 0 (none), 1 (back) or 2 (front)");
     if (cfg->subpixel_bits != 0 && cfg->subpixel_bits != 4 && cfg->subpixel_bits != 8)
         return fail(c, MDVT_ERR_INVALID_ARG, "subpixel_bits must be 0 (default: 8), 4 or 8 -- the grids this build's rasterisers are compiled for");
-    if (cfg->reserved2 != 0) return fail(c, MDVT_ERR_INVALID_ARG, "reserved2 must be 0");
+    if (cfg->samples != 0 && cfg->samples != 1 && cfg->samples != 4)
+        return fail(c, MDVT_ERR_INVALID_ARG, "samples must be 0 or 1 (single sample) or 4 (4x multisampled), got %d", (int)cfg->samples);
+    if (cfg->sample_pattern > 1) return fail(c, MDVT_ERR_INVALID_ARG, "sample_pattern must be 0 (standard) or 1 (SwiftShader), got %d", (int)cfg->sample_pattern);
+    if (cfg->sample_resolve > 1) return fail(c, MDVT_ERR_INVALID_ARG, "sample_resolve must be 0 (rounded mean) or 1 (SwiftShader), got %d", (int)cfg->sample_resolve);
     // (advisor r04: the field took over a reserved one -- a caller built against 0.11 that left it uninitialised must not get an
     //  arbitrary budget silently: anything above 1 TiB is refused, small values are honoured down to one slot)
     if (cfg->workspace_mib > (1u << 20)) return fail(c, MDVT_ERR_INVALID_ARG, "workspace_mib %u out of range (0 = default 4096, at most 1048576)", cfg->workspace_mib);
@@ -740,6 +825,10 @@ int mdvt_render_stereo_batch(mdvt_ctx* c, int n_frames, const mdvt_frame_params*
     if (n_frames <= 0 || !params || !io) return fail(c, MDVT_ERR_INVALID_ARG, "n_frames/params/io invalid");
     if (!io->depth_rgb || !io->color_rgb || !io->left_rgb || !io->right_rgb)
         return fail(c, MDVT_ERR_INVALID_ARG, "depth_rgb, color_rgb and left/right rgb buffers are required");
+    if (c->cfg.samples == 4) {
+        const int rc = msaa_refusal(c, io);
+        if (rc != MDVT_OK) return rc;
+    }
     // The byte masks may be left out (both NULL) by a caller that takes the packed mask instead -- where the compaction is fused
     // into the render kernel (pure-shift point frames: checked per run below); everywhere else they are required.
     const bool no_byte_mask = !io->left_mask && !io->right_mask && io->left_maskbits && io->right_maskbits;
@@ -775,6 +864,7 @@ int mdvt_render_stereo_batch(mdvt_ctx* c, int n_frames, const mdvt_frame_params*
         general |= fd[(size_t)k].general;
         fd[(size_t)k].div_slot = -1;
     }
+    if (c->cfg.samples == 4) return render_msaa(c, n_frames, fd, io, s);
     // Pure-shift point frames: the disparity's division proven short per parameter set (FrameDev.div_slot).  A new set costs one
     // launch of 65536 threads on this stream, once per context; clips have one set, or one per distinct field of view.
     if (c->cfg.mode == MDVT_MODE_POINTS) {

@@ -157,6 +157,23 @@ struct RenderPlan {
     int edge_rows_max;   // pure-shift launches with edge points: the most scanlines any frame leaves to k_edge_rows_exact (0: none)
     hipEvent_t after_vertices;   // general paths: recorded on the launch's stream behind the first pass (the mesh's cell walk, the points' splat; nullptr: none)
 };
+// mdvt_msaa.hip: the opt-in 4x multisampled render (mdvt_config.samples = 4), one launch set of frames [frame0, frame0 + n).
+struct MsaaArgs {
+    const uint8_t* depth; size_t depth_pitch, depth_stride;
+    const uint8_t* color; size_t color_pitch, color_stride;
+    uint8_t* rgb[2];  size_t rgb_pitch, rgb_stride;
+    uint8_t* mask[2]; size_t mask_pitch, mask_stride;
+    uint32_t* hole_counts;       // optional [n_frames][2], zeroed by the caller before the first launch set
+    const FrameDev* fp;          // device array, one per frame of the batch
+    unsigned long long* keys;    // [slot][eye][H*W][4 samples]: ~bits(1/Z) << 32 | draw id, all ones = empty (left empty again by the resolve)
+    const uint8_t* tri_invalid;  // [slot][2*(H-1)*(W-1)] or nullptr (no edge removal)
+    const uint8_t* unused;       // [slot][H*W] or nullptr
+    size_t ws_stride_px, ws_stride_tri;
+    int32_t W, H;
+    int32_t frame0;              // first frame of this launch set within the batch
+    int32_t mode, cull, pattern, resolve;     // mdvt_config: mode, cull, sample_pattern, sample_resolve
+    uint32_t key_rgb;            // R | G<<8 | B<<16
+};
 // The rasterising translation units (mdvt_kernels.hip's render sections, mdvt_mesh_*.hip) are compiled once per sub-pixel grid;
 // what they define is declared in mdvt_grid_decls.h, once per grid namespace (below, after the shared declarations).
 // (mdvt_normal_infill.hip; workspace: normal_infill_workspace_bytes(1, W, H))

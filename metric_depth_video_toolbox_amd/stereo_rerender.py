@@ -275,6 +275,51 @@ class PreparedRender:
         return self.results
 
 
+# multisampling (StereoRerenderer(samples=4)): the values of samples, and the CLI's names of the sample patterns (mdvt.h)
+SAMPLE_COUNTS = (0, 1, 4)
+SAMPLE_PATTERNS = ("standard", "swiftshader")
+
+
+def check_multisample(samples, sample_pattern=0, sample_resolve=0):
+    """ValueError unless (samples, sample_pattern, sample_resolve) is a setting mdvt_config accepts (no device needed)."""
+    if samples not in SAMPLE_COUNTS or isinstance(samples, bool):
+        raise ValueError(f"samples must be one of {SAMPLE_COUNTS} (0 and 1: single sample, 4: 4x multisampled), got {samples!r}")
+    if sample_pattern not in (0, 1) or isinstance(sample_pattern, bool):
+        raise ValueError(f"sample_pattern must be 0 (standard) or 1 (swiftshader), got {sample_pattern!r}")
+    if sample_resolve not in (0, 1) or isinstance(sample_resolve, bool):
+        raise ValueError(f"sample_resolve must be 0 (rounded mean) or 1 (SwiftShader's pairwise average), got {sample_resolve!r}")
+
+
+def multisample_conflict(args):
+    """The first flag of a parsed command line that --multisample 4 cannot serve, as an error message (None: no conflict).
+    Checked before any frame is read: the multisampled render has no edge points, seed images or depth planes (mdvt.h)."""
+    if getattr(args, "multisample", "off") == "off":
+        return None
+    rm = bool(args.infill_mask or args.remove_edges or args.do_basic_infill) and not args.dont_remove_edges
+    if args.do_basic_infill:
+        return "--multisample 4 does not cover --do_basic_infill (it needs the infill-mask seed images)"
+    if args.touchly0 or args.touchly1:
+        return f"--multisample 4 does not cover --{'touchly0' if args.touchly0 else 'touchly1'} (Touchly outputs need depth planes)"
+    if args.create_sbs_depth_video:
+        return "--multisample 4 does not cover --create_sbs_depth_video (it needs depth planes)"
+    if rm and not args.dont_place_points_in_edges:
+        return "--multisample 4 does not cover edge points: add --dont_place_points_in_edges (or --dont_remove_edges)"
+    if args.infill_mask and rm and not args.green_and_black_infill_mask:
+        return ("--multisample 4 does not cover the normal-coloured --infill_mask (it needs the seed images): "
+                "add --green_and_black_infill_mask (or --dont_remove_edges)")
+    if getattr(args, "normal_infill", False):
+        return "--multisample 4 does not cover --normal_infill (it needs the infill-mask seed images)"
+    return None
+
+
+def multisample_kwargs(args):
+    """StereoRerenderer keywords of --multisample / --sample_pattern ({} when multisampling is off)."""
+    if getattr(args, "multisample", "off") == "off":
+        return {}
+    pattern = SAMPLE_PATTERNS.index(args.sample_pattern)
+    return {"samples": 4, "sample_pattern": pattern, "sample_resolve": pattern}
+
+
 # the orders in which the infill-mask completion may inpaint: "levels" (the default, level-synchronous) or "heap" (cv2.inpaint's
 # own sequential order, byte-exact to the reference; opt-in)
 INPAINT_ORDERS = ("levels", "heap")
@@ -295,6 +340,13 @@ class StereoRerenderer:
       subpixel_bits                                  the rasteriser's sub-pixel grid (GL_SUBPIXEL_BITS of the GL that ran the
                                                      reference): 0 = 8, the default; 4 = the grid of the GL the fixtures
                                                      tests/golden/render_gl_*.npz were rendered with (mdvt.h)
+      samples                                        0 (default) or 1: one sample per pixel, at its centre; 4: 4x multisampled, as a
+                                                     GL renders into a 4x multisampled framebuffer (mdvt.h mdvt_config.samples; a
+                                                     parity mode, 17-130x slower).  Not with edge points, depth planes,
+                                                     seed images or packed masks: render() raises MdvtError (MDVT_ERR_UNSUPPORTED)
+      sample_pattern                                 samples = 4: 0 the Direct3D / Vulkan standard positions, 1 SwiftShader's
+      sample_resolve                                 samples = 4: 0 the rounded mean of the four samples, 1 SwiftShader's
+                                                     avg(avg(s0, s1), avg(s2, s3))
     """
 
     FINISH_SPLIT_FRAMES = 32         # finish_infill_mask_sbs: from this many frames per call, two concurrent half passes
@@ -303,7 +355,9 @@ class StereoRerenderer:
                  max_depth=100, master_xfov: float = 45.0, render_as_pointcloud: bool = False,
                  remove_edges: bool = False, infill_mask: bool = False, do_basic_infill: bool = False,
                  dont_remove_edges: bool = False, dont_place_points_in_edges: bool = False, cull: int = 0,
-                 workspace_mib: int = 0, subpixel_bits: int = 0):
+                 workspace_mib: int = 0, subpixel_bits: int = 0, samples: int = 0, sample_pattern: int = 0,
+                 sample_resolve: int = 0):
+        check_multisample(samples, sample_pattern, sample_resolve)
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("no ROCm GPU visible: the stereo-rerender path has no CPU fallback")
@@ -331,6 +385,8 @@ class StereoRerenderer:
         self.cull = int(cull)
         cfg.subpixel_bits = int(subpixel_bits)
         self.subpixel_bits = int(subpixel_bits)
+        cfg.samples, cfg.sample_pattern, cfg.sample_resolve = int(samples), int(sample_pattern), int(sample_resolve)
+        self.samples, self.sample_pattern, self.sample_resolve = int(samples), int(sample_pattern), int(sample_resolve)
         cfg.ipd_m = self.pupillary_distance / 1000                         # sr:458-459
         cfg.max_depth = float(self.max_depth)
         for k in range(3):
@@ -628,6 +684,16 @@ def build_arg_parser():
                     help="not a reference flag: the order of the infill-mask completion's inpaint (--infill_mask). 'levels' (default) "
                          "fills level by level; 'heap' follows cv2.inpaint's own heap order and gives the reference's bytes, "
                          "at a far lower rate that grows with the frames per call: raise --batch (e.g. 128) with 'heap' (README)")
+    ap.add_argument("--multisample", choices=("off", "4"), default="off",
+                    help="not a reference flag: 'off' (default) samples every pixel once, at its centre; '4' renders 4x multisampled, "
+                         "as a GL does into a 4x multisampled framebuffer -- a parity mode, 17-130x slower (README). Not with "
+                         "edge points, seed images or depth outputs: --infill_mask needs --dont_place_points_in_edges and "
+                         "--green_and_black_infill_mask, and --do_basic_infill, --normal_infill, --create_sbs_depth_video, "
+                         "--touchly0 / --touchly1 are refused")
+    ap.add_argument("--sample_pattern", choices=SAMPLE_PATTERNS, default="standard",
+                    help="not a reference flag: with --multisample 4, the sample positions and the resolve -- 'standard' (default): "
+                         "the Direct3D / Vulkan positions and the rounded mean; 'swiftshader': the conformant GL's positions and "
+                         "its pairwise-average resolve")
     for flag in ("--compressed", "--mask_video", "--save_background", "--load_background"):
         ap.add_argument(flag, nargs="?", const=True, default=None, help="reference flag outside the built hot path")
     return ap
@@ -643,6 +709,9 @@ def main(argv=None):
         raise ValueError("Error: Either --xfov_file, --xfov or --yfov must be provided.")       # sr:319-320
     if args.xfov is None and args.xfov_file is None:
         raise NotImplementedError("--yfov without --xfov: the reference itself fails at sr:537 in this case")
+    conflict = multisample_conflict(args)
+    if conflict is not None:
+        raise ValueError(conflict)
     if not os.path.isfile(args.depth_video):
         raise FileNotFoundError(f"Depth video not found: {args.depth_video}")                  # sr:326
     if args.color_video and not os.path.isfile(args.color_video):
@@ -660,6 +729,7 @@ def main(argv=None):
                             dont_place_points_in_edges=args.dont_place_points_in_edges,
                             vr180=args.vr180, touchly0=args.touchly0, touchly1=args.touchly1,
                             do_basic_infill=args.do_basic_infill, normal_infill=args.normal_infill, inpaint_order=args.inpaint_order,
+                            multisample=multisample_kwargs(args),
                             touchly_max_depth=args.touchly_max_depth, touchly_min_depth=args.touchly_min_depth)
     if int(os.environ.get("RANK", "0")) == 0:
         frames, secs = float(stats[:, 0].sum()), float(stats[:, 1].max())

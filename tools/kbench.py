@@ -35,16 +35,20 @@ ap.add_argument("--edges", action="store_true", help="remove_edges without --inf
 ap.add_argument("--split", type=int, default=1, help="the batch as this many sub-batches, each with its own context on its own stream")
 ap.add_argument("--stagger-us", type=float, default=0.0, help="with --split: sub-batch k starts k x this late and the streams free-run (joined once per timing)")
 ap.add_argument("--noedgepts", action="store_true", help="with --edges / --infill: dont_place_points_in_edges")
+ap.add_argument("--samples", type=int, default=0, help="mdvt_config.samples: 0 / 1 single sample, 4 = 4x multisampled (refuses --zout, --bits and edge "
+                "points: use --noedgepts with --edges / --infill)")
+ap.add_argument("--pattern", type=int, default=0, help="with --samples 4: sample pattern and resolve (0 standard, 1 SwiftShader)")
 a = ap.parse_args()
 W, H, N = a.width, a.height, a.frames
+ms = dict(samples=a.samples, sample_pattern=a.pattern, sample_resolve=a.pattern) if a.samples else {}
 if os.environ.get('KB_ORDER'):
-    r = StereoRerenderer(W, H, pupillary_distance=65, render_as_pointcloud=not a.mesh, infill_mask=a.infill, remove_edges=a.edges or a.infill, dont_place_points_in_edges=a.noedgepts)
+    r = StereoRerenderer(W, H, pupillary_distance=65, render_as_pointcloud=not a.mesh, infill_mask=a.infill, remove_edges=a.edges or a.infill, dont_place_points_in_edges=a.noedgepts, **ms)
     d, c = SyntheticScene(W, H, config_id=2).clip(N)
     d, c = torch.from_numpy(d).cuda(), torch.from_numpy(c).cuda()
 else:
     d, c = SyntheticScene(W, H, config_id=2).clip(N)
     d, c = torch.from_numpy(d).cuda(), torch.from_numpy(c).cuda()
-    r = StereoRerenderer(W, H, pupillary_distance=65, render_as_pointcloud=not a.mesh, infill_mask=a.infill, remove_edges=a.edges or a.infill, dont_place_points_in_edges=a.noedgepts)
+    r = StereoRerenderer(W, H, pupillary_distance=65, render_as_pointcloud=not a.mesh, infill_mask=a.infill, remove_edges=a.edges or a.infill, dont_place_points_in_edges=a.noedgepts, **ms)
 from metric_depth_video_toolbox_amd.synthetic import synthetic_pose_track
 Ts = synthetic_pose_track(N) if a.pose else [None] * N
 if a.c4:
@@ -60,7 +64,7 @@ stream = torch.cuda.current_stream()
 if a.split > 1:
     per = (N + a.split - 1) // a.split
     rs = [StereoRerenderer(W, H, pupillary_distance=65, render_as_pointcloud=not a.mesh, infill_mask=a.infill, remove_edges=a.edges or a.infill,
-                           dont_place_points_in_edges=a.noedgepts) for _ in range(a.split)]
+                           dont_place_points_in_edges=a.noedgepts, **ms) for _ in range(a.split)]
     streams = [torch.cuda.Stream() for _ in range(a.split)]
     jobs = [rs[k].prepare(d[k * per:(k + 1) * per], c[k * per:(k + 1) * per], p[k * per:(k + 1) * per], out_sbs=sbs[k * per:(k + 1) * per],
                           out_mask=mask[k * per:(k + 1) * per], want_depth=a.zout, out_depth=None if zo is None else zo[k * per:(k + 1) * per],
