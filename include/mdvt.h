@@ -332,6 +332,27 @@ int mdvt_infill_using_mask_normals(mdvt_ctx* ctx, uint8_t* d_img, size_t img_pit
                                    size_t hole_pitch, size_t hole_stride, const uint8_t* d_mask_img, size_t mask_pitch,
                                    size_t mask_stride, int n_images, int max_steps, void* stream);
 
+/* The FFV1 encoder of libmdvt_video.so on the device: the cv2.VideoWriter(path, fourcc('F','F','V','1'), ...).write(frame) calls of
+ * the stereo, infill-mask and depth outputs (sr:426-444, 941; dfh:125-161) without copying the raw frames to the host.
+ * n_frames frames of width x height u8 pixels at d_src (row pitch `pitch`, frame_stride bytes between frames), `channels` 3 (byte
+ * order: order 0 = RGB, 1 = BGR, as MDVT_VIDEO_RGB / MDVT_VIDEO_BGR of mdvt_video.h) or 1 (grey, coded as R = G = B).  width and
+ * height are independent of the ctx's render size (side-by-side frames are 2 W wide).  Frame k's packet is written to
+ * d_packets + d_offsets[k] (DEVICE arrays: n_frames x uint64 and uint32), d_sizes[k] bytes, and is byte for byte what
+ * mdvt_ffv1_encode_frame(width, height, slices_h, slices_v, ...) returns for the same pixels; packets follow each other in frame
+ * order without gaps.  Capacity: each slice codes into a scratch area of slice_capacity payload bytes (0 = twice the largest
+ * slice's raw bytes + 4096), at most 2^24 - 1 (the 24-bit slice size).  A frame one of whose slices passes its capacity, or whose
+ * packet does not fit the packets_cap bytes left at d_packets, gets d_sizes[k] = 0xFFFFFFFF and no bytes; a frame with a slice of
+ * 2^24 bytes or more gets 0xFFFFFFFE.  A buffer of n_frames x slices_h x slices_v x (capacity + 8) bytes always has room: then only a
+ * slice past its capacity flags a frame.  The caller re-encodes such a frame with mdvt_ffv1_encode_frame, which returns the same
+ * bytes, or refuses the frame with its MDVT_VIDEO error as it does for 0xFFFFFFFE.  Refused here: the slice counts
+ * mdvt_ffv1_encode_frame refuses (below 1, above width / height) and more than 1024 slices per frame (mdvt_video_create refuses
+ * them).  The call only enqueues work on `stream`; its workspace (the slices' scratch areas) is kept by the ctx, grown (which
+ * synchronises the device) when a call needs more, and bounded by mdvt_config.workspace_mib (default 4 GiB): a larger batch is
+ * coded in several passes.  Added in 0.15 without changing any earlier entry point: the ABI version stays 0.15. */
+int mdvt_encode_video_frames(mdvt_ctx* ctx, int width, int height, int slices_h, int slices_v, const uint8_t* d_src, size_t pitch,
+                            size_t frame_stride, int channels, int order, int n_frames, uint64_t slice_capacity, uint8_t* d_packets,
+                            uint64_t packets_cap, uint64_t* d_offsets, uint32_t* d_sizes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

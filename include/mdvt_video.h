@@ -14,6 +14,8 @@
  * INTEROPERABILITY UNPINNED: no FFmpeg exists here to read these files or to produce files for the reader.  The encoder is
  * checked by an independent decoder restated from the RFC's pseudo-code (test infrastructure: ffv1_ref.py next to the C oracle), the container by structural
  * tests (EBML sizes, CRCs); tests/golden/gen_ffv1_golden.py produces cross-check vectors on a machine that has ffmpeg.
+ * The encoder has a device twin in libmdvt_hip.so, mdvt_encode_video_frames of include/mdvt.h: it codes batches of device frames into
+ * the same packets byte for byte, for mdvt_video_write_packet.
  */
 #ifndef MDVT_VIDEO_H
 #define MDVT_VIDEO_H

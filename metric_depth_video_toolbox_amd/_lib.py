@@ -26,7 +26,8 @@ SYMBOLS = ("mdvt_version", "mdvt_create", "mdvt_destroy", "mdvt_last_error", "md
            "mdvt_equirect_tables", "mdvt_equirect_remap", "mdvt_masked_blur", "mdvt_finish_infill_mask",
            "mdvt_finish_infill_mask_stereo", "mdvt_swap_rb", "mdvt_selftest", "mdvt_normal_infill", "mdvt_infill_using_mask_normals",
            "mdvt_edge_point_pixels", "mdvt_workspace_bytes", "mdvt_release_cached_memory", "mdvt_cached_memory", "mdvt_set_cached_memory_limit",
-           "mdvt_debug_read", "mdvt_finish_infill_mask_heap", "mdvt_finish_infill_mask_heap_stereo")
+           "mdvt_debug_read", "mdvt_finish_infill_mask_heap", "mdvt_finish_infill_mask_heap_stereo",
+           "mdvt_encode_video_frames")
 
 
 class MdvtError(RuntimeError):
@@ -125,6 +126,9 @@ def load():
     L.mdvt_finish_infill_mask_heap.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_int, vp, vp]
     L.mdvt_finish_infill_mask_heap_stereo.restype = C.c_int
     L.mdvt_finish_infill_mask_heap_stereo.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, vp, vp, C.c_size_t, C.c_size_t, C.c_int, vp, vp]
+    L.mdvt_encode_video_frames.restype = C.c_int
+    L.mdvt_encode_video_frames.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int,
+                                          C.c_uint64, vp, C.c_uint64, vp, vp, vp]
     L.mdvt_swap_rb.restype = C.c_int
     L.mdvt_swap_rb.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_int, vp]
     L.mdvt_normal_infill.restype = C.c_int

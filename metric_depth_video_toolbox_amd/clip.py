@@ -327,19 +327,36 @@ class VideoFrames:
             r.close()
 
 
+VIDEO_ENCODERS = ("host", "device")
+
+
 class VideoSink:
     """An output video being written: render_clip's store threads hand it frame sub-ranges in any order (write_from), each
     thread encodes its frames itself (one FFV1 packet per frame, slices on one thread: the parallelism is across frames) and
-    the packets are appended in frame order.  Grey frames (the hole mask) are written as R = G = B."""
+    the packets are appended in frame order.  Grey frames (the hole mask) are written as R = G = B.
+    encoder="device": render_clip enqueues the encode of each batch on the device right after the frames are made (enqueue:
+    mdvt_encode_video_frames, the same bytes) and its store stage appends the packets (append_packets); only the packet bytes
+    leave the device.  write_from stays available in both modes (host encode)."""
 
-    def __init__(self, path: str, width: int, height: int, fps: float, grey: bool = False, slices=(4, 4), bgr: bool = False):
+    def __init__(self, path: str, width: int, height: int, fps: float, grey: bool = False, slices=(4, 4), bgr: bool = False,
+                 encoder: str = "host"):
         import threading
         from . import video_io
-        self._vio, self.bgr = video_io, bgr
+        if encoder not in VIDEO_ENCODERS:
+            raise ValueError(f"encoder must be one of {VIDEO_ENCODERS}, got {encoder!r}")
+        self._vio, self.bgr, self.device = video_io, bgr, encoder == "device"
         self.slices = (min(slices[0], width), min(slices[1], height))
         self._w = video_io.VideoWriter(path, width, height, fps, slices=self.slices)
         self.path, self.grey, self.shape_hw = path, grey, (height, width)
         self._pending, self._next, self._lock = {}, 0, threading.Lock()
+        self.host_frames = 0             # device mode: frames the device flagged, re-encoded on the host (reported by close)
+
+    def _append(self, t: int, pkt: bytes):
+        with self._lock:
+            self._pending[t] = pkt
+            while self._next in self._pending:
+                self._w.write_packet(self._pending.pop(self._next))
+                self._next += 1
 
     def write_from(self, src: np.ndarray, a: int, n: int):
         for i in range(n):
@@ -347,11 +364,21 @@ class VideoSink:
             if self.grey:
                 f = np.repeat(f[..., None], 3, axis=-1)
             pkt, _ = self._vio.encode_frame(f, slices=self.slices, threads=1, bgr=self.bgr)
+            self._append(a + i, pkt)
+
+    def enqueue(self, ctx, frames):
+        """Enqueues the device encode of frames ([n, H, W, 3] or grey [n, H, W] on the current stream) -> ffv1_device.PendingPackets."""
+        from . import ffv1_device
+        return ffv1_device.enqueue(ctx, frames, slices=self.slices, bgr=self.bgr)
+
+    def append_packets(self, pending, a: int):
+        """The packets of an enqueue()d batch (its stream work done), as frames a, a + 1, ...  Frames the device flagged are
+        encoded on the host."""
+        for i, pkt in enumerate(pending.collect()):
+            self._append(a + i, pkt)
+        if pending.host_frames:
             with self._lock:
-                self._pending[a + i] = pkt
-                while self._next in self._pending:
-                    self._w.write_packet(self._pending.pop(self._next))
-                    self._next += 1
+                self.host_frames += pending.host_frames
 
     def close(self) -> int:
         with self._lock:
@@ -360,6 +387,10 @@ class VideoSink:
                 self._pending.clear()
                 self._w.close()
                 raise RuntimeError(f"{self.path}: frame {missing} was never written")
+            if self.host_frames:
+                import warnings
+                warnings.warn(f"{self.path}: {self.host_frames} frame(s) had a slice past its device capacity and were encoded on "
+                              "the host (same bytes)")
             return self._w.close()
 
 
@@ -453,6 +484,14 @@ def render_clip(depth_frames, color_frames, out_sbs, out_mask, clip: D.ClipParam
         edges = [(n * k) // parts for k in range(parts + 1)]
         return [io_pool.submit(fn, host[edges[k]:edges[k + 1]], a + edges[k], edges[k + 1] - edges[k]) for k in range(parts)]
 
+    # outputs encoded on the device (VideoSink(encoder="device")): their raw frames stay there, only packets come back
+    dev_enc = {k: v for k, v in (("sbs", out_sbs), ("mask", out_mask), ("zrgb", out_depth_rgb), ("infill", out_infill),
+                                 ("infilled", out_infilled)) if isinstance(v, VideoSink) and v.device}
+    enc_ctx = None
+    if dev_enc:
+        from ._lib import Context
+        enc_ctx = Context(r.device, 16, 16)        # (its own workspace; the render size does not matter to the encoder)
+
     f_depth, f_color = _RawFrames(depth_frames, False), _RawFrames(color_frames, False)
     f_sbs, f_mask = _RawFrames(out_sbs, True), _RawFrames(out_mask, True)
     f_zrgb = _RawFrames(out_depth_rgb, True) if out_depth_rgb is not None else None
@@ -482,21 +521,26 @@ def render_clip(depth_frames, color_frames, out_sbs, out_mask, clip: D.ClipParam
         st["out_done"].synchronize()
         t_s1 = time.perf_counter()
         o = a - out_base
-        jobs = fan(f_sbs.write_from, st["h_sbs"][:n].numpy(), o, n, 6) + fan(f_mask.write_from, st["h_mask"][:n].numpy(), o, n, 1)
+        jobs = [io_pool.submit(dev_enc[k].append_packets, p, o) for k, p in st["enc"].items()]
+        if "sbs" not in st["enc"]:
+            jobs += fan(f_sbs.write_from, st["h_sbs"][:n].numpy(), o, n, 6)
+        if "mask" not in st["enc"]:
+            jobs += fan(f_mask.write_from, st["h_mask"][:n].numpy(), o, n, 1)
         h = int(st["h_counts"][:n].sum())           # hole pixels, counted on the device (mdvt_io.hole_counts)
         if st.get("check_rem") and inpaint_order == "heap":
             if bool((st["h_rem"][:, :n] == -1).any()):          # 0xFFFFFFFF: the march hit a loop bound
                 raise RuntimeError(f"heap-order infill-mask completion failed on frames {a}..{a + n - 1}")
         elif st.get("check_rem") and int(st["h_rem"][:, :n].sum()) != 0:
             redo.append((a, n))                     # a hole deeper than the default 256 levels: finished again below
-        if want_zrgb:
+        if want_zrgb and "zrgb" not in st["enc"]:
             jobs += fan(f_zrgb.write_from, st["h_zrgb"][:n].numpy(), o, n, 3)
-        if want_infill:
+        if want_infill and "infill" not in st["enc"]:
             jobs += fan(f_infill.write_from, st["h_seed"][:n].numpy(), o, n, 3)
-        if want_infilled:
+        if want_infilled and "infilled" not in st["enc"]:
             jobs += fan(f_infilled.write_from, st["h_infilled"][:n].numpy(), o, n, 3)
         for j in jobs:
             j.result()
+        st["enc"] = {}
         store_done.append(time.perf_counter())
         if trace is not None:
             trace.append(("store", a, t_s - t0, t_s1 - t_s, time.perf_counter() - t_s1))
@@ -563,21 +607,28 @@ def render_clip(depth_frames, color_frames, out_sbs, out_mask, clip: D.ClipParam
         s_cmp.wait_event(st["in_done"])
         s_cmp.wait_event(st["out_done"])            # device outputs free again
         res, main = device_stage(st, a, n, telea_rounds, True)
+        # the device encodes, on the compute stream right behind the frames they read (store() waits for out_done, behind them)
+        made = {"sbs": main, "mask": st["d_mask"][:n], "zrgb": st["d_zrgb"][:n] if want_zrgb else None,
+                "infill": st["d_infill"][:n] if (want_infill and res is not None) else None,
+                "infilled": st["d_infilled"][:n] if want_infilled else None}
+        st["enc"] = {k: sink.enqueue(enc_ctx, made[k]) for k, sink in dev_enc.items() if made[k] is not None}
         st["render_done"].record(s_cmp)
         with torch.cuda.stream(s_out):
             s_out.wait_event(st["render_done"])
-            st["h_sbs"][:n].copy_(main, non_blocking=True)
-            st["h_mask"][:n].copy_(st["d_mask"][:n], non_blocking=True)
+            if "sbs" not in st["enc"]:
+                st["h_sbs"][:n].copy_(main, non_blocking=True)
+            if "mask" not in st["enc"]:
+                st["h_mask"][:n].copy_(st["d_mask"][:n], non_blocking=True)
             if res is not None:
                 st["h_counts"][:n].copy_(res["hole_counts"], non_blocking=True)
                 res["hole_counts"].record_stream(s_out)
             else:
                 st["h_counts"][:n].zero_()
-            if want_zrgb:
+            if want_zrgb and "zrgb" not in st["enc"]:
                 st["h_zrgb"][:n].copy_(st["d_zrgb"][:n], non_blocking=True)
-            if want_infill and res is not None:
+            if want_infill and res is not None and "infill" not in st["enc"]:
                 st["h_seed"][:n].copy_(st["d_infill"][:n], non_blocking=True)
-            if want_infilled:
+            if want_infilled and "infilled" not in st["enc"]:
                 st["h_infilled"][:n].copy_(st["d_infilled"][:n], non_blocking=True)
             st["check_rem"] = st.get("d_rem") is not None
             if st["check_rem"]:
@@ -620,6 +671,8 @@ def render_clip(depth_frames, color_frames, out_sbs, out_mask, clip: D.ClipParam
     for f in (f_depth, f_color, f_sbs, f_mask, f_zrgb, f_infill, f_infilled):
         if f is not None:
             f.close()
+    if enc_ctx is not None:
+        enc_ctx.close()
     r.close()
     return hi - lo, dt, holes
 
@@ -837,16 +890,28 @@ def pin_to_gpu_numa_node(device_index: int) -> Optional[int]:
         return None
 
 
+def check_video_encoder(video_encoder: str, video: bool):
+    """ValueError unless video_encoder is "host" or "device", and "device" only where the outputs are .mkv files."""
+    if video_encoder not in VIDEO_ENCODERS:
+        raise ValueError(f"video_encoder must be one of {VIDEO_ENCODERS}, got {video_encoder!r}")
+    if video_encoder == "device" and not video:
+        raise ValueError("--video_encoder device encodes .mkv outputs: with a .npy depth input the outputs are raw .npy dumps, "
+                         "which are not encoded (use the default --video_encoder host)")
+
+
 def run(depth_path: str, color_path: Optional[str], *, batch: int = 16, create_sbs_depth_video: bool = False,
         max_frames: int = -1, green_and_black_infill_mask: bool = False, backend: Optional[str] = None,
-        normal_infill: bool = False, inpaint_order: str = "levels", multisample: Optional[dict] = None, **clip_kwargs):
+        normal_infill: bool = False, inpaint_order: str = "levels", multisample: Optional[dict] = None, video_encoder: str = "host",
+        **clip_kwargs):
     """File-level entry (what `python stereo_rerender.py --depth_video ...` is to the reference).
     Multi-process aware: under torchrun every rank renders its own contiguous frame range into its own output segment
     files (plan_outputs); rank 0 adds the index.  `backend`: torch.distributed backend (default: RCCL when a GPU is
-    visible; MDVT_DIST_BACKEND overrides -- the two-ranks-on-one-GPU tests use gloo)."""
+    visible; MDVT_DIST_BACKEND overrides -- the two-ranks-on-one-GPU tests use gloo).  video_encoder: "host" (default) or
+    "device" (the .mkv outputs are FFV1-encoded on the GPU: the same bytes; refused for .npy outputs, which are not encoded)."""
     from . import video_io
-    rank, world = D.init_process_group(backend or os.environ.get("MDVT_DIST_BACKEND"))
     video = video_io.is_matroska(depth_path)                 # the reference's own format (sr:326-341): outputs follow it
+    check_video_encoder(video_encoder, video)
+    rank, world = D.init_process_group(backend or os.environ.get("MDVT_DIST_BACKEND"))
     depth = VideoFrames(depth_path) if video else np.load(depth_path, mmap_mode="r")
     if color_path is None:
         color = depth                                                                                  # sr:508-509
@@ -880,7 +945,7 @@ def run(depth_path: str, color_path: Optional[str], *, batch: int = 16, create_s
         if video:                                   # cv2.VideoWriter(tmp, 'FFV1', frame_rate, out_size) (sr:435-444)
             shp = pl["frame_shape"]
             # (the depth-code frames are B, G, R arrays -- what sr:930-939 hands cv2 --, everything else is RGB)
-            outs[k] = VideoSink(t, shp[1], shp[0], depth.fps or 30.0, grey=len(shp) == 2, bgr=k == "depth")
+            outs[k] = VideoSink(t, shp[1], shp[0], depth.fps or 30.0, grey=len(shp) == 2, bgr=k == "depth", encoder=video_encoder)
         elif hi > lo:
             outs[k] = np.lib.format.open_memmap(t, mode="w+", dtype=np.uint8, shape=(hi - lo,) + pl["frame_shape"])
         else:                                   # more ranks than frames: an empty segment (cannot be mapped)

@@ -84,6 +84,9 @@ struct mdvt_ctx {
     int heap_images = 0;
     uint8_t* heap_ws = nullptr;
     uint32_t* heap_remaining = nullptr;
+    // FFV1 encoding (mdvt_encode_video_frames): the running packet offset (8 B), then per slice of a pass its size word and scratch
+    uint8_t* ffv1_ws = nullptr;
+    size_t ffv1_bytes = 0;
     // normal_infill / infill_using_mask_normals: about 16 B/px per image in flight
     uint8_t* ni_ws = nullptr;
     int ni_images = 0;
@@ -775,6 +778,7 @@ int mdvt_destroy(mdvt_ctx* c)
     free_telea(c);
     free_telea_heap(c);
     if (c->ni_ws) ws_free(c, c->ni_ws);
+    if (c->ffv1_ws) ws_free(c, c->ffv1_ws);
     delete c;
     return MDVT_OK;
 }
@@ -1719,6 +1723,71 @@ int mdvt_finish_infill_mask_stereo(mdvt_ctx* c, const uint8_t* d_left_seed, cons
     if (c && (!d_right_seed || !d_right_out)) return fail(c, MDVT_ERR_INVALID_ARG, "NULL buffer");
     return finish_infill_mask(c, d_left_seed, d_right_seed, seed_pitch, seed_stride, d_left_out, d_right_out, out_pitch, out_stride,
                               n_frames, max_rounds, d_remaining, stream);
+}
+
+// FFV1 packets of device frames (mdvt_ffv1.hip).  Passes: as many frames as the ctx's workspace budget affords, at least one.
+int mdvt_encode_video_frames(mdvt_ctx* c, int width, int height, int slices_h, int slices_v, const uint8_t* d_src, size_t pitch,
+                            size_t frame_stride, int channels, int order, int n_frames, uint64_t slice_capacity, uint8_t* d_packets,
+                            uint64_t packets_cap, uint64_t* d_offsets, uint32_t* d_sizes, void* stream)
+{
+    if (!c) return MDVT_ERR_INVALID_ARG;
+    if (!d_src || !d_packets || !d_offsets || !d_sizes) return fail(c, MDVT_ERR_INVALID_ARG, "NULL buffer");
+    if (width < 1 || height < 1) return fail(c, MDVT_ERR_INVALID_ARG, "bad frame size %d x %d", width, height);
+    if (slices_h < 1 || slices_v < 1 || slices_h > width || slices_v > height || slices_h * slices_v > 1024)
+        return fail(c, MDVT_ERR_INVALID_ARG, "bad slice counts %d x %d for %d x %d (each >= 1 and <= the frame's size, product <= 1024)",
+                    slices_h, slices_v, width, height);
+    if (channels != 1 && channels != 3) return fail(c, MDVT_ERR_INVALID_ARG, "channels must be 1 or 3, got %d", channels);
+    if (order != 0 && order != 1) return fail(c, MDVT_ERR_INVALID_ARG, "order must be 0 (RGB) or 1 (BGR), got %d", order);
+    if (n_frames < 1) return fail(c, MDVT_ERR_INVALID_ARG, "n_frames must be >= 1");
+    if (pitch < (size_t)width * (size_t)channels) return fail(c, MDVT_ERR_INVALID_ARG, "pitch smaller than one row");
+    if (n_frames > 1 && frame_stride < pitch * (size_t)height) return fail(c, MDVT_ERR_INVALID_ARG, "frame_stride smaller than one frame");
+    if ((uint64_t)width * (uint64_t)height > ((uint64_t)1 << 28))      // (a slice's sample count is a 32-bit word)
+        return fail(c, MDVT_ERR_UNSUPPORTED, "frame too large for the device FFV1 encoder (%d x %d)", width, height);
+    DeviceGuard g(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    const int spf = slices_h * slices_v;
+    // the largest slice: widths and heights of the slices differ by at most one
+    const uint64_t max_raw = (uint64_t)((width + slices_h - 1) / slices_h) * (uint64_t)((height + slices_v - 1) / slices_v) * 3u;
+    const uint64_t limit = ((uint64_t)1 << 24) - 1;                    // the 24-bit slice size
+    const uint64_t want_cap = slice_capacity ? slice_capacity : 2 * max_raw + 4096;
+    const uint32_t cap = (uint32_t)(want_cap < limit ? want_cap : limit);
+    const size_t slice_stride = ((size_t)cap + 15) & ~(size_t)15;
+    const size_t per_frame = (size_t)spf * (slice_stride + sizeof(uint32_t)) + 256;
+    const size_t budget = (size_t)(c->cfg.workspace_mib ? c->cfg.workspace_mib : 4096u) << 20;
+    int fchunk = (int)(budget / per_frame > (size_t)n_frames ? (size_t)n_frames : budget / per_frame);
+    if (fchunk < 1) fchunk = 1;
+    const size_t head = 256;                                           // the running offset, alone on its line
+    const size_t words = ((size_t)fchunk * spf * sizeof(uint32_t) + 255) & ~(size_t)255;
+    const size_t need = head + words + (size_t)fchunk * spf * slice_stride;
+    if (c->ffv1_bytes < need) {
+        MDVT_HIP(c, hipDeviceSynchronize());                 // earlier submissions may still use the old workspace
+        if (c->ffv1_ws) ws_free(c, c->ffv1_ws);
+        c->ffv1_ws = nullptr; c->ffv1_bytes = 0;
+        MDVT_HIP(c, ws_malloc(c, (void**)&c->ffv1_ws, need, s));
+        c->ffv1_bytes = need;
+    }
+    unsigned long long* used = reinterpret_cast<unsigned long long*>(c->ffv1_ws);
+    uint32_t* slice_n = reinterpret_cast<uint32_t*>(c->ffv1_ws + head);
+    uint8_t* scratch = c->ffv1_ws + head + words;
+    MDVT_HIP(c, hipMemsetAsync(used, 0, sizeof(unsigned long long), s));
+    static const mdvt::Ffv1StateTables tab = mdvt::ffv1_default_states();
+    mdvt::Ffv1CodeArgs ca{};
+    ca.pitch = pitch; ca.frame_stride = frame_stride; ca.channels = channels;
+    ca.ri = channels == 1 ? 0 : (order == 1 ? 2 : 0); ca.gi = channels == 1 ? 0 : 1; ca.bi = channels == 1 ? 0 : (order == 1 ? 0 : 2);
+    ca.W = width; ca.H = height; ca.nh = slices_h; ca.nv = slices_v;
+    ca.scratch = scratch; ca.slice_stride = slice_stride; ca.cap = cap; ca.cap_is_24bit = cap == (uint32_t)limit; ca.slice_n = slice_n;
+    for (int f0 = 0; f0 < n_frames; f0 += fchunk) {
+        const int nf = n_frames - f0 < fchunk ? n_frames - f0 : fchunk;
+        ca.src = d_src + (size_t)f0 * frame_stride;
+        MDVT_HIP(c, mdvt::launch_ffv1_code(ca, tab, nf * spf, s));
+        const mdvt::Ffv1LayoutArgs la{slice_n, spf, nf, d_sizes + f0, reinterpret_cast<unsigned long long*>(d_offsets) + f0, used,
+                                      (unsigned long long)packets_cap};
+        MDVT_HIP(c, mdvt::launch_ffv1_layout(la, s));
+        const mdvt::Ffv1EmitArgs ea{slice_n, scratch, slice_stride, spf, d_sizes + f0, reinterpret_cast<unsigned long long*>(d_offsets) + f0,
+                                    d_packets};
+        MDVT_HIP(c, mdvt::launch_ffv1_emit(ea, nf * spf, s));
+    }
+    return MDVT_OK;
 }
 
 }  // extern "C"

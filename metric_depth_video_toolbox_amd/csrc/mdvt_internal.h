@@ -222,6 +222,33 @@ hipError_t launch_normal_infill(const ImageSet& img, const ImageSet& mask, const
                                 const BlurKernel& K, hipStream_t s);
 hipError_t launch_infill_mask_normals(const ImageSet& img, const ImageSet& hole, const ImageSet& mask, uint8_t* workspace, int n, int W, int H,
                                       int max_steps, hipStream_t s);
+// mdvt_ffv1.hip: FFV1 encoding of device frames (mdvt_encode_video_frames).  A slice's size word holds its payload bytes or one of
+// the flags below; a frame's size word the packet bytes or the flag of its first flagged slice.
+constexpr uint32_t kSliceTooLarge = 0xFFFFFFFEu;     // the payload does not fit the 24-bit slice size
+constexpr uint32_t kSliceOverflow = 0xFFFFFFFFu;     // the payload passes the slice's capacity, or the packet the caller's buffer
+struct Ffv1StateTables { uint8_t zero[256], one[256]; };
+struct Ffv1CodeArgs {
+    const uint8_t* src; size_t pitch, frame_stride;
+    int channels, ri, gi, bi;                        // bytes per pixel and the byte of R, G, B in a pixel (grey: all 0)
+    int W, H, nh, nv;
+    uint8_t* scratch; size_t slice_stride;           // per slice of the pass: slice_stride bytes of scratch
+    uint32_t cap;                                    // payload bytes a slice may take (at most 2^24 - 1)
+    int cap_is_24bit;                                // cap is the 24-bit limit: passing it is kSliceTooLarge
+    uint32_t* slice_n;                               // [slices of the pass]
+};
+struct Ffv1LayoutArgs {
+    const uint32_t* slice_n; int spf, n_frames;
+    uint32_t* sizes; unsigned long long* offsets;    // the caller's arrays, at the pass's first frame
+    unsigned long long* used; unsigned long long packets_cap;
+};
+struct Ffv1EmitArgs {
+    const uint32_t* slice_n; const uint8_t* scratch; size_t slice_stride; int spf;
+    const uint32_t* sizes; const unsigned long long* offsets; uint8_t* packets;
+};
+Ffv1StateTables ffv1_default_states();
+hipError_t launch_ffv1_code(const Ffv1CodeArgs& a, const Ffv1StateTables& tab, int n_slices, hipStream_t s);
+hipError_t launch_ffv1_layout(const Ffv1LayoutArgs& a, hipStream_t s);
+hipError_t launch_ffv1_emit(const Ffv1EmitArgs& a, int n_slices, hipStream_t s);
 hipError_t launch_selftest(int which, unsigned long long seed, unsigned long long* d_mism, hipStream_t s);
 hipError_t launch_coherence_test(uint32_t* blk, size_t dwords, uint32_t tag, uint32_t* d_xcc, uint32_t* d_out, hipStream_t s);     // (mdvt_selftest.hip; r05 diagnosis)
 

@@ -694,6 +694,9 @@ def build_arg_parser():
                     help="not a reference flag: with --multisample 4, the sample positions and the resolve -- 'standard' (default): "
                          "the Direct3D / Vulkan positions and the rounded mean; 'swiftshader': the conformant GL's positions and "
                          "its pairwise-average resolve")
+    ap.add_argument("--video_encoder", choices=("host", "device"), default="host",
+                    help="not a reference flag: where the .mkv outputs are FFV1-encoded -- 'host' (default) or 'device' (on the GPU, "
+                         "the same bytes; only the compressed packets are copied to the host). Not with .npy input and outputs")
     for flag in ("--compressed", "--mask_video", "--save_background", "--load_background"):
         ap.add_argument(flag, nargs="?", const=True, default=None, help="reference flag outside the built hot path")
     return ap
@@ -716,6 +719,8 @@ def main(argv=None):
         raise FileNotFoundError(f"Depth video not found: {args.depth_video}")                  # sr:326
     if args.color_video and not os.path.isfile(args.color_video):
         raise FileNotFoundError(f"Color video not found: {args.color_video}")                  # sr:331
+    from . import video_io
+    clip.check_video_encoder(args.video_encoder, video_io.is_matroska(args.depth_video))
     stats, final = clip.run(args.depth_video, args.color_video, batch=args.batch,
                             create_sbs_depth_video=args.create_sbs_depth_video, max_frames=args.max_frames,
                             green_and_black_infill_mask=args.green_and_black_infill_mask,
@@ -730,6 +735,7 @@ def main(argv=None):
                             vr180=args.vr180, touchly0=args.touchly0, touchly1=args.touchly1,
                             do_basic_infill=args.do_basic_infill, normal_infill=args.normal_infill, inpaint_order=args.inpaint_order,
                             multisample=multisample_kwargs(args),
+                            video_encoder=args.video_encoder,
                             touchly_max_depth=args.touchly_max_depth, touchly_min_depth=args.touchly_min_depth)
     if int(os.environ.get("RANK", "0")) == 0:
         frames, secs = float(stats[:, 0].sum()), float(stats[:, 1].max())

@@ -1,0 +1,72 @@
+"""The CLI from .mkv to .mkv with each --video_encoder: the product default (mesh, --infill_mask, convergence) on a synthetic 1080p
+clip, frames/s including all host I/O, and a byte comparison of every output file of the two runs.
+
+    python tools/clip_mkv_encoders.py [--frames 300] [--width 1920] [--height 1080] [--batch 16] [--dir DIR] [--json out.json]"""
+import argparse
+import json
+import os
+import shutil
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=300)
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--dir", default=None)
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args(argv)
+    from metric_depth_video_toolbox_amd import stereo_rerender as sr, video_io
+    from metric_depth_video_toolbox_amd.synthetic import SyntheticScene
+    root = a.dir or tempfile.mkdtemp(prefix="clip_mkv_")
+    W, H, N = a.width, a.height, a.frames
+    dp, cp = os.path.join(root, "in_depth.mkv"), os.path.join(root, "in.mkv")
+    sc = SyntheticScene(W, H, config_id=3, n_fg=6)
+    with video_io.VideoWriter(dp, W, H, 30.0, bgr=True) as wd, video_io.VideoWriter(cp, W, H, 30.0, bgr=True) as wc:
+        for t in range(N):
+            d, c = sc.frame(t)
+            wd.write(np.ascontiguousarray(d[..., ::-1]))
+            wc.write(np.ascontiguousarray(c[..., ::-1]))
+    conv = os.path.join(root, "conv.json")
+    with open(conv, "w") as f:
+        json.dump([2.5 + 0.01 * (k % 50) for k in range(N)], f)
+    res, files = {}, {}
+    for enc in ("host", "device"):
+        d = os.path.join(root, enc)
+        os.makedirs(d, exist_ok=True)
+        for src in (dp, cp):
+            dst = os.path.join(d, os.path.basename(src))
+            if not os.path.exists(dst):
+                os.link(src, dst) if os.stat(src).st_dev == os.stat(d).st_dev else shutil.copy(src, dst)
+        t0 = time.perf_counter()
+        sr.main(["--depth_video", os.path.join(d, "in_depth.mkv"), "--color_video", os.path.join(d, "in.mkv"), "--xfov", "50",
+                 "--pupillary_distance", "65", "--infill_mask", "--convergence_file", conv, "--batch", str(a.batch),
+                 "--video_encoder", enc])
+        dt = time.perf_counter() - t0
+        outs = sorted(f for f in os.listdir(d) if f.startswith("in_depth.mkv_"))
+        files[enc] = {f: os.path.getsize(os.path.join(d, f)) for f in outs}
+        res[enc] = dict(seconds=dt, fps=N / dt, outputs=files[enc])
+        print(f"{enc:>6}: {N} frames in {dt:.2f} s = {N / dt:.1f} frames/s (whole CLI call, incl. start-up), outputs {files[enc]}",
+              flush=True)
+    same = all(open(os.path.join(root, "host", f), "rb").read() == open(os.path.join(root, "device", f), "rb").read()
+               for f in files["host"]) and files["host"].keys() == files["device"].keys()
+    res["identical"] = bool(same)
+    print("outputs byte-identical:", same)
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(res, f, indent=1)
+    if not a.dir:
+        shutil.rmtree(root)
+    return 0 if same else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -1,0 +1,90 @@
+"""Frames per second of the device FFV1 encoder (ffv1_device.encode_frames_on_device: kernels + packet read-back) against the host
+encoder (video_io.encode_frame, 16 threads across frames, one slice thread each: what clip.VideoSink does).
+
+    python tools/ffv1_bench.py [--sizes 1920x1080,3840x1080] [--contents depth,synthetic,noise] [--slices 4x4,8x8]
+                               [--frames 16,64,128] [--host-threads 16] [--json out.json]
+
+Every device packet is compared with the host's bytes before it is timed, and the run stops if the device flagged any frame
+(a flagged frame is re-encoded on the host: its time would not be the device's).  Prints one line per case and, with --json,
+writes the table."""
+import argparse
+import json
+import os
+import sys
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def frames_of(kind, W, H, n, rng):
+    from metric_depth_video_toolbox_amd.synthetic import SyntheticScene
+    if kind == "noise":
+        return rng.integers(0, 256, (n, H, W, 3), dtype=np.uint8)
+    sc = SyntheticScene(W, H, config_id=1, n_fg=6)
+    out = np.empty((n, H, W, 3), np.uint8)
+    for t in range(n):
+        d, c = sc.frame(t)
+        out[t] = d if kind == "depth" else c
+    return out
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", default="1920x1080,3840x1080")
+    ap.add_argument("--contents", default="depth,synthetic,noise")
+    ap.add_argument("--slices", default="4x4,8x8")
+    ap.add_argument("--frames", default="16,64,128")
+    ap.add_argument("--host-threads", type=int, default=16)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args(argv)
+    import torch
+    from metric_depth_video_toolbox_amd import ffv1_device, video_io
+    rng = np.random.default_rng(1)
+    pool = ThreadPoolExecutor(a.host_threads)
+
+    def device(frames, slices):
+        p = ffv1_device.enqueue(ffv1_device._context(0), frames, slices=slices)
+        pkts = p.collect()
+        if p.host_frames:
+            raise SystemExit(f"{p.host_frames} of {len(pkts)} frames were flagged by the device and re-encoded on the host "
+                             f"({tuple(frames.shape)}, slices {slices}): not a device timing")
+        return pkts
+    rows = []
+    nmax = max(int(v) for v in a.frames.split(","))
+    for size in a.sizes.split(","):
+        W, H = (int(v) for v in size.split("x"))
+        for kind in a.contents.split(","):
+            host_frames = frames_of(kind, W, H, nmax, rng)
+            dev_frames = torch.from_numpy(host_frames).cuda()
+            for sl in a.slices.split(","):
+                slices = tuple(int(v) for v in sl.split("x"))
+                for n in (int(v) for v in a.frames.split(",")):
+                    want = list(pool.map(lambda f: video_io.encode_frame(f, slices=slices, threads=1)[0], host_frames[:n]))
+                    got = device(dev_frames[:n], slices)
+                    assert got == want, (size, kind, sl, n)
+                    dt_dev, dt_host = [], []
+                    for _ in range(a.reps):
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        device(dev_frames[:n], slices)
+                        dt_dev.append(time.perf_counter() - t0)
+                        t0 = time.perf_counter()
+                        list(pool.map(lambda f: video_io.encode_frame(f, slices=slices, threads=1)[0], host_frames[:n]))
+                        dt_host.append(time.perf_counter() - t0)
+                    r = dict(size=size, content=kind, slices=sl, frames=n, device_fps=n / min(dt_dev), host_fps=n / min(dt_host),
+                             bytes_per_frame=sum(len(p) for p in got) / n)
+                    r["speedup"] = r["device_fps"] / r["host_fps"]
+                    rows.append(r)
+                    print(f"{size:>9} {kind:>9} {sl:>3} n={n:<3} device {r['device_fps']:8.1f} fps  host({a.host_threads}t) "
+                          f"{r['host_fps']:8.1f} fps  x{r['speedup']:.2f}  {r['bytes_per_frame'] / 1e6:.2f} MB/frame", flush=True)
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(rows, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
