@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- stereo frames/s of the MI355X stereo-rerender path + achieved HBM GB/s vs roofline.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -9,9 +9,13 @@ A "step" is one pass of the hot path over one batch of --frames synthetic 1920x1
 (BASELINE.json configs[1]'s shape; 128 frames = 3.7 GB of inputs + outputs, far past the 256 MiB
 Infinity Cache), already resident in HBM when the timed region starts.  Weak scaling: every rank
 renders its own batch; `value` = frames all ranks rendered / max-over-ranks wall time.  Rank 0 prints
-ONE JSON line; its "extra" object carries the other draw modes (mesh = the reference's default,
-mesh + --infill_mask + convergence = movie_2_3D.py's default), the batch-size sweep and the
-300-frame clip of BASELINE configs[2] (strong scaling: the clip's frames are split over the ranks).
+ONE JSON line.
+
+A plain run does only what that headline needs: set-up, warm-up, the K timed steps, --dump-outputs, the line.  `--full`
+adds everything else the bench measures, after the timed steps: the line's "extra" object (the other draw modes -- mesh
+= the reference's default, mesh + --infill_mask + convergence = movie_2_3D.py's default --, the batch-size sweep, the
+300-frame clip of BASELINE configs[2] with strong scaling: the clip's frames are split over the ranks, and the 4K /
+model-hop configs) and "cpu_baseline" (the C oracle on the host cores).  Without it they are {} and null.
 
 `--dump-outputs DIR` writes what the last timed step computed to DIR/<name>.npy after the timed region
 (float32 / float64, under 64 MB: whole arrays when small, else exact per-frame sums and a seeded pixel
@@ -46,14 +50,17 @@ def parse_args():
                     help="untimed spin of the same step before the W warm-up steps: the GPU leaves its idle "
                          "power state over tens of ms (measured: the first ~100 launches after idle run ~15%% slower)")
     ap.add_argument("--frames", type=int, default=128, help="frames per step (per rank)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra measurements (other modes, sweep, clip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also take the extra measurements (other modes, sweep, clips, 4K, model hop) "
+                         "and the CPU baseline; a plain run only measures the headline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extra measurements (other modes, sweep, clip)")
     ap.add_argument("--clip-frames", type=int, default=300, help="frames of the strong-scaling clip (BASELINE configs[2])")
     ap.add_argument("--clip-repeats", type=int, default=40, help="back-to-back passes over the clip per timing in extra.clip_c3_long")
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--mode", choices=["points", "mesh"], default="points")
     ap.add_argument("--remove-edges", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU-baseline sample budget")
     ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
                     help="after the timed steps, write what the last step computed (side-by-side RGB + hole mask) as DIR/<name>.npy")
@@ -414,7 +421,7 @@ def main():
         dump_outputs(args.dump_outputs, sbs, mask, torch, prefix=f"rank{rank}_" if world > 1 else "")
 
     extra = {}
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         extra = extra_measurements(args, r, sc, depth_rgb, color_rgb, sbs, mask, rank, world, dev, torch, D, barrier)
 
     if rank == 0:
@@ -449,7 +456,7 @@ def main():
                          "algorithmic_bytes_per_launch": bytes_per_launch, "launch_ms": launch_ms},
             "extra": extra,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(W, H, args.mode, args.remove_edges, args.cpu_seconds)
             # BASELINE.md section 3's other CPU figures, same port, same cores, shorter samples: C1 (640x480, the reference's own
             # CPU-runnable case) in both draw modes, and 1080p in the reference's default draw mode (mesh)

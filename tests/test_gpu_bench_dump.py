@@ -41,3 +41,21 @@ def test_dumped_outputs_are_the_timed_path_outputs(tmp_path):
     assert np.array_equal(mask, got["mask"].cpu().numpy().astype(np.float32))
     assert (mask > 0).any()
     r.close()
+
+
+def test_plain_line_is_the_headline_only():
+    """Without --full the run ends after the timed steps: the line has the headline and its roofline, no extras and no CPU
+    baseline (what --full adds is checked by tests/test_gpu_distributed.py)."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--frames", "4", "--width", "256", "--height", "144", "--prewarm-ms", "0"],
+                       env=env, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stdout + p.stderr
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["n_gpus"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["unit"] == "stereo frames/s" and line["higher_is_better"] is True and line["roofline"]["bound"] == "hbm"
+    assert line["extra"] == {} and line["cpu_baseline"] is None

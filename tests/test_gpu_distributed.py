@@ -79,7 +79,7 @@ def test_bench_line_under_torchrun_with_one_rank():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                         "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                        "--frames", "4", "--no-cpu-baseline", "--prewarm-ms", "0", "--clip-frames", "12"],
+                        "--frames", "4", "--full", "--no-cpu-baseline", "--prewarm-ms", "0", "--clip-frames", "12"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout + p.stderr
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
@@ -103,7 +103,7 @@ def test_bench_line_with_two_ranks_sharing_the_gpu():
     env.update(MDVT_DIST_BACKEND="gloo", MDVT_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--frames", "8", "--prewarm-ms", "0", "--clip-frames", "30", "--clip-repeats", "3"],
+                        "--frames", "8", "--full", "--prewarm-ms", "0", "--clip-frames", "30", "--clip-repeats", "3"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout + p.stderr
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -156,7 +156,7 @@ def test_bench_line_with_eight_ranks_sharing_the_gpu():
     env.update(MDVT_DIST_BACKEND="gloo", MDVT_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
                         "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1",
-                        "--frames", "4", "--prewarm-ms", "0", "--clip-frames", "40", "--clip-repeats", "2", "--no-cpu-baseline"],
+                        "--frames", "4", "--full", "--prewarm-ms", "0", "--clip-frames", "40", "--clip-repeats", "2", "--no-cpu-baseline"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout + p.stderr
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
