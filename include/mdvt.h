@@ -98,6 +98,23 @@ typedef struct mdvt_config {
     uint8_t sample_resolve;
 } mdvt_config;
 
+/* Near-plane clipping (set per context with mdvt_set_near_clip, not in mdvt_config: the struct and the ABI version stay as they are).
+ * The reference's GL has its near plane at z = 1e-4 (set_constant_z_near(0.0001), dmt:1520) and CLIPS a triangle that crosses it;
+ * the decree drops such a triangle whole.  near_clip = 0 (the default) keeps the decree; 1 clips as a GL
+ * does, in the mesh mode, with samples 0 / 1 and with samples = 4 -- held bit for bit to the oracle's candidate
+ * orc_render_stereo_gl(near_clip = 1): a triangle some but not all of whose vertices are behind the plane (the vertex programme's
+ * test: zsrc > near, and Z' > near on general frames) becomes a polygon whose new vertices are interpolated in f64 in eye space
+ * (colours not integers), fanned from its first vertex into one or two triangles that take the normal snap, cull, fill rule and
+ * shading and the source triangle's place in the draw order.  Single sample: the single-sample kernels render every frame as
+ * before, then a detect kernel flags the eyes where some triangle straddles the plane and only those are rendered again by the
+ * clipping kernels (a frame without depth code 0 and without a camera inside the scene costs the detect pass and nothing else).
+ * In the mesh mode the render calls answer MDVT_ERR_UNSUPPORTED for edge_points != 0, depth planes, seed images, packed mask bits
+ * and NULL byte masks (hole counts are supported), and for frames with 4 (W - 1)(H - 1) >= 2^32 - 1 (the 32-bit draw ids).  Points
+ * mode: a GL drops a point whose centre is behind the plane, as the decree does -- near_clip changes and refuses nothing there.
+ * Workspace: 16 B per pixel and frame in flight (samples 0 / 1; the key planes of both eyes) or the 4x key planes; workspace_mib
+ * bounds the frames in flight (1 ... 16).  Other values: MDVT_ERR_INVALID_ARG. */
+int mdvt_set_near_clip(mdvt_ctx* ctx, int32_t near_clip);
+
 /* Per-frame parameters: what sr:515-541, 563-566 and 707-721 compute before the render calls. */
 typedef struct mdvt_frame_params {
     double K[9];                 /* dmt.compute_camera_matrix(xfov, yfov, W, H), row major (dmt:902) */

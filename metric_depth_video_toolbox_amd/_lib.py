@@ -27,7 +27,7 @@ SYMBOLS = ("mdvt_version", "mdvt_create", "mdvt_destroy", "mdvt_last_error", "md
            "mdvt_finish_infill_mask_stereo", "mdvt_swap_rb", "mdvt_selftest", "mdvt_normal_infill", "mdvt_infill_using_mask_normals",
            "mdvt_edge_point_pixels", "mdvt_workspace_bytes", "mdvt_release_cached_memory", "mdvt_cached_memory", "mdvt_set_cached_memory_limit",
            "mdvt_debug_read", "mdvt_finish_infill_mask_heap", "mdvt_finish_infill_mask_heap_stereo",
-           "mdvt_encode_video_frames")
+           "mdvt_encode_video_frames", "mdvt_set_near_clip")
 
 
 class MdvtError(RuntimeError):
@@ -94,6 +94,8 @@ def load():
     L.mdvt_last_error.argtypes = [vp]
     L.mdvt_set_config.restype = C.c_int
     L.mdvt_set_config.argtypes = [vp, C.POINTER(MdvtConfig)]
+    L.mdvt_set_near_clip.restype = C.c_int
+    L.mdvt_set_near_clip.argtypes = [vp, C.c_int32]
     L.mdvt_selftest.restype = C.c_int
     L.mdvt_selftest.argtypes = [vp, C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]
     L.mdvt_render_stereo.restype = C.c_int

@@ -121,8 +121,10 @@ def output_shape(clip: D.ClipParameters):
     return clip.H, 2 * clip.W
 
 
-def renderer_for(clip: D.ClipParameters, device: Optional[int] = None, multisample: Optional[dict] = None) -> StereoRerenderer:
-    """The clip's renderer.  multisample: StereoRerenderer's samples / sample_pattern / sample_resolve keywords (None: off)."""
+def renderer_for(clip: D.ClipParameters, device: Optional[int] = None, multisample: Optional[dict] = None,
+                 near_clip: bool = False) -> StereoRerenderer:
+    """The clip's renderer.  multisample: StereoRerenderer's samples / sample_pattern / sample_resolve keywords (None: off);
+    near_clip: StereoRerenderer's near_clip keyword."""
     f = clip.mode_flags
     pd = clip.ipd_m * 1000
     if f & 64:
@@ -134,7 +136,7 @@ def renderer_for(clip: D.ClipParameters, device: Optional[int] = None, multisamp
                             render_as_pointcloud=bool(f & 1), remove_edges=bool(f & 2) and not bool(f & 8),
                             infill_mask=bool(f & 8), dont_place_points_in_edges=not bool(f & 4),
                             do_basic_infill=bool(f & 128) and bool(f & 2), dont_remove_edges=not bool(f & 2),
-                            **(multisample or {}))
+                            **(multisample or {}), **({"near_clip": True} if near_clip else {}))
 
 
 def frame_param_records(r: StereoRerenderer, clip: D.ClipParameters, lo: int, hi: int):
@@ -397,13 +399,14 @@ class VideoSink:
 def render_clip(depth_frames, color_frames, out_sbs, out_mask, clip: D.ClipParameters, *, lo: int = 0,
                 hi: Optional[int] = None, batch: int = 16, out_depth_rgb=None, out_infill=None, green_and_black: bool = False,
                 device: Optional[int] = None, out_base: int = 0, io_threads: int = 12, out_infilled=None, inpaint_order: str = "levels",
-                multisample: Optional[dict] = None):
+                multisample: Optional[dict] = None, near_clip: bool = False):
     """Render frames [lo, hi) of a clip.  depth_frames / color_frames / out_*: array-likes indexed
     [frame] (NumPy arrays or memmaps, uint8); frame t is written to out_*[t - out_base] (a rank that owns the output
     segment [lo, hi) passes out_base = lo).  out_infilled (optional, [frames, H, 2W, 3]): the stereo frames after
     basic_nomal_infill.normal_infill of both eyes with the finished infill mask -- movie_2_3D.py's next step, run here
     while frame and mask are still on the device instead of through two more video files.  multisample: the renderer's
-    samples / sample_pattern / sample_resolve keywords (None: single sample; stereo_rerender.multisample_kwargs).
+    samples / sample_pattern / sample_resolve keywords (None: single sample; stereo_rerender.multisample_kwargs).  near_clip: clip
+    mesh triangles at the near plane as a GL does (StereoRerenderer's keyword).
     Returns (frames, seconds, hole_pixels)."""
     import time
     import torch
@@ -411,7 +414,7 @@ def render_clip(depth_frames, color_frames, out_sbs, out_mask, clip: D.ClipParam
 
     hi = clip.n_frames if hi is None else hi
     W, H = clip.W, clip.H
-    r = renderer_for(clip, device, multisample)
+    r = renderer_for(clip, device, multisample, near_clip)
     dev = torch.device("cuda", r.device)
     recs = frame_param_records(r, clip, lo, hi)
     B = max(1, min(batch, hi - lo))
@@ -901,7 +904,8 @@ def check_video_encoder(video_encoder: str, video: bool):
 
 def run(depth_path: str, color_path: Optional[str], *, batch: int = 16, create_sbs_depth_video: bool = False,
         max_frames: int = -1, green_and_black_infill_mask: bool = False, backend: Optional[str] = None,
-        normal_infill: bool = False, inpaint_order: str = "levels", multisample: Optional[dict] = None, video_encoder: str = "host",
+        normal_infill: bool = False, inpaint_order: str = "levels", multisample: Optional[dict] = None, near_clip: bool = False,
+        video_encoder: str = "host",
         **clip_kwargs):
     """File-level entry (what `python stereo_rerender.py --depth_video ...` is to the reference).
     Multi-process aware: under torchrun every rank renders its own contiguous frame range into its own output segment
@@ -958,7 +962,8 @@ def run(depth_path: str, color_path: Optional[str], *, batch: int = 16, create_s
                                       # (the default order is not passed on: tests/test_distributed_cpu.py replaces render_clip
                                       #  with a stand-in that predates the keyword)
                                       **({} if inpaint_order == "levels" else {"inpaint_order": inpaint_order}),
-                                      **({"multisample": multisample} if multisample else {}))
+                                      **({"multisample": multisample} if multisample else {}),
+                                      **({"near_clip": True} if near_clip else {}))
     # (no msync: the dumps were written through the page cache, which every later reader shares; forcing 6 GB of dirty pages
     #  to the disk before the rename is what the reference's writers do not do either, and costs seconds on a container fs)
     if video:

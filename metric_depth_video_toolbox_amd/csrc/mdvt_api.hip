@@ -107,6 +107,13 @@ struct mdvt_ctx {
     unsigned long long* msaa_keys = nullptr;
     int msaa_frames = 0;
     bool msaa_dirty = false;          // a submission stopped between raster and resolve: the planes are not all empty
+    // near-plane clipping (mdvt_set_near_clip; mdvt_near_clip.hip).  With samples = 4 it uses msaa_keys; single-sample: the key planes
+    // of clip_frames frames in flight, [slot][eye][H*W], and one flag per slot and eye (an eye where some triangle straddles the plane)
+    int32_t near_clip = 0;
+    unsigned long long* clip_keys = nullptr;
+    uint32_t* clip_flags = nullptr;
+    int clip_frames = 0;
+    bool clip_dirty = false;
 };
 
 namespace {
@@ -581,7 +588,7 @@ int ensure_rowcell(mdvt_ctx* c, hipStream_t s)
 
 // ---- 4x multisampled render (mdvt_config.samples = 4; mdvt_msaa.hip) ---------------------------------------------------------
 // What the mode does not cover is refused before anything is checked or launched, with the output named.
-int msaa_refusal(mdvt_ctx* c, const mdvt_io* io)
+int msaa_refusal(mdvt_ctx* c, const mdvt_io* io, const char* mode = "multisampling (samples = 4)")
 {
     const char* what = nullptr;
     if (c->cfg.edge_points) what = "edge points (mdvt_config.edge_points != 0)";
@@ -590,7 +597,7 @@ int msaa_refusal(mdvt_ctx* c, const mdvt_io* io)
     else if (io->left_maskbits || io->right_maskbits) what = "packed mask bits (left_maskbits / right_maskbits)";
     else if (!io->left_mask || !io->right_mask) what = "a NULL byte mask (left_mask / right_mask are required)";
     if (!what) return MDVT_OK;
-    return fail(c, MDVT_ERR_UNSUPPORTED, "multisampling (samples = 4) does not cover %s", what);
+    return fail(c, MDVT_ERR_UNSUPPORTED, "%s does not cover %s", mode, what);
 }
 
 // Launch sets of up to 16 frames, as many as workspace_mib affords (64 B/px of sample keys, 3 B/px of edge-filter flags).
@@ -612,6 +619,7 @@ int render_msaa(mdvt_ctx* c, int n_frames, const std::vector<FrameDev>& fd, cons
     int rc = stage_params(c, fd, s, &dfp, &slot);
     if (rc != MDVT_OK) return rc;
     if (rm && (rc = ensure_workspace(c, chunk, false, false, true, false, s)) != MDVT_OK) return rc;
+    const bool clip = c->near_clip && c->cfg.mode == MDVT_MODE_MESH;      // (the clipping render of every frame, mdvt_near_clip.hip)
     const size_t plane_bytes = npx * 2 * 4 * sizeof(unsigned long long);       // one slot, both eyes
     if (c->msaa_frames < chunk) {
         if (c->msaa_keys) { MDVT_HIP(c, hipDeviceSynchronize()); ws_free(c, c->msaa_keys); }     // (earlier submissions may still use it)
@@ -649,10 +657,70 @@ int render_msaa(mdvt_ctx* c, int n_frames, const std::vector<FrameDev>& fd, cons
                                            c->tri_invalid, a.ws_stride_tri, c->unused, npx, s));
         }
         c->msaa_dirty = true;
-        MDVT_HIP(c, MDVT_GRID_CALL(c, launch_msaa_render, a, n, s));
+        if (clip) MDVT_HIP(c, MDVT_GRID_CALL(c, launch_near_clip_render, a, n, 4, nullptr, s));
+        else MDVT_HIP(c, MDVT_GRID_CALL(c, launch_msaa_render, a, n, s));
         c->msaa_dirty = false;
     }
     MDVT_HIP(c, hipEventRecord(slot->done, s));
+    return MDVT_OK;
+}
+
+// ---- near-plane clipping, single sample (mdvt_set_near_clip; mdvt_near_clip.hip) -------------------------------------------------
+// Runs after the single-sample kernels have rendered every frame of the batch, on the same stream: a detect kernel flags the (frame,
+// eye) where some triangle may straddle the plane, and the key-plane kernels re-render only those eyes (the others leave at once;
+// nothing is read back).  Launch sets of up to 16 frames, as many as workspace_mib affords (16 B/px of keys; with remove_edges the
+// edge filter's flags of the slots the render before has already allocated).
+int render_near_clip_gate(mdvt_ctx* c, int n_frames, const FrameDev* dfp, const mdvt_io* io, hipStream_t s)
+{
+    const int W = c->W, H = c->H;
+    const size_t npx = (size_t)W * (size_t)H;
+    const bool rm = c->cfg.remove_edges != 0;
+    const size_t per_slot = npx * 2 * sizeof(unsigned long long);
+    const size_t budget = (size_t)(c->cfg.workspace_mib ? c->cfg.workspace_mib : 4096u) << 20;
+    int chunk = 16;
+    if ((size_t)chunk > budget / per_slot) chunk = budget / per_slot < 1 ? 1 : (int)(budget / per_slot);
+    if (rm && chunk > c->ws_frames) chunk = c->ws_frames;        // (the render before has made at least one slot of edge flags)
+    if (chunk > n_frames) chunk = n_frames;
+    if (chunk < 1) return fail(c, MDVT_ERR_INVALID_ARG, "near-plane clipping: no workspace slot for the edge filter");
+    if (c->clip_frames < chunk) {
+        if (c->clip_keys) { MDVT_HIP(c, hipDeviceSynchronize()); ws_free(c, c->clip_keys); ws_free(c, c->clip_flags); }     // (earlier submissions may still use them)
+        c->clip_keys = nullptr; c->clip_flags = nullptr; c->clip_frames = 0;
+        MDVT_HIP(c, ws_malloc(c, (void**)&c->clip_keys, (size_t)chunk * per_slot, s));
+        MDVT_HIP(c, ws_malloc(c, (void**)&c->clip_flags, (size_t)chunk * 2 * sizeof(uint32_t), s));
+        c->clip_frames = chunk;
+        c->clip_dirty = true;
+    }
+    if (c->clip_dirty) MDVT_HIP(c, hipMemsetAsync(c->clip_keys, 0xFF, (size_t)c->clip_frames * per_slot, s));
+    c->clip_dirty = false;
+
+    MsaaArgs a{};
+    a.depth = io->depth_rgb; a.depth_pitch = io->depth_pitch; a.depth_stride = io->depth_stride;
+    a.color = io->color_rgb; a.color_pitch = io->color_pitch; a.color_stride = io->color_stride;
+    a.rgb[0] = io->left_rgb; a.rgb[1] = io->right_rgb; a.rgb_pitch = io->rgb_pitch; a.rgb_stride = io->rgb_stride;
+    a.mask[0] = io->left_mask; a.mask[1] = io->right_mask; a.mask_pitch = io->mask_pitch; a.mask_stride = io->mask_stride;
+    a.hole_counts = io->hole_counts;
+    a.fp = dfp;
+    a.keys = c->clip_keys;
+    a.tri_invalid = rm ? c->tri_invalid : nullptr;
+    a.unused = rm ? c->unused : nullptr;
+    a.ws_stride_px = npx;
+    a.ws_stride_tri = 2 * (size_t)(W - 1) * (H - 1);
+    a.W = W; a.H = H;
+    a.mode = c->cfg.mode; a.cull = c->cfg.cull;
+    a.key_rgb = (uint32_t)c->cfg.key_rgb[0] | ((uint32_t)c->cfg.key_rgb[1] << 8) | ((uint32_t)c->cfg.key_rgb[2] << 16);
+    for (int f0 = 0; f0 < n_frames; f0 += chunk) {
+        const int n = n_frames - f0 < chunk ? n_frames - f0 : chunk;
+        a.frame0 = f0;
+        MDVT_HIP(c, hipMemsetAsync(c->clip_flags, 0, (size_t)n * 2 * sizeof(uint32_t), s));
+        if (rm) {
+            MDVT_HIP(c, launch_zero_bytes(c->unused, (size_t)n * npx, s));
+            MDVT_HIP(c, launch_edge_filter(a.depth, a.depth_pitch, a.depth_stride, dfp, f0, n, W, H, true,
+                                           c->tri_invalid, a.ws_stride_tri, c->unused, npx, s));
+        }
+        c->clip_dirty = true;
+        MDVT_HIP(c, MDVT_GRID_CALL(c, launch_near_clip_render, a, n, 1, c->clip_flags, s));
+        c->clip_dirty = false;
+    }
     return MDVT_OK;
 }
 
@@ -774,6 +842,8 @@ int mdvt_destroy(mdvt_ctx* c)
     if (c->divcheck) ws_free(c, c->divcheck);
     if (c->rowcell) ws_free(c, c->rowcell);
     if (c->msaa_keys) ws_free(c, c->msaa_keys);
+    if (c->clip_keys) ws_free(c, c->clip_keys);
+    if (c->clip_flags) ws_free(c, c->clip_flags);
     pool_give(c->telea_levels_host, nullptr, 64, -1);
     free_telea(c);
     free_telea_heap(c);
@@ -807,6 +877,15 @@ int mdvt_set_config(mdvt_ctx* c, const mdvt_config* cfg)
     return MDVT_OK;
 }
 
+int mdvt_set_near_clip(mdvt_ctx* c, int32_t near_clip)
+{
+    if (!c) return MDVT_ERR_INVALID_ARG;
+    if (near_clip != 0 && near_clip != 1)
+        return fail(c, MDVT_ERR_INVALID_ARG, "near_clip must be 0 (drop a triangle that crosses the near plane) or 1 (clip it), got %d", (int)near_clip);
+    c->near_clip = near_clip;
+    return MDVT_OK;
+}
+
 int mdvt_selftest(mdvt_ctx* c, int which, uint64_t seed, uint64_t* h_mismatches)
 {
     if (!c) return MDVT_ERR_INVALID_ARG;
@@ -832,6 +911,14 @@ int mdvt_render_stereo_batch(mdvt_ctx* c, int n_frames, const mdvt_frame_params*
     if (c->cfg.samples == 4) {
         const int rc = msaa_refusal(c, io);
         if (rc != MDVT_OK) return rc;
+    }
+    const bool near_clip = c->near_clip && c->cfg.mode == MDVT_MODE_MESH;     // (points: a GL drops a point behind the plane, as the decree does)
+    if (near_clip) {
+        const int rc = msaa_refusal(c, io, "near-plane clipping (near_clip = 1)");
+        if (rc != MDVT_OK) return rc;
+        // fan triangle f of source triangle d is drawn as 2 d + f: 4 (W - 1) (H - 1) ids in the 32 bits of a key
+        if (c->W >= 2 && c->H >= 2 && 4 * (uint64_t)(c->W - 1) * (uint64_t)(c->H - 1) >= (uint64_t)0xFFFFFFFFu)
+            return fail(c, MDVT_ERR_UNSUPPORTED, "near-plane clipping: a %d x %d frame has more fan triangles than its 32-bit draw ids can name", c->W, c->H);
     }
     // The byte masks may be left out (both NULL) by a caller that takes the packed mask instead -- where the compaction is fused
     // into the render kernel (pure-shift point frames: checked per run below); everywhere else they are required.
@@ -1145,6 +1232,7 @@ int mdvt_render_stereo_batch(mdvt_ctx* c, int n_frames, const mdvt_frame_params*
       }
     }
     if (general) c->keys_dirty = false;
+    if (near_clip && (rc = render_near_clip_gate(c, n_frames, dfp, io, s)) != MDVT_OK) return rc;
     MDVT_HIP(c, hipEventRecord(slot->done, s));
     return MDVT_OK;
 }

@@ -26,3 +26,6 @@ bool points_fused_bits_applies(const RenderPlan& plan, const RenderArgs& a);    
 hipError_t launch_divcheck(float mult, float scale, float dl, uint32_t* bad, hipStream_t s);      // FrameDev.div_slot: the short division tried on every depth code
 // mdvt_msaa.hip: the opt-in 4x multisampled render of n frames (raster into the key planes, then the resolve)
 hipError_t launch_msaa_render(const MsaaArgs& a, int n, hipStream_t s);
+// mdvt_near_clip.hip: the opt-in near-plane clipping render of n mesh frames with 1 or 4 samples.  flags ([slot][eye], zeroed by the
+// caller): detect the eyes where some triangle straddles the plane and re-render only those; nullptr: render every eye
+hipError_t launch_near_clip_render(const MsaaArgs& a, int n, int samples, uint32_t* flags, hipStream_t s);

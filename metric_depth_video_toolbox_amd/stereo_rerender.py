@@ -320,6 +320,35 @@ def multisample_kwargs(args):
     return {"samples": 4, "sample_pattern": pattern, "sample_resolve": pattern}
 
 
+def check_near_clip(near_clip):
+    """ValueError unless near_clip is a bool or 0 / 1 (no device needed)."""
+    if not (isinstance(near_clip, bool) or (isinstance(near_clip, int) and near_clip in (0, 1))):
+        raise ValueError(f"near_clip must be a bool (or 0 / 1), got {near_clip!r}")
+
+
+def near_clip_conflict(args):
+    """The first flag of a parsed command line that --near_clip cannot serve, as an error message (None: no conflict).
+    Checked before any frame is read: the mesh render with near-plane clipping has no edge points, seed images or depth planes
+    (mdvt.h); in points mode the switch changes nothing and refuses nothing."""
+    if not getattr(args, "near_clip", False) or args.render_as_pointcloud:
+        return None
+    rm = bool(args.infill_mask or args.remove_edges or args.do_basic_infill) and not args.dont_remove_edges
+    if args.do_basic_infill:
+        return "--near_clip does not cover --do_basic_infill (it needs the infill-mask seed images)"
+    if args.touchly0 or args.touchly1:
+        return f"--near_clip does not cover --{'touchly0' if args.touchly0 else 'touchly1'} (Touchly outputs need depth planes)"
+    if args.create_sbs_depth_video:
+        return "--near_clip does not cover --create_sbs_depth_video (it needs depth planes)"
+    if rm and not args.dont_place_points_in_edges:
+        return "--near_clip does not cover edge points: add --dont_place_points_in_edges (or --dont_remove_edges)"
+    if args.infill_mask and rm and not args.green_and_black_infill_mask:
+        return ("--near_clip does not cover the normal-coloured --infill_mask (it needs the seed images): "
+                "add --green_and_black_infill_mask (or --dont_remove_edges)")
+    if getattr(args, "normal_infill", False):
+        return "--near_clip does not cover --normal_infill (it needs the infill-mask seed images)"
+    return None
+
+
 # the orders in which the infill-mask completion may inpaint: "levels" (the default, level-synchronous) or "heap" (cv2.inpaint's
 # own sequential order, byte-exact to the reference; opt-in)
 INPAINT_ORDERS = ("levels", "heap")
@@ -347,6 +376,11 @@ class StereoRerenderer:
       sample_pattern                                 samples = 4: 0 the Direct3D / Vulkan standard positions, 1 SwiftShader's
       sample_resolve                                 samples = 4: 0 the rounded mean of the four samples, 1 SwiftShader's
                                                      avg(avg(s0, s1), avg(s2, s3))
+      near_clip                                      False (default): a mesh triangle that crosses the near plane z = 1e-4
+                                                     (dmt:1520) is dropped whole (the decree); True: it is clipped as a GL clips
+                                                     it (mdvt.h mdvt_set_near_clip), with samples 0 / 1 and 4.  Mesh mode: not
+                                                     with edge points, depth planes, seed images or packed masks (render() raises
+                                                     MdvtError, MDVT_ERR_UNSUPPORTED); points mode: changes nothing
     """
 
     FINISH_SPLIT_FRAMES = 32         # finish_infill_mask_sbs: from this many frames per call, two concurrent half passes
@@ -356,8 +390,9 @@ class StereoRerenderer:
                  remove_edges: bool = False, infill_mask: bool = False, do_basic_infill: bool = False,
                  dont_remove_edges: bool = False, dont_place_points_in_edges: bool = False, cull: int = 0,
                  workspace_mib: int = 0, subpixel_bits: int = 0, samples: int = 0, sample_pattern: int = 0,
-                 sample_resolve: int = 0):
+                 sample_resolve: int = 0, near_clip: bool = False):
         check_multisample(samples, sample_pattern, sample_resolve)
+        check_near_clip(near_clip)
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("no ROCm GPU visible: the stereo-rerender path has no CPU fallback")
@@ -392,6 +427,8 @@ class StereoRerenderer:
         for k in range(3):
             cfg.key_rgb[k] = self.key_rgb[k]
         self.ctx.check(self._L.mdvt_set_config(self.ctx.handle, C.byref(cfg)))
+        self.near_clip = bool(near_clip)
+        self.ctx.check(self._L.mdvt_set_near_clip(self.ctx.handle, int(self.near_clip)))
         self._cfg, self._ctx2, self._side = cfg, None, None      # (finish_infill_mask_sbs's second context, made on first use)
 
     @property
@@ -697,6 +734,12 @@ def build_arg_parser():
     ap.add_argument("--video_encoder", choices=("host", "device"), default="host",
                     help="not a reference flag: where the .mkv outputs are FFV1-encoded -- 'host' (default) or 'device' (on the GPU, "
                          "the same bytes; only the compressed packets are copied to the host). Not with .npy input and outputs")
+    ap.add_argument("--near_clip", action="store_true",
+                    help="not a reference flag: clip a mesh triangle that crosses the near plane (z = 1e-4 m) as a GL does, instead of "
+                         "dropping it whole (the default) -- matters where depth code 0 or a pose puts the camera inside the scene "
+                         "(README). Mesh mode: not with edge points, seed images or depth outputs: --infill_mask needs "
+                         "--dont_place_points_in_edges and --green_and_black_infill_mask, and --do_basic_infill, --normal_infill, "
+                         "--create_sbs_depth_video, --touchly0 / --touchly1 are refused")
     for flag in ("--compressed", "--mask_video", "--save_background", "--load_background"):
         ap.add_argument(flag, nargs="?", const=True, default=None, help="reference flag outside the built hot path")
     return ap
@@ -712,7 +755,7 @@ def main(argv=None):
         raise ValueError("Error: Either --xfov_file, --xfov or --yfov must be provided.")       # sr:319-320
     if args.xfov is None and args.xfov_file is None:
         raise NotImplementedError("--yfov without --xfov: the reference itself fails at sr:537 in this case")
-    conflict = multisample_conflict(args)
+    conflict = multisample_conflict(args) or near_clip_conflict(args)
     if conflict is not None:
         raise ValueError(conflict)
     if not os.path.isfile(args.depth_video):
@@ -734,7 +777,7 @@ def main(argv=None):
                             dont_place_points_in_edges=args.dont_place_points_in_edges,
                             vr180=args.vr180, touchly0=args.touchly0, touchly1=args.touchly1,
                             do_basic_infill=args.do_basic_infill, normal_infill=args.normal_infill, inpaint_order=args.inpaint_order,
-                            multisample=multisample_kwargs(args),
+                            multisample=multisample_kwargs(args), near_clip=bool(args.near_clip),
                             video_encoder=args.video_encoder,
                             touchly_max_depth=args.touchly_max_depth, touchly_min_depth=args.touchly_min_depth)
     if int(os.environ.get("RANK", "0")) == 0:

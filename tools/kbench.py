@@ -38,9 +38,15 @@ ap.add_argument("--noedgepts", action="store_true", help="with --edges / --infil
 ap.add_argument("--samples", type=int, default=0, help="mdvt_config.samples: 0 / 1 single sample, 4 = 4x multisampled (refuses --zout, --bits and edge "
                 "points: use --noedgepts with --edges / --infill)")
 ap.add_argument("--pattern", type=int, default=0, help="with --samples 4: sample pattern and resolve (0 standard, 1 SwiftShader)")
+ap.add_argument("--near_clip", action="store_true", help="mesh: clip triangles at the near plane as a GL does (mdvt_set_near_clip; refuses --zout, "
+                "--bits and edge points like --samples 4)")
+ap.add_argument("--tz", type=float, default=None, help="every frame posed: translate z by this many metres (-2: the camera inside the scene)")
+ap.add_argument("--zero_patch", action="store_true", help="a centred W/8 x H/8 patch of depth code 0 in every frame (depth 0 m: behind the near plane)")
 a = ap.parse_args()
 W, H, N = a.width, a.height, a.frames
 ms = dict(samples=a.samples, sample_pattern=a.pattern, sample_resolve=a.pattern) if a.samples else {}
+if a.near_clip:
+    ms["near_clip"] = True
 if os.environ.get('KB_ORDER'):
     r = StereoRerenderer(W, H, pupillary_distance=65, render_as_pointcloud=not a.mesh, infill_mask=a.infill, remove_edges=a.edges or a.infill, dont_place_points_in_edges=a.noedgepts, **ms)
     d, c = SyntheticScene(W, H, config_id=2).clip(N)
@@ -51,6 +57,11 @@ else:
     r = StereoRerenderer(W, H, pupillary_distance=65, render_as_pointcloud=not a.mesh, infill_mask=a.infill, remove_edges=a.edges or a.infill, dont_place_points_in_edges=a.noedgepts, **ms)
 from metric_depth_video_toolbox_amd.synthetic import synthetic_pose_track
 Ts = synthetic_pose_track(N) if a.pose else [None] * N
+if a.tz is not None:
+    T = np.eye(4); T[2, 3] = a.tz
+    Ts = [T] * N
+if a.zero_patch:
+    d[:, H // 2 - H // 16:H // 2 + H // 16, W // 2 - W // 16:W // 2 + W // 16, :] = 0
 if a.c4:
     from metric_depth_video_toolbox_amd.synthetic import c4_clip
     d4, c4, Ts = c4_clip(N, W, H)          # (the clip bench.py times and tests/test_gpu_bench_sizes.py holds to the oracle)
