@@ -20,6 +20,8 @@
  *     the workspace unordered, and growing a workspace synchronises the device.
  *     (mdvt_render_stereo_batch may itself run part of a long posed / converged mesh batch on a second, library-owned stream;
  *     it forks from and joins the given stream with events, so the call's results are still ordered on the given stream.)
+ *     (The per-context table that proves the pure-shift point render's short division per parameter set is ordered across
+ *     streams by the library itself: a render on another stream than the one that checked a set waits for that check.)
  *   - there is NO CPU fallback: without a HIP device mdvt_create fails with MDVT_ERR_NO_DEVICE.
  */
 #ifndef MDVT_H

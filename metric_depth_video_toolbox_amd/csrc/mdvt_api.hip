@@ -75,6 +75,8 @@ struct mdvt_ctx {
     uint32_t* wave_counts = nullptr;  // [row_counts_frames][H][16] (RenderArgs.wave_counts)
     uint32_t* divcheck = nullptr;     // [kDivSlots] (RenderArgs.divcheck), zeroed when allocated; slot k belongs to div_keys[k]
     std::vector<std::array<uint32_t, 3>> div_keys;      // bits of (mult, scale, dl) of the parameter sets checked so far
+    hipEvent_t div_done = nullptr;    // recorded after the latest division check (every earlier check and the table's fill before it) ...
+    hipStream_t div_stream = nullptr; // ... on this stream: a render on another stream waits for it before it reads the table
     int row_counts_frames = 0;
     // infill-mask completion: per image stamp u16 + T f32 + work image u8x3, and the per-image counters
     int telea_images = 0, telea_rounds = 0;
@@ -840,6 +842,7 @@ int mdvt_destroy(mdvt_ctx* c)
     if (c->row_counts) ws_free(c, c->row_counts);
     if (c->wave_counts) ws_free(c, c->wave_counts);
     if (c->divcheck) ws_free(c, c->divcheck);
+    if (c->div_done) (void)hipEventDestroy(c->div_done);
     if (c->rowcell) ws_free(c, c->rowcell);
     if (c->msaa_keys) ws_free(c, c->msaa_keys);
     if (c->clip_keys) ws_free(c, c->clip_keys);
@@ -958,10 +961,17 @@ int mdvt_render_stereo_batch(mdvt_ctx* c, int n_frames, const mdvt_frame_params*
     if (c->cfg.samples == 4) return render_msaa(c, n_frames, fd, io, s);
     // Pure-shift point frames: the disparity's division proven short per parameter set (FrameDev.div_slot).  A new set costs one
     // launch of 65536 threads on this stream, once per context; clips have one set, or one per distinct field of view.
+    // The checks run on the stream of the call that brought their set in; a call on another stream (a pure-shift point render
+    // without hole counts uses no other workspace, so nothing else orders it after that call) first waits for the latest check,
+    // and with it for every earlier one and the table's fill: each check is recorded after a wait for the one before it, whichever
+    // stream that was on.
     if (c->cfg.mode == MDVT_MODE_POINTS) {
+        bool ordered = false;
         for (int k = 0; k < n_frames; ++k) {
             FrameDev& f = fd[(size_t)k];
             if (f.general) continue;
+            if (!ordered && c->div_done && c->div_stream != s) MDVT_HIP(c, hipStreamWaitEvent(s, c->div_done, 0));
+            ordered = true;
             std::array<uint32_t, 3> key;
             memcpy(&key[0], &f.mult, 4); memcpy(&key[1], &f.scale, 4); memcpy(&key[2], &f.dl, 4);
             int slot = -1;
@@ -971,8 +981,11 @@ int mdvt_render_stereo_batch(mdvt_ctx* c, int n_frames, const mdvt_frame_params*
                     MDVT_HIP(c, ws_malloc(c, (void**)&c->divcheck, mdvt::kDivSlots * sizeof(uint32_t), s));
                     MDVT_HIP(c, hipMemsetAsync(c->divcheck, 0, mdvt::kDivSlots * sizeof(uint32_t), s));
                 }
+                if (!c->div_done) MDVT_HIP(c, hipEventCreateWithFlags(&c->div_done, hipEventDisableTiming));
                 slot = (int)c->div_keys.size();
                 MDVT_HIP(c, MDVT_GRID_CALL(c, launch_divcheck, f.mult, f.scale, f.dl, c->divcheck + slot, s));
+                MDVT_HIP(c, hipEventRecord(c->div_done, s));
+                c->div_stream = s;
                 c->div_keys.push_back(key);
             }
             f.div_slot = slot;

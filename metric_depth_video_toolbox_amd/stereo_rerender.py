@@ -571,8 +571,10 @@ class StereoRerenderer:
             # first use (14 B per pixel and image, at most 32 images).  Same bytes: a frame's mask does not depend on its batch.
             if self._ctx2 is None:
                 self._ctx2 = _lib.Context(self.device, self.W, self.H)
-                self._ctx2.check(self._L.mdvt_set_config(self._ctx2.handle, C.byref(self._cfg)))
                 self._side = torch.cuda.Stream(device=seed_sbs.device)
+            # (the configuration of the first context as it is now -- its key colour decides which pixels are filled -- not as it
+            #  was when the second one was made: a caller may have changed it on the live context since)
+            self._ctx2.check(self._L.mdvt_set_config(self._ctx2.handle, C.byref(self._cfg)))
             h = N // 2
             # (the counters of both halves are allocated and zeroed on the caller's stream BEFORE the side stream waits for it, and
             #  the second half's tensor is recorded on the side stream: the fill and the library's writes are ordered, and the

@@ -158,7 +158,7 @@ def test_full_hd_single_frame_matches_oracle(mods, orc):
 
 
 # ----------------------------------------------------------------------------------------------- mesh mode
-@pytest.mark.parametrize("W,H", [(64, 48), (96, 64), (250, 37), (33, 17), (320, 240)])
+@pytest.mark.parametrize("W,H", [(64, 48), (96, 64), (250, 37), (33, 17), (320, 240), (640, 480)])
 @pytest.mark.parametrize("infill_mask", [False, True])
 def test_mesh_pure_shift(mods, orc, W, H, infill_mask):
     """Default mode of the reference (grid mesh).  infill_mask=True is the product default of
