@@ -138,13 +138,18 @@ typedef struct mdvt_io {
     uint8_t* left_rgb; uint8_t* right_rgb; size_t rgb_pitch;  size_t rgb_stride;    /* sr:819, 907           */
     uint8_t* left_mask; uint8_t* right_mask; size_t mask_pitch; size_t mask_stride; /* 255 = hole (sr:740, 854) */
     /* (ABI 0.15: both byte masks may be NULL when the packed mask below is requested and the frames are rendered by the kernel
-     *  that compacts the mask itself -- points mode, pure stereo shift, no edge removal, W % 4 == 0, W <= 4096 --: 12.25
-     *  instead of 14 bytes per pixel leave the chip.  Every other path answers MDVT_ERR_INVALID_ARG.) */
+     *  that compacts the mask itself -- points mode, pure stereo shift, no edge removal, W % 4 == 0, W <= 4096, and a dword-aligned
+     *  layout: depth_rgb, color_rgb, left_rgb and right_rgb, their pitches and their strides all multiples of 4, mask_pitch and
+     *  mask_stride 0 or multiples of 4 although the masks are NULL (depth planes, if requested: pointers, zout_pitch and zout_stride
+     *  multiples of 16) --: 12.25 instead of 14 bytes per pixel leave the chip.
+     *  Every other path or layout answers MDVT_ERR_INVALID_ARG.) */
     float* left_depth; float* right_depth; size_t zout_pitch; size_t zout_stride;   /* optional; 0 = background (dmt:1563) */
     /* optional compacted hole mask: 1 bit per pixel, bit k of byte b = pixel 8b+k (np.packbits(mask > 0,
      * bitorder="little")), rows padded to whole dwords: maskbits_pitch >= 4*ceil(W/32) */
     uint8_t* left_maskbits; uint8_t* right_maskbits; size_t maskbits_pitch; size_t maskbits_stride;
-    /* optional: hole_counts[2*frame + eye] = number of hole pixels (uint32, overwritten) */
+    /* (The call owns the whole 4*ceil(W/32) bytes of every packed row: bits beyond pixel W - 1 are written as zero.  Bytes of a row
+     *  beyond that, up to maskbits_pitch, are not touched.) */
+    /* optional: hole_counts[2*frame + eye] = number of hole pixels (uint32, dword aligned; overwritten: the caller need not zero it) */
     uint32_t* hole_counts;
     /* optional (needs remove_edges): the infill-mask SEED image of each eye, u8 RGB -- left_img_mask of
      * sr:787-803 as (x*255).astype(uint8) just before cv2.inpaint: black outside holes; in holes the key
@@ -362,7 +367,8 @@ int mdvt_infill_using_mask_normals(mdvt_ctx* ctx, uint8_t* d_img, size_t img_pit
  * slice's raw bytes + 4096), at most 2^24 - 1 (the 24-bit slice size).  A frame one of whose slices passes its capacity, or whose
  * packet does not fit the packets_cap bytes left at d_packets, gets d_sizes[k] = 0xFFFFFFFF and no bytes; a frame with a slice of
  * 2^24 bytes or more gets 0xFFFFFFFE.  A buffer of n_frames x slices_h x slices_v x (capacity + 8) bytes always has room: then only a
- * slice past its capacity flags a frame.  The caller re-encodes such a frame with mdvt_ffv1_encode_frame, which returns the same
+ * slice past its capacity flags a frame.  d_sizes[k] is written for every frame, d_offsets[k] for every frame that got a packet; bytes of d_packets behind the last
+ * packet, up to packets_cap, belong to the call (unspecified content), nothing beyond packets_cap is touched.  The caller re-encodes such a frame with mdvt_ffv1_encode_frame, which returns the same
  * bytes, or refuses the frame with its MDVT_VIDEO error as it does for 0xFFFFFFFE.  Refused here: the slice counts
  * mdvt_ffv1_encode_frame refuses (below 1, above width / height) and more than 1024 slices per frame (mdvt_video_create refuses
  * them).  The call only enqueues work on `stream`; its workspace (the slices' scratch areas) is kept by the ctx, grown (which

@@ -1222,7 +1222,7 @@ int mdvt_render_stereo_batch(mdvt_ctx* c, int n_frames, const mdvt_frame_params*
         }
         if (no_byte_mask && !MDVT_GRID_CALL(c, points_fused_bits_applies, plan, a))
             return fail(c, MDVT_ERR_INVALID_ARG, "the byte masks may be NULL only where the mask compaction is fused into the render "
-                        "(points mode, pure stereo shift, no edge removal, W %% 4 == 0, W <= 4096)");
+                        "(points mode, pure stereo shift, no edge removal, W %% 4 == 0, W <= 4096, dword-aligned image pointers, pitches and strides)");
         a.key_parity = c->key_parity >> slot0;
         plan.edge_rows_max = 0;
         if (!r.general && !r.conv && plan.edge_points)

@@ -490,12 +490,14 @@ class StereoRerenderer:
         bits = counts = None
         if want_maskbits:       # [N, H, 2, 4*ceil(W/32)] u8: packed 1 bit/px rows, left then right eye
             rowb = 4 * ((W + 31) // 32)
-            bits = torch.zeros((N, H, 2, rowb), dtype=torch.uint8, device=dev)
+            # (torch.empty here, for the counts and for `rem` below: the library overwrites all three in full -- the packed rows up to
+            #  their last dword, bits beyond W as zero -- whatever they held: tests/test_gpu_footprint.py hands them over poisoned)
+            bits = torch.empty((N, H, 2, rowb), dtype=torch.uint8, device=dev)
             io.left_maskbits, io.right_maskbits = bits.data_ptr(), bits.data_ptr() + rowb
             io.maskbits_pitch, io.maskbits_stride = 2 * rowb, 2 * rowb * H
             res["maskbits"] = bits[0] if single else bits
         if want_hole_counts:    # [N, 2] int32 (left, right)
-            counts = torch.zeros((N, 2), dtype=torch.int32, device=dev)
+            counts = torch.empty((N, 2), dtype=torch.int32, device=dev)
             io.hole_counts = counts.data_ptr()
             res["hole_counts"] = counts[0] if single else counts
         seed = None
@@ -546,7 +548,7 @@ class StereoRerenderer:
         elif out.dim() == 3:
             out = out[None]
         assert tuple(out.shape) == (N, H, 2 * W, 3) and out.stride(-1) == 1 and out.stride(-2) == 3
-        rem = torch.zeros((2, N), dtype=torch.int32, device=seed_sbs.device) if want_remaining else None
+        rem = torch.empty((2, N), dtype=torch.int32, device=seed_sbs.device) if want_remaining else None
         s = torch.cuda.current_stream(seed_sbs.device)
 
         if order == "heap":
@@ -576,11 +578,11 @@ class StereoRerenderer:
             #  was when the second one was made: a caller may have changed it on the live context since)
             self._ctx2.check(self._L.mdvt_set_config(self._ctx2.handle, C.byref(self._cfg)))
             h = N // 2
-            # (the counters of both halves are allocated and zeroed on the caller's stream BEFORE the side stream waits for it, and
+            # (the counters of both halves are allocated on the caller's stream BEFORE the side stream waits for it, and
             #  the second half's tensor is recorded on the side stream: the fill and the library's writes are ordered, and the
             #  caching allocator will not hand the block on while the side stream may still write it -- advisor, r04)
-            r1 = torch.zeros((2, h), dtype=torch.int32, device=seed_sbs.device) if want_remaining else None
-            r2 = torch.zeros((2, N - h), dtype=torch.int32, device=seed_sbs.device) if want_remaining else None
+            r1 = torch.empty((2, h), dtype=torch.int32, device=seed_sbs.device) if want_remaining else None
+            r2 = torch.empty((2, N - h), dtype=torch.int32, device=seed_sbs.device) if want_remaining else None
             self._side.wait_stream(s)
             if r2 is not None:
                 r2.record_stream(self._side)
@@ -612,7 +614,7 @@ class StereoRerenderer:
         if out is None:
             out = torch.empty(tuple(seed.shape), dtype=torch.uint8, device=seed.device)
         assert out.shape == seed.shape and out.stride(-1) == 1 and out.stride(-2) == 3
-        rem = torch.zeros(N, dtype=torch.int32, device=seed.device) if want_remaining else None
+        rem = torch.empty(N, dtype=torch.int32, device=seed.device) if want_remaining else None
         s = torch.cuda.current_stream(seed.device)
         if order == "heap":
             self.ctx.check(self._L.mdvt_finish_infill_mask_heap(

@@ -613,11 +613,7 @@ def test_infill_using_normals_on_device(mods, orc, golden):
 
 
 # ----------------------------------------------------------------------------------------------- raw ABI use
-def _raw_io(_lib, **kw):
-    io = _lib.MdvtIO()
-    for k, v in kw.items():
-        setattr(io, k, v)
-    return io
+from footprint import raw_io as _raw_io  # noqa: E402  (moved into the footprint helper, unchanged)
 
 
 @pytest.mark.parametrize("mode", ["points", "mesh"])
