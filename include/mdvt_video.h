@@ -15,7 +15,8 @@
  * checked by an independent decoder restated from the RFC's pseudo-code (test infrastructure: ffv1_ref.py next to the C oracle), the container by structural
  * tests (EBML sizes, CRCs); tests/golden/gen_ffv1_golden.py produces cross-check vectors on a machine that has ffmpeg.
  * The encoder has a device twin in libmdvt_hip.so, mdvt_encode_video_frames of include/mdvt.h: it codes batches of device frames into
- * the same packets byte for byte, for mdvt_video_write_packet.
+ * the same packets byte for byte, for mdvt_video_write_packet.  The decoder has one too, mdvt_decode_video_frames of
+ * include/mdvt_ffv1_decode.h: packets of the stream class this writer makes, in device memory, into the frames mdvt_video_read gives.
  */
 #ifndef MDVT_VIDEO_H
 #define MDVT_VIDEO_H
@@ -86,6 +87,10 @@ int mdvt_video_finish(mdvt_video_writer* w, int64_t* frames);
 int mdvt_ffv1_encode_frame(int width, int height, int slices_h, int slices_v, const uint8_t* src, size_t pitch, int order,
                            int threads, uint8_t* packet, size_t packet_cap, size_t* packet_size,
                            uint8_t* config, size_t config_cap, size_t* config_size);
+/* One packet of a stream with this configuration record (version 3) -> width x 3 bytes of each of height rows of dst: what
+ * mdvt_video_read gives for a key frame (an inter frame has no predecessor here and is refused). */
+int mdvt_ffv1_decode_frame(int width, int height, const uint8_t* config, size_t config_size, const uint8_t* packet, size_t packet_size,
+                           uint8_t* dst, size_t pitch, int order, int threads);
 
 #ifdef __cplusplus
 }

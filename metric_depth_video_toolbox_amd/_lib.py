@@ -29,6 +29,9 @@ SYMBOLS = ("mdvt_version", "mdvt_create", "mdvt_destroy", "mdvt_last_error", "md
            "mdvt_debug_read", "mdvt_finish_infill_mask_heap", "mdvt_finish_infill_mask_heap_stereo",
            "mdvt_encode_video_frames", "mdvt_set_near_clip")
 
+# the entry points include/mdvt_ffv1_decode.h declares (the device FFV1 decoder): bound like the others, listed apart from mdvt.h's
+DECODE_SYMBOLS = ("mdvt_decode_video_frames", "mdvt_ffv1_decode_supported")
+
 
 class MdvtError(RuntimeError):
     def __init__(self, code: int, text: str):
@@ -150,6 +153,11 @@ def load():
     L.mdvt_set_cached_memory_limit.argtypes = [C.c_uint64]
     L.mdvt_debug_read.restype = C.c_int
     L.mdvt_debug_read.argtypes = [vp, C.c_int, vp, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.mdvt_decode_video_frames.restype = C.c_int
+    L.mdvt_decode_video_frames.argtypes = [vp, C.c_int, C.c_int, C.c_char_p, C.c_size_t, vp, C.c_uint64, vp, vp, C.c_int, vp, C.c_size_t,
+                                          C.c_size_t, C.c_int, vp, vp]
+    L.mdvt_ffv1_decode_supported.restype = C.c_char_p
+    L.mdvt_ffv1_decode_supported.argtypes = [C.c_char_p, C.c_size_t]
     _libs[variant] = L
     return L
 

@@ -2,14 +2,15 @@
 same names and argument meaning, on PyTorch-ROCm tensors through libmdvt_hip.so.  No CPU fallback.
 
     normal_infill(img, infill_mask)            basic_nomal_infill.py:87-119, one eye
-    process_pair(sbs_color, sbs_mask)          basic_nomal_infill.py:124-236, on frame dumps (clip.py's formats)
-    python -m metric_depth_video_toolbox_amd.basic_nomal_infill --sbs_color_video X.npy --sbs_mask_video Y.npy
+    process_pair(sbs_color, sbs_mask)          basic_nomal_infill.py:124-236, on the clip driver's outputs (clip.py's formats)
+    python -m metric_depth_video_toolbox_amd.basic_nomal_infill --sbs_color_video X.mkv --sbs_mask_video Y.mkv
 
-The reference reads and writes FFV1 videos through OpenCV; here the inputs are the `.npy` dumps the clip driver writes
-(`<depth>_stereo.npy`, `<depth>_stereo.npy_infillmask.npy`: uint8 [N, H, 2W, 3], RGB order) and the output is
-`<sbs_color>_infilled.npy` (the reference appends `_infilled.mkv` to the colour video's full name, bni:141), written as
-`<sbs_color>_tmp_infilled.npy` and renamed once every frame is in
-(depth_frames_helper.verify_and_move, dfh:163-179).
+The reference reads and writes FFV1 videos through OpenCV (bni:129-145).  So does this module when the inputs are the `.mkv`
+files the clip driver writes (`<depth>_stereo.mkv`, `<depth>_stereo.mkv_infillmask.mkv`): the output is
+`<sbs_color>_infilled.mkv` (the reference appends `_infilled.mkv` to the colour video's full name, bni:141), optionally decoded
+and encoded on the GPU (--video_decoder / --video_encoder device).  With the `.npy` dumps the clip driver writes for `.npy`
+inputs (uint8 [N, H, 2W, 3], RGB order) the output is `<sbs_color>_infilled.npy`.  Either is written under its `_tmp_infilled`
+name and renamed once every frame is in (depth_frames_helper.verify_and_move, dfh:163-179).
 """
 from __future__ import annotations
 
@@ -64,12 +65,43 @@ def normal_infill_sbs(sbs, sbs_mask, out=None):
     return out
 
 
-def process_pair(sbs_color_video_path: str, sbs_mask_video_path: str, max_frames: int = -1, batch: int = 8, device=None):
-    """basic_nomal_infill.process_pair (basic_nomal_infill.py:124-236) on frame dumps.  A mask clip shorter than the colour
-    clip means "no holes" for the remaining frames (basic_nomal_infill.py:165-167).  Returns the output path."""
+def _video_parts(frames):
+    """[(VideoFrames, first frame)] of an opened output that is one video or per-rank video segments; [] for frame dumps."""
+    from .clip import SegmentedFrames, VideoFrames
+    if isinstance(frames, VideoFrames):
+        return [(frames, 0)]
+    if isinstance(frames, SegmentedFrames) and all(isinstance(p, VideoFrames) for p in frames.parts):
+        return list(zip(frames.parts, frames.bounds[:-1]))
+    return []
+
+
+def _fetch(frames, a: int, b: int, dev, dec_ctx):
+    """Frames [a, b) as a uint8 CUDA tensor.  Videos switched to the device decoder hand over their packets (decoded on the
+    device, straight into the tensor); everything else is read on the host and copied."""
     import torch
-    from .clip import verify_and_move
-    from .clip import open_output
+    parts = _video_parts(frames)
+    if dec_ctx is None or not parts or not all(p.device_decode for p, _ in parts):
+        return torch.from_numpy(np.array(frames[a:b])).to(dev)
+    from . import ffv1_device
+    H, W = int(frames.shape[1]), int(frames.shape[2])
+    out = torch.empty((b - a, H, W, 3), dtype=torch.uint8, device=dev)
+    for p, b0 in parts:
+        lo, hi = max(a, b0), min(b, b0 + len(p))
+        if lo < hi:
+            ffv1_device.enqueue_decode(dec_ctx, p.read_packets(lo - b0, hi - lo), p.config, W, H, out=out[lo - a:hi - a]).collect()
+    return out
+
+
+def process_pair(sbs_color_video_path: str, sbs_mask_video_path: str, max_frames: int = -1, batch: int = 8, device=None, *,
+                 video_decoder: str = "host", video_encoder: str = "host"):
+    """basic_nomal_infill.process_pair (basic_nomal_infill.py:124-236).  `.mkv` inputs (the reference's format: `<x>_stereo.mkv`
+    and `<x>_stereo.mkv_infillmask.mkv`, bni:129-145) give `<sbs_color>_infilled.mkv` at the colour video's frame rate, frame
+    dumps give `<sbs_color>_infilled.npy`; either is written under its `_tmp_infilled` name and renamed once every frame is in.
+    A mask clip shorter than the colour clip means "no holes" for the remaining frames (basic_nomal_infill.py:165-167).
+    video_decoder / video_encoder: "host" (default) or "device" for .mkv files (the same bytes; clip.check_video_decoder /
+    check_video_encoder refuse "device" for frame dumps).  Returns the output path."""
+    import torch
+    from .clip import VideoSink, check_video_decoder, check_video_encoder, open_output, verify_and_move
     # (a clip rendered by several ranks exists as per-rank segments + index: open_output reads either form)
     if not (os.path.isfile(sbs_color_video_path) or os.path.isfile(sbs_color_video_path + ".index.json")):
         raise Exception(f"input sbs_color_video does not exist: {sbs_color_video_path}")
@@ -77,6 +109,9 @@ def process_pair(sbs_color_video_path: str, sbs_mask_video_path: str, max_frames
         raise Exception(f"input sbs_mask_video does not exist: {sbs_mask_video_path}")
     color = open_output(sbs_color_video_path)
     mask = open_output(sbs_mask_video_path)
+    video = bool(_video_parts(color))
+    check_video_decoder(video_decoder, video)
+    check_video_encoder(video_encoder, video)
     assert color.ndim == 4 and color.shape[-1] == 3 and color.dtype == np.uint8, "uint8 [N, H, 2W, 3] expected"
     assert color.shape[1:] == mask.shape[1:], "mask and color video not same resolution"
     if color.shape[2] % 2:
@@ -84,19 +119,52 @@ def process_pair(sbs_color_video_path: str, sbs_mask_video_path: str, max_frames
     if max_frames == 0:
         raise ValueError("max_frames = 0: the reference still processes one frame (bni:226-228); ask for -1 (all) or a positive count")
     n = color.shape[0] if max_frames == -1 else min(color.shape[0], max_frames)
-    tmp, final = sbs_color_video_path + "_tmp_infilled.npy", sbs_color_video_path + "_infilled.npy"      # bni:140-141
-    out = np.lib.format.open_memmap(tmp, mode="w+", dtype=np.uint8, shape=(n,) + tuple(color.shape[1:]))
+    batch = max(1, int(batch))
+    ext = ".mkv" if video else ".npy"
+    tmp, final = sbs_color_video_path + "_tmp_infilled" + ext, sbs_color_video_path + "_infilled" + ext      # bni:140-141
     dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-    for a in range(0, n, batch):
-        b = min(a + batch, n)
-        d_color = torch.from_numpy(np.array(color[a:b])).to(dev)
-        m = np.zeros((b - a,) + tuple(color.shape[1:]), np.uint8)
-        have = max(0, min(b, mask.shape[0]) - a)
-        if have:
-            m[:have] = mask[a:a + have]
-        d_out = normal_infill_sbs(d_color, torch.from_numpy(m).to(dev))
-        out[a:b] = d_out.cpu().numpy()
-    out.flush()
+    ctx = None
+    if video:
+        fps = _video_parts(color)[0][0].fps or 30.0                                      # bni:134: the colour video's frame rate
+        out = VideoSink(tmp, int(color.shape[2]), int(color.shape[1]), fps, encoder=video_encoder)
+        if video_decoder == "device" or video_encoder == "device":
+            ctx = _lib.Context(dev.index, 16, 16)
+        if video_decoder == "device":
+            for name, frames in (("sbs_color_video", color), ("sbs_mask_video", mask)):
+                for p, _ in _video_parts(frames):
+                    p.use_device_decoder(name)
+    else:
+        out = np.lib.format.open_memmap(tmp, mode="w+", dtype=np.uint8, shape=(n,) + tuple(color.shape[1:]))
+    dec_ctx = ctx if video_decoder == "device" else None
+    try:
+        with torch.cuda.device(dev):
+            for a in range(0, n, batch):
+                b = min(a + batch, n)
+                d_color = _fetch(color, a, b, dev, dec_ctx)
+                have = max(0, min(b, mask.shape[0]) - a)
+                if have == b - a:
+                    d_mask = _fetch(mask, a, b, dev, dec_ctx)
+                else:
+                    d_mask = torch.zeros((b - a,) + tuple(color.shape[1:]), dtype=torch.uint8, device=dev)
+                    if have:
+                        d_mask[:have] = _fetch(mask, a, a + have, dev, dec_ctx)
+                d_out = normal_infill_sbs(d_color, d_mask)
+                if not video:
+                    out[a:b] = d_out.cpu().numpy()
+                elif video_encoder == "device":
+                    out.append_packets(out.enqueue(ctx, d_out), a)
+                else:
+                    out.write_from(d_out.cpu().numpy(), a, b - a)
+        if video:
+            out.close()
+        else:
+            out.flush()
+    finally:
+        if ctx is not None:
+            ctx.close()
+        for frames in (color, mask):
+            for p, _ in _video_parts(frames):
+                p.close()
     del out
     verify_and_move(tmp, n, final)
     return final
@@ -124,12 +192,25 @@ def pairs_from_arguments(sbs_color_video: str, sbs_mask_video: str):
     return list(zip(colors, masks))
 
 
-def main(argv=None):
-    p = argparse.ArgumentParser(description="Normal infill script (frame dumps)")
-    p.add_argument("--sbs_color_video", type=str, required=True, help="side by side stereo frames (.npy) rendered with point clouds in the masked area, or a .txt list of them")
-    p.add_argument("--sbs_mask_video", type=str, required=True, help="side by side infill mask frames (.npy), or the matching .txt list")
+def build_parser():
+    p = argparse.ArgumentParser(description="Normal infill script (FFV1 .mkv videos, or frame dumps)")
+    p.add_argument("--sbs_color_video", type=str, required=True, help="side by side stereo video (.mkv, or a .npy frame dump) rendered with point clouds in the masked area, or a .txt list of them")
+    p.add_argument("--sbs_mask_video", type=str, required=True, help="side by side infill mask video (.mkv, or a .npy frame dump), or the matching .txt list")
     p.add_argument("--max_frames", default=-1, type=int, help="quit after max_frames nr of frames", required=False)
-    args = p.parse_args(argv)
+    p.add_argument("--batch", default=8, type=int, help="not a reference flag: frames per device batch")
+    p.add_argument("--video_decoder", choices=("host", "device"), default="host",
+                   help="not a reference flag: where the .mkv inputs are FFV1-decoded -- 'host' (default) or 'device' (on the GPU, the "
+                        "same bytes; only the compressed packets are copied to the device; a stream the device does not decode is "
+                        "read on the host). Not with .npy inputs")
+    p.add_argument("--video_encoder", choices=("host", "device"), default="host",
+                   help="not a reference flag: where the .mkv output is FFV1-encoded -- 'host' (default) or 'device' (on the GPU, the "
+                        "same bytes). Not with .npy inputs")
+    return p
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    kw = dict(batch=args.batch, video_decoder=args.video_decoder, video_encoder=args.video_encoder)
     pairs = pairs_from_arguments(args.sbs_color_video, args.sbs_mask_video)
     if _is_txt(args.sbs_color_video):
         # (the reference runs two clips at a time with the GPU sections serialised, bni:262-274; here a clip is I/O and one
@@ -137,11 +218,11 @@ def main(argv=None):
         print(f"Batch mode: {len(pairs)} pairs")
         for c_path, m_path in pairs:
             try:
-                print("Done. Wrote:", process_pair(c_path, m_path, args.max_frames))
+                print("Done. Wrote:", process_pair(c_path, m_path, args.max_frames, **kw))
             except Exception as e:                                    # bni:270-274: surface the error, keep the other clips going
                 print(f"[ERROR] A clip failed: {e}")
         return 0
-    print("Done. Wrote:", process_pair(*pairs[0], args.max_frames))
+    print("Done. Wrote:", process_pair(*pairs[0], args.max_frames, **kw))
     return 0
 
 

@@ -3,7 +3,8 @@ for frame dumps, with frames streamed through the GPU in batches and sharded ove
 
 On-disk formats.  The reference reads/writes FFV1-in-MKV through OpenCV (sr:327-341, 435-444, 941).  This driver does the
 same when --depth_video is a Matroska file (video_io.py / libmdvt_video.so: a host-side FFV1 + Matroska reader and writer written
-from the RFCs; a device-side FFV1 codec is out of scope): `x.mkv` [+ `y.mkv`] in, `x.mkv_stereo.mkv`, `x.mkv_stereo.mkv_infillmask.mkv`,
+from the RFCs; ffv1_device.py codes and decodes the writer's own stream class on the GPU, opt-in: video_encoder / video_decoder
+= "device"): `x.mkv` [+ `y.mkv`] in, `x.mkv_stereo.mkv`, `x.mkv_stereo.mkv_infillmask.mkv`,
 `x.mkv_stereo.mkv_depth.mkv` (the reference's names, sr:411-444) and `x.mkv_stereo.mkv_holemask.mkv` (this build's extra, grey) out,
 each written as `x.mkv_tmp_...` and renamed once its frame count is right (dfh:163-179).  A colour video in another codec
 (H.264 ...) cannot be decoded here.  Otherwise it works on raw frame dumps, the format for benchmarking:
@@ -42,6 +43,7 @@ from __future__ import annotations
 import json
 import math
 import os
+import threading
 from typing import Optional
 
 import numpy as np
@@ -259,7 +261,6 @@ class VideoFrames:
     last key frame, so it gets ONE decoder and all the slice threads instead of several decoders leap-frogging)."""
 
     def __init__(self, path: str, readers: int = 2):
-        import threading
         from . import video_io
         first = video_io.VideoReader(path)
         self.path, self.fps, self.info = path, first.fps, first.info
@@ -272,9 +273,46 @@ class VideoFrames:
         self._pos = [0] * n
         self._busy = [False] * n
         self._cv = threading.Condition()
+        # render_clip decodes this file's frames on the device (use_device_decoder): it asks for packets, not for frames
+        self.device_decode = False
+        self._packet_reader = None
 
     def __len__(self):
         return self.shape[0]
+
+    def use_device_decoder(self, name: str = "input") -> bool:
+        """Switches render_clip's reads of this file to the device decoder (ffv1_device) if the stream is in its class; if not,
+        says so on stderr and leaves the host decoder in charge (files the reference made must keep working)."""
+        import sys
+        from . import ffv1_device
+        self.config = self._readers[0].config_record()
+        why = ffv1_device.supported(self.info, self.config)
+        if why is not None:
+            print(f"video_decoder device: {name} {self.path} is decoded on the host ({why})", file=sys.stderr)
+            return False
+        self.device_decode = True
+        return True
+
+    def read_packets(self, a: int, n: int):
+        """The stored FFV1 packets of frames a ... a + n - 1 (a reader of its own: packets are not decoded, so nothing is shared
+        with the decoders' positions)."""
+        with self._cv:
+            if self._packet_reader is None:
+                from . import video_io
+                self._packet_reader = [video_io.VideoReader(self.path, threads=1), -1, threading.Lock()]
+        r = self._packet_reader
+        with r[2]:
+            if r[1] != a:
+                r[0].seek(a)
+            out = []
+            for i in range(n):
+                pkt = r[0].next_packet()
+                if pkt is None:
+                    r[1] = -1
+                    raise IOError(f"{self.path}: ends at frame {a + i}")
+                out.append(pkt)
+            r[1] = a + n
+        return out
 
     def read_into(self, dst: np.ndarray, a: int, n: int):
         with self._cv:
@@ -327,9 +365,12 @@ class VideoFrames:
     def close(self):
         for r in self._readers:
             r.close()
+        if self._packet_reader is not None:
+            self._packet_reader[0].close()
 
 
 VIDEO_ENCODERS = ("host", "device")
+VIDEO_DECODERS = ("host", "device")
 
 
 class VideoSink:
@@ -495,6 +536,17 @@ def render_clip(depth_frames, color_frames, out_sbs, out_mask, clip: D.ClipParam
         from ._lib import Context
         enc_ctx = Context(r.device, 16, 16)        # (its own workspace; the render size does not matter to the encoder)
 
+    # inputs decoded on the device (VideoFrames.use_device_decoder): their packets are copied as stored, raw frames never exist on the host
+    dec_d = isinstance(depth_frames, VideoFrames) and depth_frames.device_decode
+    dec_c = isinstance(color_frames, VideoFrames) and color_frames.device_decode
+    same_video = color_frames is depth_frames and isinstance(depth_frames, VideoFrames)
+    dec_ctx = None
+    if dec_d or dec_c:
+        from . import ffv1_device
+        from ._lib import Context
+        dec_ctx = Context(r.device, 16, 16)
+    dec_host_frames = [0]
+
     f_depth, f_color = _RawFrames(depth_frames, False), _RawFrames(color_frames, False)
     f_sbs, f_mask = _RawFrames(out_sbs, True), _RawFrames(out_mask, True)
     f_zrgb = _RawFrames(out_depth_rgb, True) if out_depth_rgb is not None else None
@@ -507,13 +559,25 @@ def render_clip(depth_frames, color_frames, out_sbs, out_mask, clip: D.ClipParam
         t_l = time.perf_counter()
         st["in_done"].synchronize()                 # the H2D copies that last read these pinned buffers are done
         t_l1 = time.perf_counter()
-        if color_frames is depth_frames and isinstance(depth_frames, VideoFrames):      # sr:508-509 on one video: decode it once
+        st["p_d"] = st["p_c"] = None
+        if same_video and dec_d:                    # one video, decoded once on the device
+            st["p_d"] = depth_frames.read_packets(a, n)
+            jobs = []
+        elif same_video:                            # sr:508-509 on one video: decode it once
             for j in fan(f_depth.read_into, st["h_d"][:n].numpy(), a, n, 2):
                 j.result()
             np.copyto(st["h_c"][:n].numpy(), st["h_d"][:n].numpy())
             jobs = []
         else:
-            jobs = fan(f_color.read_into, st["h_c"][:n].numpy(), a, n, 2) + fan(f_depth.read_into, st["h_d"][:n].numpy(), a, n, 2)
+            jobs = []
+            if dec_c:
+                st["p_c"] = color_frames.read_packets(a, n)
+            else:
+                jobs += fan(f_color.read_into, st["h_c"][:n].numpy(), a, n, 2)
+            if dec_d:
+                st["p_d"] = depth_frames.read_packets(a, n)
+            else:
+                jobs += fan(f_depth.read_into, st["h_d"][:n].numpy(), a, n, 2)
         for j in jobs:
             j.result()
         if trace is not None:
@@ -604,8 +668,23 @@ def render_clip(depth_frames, color_frames, out_sbs, out_mask, clip: D.ClipParam
             st["stored"].result()                   # this set's pinned outputs have been written out
         with torch.cuda.stream(s_in):
             s_in.wait_event(st["render_done"])      # device inputs free again
-            st["d_d"][:n].copy_(st["h_d"][:n], non_blocking=True)
-            st["d_c"][:n].copy_(st["h_c"][:n], non_blocking=True)
+            pend = []
+            if st["p_d"] is not None:               # packets -> device -> frames, straight into the batch's input tensors
+                pend.append(ffv1_device.enqueue_decode(dec_ctx, st["p_d"], depth_frames.config, W, H, out=st["d_d"][:n], stream=s_in))
+            else:
+                st["d_d"][:n].copy_(st["h_d"][:n], non_blocking=True)
+            if st["p_c"] is not None:
+                pend.append(ffv1_device.enqueue_decode(dec_ctx, st["p_c"], color_frames.config, W, H, out=st["d_c"][:n], stream=s_in))
+            elif same_video and dec_d:
+                st["d_c"][:n].copy_(st["d_d"][:n], non_blocking=True)
+            else:
+                st["d_c"][:n].copy_(st["h_c"][:n], non_blocking=True)
+            for p in pend:                          # a frame the device flagged is decoded on the host (or raises the host's error)
+                p.collect()
+                dec_host_frames[0] += p.host_frames
+            if same_video and dec_d and pend[0].host_frames:
+                st["d_c"][:n].copy_(st["d_d"][:n], non_blocking=True)
+            st["p_d"] = st["p_c"] = None
             st["in_done"].record(s_in)
         s_cmp.wait_event(st["in_done"])
         s_cmp.wait_event(st["out_done"])            # device outputs free again
@@ -676,6 +755,11 @@ def render_clip(depth_frames, color_frames, out_sbs, out_mask, clip: D.ClipParam
             f.close()
     if enc_ctx is not None:
         enc_ctx.close()
+    if dec_ctx is not None:
+        dec_ctx.close()
+        if dec_host_frames[0]:
+            import warnings
+            warnings.warn(f"{dec_host_frames[0]} input frame(s) were flagged by the device decoder and decoded on the host (same bytes)")
     r.close()
     return hi - lo, dt, holes
 
@@ -902,25 +986,43 @@ def check_video_encoder(video_encoder: str, video: bool):
                          "which are not encoded (use the default --video_encoder host)")
 
 
+def check_video_decoder(video_decoder: str, video: bool) -> str:
+    """ValueError unless video_decoder is "host" or "device", and "device" only where the inputs are .mkv files."""
+    if video_decoder not in VIDEO_DECODERS:
+        raise ValueError(f"video_decoder must be one of {VIDEO_DECODERS}, got {video_decoder!r}")
+    if video_decoder == "device" and not video:
+        raise ValueError("--video_decoder device decodes .mkv inputs: a .npy input is a raw frame dump, which is not decoded "
+                         "(use the default --video_decoder host)")
+    return video_decoder
+
+
 def run(depth_path: str, color_path: Optional[str], *, batch: int = 16, create_sbs_depth_video: bool = False,
         max_frames: int = -1, green_and_black_infill_mask: bool = False, backend: Optional[str] = None,
         normal_infill: bool = False, inpaint_order: str = "levels", multisample: Optional[dict] = None, near_clip: bool = False,
-        video_encoder: str = "host",
+        video_encoder: str = "host", video_decoder: str = "host",
         **clip_kwargs):
     """File-level entry (what `python stereo_rerender.py --depth_video ...` is to the reference).
     Multi-process aware: under torchrun every rank renders its own contiguous frame range into its own output segment
     files (plan_outputs); rank 0 adds the index.  `backend`: torch.distributed backend (default: RCCL when a GPU is
     visible; MDVT_DIST_BACKEND overrides -- the two-ranks-on-one-GPU tests use gloo).  video_encoder: "host" (default) or
-    "device" (the .mkv outputs are FFV1-encoded on the GPU: the same bytes; refused for .npy outputs, which are not encoded)."""
+    "device" (the .mkv outputs are FFV1-encoded on the GPU: the same bytes; refused for .npy outputs, which are not encoded).
+    video_decoder: "host" (default) or "device" (the .mkv inputs' packets are copied to the GPU and decoded there, straight into
+    the batch's input tensors: the same bytes; an input outside the device's stream class is read by the host decoder, with one
+    line on stderr; refused for .npy inputs, which are not decoded)."""
     from . import video_io
     video = video_io.is_matroska(depth_path)                 # the reference's own format (sr:326-341): outputs follow it
     check_video_encoder(video_encoder, video)
+    check_video_decoder(video_decoder, video)
     rank, world = D.init_process_group(backend or os.environ.get("MDVT_DIST_BACKEND"))
     depth = VideoFrames(depth_path) if video else np.load(depth_path, mmap_mode="r")
     if color_path is None:
         color = depth                                                                                  # sr:508-509
     else:
         color = VideoFrames(color_path) if video_io.is_matroska(color_path) else np.load(color_path, mmap_mode="r")
+    if video_decoder == "device":
+        depth.use_device_decoder("depth video")
+        if color is not depth and isinstance(color, VideoFrames):
+            color.use_device_decoder("color video")
     if depth.ndim != 4 or depth.shape[3] != 3 or depth.dtype != np.uint8:
         raise ValueError("depth dump must be uint8 [N, H, W, 3]")
     if color.shape != depth.shape:

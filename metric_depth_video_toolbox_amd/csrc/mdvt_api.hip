@@ -2,6 +2,8 @@
 // Host code only; the kernels are in mdvt_kernels.hip.  Compiled with -ffp-contract=off (the f64
 // composition of the eye matrices below is part of the arithmetic decree).
 #include "mdvt_internal.h"
+#include "mdvt_ffv1_core.h"
+#include "mdvt_ffv1_decode.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -89,6 +91,9 @@ struct mdvt_ctx {
     // FFV1 encoding (mdvt_encode_video_frames): the running packet offset (8 B), then per slice of a pass its size word and scratch
     uint8_t* ffv1_ws = nullptr;
     size_t ffv1_bytes = 0;
+    // FFV1 decoding (mdvt_decode_video_frames): per slice of a pass its offset, payload bytes and cell claim
+    uint8_t* ffv1_dec_ws = nullptr;
+    size_t ffv1_dec_bytes = 0;
     // normal_infill / infill_using_mask_normals: about 16 B/px per image in flight
     uint8_t* ni_ws = nullptr;
     int ni_images = 0;
@@ -852,6 +857,7 @@ int mdvt_destroy(mdvt_ctx* c)
     free_telea_heap(c);
     if (c->ni_ws) ws_free(c, c->ni_ws);
     if (c->ffv1_ws) ws_free(c, c->ffv1_ws);
+    if (c->ffv1_dec_ws) ws_free(c, c->ffv1_dec_ws);
     delete c;
     return MDVT_OK;
 }
@@ -1887,6 +1893,70 @@ int mdvt_encode_video_frames(mdvt_ctx* c, int width, int height, int slices_h, i
         const mdvt::Ffv1EmitArgs ea{slice_n, scratch, slice_stride, spf, d_sizes + f0, reinterpret_cast<unsigned long long*>(d_offsets) + f0,
                                     d_packets};
         MDVT_HIP(c, mdvt::launch_ffv1_emit(ea, nf * spf, s));
+    }
+    return MDVT_OK;
+}
+
+const char* mdvt_ffv1_decode_supported(const uint8_t* h_config, size_t config_size)
+{
+    mdvt_ffv1::StreamClass sc{};
+    return mdvt_ffv1::parse_stream_class(h_config, config_size, &sc);
+}
+
+// FFV1 packets in device memory -> frames (mdvt_ffv1_decode.hip).  Passes: as many frames as the ctx's workspace budget affords.
+int mdvt_decode_video_frames(mdvt_ctx* c, int width, int height, const uint8_t* h_config, size_t config_size, const uint8_t* d_packets,
+                             uint64_t packets_bytes, const uint64_t* d_offsets, const uint32_t* d_sizes, int n_frames, uint8_t* d_dst,
+                             size_t pitch, size_t frame_stride, int order, uint32_t* d_status, void* stream)
+{
+    if (!c) return MDVT_ERR_INVALID_ARG;
+    if (!h_config || !d_packets || !d_offsets || !d_sizes || !d_dst || !d_status) return fail(c, MDVT_ERR_INVALID_ARG, "NULL buffer");
+    if (width < 1 || height < 1) return fail(c, MDVT_ERR_INVALID_ARG, "bad frame size %d x %d", width, height);
+    if (order != 0 && order != 1) return fail(c, MDVT_ERR_INVALID_ARG, "order must be 0 (RGB) or 1 (BGR), got %d", order);
+    if (n_frames < 1) return fail(c, MDVT_ERR_INVALID_ARG, "n_frames must be >= 1");
+    if (pitch < (size_t)width * 3u) return fail(c, MDVT_ERR_INVALID_ARG, "pitch smaller than one row");
+    if (n_frames > 1 && frame_stride < pitch * (size_t)height) return fail(c, MDVT_ERR_INVALID_ARG, "frame_stride smaller than one frame");
+    mdvt_ffv1::StreamClass sc{};
+    if (const char* why = mdvt_ffv1::parse_stream_class(h_config, config_size, &sc))
+        return fail(c, MDVT_ERR_UNSUPPORTED, "FFV1 stream outside the device decoder's class: %s", why);
+    if (sc.nh > width || sc.nv > height)
+        return fail(c, MDVT_ERR_UNSUPPORTED, "FFV1 stream outside the device decoder's class: num_h_slices / num_v_slices %d x %d for a frame of %d x %d",
+                    sc.nh, sc.nv, width, height);
+    if ((uint64_t)width * (uint64_t)height > ((uint64_t)1 << 28))
+        return fail(c, MDVT_ERR_UNSUPPORTED, "frame too large for the device FFV1 decoder (%d x %d)", width, height);
+    const int line_stride = (width + sc.nh - 1) / sc.nh + 2;           // the widest slice, its left and right neighbours
+    if (mdvt::ffv1_decode_static_lds_bytes() + mdvt::ffv1_decode_lds_bytes(line_stride) > (size_t)160 * 1024)
+        return fail(c, MDVT_ERR_UNSUPPORTED, "a slice of %d pixels' width does not fit the device FFV1 decoder's row buffers (num_h_slices %d)",
+                    line_stride - 2, sc.nh);
+    DeviceGuard g(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    const int spf = sc.nh * sc.nv;
+    const size_t per_frame = (size_t)spf * 3 * sizeof(uint32_t);
+    const size_t budget = (size_t)(c->cfg.workspace_mib ? c->cfg.workspace_mib : 4096u) << 20;
+    int fchunk = (int)(budget / per_frame > (size_t)n_frames ? (size_t)n_frames : budget / per_frame);
+    if (fchunk < 1) fchunk = 1;
+    const size_t need = (size_t)fchunk * per_frame;
+    if (c->ffv1_dec_bytes < need) {
+        MDVT_HIP(c, hipDeviceSynchronize());                 // earlier submissions may still use the old workspace
+        if (c->ffv1_dec_ws) ws_free(c, c->ffv1_dec_ws);
+        c->ffv1_dec_ws = nullptr; c->ffv1_dec_bytes = 0;
+        MDVT_HIP(c, ws_malloc(c, (void**)&c->ffv1_dec_ws, need, s));
+        c->ffv1_dec_bytes = need;
+    }
+    static const mdvt::Ffv1StateTables tab = mdvt::ffv1_default_states();
+    mdvt::Ffv1DecodeArgs a{};
+    a.packets = d_packets; a.packets_bytes = packets_bytes;
+    a.W = width; a.H = height; a.nh = sc.nh; a.nv = sc.nv; a.ec = sc.ec;
+    a.pitch = pitch; a.frame_stride = frame_stride; a.ri = order == 1 ? 2 : 0; a.bi = order == 1 ? 0 : 2;
+    a.line_stride = line_stride;
+    for (int f0 = 0; f0 < n_frames; f0 += fchunk) {
+        const int nf = n_frames - f0 < fchunk ? n_frames - f0 : fchunk;
+        a.n_frames = nf;
+        a.offsets = reinterpret_cast<const unsigned long long*>(d_offsets) + f0; a.sizes = d_sizes + f0;
+        a.dst = d_dst + (size_t)f0 * frame_stride; a.status = d_status + f0;
+        a.table = reinterpret_cast<uint32_t*>(c->ffv1_dec_ws);
+        a.claims = a.table + (size_t)2 * nf * spf;
+        MDVT_HIP(c, hipMemsetAsync(a.claims, 0, (size_t)nf * spf * sizeof(uint32_t), s));
+        MDVT_HIP(c, mdvt::launch_ffv1_decode(a, tab, s));
     }
     return MDVT_OK;
 }

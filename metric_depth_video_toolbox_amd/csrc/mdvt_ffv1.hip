@@ -15,29 +15,17 @@
 //                  error byte, and the CRC-32 of both: the lanes take contiguous chunks, each chunk's CRC is shifted over the
 //                  bytes behind it (multiplication by x^(8 n) mod P in GF(2)) and the shifted CRCs are XORed.
 #include "mdvt_internal.h"
+#include "mdvt_ffv1_core.h"
 
 namespace mdvt {
 namespace {
 
 constexpr int kFfv1Threads = 64;
-constexpr int kContexts = (11 * 11 * 11 + 1) / 2;         // 666
-constexpr int kStateBytes = kContexts * 32;                // one state set
+using mdvt_ffv1::kStateBytes;                               // one state set: 666 contexts x 32 B (mdvt_ffv1_core.h, with the tables and the CRC algebra)
+using mdvt_ffv1::quant11;
+using mdvt_ffv1::median3;
+using mdvt_ffv1::crc_shift;
 constexpr int kRecChunk = 2048;                             // records per coding chunk (8 KiB of LDS)
-
-// FFmpeg's quant11 (the host's quant11_of): the 11-level quantisation of (difference & 0xFF), with the i == 128 entry at -5
-__device__ __forceinline__ int quant11(int i)
-{
-    const int d = i < 128 ? i : i - 256;
-    const int a = d < 0 ? -d : d;
-    int q = a == 0 ? 0 : a < 2 ? 1 : a < 5 ? 2 : a < 12 ? 3 : a < 32 ? 4 : 5;
-    if (i == 128) q = 5;
-    return d < 0 ? -q : q;
-}
-
-__device__ __forceinline__ int median3(int a, int b, int c)
-{
-    return a > b ? (b > c ? b : (a > c ? c : a)) : (a > c ? a : (b > c ? c : b));
-}
 
 struct SliceGeom { int x0, y0, sw, sh; };
 
@@ -231,28 +219,6 @@ __global__ void __launch_bounds__(kFfv1Threads) k_ffv1_layout(Ffv1LayoutArgs a)
     }
 }
 
-// a(x) * b(x) mod P(x), P = 0x104C11DB7, most significant bit = highest power
-__device__ __forceinline__ uint32_t gf2_mulmod(uint32_t a, uint32_t b)
-{
-    uint32_t r = 0;
-    for (int k = 31; k >= 0; --k) {
-        r = (r << 1) ^ ((r & 0x80000000u) ? 0x04C11DB7u : 0u);
-        if ((b >> k) & 1u) r ^= a;
-    }
-    return r;
-}
-
-// crc * x^(8 n) mod P: the CRC of a chunk followed by n more bytes (initial value 0, no final XOR: the CRC is linear)
-__device__ uint32_t crc_shift(uint32_t crc, uint32_t n)
-{
-    uint32_t p = 0x100u;                                   // x^8
-    for (; n && crc; n >>= 1) {                            // (at most 32 rounds)
-        if (n & 1u) crc = gf2_mulmod(crc, p);
-        p = gf2_mulmod(p, p);
-    }
-    return crc;
-}
-
 __global__ void __launch_bounds__(kFfv1Threads) k_ffv1_emit(Ffv1EmitArgs a)
 {
     __shared__ uint32_t s_crc[256];
@@ -263,9 +229,7 @@ __global__ void __launch_bounds__(kFfv1Threads) k_ffv1_emit(Ffv1EmitArgs a)
     const uint32_t fsize = a.sizes[f];
     if (fsize >= kSliceTooLarge) return;                   // flagged frame: nothing is written
     for (int k = tid; k < 256; k += kFfv1Threads) {
-        uint32_t v = (uint32_t)k << 24;
-        for (int b = 0; b < 8; ++b) v = (v << 1) ^ ((v & 0x80000000u) ? 0x04C11DB7u : 0u);
-        s_crc[k] = v;
+        s_crc[k] = mdvt_ffv1::crc_table_entry((uint32_t)k);
     }
     // this slice's place: the frame's offset + the earlier slices of the frame
     unsigned long long before = 0;
@@ -304,29 +268,7 @@ __global__ void __launch_bounds__(kFfv1Threads) k_ffv1_emit(Ffv1EmitArgs a)
 Ffv1StateTables ffv1_default_states()
 {
     Ffv1StateTables s;
-    const long long one = 1LL << 32;
-    const int factor = (int)(0.05 * (double)(1LL << 32));
-    const int max_p = 256 - 8;
-    for (int k = 0; k < 256; ++k) { s.zero[k] = 0; s.one[k] = 0; }
-    int last_p8 = 0;
-    long long p = one / 2;
-    for (int k = 0; k < 128; ++k) {
-        int p8 = (int)((256 * p + one / 2) >> 32);
-        if (p8 <= last_p8) p8 = last_p8 + 1;
-        if (last_p8 && last_p8 < 256 && p8 <= max_p) s.one[last_p8] = (uint8_t)p8;
-        p += ((one - p) * factor + one / 2) >> 32;
-        last_p8 = p8;
-    }
-    for (int k = 256 - max_p; k <= max_p; ++k) {
-        if (s.one[k]) continue;
-        p = (k * one + 128) >> 8;
-        p += ((one - p) * factor + one / 2) >> 32;
-        int p8 = (int)((256 * p + one / 2) >> 32);
-        if (p8 <= k) p8 = k + 1;
-        if (p8 > max_p) p8 = max_p;
-        s.one[k] = (uint8_t)p8;
-    }
-    for (int k = 1; k < 255; ++k) s.zero[k] = (uint8_t)(256 - s.one[256 - k]);
+    mdvt_ffv1::default_states(s.zero, s.one);
     return s;
 }
 

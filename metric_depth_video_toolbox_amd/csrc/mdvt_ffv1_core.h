@@ -1,0 +1,310 @@
+// mdvt_ffv1_core.h -- the parts of FFV1 (RFC 9043) that the device encoder (mdvt_ffv1.hip), the device decoder
+// (mdvt_ffv1_decode.hip), the C ABI (mdvt_api.hip) and a host test program share: the tables, the CRC algebra, the slice-table
+// walk, the configuration record's parser and the range decoder of one slice.  Plain C++: it compiles for the host alone (g++,
+// where the tests run it under the sanitizers) and for host + device under hipcc; no HIP intrinsic, no allocation, no recursion.
+//
+// The decoder side restates csrc_host/mdvt_video.cpp (RacDec, get_symbol, Decoder::decode_frame / decode_slice) for the one
+// stream class the device reads: version 3, range coder with the default state table, key frames only, RGB (JPEG 2000 RCT),
+// 8 bits, no alpha, the default 666-context quantisation tables.  Nothing read from a packet steers a loop or an address: every
+// loop runs to a count fixed by the frame's geometry, bytes past a slice's end read as zero and are counted (the host's overread),
+// a symbol's exponent loop has the RFC's bound, and a context index is bounded by the quantisation arithmetic (|ctx| <= 665).
+#pragma once
+
+#include <stddef.h>
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define MDVT_HD __host__ __device__ inline
+#else
+#define MDVT_HD inline
+#endif
+
+namespace mdvt_ffv1 {
+
+constexpr int kContexts = (11 * 11 * 11 + 1) / 2;         // 666
+constexpr int kStateBytes = kContexts * 32;                // one state set
+constexpr int kMaxSlices = 1024;                           // slices per frame the device codes / decodes
+
+// per-frame status words of mdvt_decode_video_frames (include/mdvt_ffv1_decode.h); the largest of a frame's slices wins
+enum : uint32_t { kOk = 0, kCrcMismatch = 1, kBadSliceHeader = 2, kDamaged = 3, kBadPacket = 4 };
+
+// FFmpeg's quant11 (the host's quant11_of): the 11-level quantisation of (difference & 0xFF), with the i == 128 entry at -5
+MDVT_HD int quant11(int i)
+{
+    const int d = i < 128 ? i : i - 256;
+    const int a = d < 0 ? -d : d;
+    int q = a == 0 ? 0 : a < 2 ? 1 : a < 5 ? 2 : a < 12 ? 3 : a < 32 ? 4 : 5;
+    if (i == 128) q = 5;
+    return d < 0 ? -q : q;
+}
+
+MDVT_HD int median3(int a, int b, int c)
+{
+    return a > b ? (b > c ? b : (a > c ? c : a)) : (a > c ? a : (b > c ? c : b));
+}
+
+// the default state-transition table (RFC 9043 section 3.8.1.3), built as the host encoder builds it
+inline void default_states(uint8_t* zero, uint8_t* one_state)
+{
+    const long long one = 1LL << 32;
+    const int factor = (int)(0.05 * (double)(1LL << 32));
+    const int max_p = 256 - 8;
+    for (int k = 0; k < 256; ++k) { zero[k] = 0; one_state[k] = 0; }
+    int last_p8 = 0;
+    long long p = one / 2;
+    for (int k = 0; k < 128; ++k) {
+        int p8 = (int)((256 * p + one / 2) >> 32);
+        if (p8 <= last_p8) p8 = last_p8 + 1;
+        if (last_p8 && last_p8 < 256 && p8 <= max_p) one_state[last_p8] = (uint8_t)p8;
+        p += ((one - p) * factor + one / 2) >> 32;
+        last_p8 = p8;
+    }
+    for (int k = 256 - max_p; k <= max_p; ++k) {
+        if (one_state[k]) continue;
+        p = (k * one + 128) >> 8;
+        p += ((one - p) * factor + one / 2) >> 32;
+        int p8 = (int)((256 * p + one / 2) >> 32);
+        if (p8 <= k) p8 = k + 1;
+        if (p8 > max_p) p8 = max_p;
+        one_state[k] = (uint8_t)p8;
+    }
+    for (int k = 1; k < 255; ++k) zero[k] = (uint8_t)(256 - one_state[256 - k]);
+}
+
+// ---- CRC-32, generator 0x04C11DB7, most significant bit first, initial value 0, no final XOR ----
+MDVT_HD uint32_t crc_table_entry(uint32_t k)
+{
+    uint32_t v = k << 24;
+    for (int b = 0; b < 8; ++b) v = (v << 1) ^ ((v & 0x80000000u) ? 0x04C11DB7u : 0u);
+    return v;
+}
+
+// a(x) * b(x) mod P(x), P = 0x104C11DB7, most significant bit = highest power
+MDVT_HD uint32_t gf2_mulmod(uint32_t a, uint32_t b)
+{
+    uint32_t r = 0;
+    for (int k = 31; k >= 0; --k) {
+        r = (r << 1) ^ ((r & 0x80000000u) ? 0x04C11DB7u : 0u);
+        if ((b >> k) & 1u) r ^= a;
+    }
+    return r;
+}
+
+// crc * x^(8 n) mod P: the CRC of a chunk followed by n more bytes (initial value 0, no final XOR: the CRC is linear)
+MDVT_HD uint32_t crc_shift(uint32_t crc, uint32_t n)
+{
+    uint32_t p = 0x100u;                                   // x^8
+    for (; n && crc; n >>= 1) {                            // (at most 32 rounds)
+        if (n & 1u) crc = gf2_mulmod(crc, p);
+        p = gf2_mulmod(p, p);
+    }
+    return crc;
+}
+
+// ---- the slice table: every slice ends in a 24-bit payload size (+ an error byte + a CRC-32 when ec), so the extents are found
+// by walking back from the packet's end (the host reader's checks, Decoder::decode_frame).  `byte(k)` reads packet byte k < size.
+// n <= kMaxSlices steps.  -> kOk, or kBadPacket with nothing in off / len to be used. ----
+template <class Byte>
+MDVT_HD uint32_t walk_slices(Byte byte, uint32_t size, int n, int ec, uint32_t* off, uint32_t* len)
+{
+    if (size < 3u) return kBadPacket;
+    const uint32_t trailer = 3u + (ec ? 5u : 0u);
+    uint32_t end = size;
+    for (int i = n - 1; i >= 0; --i) {
+        if (end < trailer) return kBadPacket;                                    // "packet too short for n slices"
+        const uint32_t t = end - trailer;
+        const uint32_t payload = ((uint32_t)byte(t) << 16) | ((uint32_t)byte(t + 1u) << 8) | (uint32_t)byte(t + 2u);
+        if (payload + trailer > end) return kBadPacket;                          // "slice i claims ... bytes"
+        off[i] = end - trailer - payload;
+        len[i] = payload;
+        end = off[i];
+    }
+    return end ? kBadPacket : kOk;                                               // "stray bytes before the first slice"
+}
+
+// ---- the range decoder (the host's RacDec) over a byte source: Src::byte(k) for k < avail ----
+template <class Src>
+struct RacDec {
+    Src src;
+    uint32_t pos, end;             // next byte, and the first byte that reads as zero
+    int low, range, overread;
+    const uint16_t* next;          // next[s] = zero_state[s] | one_state[s] << 8: one lookup per decision, whatever the bit
+
+    MDVT_HD int get(uint8_t* state)
+    {
+        const int s = *state;
+        const unsigned t = next[s];
+        const int range1 = (range * s) >> 8;
+        range -= range1;
+        int bit;
+        if (low < range) { *state = (uint8_t)t; bit = 0; }
+        else { low -= range; range = range1; *state = (uint8_t)(t >> 8); bit = 1; }
+        if (range < 0x100) {
+            range <<= 8; low <<= 8;
+            if (pos < end) low += src.byte(pos++);
+            else ++overread;
+        }
+        return bit;
+    }
+
+    // the range-coded integer binarisation (RFC 9043 section 3.8.1.2): 32 states per context; the exponent has the RFC's bound
+    MDVT_HD int symbol(uint8_t* state, bool is_signed, bool* bad)
+    {
+        if (get(state)) return 0;
+        int e = 0;
+        while (get(state + 1 + (e < 9 ? e : 9))) {
+            if (++e > 31) { *bad = true; return 0; }
+        }
+        unsigned a = 1;
+        for (int i = e - 1; i >= 0; --i) a += a + (unsigned)get(state + 22 + (i < 9 ? i : 9));
+        const int neg = (is_signed && get(state + 11 + (e < 10 ? e : 10))) ? -1 : 0;
+        return (int)((a ^ (unsigned)neg) - (unsigned)neg);
+    }
+};
+
+// One slice of an in-class frame.  The caller owns the memory: `st` two state sets (2 * kStateBytes, all 128), `lines` three
+// planes x three row slots x `stride` samples (stride >= slice width + 2, all zero), `misc` 64 bytes, q11[256] = quant11.
+// begin() reads the key-frame bit (first slice) and the slice header; row(y) decodes the three planes of slice row y into slot
+// y % 3 (sample k of plane p at lines[(p * 3 + y % 3) * stride + 1 + k]: Y, Cb + 256, Cr + 256 of the RCT); finish() gives the status.
+template <class Src>
+struct SliceDec {
+    RacDec<Src> c;
+    uint8_t* st; int16_t* lines; uint8_t* misc; const int8_t* q11;
+    int stride, sw, sh, x0, y0, cell;        // cell: the slice's index in the frame's nh x nv grid
+    bool error;
+
+    // `avail` bytes can be read through src (the payload and what follows it in the packet), `size` of them are the payload
+    MDVT_HD uint32_t begin(Src src, uint32_t avail, uint32_t size, bool first, int W, int H, int nh, int nv, const uint16_t* next)
+    {
+        c.src = src; c.next = next;
+        c.range = 0xFF00; c.overread = 0; c.pos = 2; c.end = size;
+        error = false; sw = sh = 0; x0 = y0 = 0; cell = 0;
+        // the host starts the first slice's coder on the whole packet (>= 3 bytes), the others on their payload (>= 2 bytes, or refused)
+        if (first ? avail < 2u : size < 2u) return kDamaged;
+        c.low = ((int)src.byte(0) << 8) | (int)src.byte(1);
+        if (c.low >= 0xFF00) { c.low = 0xFF00; if (!first) c.end = 2; }
+        for (int k = 0; k < 64; ++k) misc[k] = 128;
+        if (first && !c.get(misc + 32)) return kBadSliceHeader;                   // not a key frame: outside the device's class
+        bool bad = false;
+        const unsigned sx = (unsigned)c.symbol(misc, false, &bad), sy = (unsigned)c.symbol(misc, false, &bad);
+        const unsigned cw = (unsigned)c.symbol(misc, false, &bad) + 1u, ch = (unsigned)c.symbol(misc, false, &bad) + 1u;
+        if (bad || sx >= (unsigned)nh || sy >= (unsigned)nv || cw > (unsigned)nh - sx || ch > (unsigned)nv - sy) return kBadSliceHeader;
+        // nh * nv slices share nh * nv cells: a slice of more than one cell overlaps another or leaves a hole (the caller checks
+        // that no two slices claim the same cell, so the frame's slices tile it)
+        if (cw != 1u || ch != 1u) return kBadSliceHeader;
+        for (int p = 0; p < 2; ++p)
+            if (c.symbol(misc, false, &bad) != 0 || bad) return kBadSliceHeader;     // quant_table_set_index: one set
+        (void)c.symbol(misc, false, &bad);                                         // picture_structure, sar_num, sar_den
+        (void)c.symbol(misc, false, &bad);
+        (void)c.symbol(misc, false, &bad);
+        if (bad) return kBadSliceHeader;
+        cell = (int)(sy * (unsigned)nh + sx);
+        x0 = (int)((long long)sx * W / nh); y0 = (int)((long long)sy * H / nv);
+        sw = (int)((long long)(sx + 1u) * W / nh) - x0; sh = (int)((long long)(sy + 1u) * H / nv) - y0;
+        if (sw < 1 || sh < 1 || sw + 2 > stride) return kBadSliceHeader;
+        return kOk;
+    }
+
+    MDVT_HD void row(int y)
+    {
+        const int cs = y % 3, ls = (y + 2) % 3;
+        for (int p = 0; p < 3; ++p) {
+            int16_t* cur = lines + (size_t)(p * 3 + cs) * (size_t)stride + 1;
+            int16_t* last = lines + (size_t)(p * 3 + ls) * (size_t)stride + 1;
+            cur[-1] = last[0];
+            last[sw] = last[sw - 1];
+            uint8_t* states = st + (p ? kStateBytes : 0);
+            int L = cur[-1], LT = last[-1], T = last[0];
+            int q_lt_t = q11[(LT - T) & 0xFF];                 // (this sample's T - RT is the next one's LT - T)
+            for (int x = 0; x < sw; ++x) {
+                const int RT = last[x + 1];
+                const int q_t_rt = q11[(T - RT) & 0xFF];
+                int context = q11[(L - LT) & 0xFF] + 11 * q_lt_t + 121 * q_t_rt;
+                q_lt_t = q_t_rt;
+                const bool sign = context < 0;
+                if (sign) context = -context;
+                bool bad = false;
+                int diff = c.symbol(states + (size_t)context * 32u, true, &bad);
+                error |= bad;
+                if (sign) diff = -diff;
+                const int v = (median3(L, T, L + T - LT) + diff) & 511;
+                cur[x] = (int16_t)v;
+                L = v; LT = T; T = RT;
+            }
+        }
+    }
+
+    MDVT_HD uint32_t finish() const { return (error || c.overread > 4) ? kDamaged : kOk; }
+};
+
+// ---- the configuration record (RFC 9043 section 4.2), host side: is the stream in the device's class? ----
+struct PtrSrc {
+    const uint8_t* p;
+    MDVT_HD uint8_t byte(uint32_t k) const { return p[k]; }
+};
+
+struct StreamClass { int version, micro, nh, nv, ec; };
+
+// -> nullptr and *out when the device decodes the stream; else the reason (a static string naming the field)
+inline const char* parse_stream_class(const uint8_t* data, size_t size, StreamClass* out)
+{
+    if (!data || size < 6 || size > (1u << 20)) return "configuration record: missing or of an impossible size";
+    uint32_t crc = 0;
+    for (size_t i = 0; i < size; ++i) crc = (crc << 8) ^ crc_table_entry((crc >> 24) ^ data[i]);
+    uint8_t zero[256], one[256], state[32];
+    uint16_t next[256];
+    default_states(zero, one);
+    for (int k = 0; k < 256; ++k) next[k] = (uint16_t)(zero[k] | (one[k] << 8));
+    for (int k = 0; k < 32; ++k) state[k] = 128;
+    RacDec<PtrSrc> c;
+    c.src = PtrSrc{data}; c.next = next; c.range = 0xFF00; c.overread = 0; c.pos = 2; c.end = (uint32_t)size;
+    c.low = (data[0] << 8) | data[1];
+    if (c.low >= 0xFF00) { c.low = 0xFF00; c.end = 2; }
+    bool bad = false;
+    const int version = c.symbol(state, false, &bad);
+    if (bad || version != 3) return "version: only FFV1 version 3 is decoded on the device";
+    c.end = c.end >= 4u ? c.end - 4u : 0u;                   // the record's CRC parity is not range-coded
+    const int micro = c.symbol(state, false, &bad);
+    const int coder = c.symbol(state, false, &bad);
+    if (bad || coder != 1) return "coder_type: only the range coder with the default state table (coder_type 1) is decoded on the device";
+    const int colorspace = c.symbol(state, false, &bad);
+    if (bad || colorspace != 1) return "colorspace_type: only RGB (JPEG 2000 RCT) is decoded on the device";
+    const int bits = c.symbol(state, false, &bad);
+    if (bad || (bits != 0 && bits != 8)) return "bits_per_raw_sample: only 8 bits are decoded on the device";
+    (void)c.get(state);                                      // chroma_planes
+    (void)c.symbol(state, false, &bad);                      // log2_h_chroma_subsample, log2_v_chroma_subsample
+    (void)c.symbol(state, false, &bad);
+    if (c.get(state)) return "extra_plane: alpha planes are not decoded on the device";
+    const int nh = 1 + c.symbol(state, false, &bad), nv = 1 + c.symbol(state, false, &bad);
+    if (bad || nh < 1 || nv < 1 || nh > kMaxSlices || nv > kMaxSlices || nh * nv > kMaxSlices)
+        return "num_h_slices / num_v_slices: 1 to 1024 slices per frame are decoded on the device";
+    const int qcount = c.symbol(state, false, &bad);
+    if (bad || qcount != 1) return "quant_table_set_count: only one quantisation table set is decoded on the device";
+    int scale = 1;
+    for (int t = 0; t < 5; ++t) {                            // the host's read_quant_tables, compared with the default set
+        uint8_t qs[32];
+        for (int k = 0; k < 32; ++k) qs[k] = 128;
+        int i = 0, v = 0;
+        for (; i < 128; ++v) {
+            const unsigned len = (unsigned)c.symbol(qs, false, &bad) + 1u;
+            if (bad || len > (unsigned)(128 - i)) return "quantisation tables: malformed";
+            for (unsigned k = 0; k < len; ++k, ++i)
+                if (scale * v != (t < 3 ? scale * quant11(i) : 0))
+                    return "quantisation tables: only the default 666-context set (quant11, three inputs) is decoded on the device";
+        }
+        scale *= 2 * v - 1;
+        if (scale > 32768 || scale <= 0) return "quantisation tables: malformed";
+    }
+    if (scale != 11 * 11 * 11) return "quantisation tables: only the default 666-context set (quant11, three inputs) is decoded on the device";
+    if (c.get(state)) return "states_coded: initial states other than 128 are not decoded on the device";
+    const int ec = c.symbol(state, false, &bad);
+    if (bad || (ec != 0 && ec != 1)) return "ec: unknown error-correction mode";
+    const int intra = micro > 2 ? c.symbol(state, false, &bad) : 0;
+    if (bad) return "configuration record: malformed symbol";
+    if (!intra) return "intra: only streams whose every frame is a key frame are decoded on the device";
+    if (crc != 0) return "configuration record: CRC mismatch";
+    out->version = version; out->micro = micro; out->nh = nh; out->nv = nv; out->ec = ec;
+    return nullptr;
+}
+
+}  // namespace mdvt_ffv1

@@ -249,6 +249,20 @@ Ffv1StateTables ffv1_default_states();
 hipError_t launch_ffv1_code(const Ffv1CodeArgs& a, const Ffv1StateTables& tab, int n_slices, hipStream_t s);
 hipError_t launch_ffv1_layout(const Ffv1LayoutArgs& a, hipStream_t s);
 hipError_t launch_ffv1_emit(const Ffv1EmitArgs& a, int n_slices, hipStream_t s);
+// mdvt_ffv1_decode.hip: FFV1 decoding of packets in device memory (mdvt_decode_video_frames, include/mdvt_ffv1_decode.h)
+struct Ffv1DecodeArgs {
+    const uint8_t* packets; unsigned long long packets_bytes;      // the packet buffer and its size: no packet may pass it
+    const unsigned long long* offsets; const uint32_t* sizes;      // the caller's arrays, at the pass's first frame
+    int n_frames, W, H, nh, nv, ec;
+    uint8_t* dst; size_t pitch, frame_stride; int ri, bi;          // the pass's first frame; the byte of R and of B in a pixel
+    uint32_t* status;                                              // the caller's status words, at the pass's first frame
+    uint32_t* table;                                               // workspace [2][frames of the pass * slices]: slice offsets, payload bytes
+    uint32_t* claims;                                              // workspace [frames of the pass * slices], zeroed: a cell's claim
+    int line_stride;                                               // samples per row slot in LDS: the widest slice + 2
+};
+size_t ffv1_decode_lds_bytes(int line_stride);                     // dynamic LDS of the slice kernel
+size_t ffv1_decode_static_lds_bytes();
+hipError_t launch_ffv1_decode(const Ffv1DecodeArgs& a, const Ffv1StateTables& tab, hipStream_t s);
 hipError_t launch_selftest(int which, unsigned long long seed, unsigned long long* d_mism, hipStream_t s);
 hipError_t launch_coherence_test(uint32_t* blk, size_t dwords, uint32_t tag, uint32_t* d_xcc, uint32_t* d_out, hipStream_t s);     // (mdvt_selftest.hip; r05 diagnosis)
 

@@ -1179,6 +1179,20 @@ int mdvt_ffv1_encode_frame(int width, int height, int slices_h, int slices_v, co
     return 0;
 }
 
+int mdvt_ffv1_decode_frame(int width, int height, const uint8_t* config, size_t config_size, const uint8_t* packet, size_t packet_size,
+                           uint8_t* dst, size_t pitch, int order, int threads)
+{
+    if (!config || !packet || !dst || width < 1 || height < 1 || pitch < (size_t)width * 3) return fail(ERR_ARG, "bad argument");
+    Decoder dec;
+    dec.W = width; dec.H = height;
+    int rc = parse_config_record(config, config_size, dec.f);
+    if (rc) return rc;
+    dec.have_config = true;
+    rc = dec.check_supported();
+    if (rc) return rc;
+    return dec.decode_frame(packet, packet_size, dst, pitch, order, threads);
+}
+
 int mdvt_video_create(const char* path, int width, int height, int fps_num, int fps_den, int slices_h, int slices_v, mdvt_video_writer** out)
 {
     if (!path || !out || width < 1 || height < 1 || fps_num < 1 || fps_den < 1) return fail(ERR_ARG, "bad argument");

@@ -1,6 +1,10 @@
 """FFV1 packets of device frames (mdvt_encode_video_frames): byte for byte those of video_io.encode_frame, without copying the raw
 frames to the host.  A frame the device could not code (a slice past its capacity, or a packet past the packet buffer) is
-re-encoded on the host, which gives the same bytes, or refuses the frame as the host encoder refuses it."""
+re-encoded on the host, which gives the same bytes, or refuses the frame as the host encoder refuses it.
+
+The other direction (mdvt_decode_video_frames, include/mdvt_ffv1_decode.h): packets of the stream class the project's writer makes
+are copied to the device as stored and decoded there into the bytes video_io.VideoReader gives; a frame the device flags is
+decoded on the host, which gives the same bytes or the host's own VideoError."""
 from __future__ import annotations
 
 import ctypes as C
@@ -152,3 +156,146 @@ def encode_frames_on_device(frames, slices=(4, 4), bgr: bool = False, slice_capa
     p = enqueue(_context(frames.device.index if frames.device.index is not None else 0), frames, slices, bgr, slice_capacity,
                 packets_cap)
     return p.collect()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# decoding
+# ---------------------------------------------------------------------------------------------------------------------
+DECODE_STATUS = {0: "decoded", 1: "CRC mismatch in a slice", 2: "malformed slice header / rectangle", 3: "bitstream damaged",
+                 4: "slice sizes do not add up to the packet"}
+
+
+def supported(info, config: Optional[bytes] = None) -> Optional[str]:
+    """None when the device decodes the stream of a video_io.VideoInfo (and, when given, its configuration record), else the
+    reason, naming the field.  Touches no GPU: the record is parsed by the library's host code."""
+    if info.ffv1_version != 3:
+        return f"version: FFV1 version {info.ffv1_version} (only version 3 is decoded on the device)"
+    if info.coder_type != 1:
+        return f"coder_type: {info.coder_type} (only the range coder with the default state table, 1, is decoded on the device)"
+    if info.alpha:
+        return "extra_plane: alpha planes are not decoded on the device"
+    if not info.intra:
+        return "intra: only streams whose every frame is a key frame are decoded on the device"
+    if not 1 <= info.slices <= 1024:
+        return f"num_h_slices / num_v_slices: {info.slices} slices per frame (1 to 1024 are decoded on the device)"
+    if config is not None:
+        why = _lib.load().mdvt_ffv1_decode_supported(config, len(config))
+        if why:
+            return why.decode()
+    return None
+
+
+def check_out(out, N: int, H: int, W: int) -> None:
+    """ValueError unless `out` is a CUDA uint8 tensor of N x H x W x 3 whose pixels are dense (rows and frames may be padded)."""
+    import torch
+    if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.uint8:
+        raise ValueError("out must be a uint8 torch.Tensor on a CUDA device")
+    if tuple(out.shape) != (N, H, W, 3):
+        raise ValueError(f"out must be {(N, H, W, 3)}, got {tuple(out.shape)}")
+    if out.stride(3) != 1 or out.stride(2) != 3 or out.stride(1) < 3 * W or (N > 1 and out.stride(0) < out.stride(1) * H):
+        raise ValueError(f"out must have dense pixels, rows of at least {3 * W} bytes and frames that do not overlap, got strides {out.stride()}")
+
+
+class PendingFrames:
+    """The device side of one decode: `out` and the status words, filled on the stream the decode was enqueued on (`done` is
+    recorded there behind it).  The pinned staging buffers live as long as this object."""
+
+    def __init__(self, packets, config, W, H, bgr, out, status, done, staged):
+        self.packets, self.config, self.W, self.H, self.bgr = packets, config, W, H, bgr
+        self.out, self.status, self.done, self._staged = out, status, done, staged
+        self.host_frames = 0                  # frames collect() had to decode on the host (flagged by the device)
+        self.flags = None                     # numpy uint32 [N] after collect(): the device's status words
+
+    def collect(self, threads: int = 1):
+        """Waits for the decode and reads the status words.  A flagged frame is decoded on the host (video_io.decode_frame: the
+        same bytes, or the host's VideoError for a packet the host refuses too), copied into its place and counted in
+        host_frames.  -> out"""
+        import torch
+        from . import video_io
+        self.done.synchronize()
+        self.flags = self.status.cpu().numpy().view(np.uint32)
+        self._staged = None
+        for k in np.nonzero(self.flags)[0]:
+            self.host_frames += 1
+            frame = video_io.decode_frame(self.packets[k], self.config, self.W, self.H, bgr=self.bgr, threads=threads)
+            self.out[int(k)].copy_(torch.from_numpy(frame))
+        return self.out
+
+
+class StagedPackets:
+    """Packets packed into one pinned blob, with their offsets and sizes (pinned too): what enqueue_decode copies to the device."""
+
+    def __init__(self, packets):
+        import torch
+        self.packets = list(packets)
+        N = len(self.packets)
+        if N < 1:
+            raise ValueError("no packets")
+        sizes = np.array([len(p) for p in self.packets], np.int64)
+        if sizes.max() >= 1 << 32:
+            raise ValueError("a packet of 4 GiB or more")
+        offsets = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
+        self.total = int(sizes.sum())
+        self.h_blob = torch.empty(max(1, self.total), dtype=torch.uint8, pin_memory=True)
+        blob = self.h_blob.numpy()
+        for o, p in zip(offsets, self.packets):
+            blob[o:o + len(p)] = np.frombuffer(p, np.uint8)
+        self.h_meta = torch.empty(2 * N, dtype=torch.int64, pin_memory=True)
+        self.h_meta[:N] = torch.from_numpy(offsets)
+        self.h_meta[N:] = torch.from_numpy(sizes)
+
+    def __len__(self):
+        return len(self.packets)
+
+
+def enqueue_decode(ctx: "_lib.Context", packets, config: bytes, width: int, height: int, bgr: bool = False, out=None,
+                   stream=None) -> PendingFrames:
+    """Packs the packets into one pinned blob (or takes a StagedPackets), copies it on a side stream and enqueues the decode into
+    `out` (default: a new N x H x W x 3 tensor on the ctx's device) on `stream` (default: the current stream).  MdvtError
+    (MDVT_ERR_UNSUPPORTED) for a configuration record outside the device's class, before anything is copied."""
+    import torch
+    W, H = int(width), int(height)
+    if W < 1 or H < 1:
+        raise ValueError(f"frames of {W} x {H}")
+    why = _lib.load().mdvt_ffv1_decode_supported(config, len(config))
+    if why:
+        raise _lib.MdvtError(-3, f"FFV1 stream outside the device decoder's class: {why.decode()}")
+    staged = packets if isinstance(packets, StagedPackets) else StagedPackets(packets)
+    N, total = len(staged), staged.total
+    dev = torch.device("cuda", ctx.device)
+    if out is None:
+        out = torch.empty((N, H, W, 3), dtype=torch.uint8, device=dev)
+    check_out(out, N, H, W)
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    side = torch.cuda.Stream(dev)
+    with torch.cuda.stream(side):
+        d_blob = torch.empty(max(1, total), dtype=torch.uint8, device=dev)
+        d_meta = torch.empty(2 * N, dtype=torch.int64, device=dev)
+        d_blob.copy_(staged.h_blob, non_blocking=True)
+        d_meta.copy_(staged.h_meta, non_blocking=True)
+        d_sizes = d_meta[N:].to(torch.int32)
+        status = torch.empty(N, dtype=torch.int32, device=dev)
+        copied = torch.cuda.Event()
+        copied.record(side)
+    s.wait_event(copied)
+    for t in (d_blob, d_meta, d_sizes, status):
+        t.record_stream(s)
+    ctx.check(ctx._L.mdvt_decode_video_frames(ctx.handle, W, H, config, len(config), C.c_void_p(d_blob.data_ptr()), total,
+                                             C.c_void_p(d_meta.data_ptr()), C.c_void_p(d_sizes.data_ptr()), N,
+                                             C.c_void_p(out.data_ptr()), out.stride(1), out.stride(0) if N > 1 else out.stride(1) * H,
+                                             1 if bgr else 0, C.c_void_p(status.data_ptr()), C.c_void_p(s.cuda_stream)))
+    done = torch.cuda.Event()
+    done.record(s)
+    return PendingFrames(staged.packets, config, W, H, bgr, out, status, done, (staged, d_blob, d_meta, d_sizes))
+
+
+def decode_frames_on_device(packets, config: bytes, width: int, height: int, *, bgr: bool = False, out=None, stream=None,
+                            device: int = 0):
+    """-> (frames, status): the N x H x W x 3 uint8 CUDA frames video_io.VideoReader gives for these packets (RGB, or BGR with
+    bgr=True; into `out`, whose rows and frames may be padded) and the device's status words (numpy uint32 [N]; a nonzero word:
+    that frame was decoded on the host instead)."""
+    if out is not None:
+        device = out.device.index if out.device.index is not None else 0
+    p = enqueue_decode(_context(device), packets, config, width, height, bgr, out, stream)
+    frames = p.collect()
+    return frames, p.flags

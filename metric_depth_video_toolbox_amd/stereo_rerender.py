@@ -738,6 +738,10 @@ def build_arg_parser():
     ap.add_argument("--video_encoder", choices=("host", "device"), default="host",
                     help="not a reference flag: where the .mkv outputs are FFV1-encoded -- 'host' (default) or 'device' (on the GPU, "
                          "the same bytes; only the compressed packets are copied to the host). Not with .npy input and outputs")
+    ap.add_argument("--video_decoder", choices=("host", "device"), default="host",
+                    help="not a reference flag: where the .mkv inputs are FFV1-decoded -- 'host' (default) or 'device' (on the GPU, "
+                         "the same bytes; only the compressed packets are copied to the device; an input the device does not decode, "
+                         "such as a file FFmpeg made, is read on the host). Not with .npy inputs")
     ap.add_argument("--near_clip", action="store_true",
                     help="not a reference flag: clip a mesh triangle that crosses the near plane (z = 1e-4 m) as a GL does, instead of "
                          "dropping it whole (the default) -- matters where depth code 0 or a pose puts the camera inside the scene "
@@ -768,6 +772,7 @@ def main(argv=None):
         raise FileNotFoundError(f"Color video not found: {args.color_video}")                  # sr:331
     from . import video_io
     clip.check_video_encoder(args.video_encoder, video_io.is_matroska(args.depth_video))
+    clip.check_video_decoder(args.video_decoder, video_io.is_matroska(args.depth_video))
     stats, final = clip.run(args.depth_video, args.color_video, batch=args.batch,
                             create_sbs_depth_video=args.create_sbs_depth_video, max_frames=args.max_frames,
                             green_and_black_infill_mask=args.green_and_black_infill_mask,
@@ -783,6 +788,7 @@ def main(argv=None):
                             do_basic_infill=args.do_basic_infill, normal_infill=args.normal_infill, inpaint_order=args.inpaint_order,
                             multisample=multisample_kwargs(args), near_clip=bool(args.near_clip),
                             video_encoder=args.video_encoder,
+                            **({"video_decoder": "device"} if args.video_decoder == "device" else {}),
                             touchly_max_depth=args.touchly_max_depth, touchly_min_depth=args.touchly_min_depth)
     if int(os.environ.get("RANK", "0")) == 0:
         frames, secs = float(stats[:, 0].sum()), float(stats[:, 1].max())

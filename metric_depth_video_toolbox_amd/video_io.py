@@ -22,7 +22,7 @@ LIB_PATH = os.path.join(_PKG, "libmdvt_video.so")
 
 SYMBOLS = ("mdvt_video_last_error", "mdvt_video_abi", "mdvt_video_open", "mdvt_video_read", "mdvt_video_rewind", "mdvt_video_seek",
            "mdvt_video_next_packet", "mdvt_video_config_record", "mdvt_video_close", "mdvt_video_create", "mdvt_video_write",
-           "mdvt_video_write_packet", "mdvt_video_finish", "mdvt_ffv1_encode_frame")
+           "mdvt_video_write_packet", "mdvt_video_finish", "mdvt_ffv1_encode_frame", "mdvt_ffv1_decode_frame")
 
 RGB, BGR = 0, 1
 
@@ -62,6 +62,8 @@ def load():
         L.mdvt_video_finish.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
         L.mdvt_ffv1_encode_frame.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int,
                                              C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.mdvt_ffv1_decode_frame.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                             C.c_int, C.c_int]
         _lib = L
     return _lib
 
@@ -181,3 +183,14 @@ def encode_frame(frame: np.ndarray, slices=(2, 2), bgr: bool = False, threads: i
     _check(load().mdvt_ffv1_encode_frame(W, H, slices[0], slices[1], frame.ctypes.data, frame.strides[0], BGR if bgr else RGB, threads,
                                          pkt.ctypes.data, cap, C.byref(ps), cfg.ctypes.data, 4096, C.byref(cs)))
     return pkt[:ps.value].tobytes(), cfg[:cs.value].tobytes()
+
+
+def decode_frame(packet: bytes, config: bytes, width: int, height: int, bgr: bool = False, threads: int = 1, out=None) -> np.ndarray:
+    """One FFV1 packet of a version-3 stream with this configuration record -> H x W x 3 uint8 (into `out` when given): the codec
+    without the container.  VideoError for what VideoReader.read refuses."""
+    if out is None:
+        out = np.empty((height, width, 3), np.uint8)
+    assert out.dtype == np.uint8 and out.shape == (height, width, 3) and out.strides[2] == 1 and out.strides[1] == 3
+    _check(load().mdvt_ffv1_decode_frame(int(width), int(height), config, len(config), packet, len(packet), out.ctypes.data, out.strides[0],
+                                         BGR if bgr else RGB, int(threads)))
+    return out

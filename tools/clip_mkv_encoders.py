@@ -1,7 +1,10 @@
 """The CLI from .mkv to .mkv with each --video_encoder: the product default (mesh, --infill_mask, convergence) on a synthetic 1080p
-clip, frames/s including all host I/O, and a byte comparison of every output file of the two runs.
+clip, frames/s including all host I/O, and a byte comparison of every output file of the two runs.  With --decoders the four
+--video_decoder x --video_encoder combinations run, each followed by basic_nomal_infill on its outputs with the same decoder
+(the two-step chain on .mkv files), and every file is compared with the all-host run's.
 
-    python tools/clip_mkv_encoders.py [--frames 300] [--width 1920] [--height 1080] [--batch 16] [--dir DIR] [--json out.json]"""
+    python tools/clip_mkv_encoders.py [--frames 300] [--width 1920] [--height 1080] [--batch 16] [--dir DIR] [--json out.json]
+                                      [--decoders]"""
 import argparse
 import json
 import os
@@ -23,8 +26,9 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--dir", default=None)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--decoders", action="store_true", help="also the --video_decoder axis and the basic_nomal_infill step")
     a = ap.parse_args(argv)
-    from metric_depth_video_toolbox_amd import stereo_rerender as sr, video_io
+    from metric_depth_video_toolbox_amd import basic_nomal_infill as bni, stereo_rerender as sr, video_io
     from metric_depth_video_toolbox_amd.synthetic import SyntheticScene
     root = a.dir or tempfile.mkdtemp(prefix="clip_mkv_")
     W, H, N = a.width, a.height, a.frames
@@ -39,8 +43,10 @@ def main(argv=None):
     with open(conv, "w") as f:
         json.dump([2.5 + 0.01 * (k % 50) for k in range(N)], f)
     res, files = {}, {}
-    for enc in ("host", "device"):
-        d = os.path.join(root, enc)
+    combos = [("host", e) for e in ("host", "device")] + ([("device", e) for e in ("host", "device")] if a.decoders else [])
+    for dec, enc in combos:
+        name = enc if dec == "host" else f"{dec}_decoder_{enc}"
+        d = os.path.join(root, name)
         os.makedirs(d, exist_ok=True)
         for src in (dp, cp):
             dst = os.path.join(d, os.path.basename(src))
@@ -49,15 +55,26 @@ def main(argv=None):
         t0 = time.perf_counter()
         sr.main(["--depth_video", os.path.join(d, "in_depth.mkv"), "--color_video", os.path.join(d, "in.mkv"), "--xfov", "50",
                  "--pupillary_distance", "65", "--infill_mask", "--convergence_file", conv, "--batch", str(a.batch),
-                 "--video_encoder", enc])
+                 "--video_encoder", enc] + (["--video_decoder", dec] if a.decoders else []))
         dt = time.perf_counter() - t0
+        dt2 = None
+        if a.decoders:
+            t0 = time.perf_counter()
+            bni.main(["--sbs_color_video", os.path.join(d, "in_depth.mkv_stereo.mkv"), "--sbs_mask_video",
+                      os.path.join(d, "in_depth.mkv_stereo.mkv_infillmask.mkv"), "--batch", str(a.batch), "--video_decoder", dec,
+                      "--video_encoder", enc])
+            dt2 = time.perf_counter() - t0
         outs = sorted(f for f in os.listdir(d) if f.startswith("in_depth.mkv_"))
-        files[enc] = {f: os.path.getsize(os.path.join(d, f)) for f in outs}
-        res[enc] = dict(seconds=dt, fps=N / dt, outputs=files[enc])
-        print(f"{enc:>6}: {N} frames in {dt:.2f} s = {N / dt:.1f} frames/s (whole CLI call, incl. start-up), outputs {files[enc]}",
-              flush=True)
-    same = all(open(os.path.join(root, "host", f), "rb").read() == open(os.path.join(root, "device", f), "rb").read()
-               for f in files["host"]) and files["host"].keys() == files["device"].keys()
+        files[name] = {f: os.path.getsize(os.path.join(d, f)) for f in outs}
+        res[name] = dict(decoder=dec, encoder=enc, seconds=dt, fps=N / dt, outputs=files[name])
+        print(f"decoder {dec:>6} encoder {enc:>6}: {N} frames in {dt:.2f} s = {N / dt:.1f} frames/s (whole CLI call, incl. start-up), "
+              f"outputs {files[name]}", flush=True)
+        if dt2 is not None:
+            res[name].update(infill_seconds=dt2, infill_fps=N / dt2)
+            print(f"        basic_nomal_infill on them: {dt2:.2f} s = {N / dt2:.1f} frames/s", flush=True)
+    same = all(files["host"].keys() == files[k].keys() and
+               all(open(os.path.join(root, "host", f), "rb").read() == open(os.path.join(root, k, f), "rb").read() for f in files["host"])
+               for k in files if k != "host")
     res["identical"] = bool(same)
     print("outputs byte-identical:", same)
     if a.json:

@@ -4,6 +4,11 @@ encoder (video_io.encode_frame, 16 threads across frames, one slice thread each:
     python tools/ffv1_bench.py [--sizes 1920x1080,3840x1080] [--contents depth,synthetic,noise] [--slices 4x4,8x8]
                                [--frames 16,64,128] [--host-threads 16] [--json out.json]
 
+With --decode the table is the decoder's: ffv1_device.enqueue_decode + the status read-back (packets already packed in pinned host
+memory, frames left on the device) against the host decoder as the clip driver uses it (clip.VideoFrames.read_into into pinned memory,
+two readers sharing the host threads, + the copy of the raw frames to the device); every timed batch is compared with the host's
+bytes first, and the run stops if the device flagged a frame.
+
 Every device packet is compared with the host's bytes before it is timed, and the run stops if the device flagged any frame
 (a flagged frame is re-encoded on the host: its time would not be the device's).  Prints one line per case and, with --json,
 writes the table."""
@@ -40,7 +45,10 @@ def main(argv=None):
     ap.add_argument("--host-threads", type=int, default=16)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--decode", action="store_true", help="measure the decoders instead of the encoders")
     a = ap.parse_args(argv)
+    if a.decode:
+        return decode_main(a)
     import torch
     from metric_depth_video_toolbox_amd import ffv1_device, video_io
     rng = np.random.default_rng(1)
@@ -81,6 +89,78 @@ def main(argv=None):
                     rows.append(r)
                     print(f"{size:>9} {kind:>9} {sl:>3} n={n:<3} device {r['device_fps']:8.1f} fps  host({a.host_threads}t) "
                           f"{r['host_fps']:8.1f} fps  x{r['speedup']:.2f}  {r['bytes_per_frame'] / 1e6:.2f} MB/frame", flush=True)
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(rows, f, indent=1)
+
+
+def decode_main(a):
+    import tempfile
+    import torch
+    from metric_depth_video_toolbox_amd import clip, ffv1_device, video_io
+    rng = np.random.default_rng(1)
+    pool = ThreadPoolExecutor(a.host_threads)
+    ctx = ffv1_device._context(0)
+    rows = []
+    nmax = max(int(v) for v in a.frames.split(","))
+    tmp = tempfile.mkdtemp(prefix="ffv1_bench_")
+    for size in a.sizes.split(","):
+        W, H = (int(v) for v in size.split("x"))
+        pinned = torch.empty((nmax, H, W, 3), dtype=torch.uint8, pin_memory=True)
+        d_host = torch.empty((nmax, H, W, 3), dtype=torch.uint8, device="cuda")
+        d_dev = torch.empty((nmax, H, W, 3), dtype=torch.uint8, device="cuda")
+        for kind in a.contents.split(","):
+            frames = frames_of(kind, W, H, nmax, rng)
+            for sl in a.slices.split(","):
+                slices = tuple(int(v) for v in sl.split("x"))
+                path = os.path.join(tmp, f"{size}_{kind}_{sl}.mkv")
+                enc = list(pool.map(lambda f: video_io.encode_frame(f, slices=slices, threads=1), frames))
+                with video_io.VideoWriter(path, W, H, 30.0, slices=slices) as w:
+                    for pkt, _ in enc:
+                        w.write_packet(pkt)
+                packets, cfg = [e[0] for e in enc], enc[0][1]
+                vf = clip.VideoFrames(path)
+
+                def host(n):                      # render_clip's load() + its H2D copy
+                    h = pinned[:n].numpy()
+                    half = n // 2
+                    jobs = [pool.submit(vf.read_into, h[:half], 0, half)] if half else []
+                    jobs.append(pool.submit(vf.read_into, h[half:], half, n - half))
+                    for j in jobs:
+                        j.result()
+                    d_host[:n].copy_(pinned[:n], non_blocking=True)
+                    torch.cuda.synchronize()
+
+                def device(staged):
+                    p = ffv1_device.enqueue_decode(ctx, staged, cfg, W, H, out=d_dev[:len(staged)])
+                    p.done.synchronize()
+                    flags = p.status.cpu()
+                    if bool(flags.any()):
+                        raise SystemExit(f"the device flagged {int((flags != 0).sum())} of {len(staged)} frames ({size}, {kind}, {sl}): "
+                                         "not a device timing")
+                for n in (int(v) for v in a.frames.split(",")):
+                    staged = ffv1_device.StagedPackets(packets[:n])
+                    host(n)
+                    device(staged)
+                    assert torch.equal(d_dev[:n], d_host[:n]) and np.array_equal(pinned[:n].numpy(), frames[:n]), (size, kind, sl, n)
+                    dt_dev, dt_host = [], []
+                    for _ in range(a.reps):
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        device(staged)
+                        dt_dev.append(time.perf_counter() - t0)
+                        t0 = time.perf_counter()
+                        host(n)
+                        dt_host.append(time.perf_counter() - t0)
+                    r = dict(size=size, content=kind, slices=sl, frames=n, device_fps=n / min(dt_dev), host_fps=n / min(dt_host),
+                             bytes_per_frame=staged.total / n)
+                    r["speedup"] = r["device_fps"] / r["host_fps"]
+                    rows.append(r)
+                    print(f"decode {size:>9} {kind:>9} {sl:>3} n={n:<3} device {r['device_fps']:8.1f} fps  host({a.host_threads}t) "
+                          f"{r['host_fps']:8.1f} fps  x{r['speedup']:.2f}  {r['bytes_per_frame'] / 1e6:.2f} MB/frame", flush=True)
+                vf.close()
+                os.remove(path)
+    os.rmdir(tmp)
     if a.json:
         with open(a.json, "w") as f:
             json.dump(rows, f, indent=1)
