@@ -68,8 +68,7 @@ struct mdvt_ctx {
     uint8_t* tri_invalid = nullptr;
     uint8_t* unused = nullptr;
     uint32_t* bigq = nullptr;         // general mesh path: queue of large triangles + its counter (last dword)
-    uint32_t bigq_cap = 0;
-    size_t bigq_bytes = 0;            // the queue block as laid out (without tuning padding)
+    size_t bigq_bytes = 0, bigq_counters_at = 0;      // the queue block as laid out (without tuning padding), the dword offset of its counters
     int huge_lists = 1;               // huge lists inside the queue block (2: tuning layout "joint")
     mdvt::RowCell* rowcell = nullptr; // [H] scanline -> cell row table of the mesh grid (pure-shift band kernel)
     int rowcell_bits = 0;             // the sub-pixel grid that table was built for
@@ -185,6 +184,32 @@ size_t ws_size_class(size_t bytes)
     while ((step << 5) < bytes) step <<= 1;              // bytes in (16 step, 32 step]
     return (bytes + step - 1) / step * step;
 }
+// Gives the idle blocks that `pick` chooses (called under the pool's lock, oldest block first) back to the driver.
+template <class Pick>
+void drain_dev_pool(Pick pick, const size_t* new_idle_cap = nullptr)
+{
+    std::vector<DevBlock> out;
+    {
+        std::lock_guard<std::mutex> lock(g_dev_pool_mutex);
+        if (new_idle_cap) g_dev_pool_idle_cap = *new_idle_cap;
+        auto& pool = dev_pool();
+        for (size_t k = 0; k < pool.size();) {
+            if (!pick(pool[k])) { ++k; continue; }
+            out.push_back(pool[k]);
+            dev_pool_idle()[pool[k].tag] -= pool[k].bytes;
+            pool.erase(pool.begin() + (long)k);
+        }
+    }
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess) count = 0;
+    for (const DevBlock& b : out) {
+        // (a block tagged for a GPU this process does not have -- the tuning build's MDVT_POOL_TAG -- lives on the current one)
+        DeviceGuard g(b.tag >= 0 && b.tag < count ? b.tag : 0);
+        (void)hipDeviceSynchronize();
+        (void)hipFree(b.p);
+    }
+}
+
 bool dev_pool_off() { const char* e = tuning_env(TUNE_WS_POOL); return e && (strcmp(e, "off") == 0 || strcmp(e, "delay") == 0); }
 
 // device memory owned by a context, accounted for mdvt_workspace_bytes; `s`: the stream the fresh-block fill goes to
@@ -465,12 +490,11 @@ int stage_params(mdvt_ctx* c, const std::vector<FrameDev>& v, hipStream_t s, con
     return MDVT_OK;
 }
 
+RenderWorkspaceLayout layout_of(const mdvt_ctx* c) { return RenderWorkspaceLayout(c->W, c->H, c->ws_frames, c->huge_lists); }
 // (the EMPTY fill of fresh key buffers goes on the caller's stream: PyTorch's pool streams do not synchronise with the
 //  legacy null stream, so a fill issued there could land after the first splat)
 int ensure_workspace(mdvt_ctx* c, int frames, bool need_keys, bool need_ekeys, bool need_edges, bool need_mesh_ws, hipStream_t s)
 {
-    const size_t npx = (size_t)c->W * c->H;
-    const size_t ntri = 2 * (size_t)(c->W - 1) * (c->H - 1);
     const bool grow = frames > c->ws_frames;
     // (blocks that are replaced go back to the pool, where another context may pick them up at once: whatever was submitted
     //  with them -- to any stream -- has to be through first; hipFree used to wait for that implicitly)
@@ -480,73 +504,47 @@ int ensure_workspace(mdvt_ctx* c, int frames, bool need_keys, bool need_ekeys, b
     if (!grow && ((need_keys && !c->ws_keys && (c->keys[0] || c->keys[1])) || (need_ekeys && !c->ws_ekeys && (c->ekeys[0] || c->ekeys[1] || c->elist)) ||
                   (need_edges && !c->ws_edges && (c->tri_invalid || c->unused)) || (need_mesh_ws && !c->ws_mesh && (c->cbuf[0] || c->cbuf[1]))))
         MDVT_HIP(c, hipDeviceSynchronize());
-    if (grow || (need_keys && !c->ws_keys)) {
-        for (int e = 0; e < 2; ++e) { if (c->keys[e]) ws_free(c, c->keys[e]); c->keys[e] = nullptr; }
-        c->ws_keys = false;
-    }
-    if (grow || (need_ekeys && !c->ws_ekeys)) {
-        for (int e = 0; e < 2; ++e) { if (c->ekeys[e]) ws_free(c, c->ekeys[e]); c->ekeys[e] = nullptr; }
-        if (c->elist) ws_free(c, c->elist);
-        c->elist = nullptr;
-        c->ws_ekeys = false;
-    }
-    if (grow || (need_edges && !c->ws_edges)) {
-        if (c->tri_invalid) ws_free(c, c->tri_invalid);
-        if (c->unused) ws_free(c, c->unused);
-        c->tri_invalid = nullptr; c->unused = nullptr; c->ws_edges = false;
-    }
-    if (grow || (need_mesh_ws && !c->ws_mesh)) {
-        for (int e = 0; e < 2; ++e) { if (c->cbuf[e]) ws_free(c, c->cbuf[e]); c->cbuf[e] = nullptr; }
-        c->ws_mesh = false;
-    }
+    auto drop = [c](auto*& p) { ws_free(c, p); p = nullptr; };      // (ws_free takes a null pointer)
+    if (grow || (need_keys && !c->ws_keys)) { drop(c->keys[0]); drop(c->keys[1]); c->ws_keys = false; }
+    if (grow || (need_ekeys && !c->ws_ekeys)) { drop(c->ekeys[0]); drop(c->ekeys[1]); drop(c->elist); c->ws_ekeys = false; }
+    if (grow || (need_edges && !c->ws_edges)) { drop(c->tri_invalid); drop(c->unused); c->ws_edges = false; }
+    if (grow || (need_mesh_ws && !c->ws_mesh)) { drop(c->cbuf[0]); drop(c->cbuf[1]); c->ws_mesh = false; }
     if (grow) c->ws_frames = frames;
-    const size_t nf = (size_t)c->ws_frames;
+    // (tuning build, the r04 diagnosis: MDVT_WS_LAYOUT=joint puts the second bank's huge list back into the queue block, as at 47b4117 --
+    //  2.2 MB for a 100 x 31 frame; it takes effect when that block is made, so it is read before the layout is)
+    if (need_mesh_ws && !c->ws_mesh) { const char* e = tuning_env(TUNE_WS_LAYOUT); c->huge_lists = (e && strcmp(e, "joint") == 0) ? 2 : 1; }
+    const RenderWorkspaceLayout L = layout_of(c);
     if (need_keys && !c->ws_keys) {
         for (int e = 0; e < 2; ++e) {
-            MDVT_HIP(c, ws_malloc(c, (void**)&c->keys[e], nf * npx * sizeof(unsigned long long), s));
-            MDVT_HIP(c, hipMemsetAsync(c->keys[e], 0xFF, nf * npx * sizeof(unsigned long long), s));     // parity 0's empty value
+            MDVT_HIP(c, ws_malloc(c, (void**)&c->keys[e], L.plane_bytes(), s));
+            MDVT_HIP(c, hipMemsetAsync(c->keys[e], 0xFF, L.plane_bytes(), s));     // parity 0's empty value
         }
         c->key_parity = 0;
         c->ws_keys = true;
     }
     if (need_ekeys && !c->ws_ekeys) {
         for (int e = 0; e < 2; ++e) {
-            MDVT_HIP(c, ws_malloc(c, (void**)&c->ekeys[e], nf * npx * sizeof(unsigned long long), s));
-            MDVT_HIP(c, hipMemsetAsync(c->ekeys[e], 0xFF, nf * npx * sizeof(unsigned long long), s));
+            MDVT_HIP(c, ws_malloc(c, (void**)&c->ekeys[e], L.plane_bytes(), s));
+            MDVT_HIP(c, hipMemsetAsync(c->ekeys[e], 0xFF, L.plane_bytes(), s));
         }
-        // (+ the vertex list of the mesh path's edge-point splat: npx entries and a counter per slot)
-        MDVT_HIP(c, ws_malloc(c, (void**)&c->elist, (nf * 2 * npx + nf * (size_t)c->H + nf * npx + nf) * sizeof(uint32_t), s));
-        MDVT_HIP(c, hipMemsetAsync(c->elist + nf * 2 * npx, 0, nf * (size_t)c->H * sizeof(uint32_t), s));   // counters; the reset pass keeps them 0
+        MDVT_HIP(c, ws_malloc(c, (void**)&c->elist, L.elist_bytes(), s));
+        MDVT_HIP(c, hipMemsetAsync(c->elist + L.elist_count_at(), 0, L.slots * L.H * sizeof(uint32_t), s));   // counters; the reset pass keeps them 0
         c->ws_ekeys = true;
     }
     if (need_mesh_ws && !c->ws_mesh) {
-        for (int e = 0; e < 2; ++e) {
-            MDVT_HIP(c, ws_malloc(c, (void**)&c->cbuf[e], nf * npx * sizeof(unsigned long long), s));   // tie side words: a word is initialised by the fragment that marks its pixel, so the plane needs no clearing
-        }
-        if (c->bigq) ws_free(c, c->bigq);
-        c->bigq = nullptr;
-        // one segment per (frame slot, cell row), each with room for all four triangles of every cell of the row (8 bytes
-        // per triangle) and its own counter: the queue cannot overflow
-        // (entry indices are 32-bit: chunk_of() keeps nf * npx * 4 below 2^32, so allocation and counter offset use ONE value)
-        size_t nfq = (size_t)0xFFFFFFF0u / (4 * npx);          // a general launch set never has more slots than this (chunk_of)
-        if (nfq < 1) return fail(c, MDVT_ERR_UNSUPPORTED, "general mesh path: a %d x %d frame exceeds the 32-bit triangle queue", c->W, c->H);
-        if (nfq > nf) nfq = nf;
-        const size_t cap = nfq * npx * 4;
-        c->bigq_cap = (uint32_t)cap;
-        // entries, counters, prefix sums; row blocks of huge triangles + their counter; tie flags and tile bits
-        // (tuning build, the r04 diagnosis: MDVT_WS_LAYOUT=joint puts the second bank's huge list back into this block, as at
-        //  47b4117 -- 2.2 MB for a 100 x 31 frame; MDVT_WS_PAD=n appends n unused bytes)
-        c->huge_lists = 1;
-        if (const char* e = tuning_env(TUNE_WS_LAYOUT)) c->huge_lists = strcmp(e, "joint") == 0 ? 2 : 1;
-        size_t pad = 0;
+        for (int e = 0; e < 2; ++e) MDVT_HIP(c, ws_malloc(c, (void**)&c->cbuf[e], L.plane_bytes(), s));   // tie side words: a word is initialised by the fragment that marks its pixel, so the plane needs no clearing
+        drop(c->bigq);
+        // (entry indices are 32-bit: chunk_of() keeps a launch set's slots * npx * 4 below 2^32)
+        if (queue_slots_max(c->W, c->H) < 1) return fail(c, MDVT_ERR_UNSUPPORTED, "general mesh path: a %d x %d frame exceeds the 32-bit triangle queue", c->W, c->H);
+        size_t pad = 0;      // (tuning build: MDVT_WS_PAD=n appends n unused bytes to the queue block)
         if (const char* e = tuning_env(TUNE_WS_PAD)) pad = (size_t)strtoull(e, nullptr, 10);
-        c->bigq_bytes = (cap * mdvt::kBigRecDwords + 2 * nf * (size_t)c->H + 8 + (size_t)c->huge_lists * (2 * (size_t)mdvt::kHugeCap + 2) + nf * (1 + 2 * mdvt::tie_words_of(c->W, c->H))) * sizeof(uint32_t);
+        c->bigq_bytes = L.queue_bytes(); c->bigq_counters_at = L.counters_at();
         MDVT_HIP(c, ws_malloc(c, (void**)&c->bigq, c->bigq_bytes + pad, s));
         c->ws_mesh = true;
     }
     if (need_edges && !c->ws_edges) {
-        MDVT_HIP(c, ws_malloc(c, (void**)&c->tri_invalid, nf * ntri, s));
-        MDVT_HIP(c, ws_malloc(c, (void**)&c->unused, nf * npx, s));
+        MDVT_HIP(c, ws_malloc(c, (void**)&c->tri_invalid, L.tri_invalid_bytes(), s));
+        MDVT_HIP(c, ws_malloc(c, (void**)&c->unused, L.unused_bytes(), s));
         c->ws_edges = true;
     }
     return MDVT_OK;
@@ -593,6 +591,37 @@ int ensure_rowcell(mdvt_ctx* c, hipStream_t s)
     return MDVT_OK;
 }
 
+uint32_t packed_key_rgb(const mdvt_ctx* c) { return (uint32_t)c->cfg.key_rgb[0] | ((uint32_t)c->cfg.key_rgb[1] << 8) | ((uint32_t)c->cfg.key_rgb[2] << 16); }
+size_t workspace_budget_bytes(const mdvt_ctx* c) { return (size_t)(c->cfg.workspace_mib ? c->cfg.workspace_mib : 4096u) << 20; }
+// the slots of per_slot bytes each that the budget affords: at least one, at most cap
+int slots_afforded(const mdvt_ctx* c, size_t per_slot, int cap)
+{
+    const size_t afford = workspace_budget_bytes(c) / per_slot;
+    return (size_t)cap > afford ? (afford < 1 ? 1 : (int)afford) : cap;
+}
+
+// What RenderArgs and MsaaArgs share: the caller's images, the staged parameters, the frame size and the slot strides.
+template <class Args>
+void bind_io(Args& a, const mdvt_ctx* c, const mdvt_io* io, const FrameDev* dfp)
+{
+    a.depth = io->depth_rgb; a.depth_pitch = io->depth_pitch; a.depth_stride = io->depth_stride;
+    a.color = io->color_rgb; a.color_pitch = io->color_pitch; a.color_stride = io->color_stride;
+    a.rgb[0] = io->left_rgb; a.rgb[1] = io->right_rgb; a.rgb_pitch = io->rgb_pitch; a.rgb_stride = io->rgb_stride;
+    a.mask[0] = io->left_mask; a.mask[1] = io->right_mask; a.mask_pitch = io->mask_pitch; a.mask_stride = io->mask_stride;
+    a.hole_counts = io->hole_counts; a.fp = dfp; a.key_rgb = packed_key_rgb(c);
+    a.W = c->W; a.H = c->H; a.ws_stride_px = (size_t)c->W * c->H; a.ws_stride_tri = 2 * (size_t)(c->W - 1) * (c->H - 1);
+}
+
+// The edge filter's flags of the n frames from a.frame0 on, into the workspace slots that tri_invalid / unused start at.
+template <class Args>
+int filter_edges(mdvt_ctx* c, const Args& a, int n, uint8_t* tri_invalid, uint8_t* unused, hipStream_t s)
+{
+    MDVT_HIP(c, launch_zero_bytes(unused, (size_t)n * a.ws_stride_px, s));
+    MDVT_HIP(c, launch_edge_filter(a.depth, a.depth_pitch, a.depth_stride, a.fp, a.frame0, n, a.W, a.H, c->cfg.mode == MDVT_MODE_MESH,
+                                   tri_invalid, a.ws_stride_tri, unused, a.ws_stride_px, s));
+    return MDVT_OK;
+}
+
 // ---- 4x multisampled render (mdvt_config.samples = 4; mdvt_msaa.hip) ---------------------------------------------------------
 // What the mode does not cover is refused before anything is checked or launched, with the output named.
 int msaa_refusal(mdvt_ctx* c, const mdvt_io* io, const char* mode = "multisampling (samples = 4)")
@@ -615,10 +644,7 @@ int render_msaa(mdvt_ctx* c, int n_frames, const std::vector<FrameDev>& fd, cons
     if (2 * npx >= (size_t)0xFFFFFFFFu)
         return fail(c, MDVT_ERR_UNSUPPORTED, "multisampling: a %d x %d frame has more triangles than its 32-bit draw ids can name", W, H);
     const bool rm = c->cfg.remove_edges != 0;
-    const size_t per_slot = npx * (2 * 4 * sizeof(unsigned long long) + (rm ? 3 : 0));
-    const size_t budget = (size_t)(c->cfg.workspace_mib ? c->cfg.workspace_mib : 4096u) << 20;
-    int chunk = 16;
-    if ((size_t)chunk > budget / per_slot) chunk = budget / per_slot < 1 ? 1 : (int)(budget / per_slot);
+    int chunk = slots_afforded(c, npx * (2 * 4 * sizeof(unsigned long long) + (rm ? kNominalEdgeFlagBytesPerPx : 0)), 16);
     if (chunk > n_frames) chunk = n_frames;
 
     const FrameDev* dfp = nullptr;
@@ -640,29 +666,14 @@ int render_msaa(mdvt_ctx* c, int n_frames, const std::vector<FrameDev>& fd, cons
     if (io->hole_counts) MDVT_HIP(c, hipMemsetAsync(io->hole_counts, 0, 2 * (size_t)n_frames * sizeof(uint32_t), s));
 
     MsaaArgs a{};
-    a.depth = io->depth_rgb; a.depth_pitch = io->depth_pitch; a.depth_stride = io->depth_stride;
-    a.color = io->color_rgb; a.color_pitch = io->color_pitch; a.color_stride = io->color_stride;
-    a.rgb[0] = io->left_rgb; a.rgb[1] = io->right_rgb; a.rgb_pitch = io->rgb_pitch; a.rgb_stride = io->rgb_stride;
-    a.mask[0] = io->left_mask; a.mask[1] = io->right_mask; a.mask_pitch = io->mask_pitch; a.mask_stride = io->mask_stride;
-    a.hole_counts = io->hole_counts;
-    a.fp = dfp;
+    bind_io(a, c, io, dfp);
     a.keys = c->msaa_keys;
-    a.tri_invalid = rm ? c->tri_invalid : nullptr;
-    a.unused = rm ? c->unused : nullptr;
-    a.ws_stride_px = npx;
-    a.ws_stride_tri = 2 * (size_t)(W - 1) * (H - 1);
-    a.W = W; a.H = H;
-    a.mode = c->cfg.mode; a.cull = c->cfg.cull;
-    a.pattern = c->cfg.sample_pattern; a.resolve = c->cfg.sample_resolve;
-    a.key_rgb = (uint32_t)c->cfg.key_rgb[0] | ((uint32_t)c->cfg.key_rgb[1] << 8) | ((uint32_t)c->cfg.key_rgb[2] << 16);
+    a.tri_invalid = rm ? c->tri_invalid : nullptr; a.unused = rm ? c->unused : nullptr;
+    a.mode = c->cfg.mode; a.cull = c->cfg.cull; a.pattern = c->cfg.sample_pattern; a.resolve = c->cfg.sample_resolve;
     for (int f0 = 0; f0 < n_frames; f0 += chunk) {
         const int n = n_frames - f0 < chunk ? n_frames - f0 : chunk;
         a.frame0 = f0;
-        if (rm) {
-            MDVT_HIP(c, launch_zero_bytes(c->unused, (size_t)n * npx, s));
-            MDVT_HIP(c, launch_edge_filter(a.depth, a.depth_pitch, a.depth_stride, dfp, f0, n, W, H, c->cfg.mode == MDVT_MODE_MESH,
-                                           c->tri_invalid, a.ws_stride_tri, c->unused, npx, s));
-        }
+        if (rm && (rc = filter_edges(c, a, n, c->tri_invalid, c->unused, s)) != MDVT_OK) return rc;
         c->msaa_dirty = true;
         if (clip) MDVT_HIP(c, MDVT_GRID_CALL(c, launch_near_clip_render, a, n, 4, nullptr, s));
         else MDVT_HIP(c, MDVT_GRID_CALL(c, launch_msaa_render, a, n, s));
@@ -683,9 +694,7 @@ int render_near_clip_gate(mdvt_ctx* c, int n_frames, const FrameDev* dfp, const 
     const size_t npx = (size_t)W * (size_t)H;
     const bool rm = c->cfg.remove_edges != 0;
     const size_t per_slot = npx * 2 * sizeof(unsigned long long);
-    const size_t budget = (size_t)(c->cfg.workspace_mib ? c->cfg.workspace_mib : 4096u) << 20;
-    int chunk = 16;
-    if ((size_t)chunk > budget / per_slot) chunk = budget / per_slot < 1 ? 1 : (int)(budget / per_slot);
+    int chunk = slots_afforded(c, per_slot, 16);
     if (rm && chunk > c->ws_frames) chunk = c->ws_frames;        // (the render before has made at least one slot of edge flags)
     if (chunk > n_frames) chunk = n_frames;
     if (chunk < 1) return fail(c, MDVT_ERR_INVALID_ARG, "near-plane clipping: no workspace slot for the edge filter");
@@ -701,29 +710,15 @@ int render_near_clip_gate(mdvt_ctx* c, int n_frames, const FrameDev* dfp, const 
     c->clip_dirty = false;
 
     MsaaArgs a{};
-    a.depth = io->depth_rgb; a.depth_pitch = io->depth_pitch; a.depth_stride = io->depth_stride;
-    a.color = io->color_rgb; a.color_pitch = io->color_pitch; a.color_stride = io->color_stride;
-    a.rgb[0] = io->left_rgb; a.rgb[1] = io->right_rgb; a.rgb_pitch = io->rgb_pitch; a.rgb_stride = io->rgb_stride;
-    a.mask[0] = io->left_mask; a.mask[1] = io->right_mask; a.mask_pitch = io->mask_pitch; a.mask_stride = io->mask_stride;
-    a.hole_counts = io->hole_counts;
-    a.fp = dfp;
+    bind_io(a, c, io, dfp);
     a.keys = c->clip_keys;
-    a.tri_invalid = rm ? c->tri_invalid : nullptr;
-    a.unused = rm ? c->unused : nullptr;
-    a.ws_stride_px = npx;
-    a.ws_stride_tri = 2 * (size_t)(W - 1) * (H - 1);
-    a.W = W; a.H = H;
+    a.tri_invalid = rm ? c->tri_invalid : nullptr; a.unused = rm ? c->unused : nullptr;
     a.mode = c->cfg.mode; a.cull = c->cfg.cull;
-    a.key_rgb = (uint32_t)c->cfg.key_rgb[0] | ((uint32_t)c->cfg.key_rgb[1] << 8) | ((uint32_t)c->cfg.key_rgb[2] << 16);
     for (int f0 = 0; f0 < n_frames; f0 += chunk) {
         const int n = n_frames - f0 < chunk ? n_frames - f0 : chunk;
         a.frame0 = f0;
         MDVT_HIP(c, hipMemsetAsync(c->clip_flags, 0, (size_t)n * 2 * sizeof(uint32_t), s));
-        if (rm) {
-            MDVT_HIP(c, launch_zero_bytes(c->unused, (size_t)n * npx, s));
-            MDVT_HIP(c, launch_edge_filter(a.depth, a.depth_pitch, a.depth_stride, dfp, f0, n, W, H, true,
-                                           c->tri_invalid, a.ws_stride_tri, c->unused, npx, s));
-        }
+        if (rm) { if (int rc = filter_edges(c, a, n, c->tri_invalid, c->unused, s)) return rc; }      // (mesh mode: near_clip)
         c->clip_dirty = true;
         MDVT_HIP(c, MDVT_GRID_CALL(c, launch_near_clip_render, a, n, 1, c->clip_flags, s));
         c->clip_dirty = false;
@@ -834,30 +829,19 @@ int mdvt_destroy(mdvt_ctx* c)
     DeviceGuard g(c->device);
     (void)hipDeviceSynchronize();
     bank_res_give(c);
-    if (c->hugeq2) ws_free(c, c->hugeq2);
     for (auto& sl : c->slots) {
         pool_give(sl.host, sl.dev, sl.capacity * sizeof(FrameDev), c->pool_tag);
         if (sl.done) (void)hipEventDestroy(sl.done);
     }
-    for (int e = 0; e < 2; ++e) { if (c->keys[e]) ws_free(c, c->keys[e]); if (c->ekeys[e]) ws_free(c, c->ekeys[e]); if (c->cbuf[e]) ws_free(c, c->cbuf[e]); }
-    if (c->bigq) ws_free(c, c->bigq);
-    if (c->tri_invalid) ws_free(c, c->tri_invalid);
-    if (c->unused) ws_free(c, c->unused);
-    if (c->elist) ws_free(c, c->elist);
-    if (c->row_counts) ws_free(c, c->row_counts);
-    if (c->wave_counts) ws_free(c, c->wave_counts);
-    if (c->divcheck) ws_free(c, c->divcheck);
+    void* const render_ws[] = {c->hugeq2, c->keys[0], c->ekeys[0], c->cbuf[0], c->keys[1], c->ekeys[1], c->cbuf[1], c->bigq, c->tri_invalid, c->unused, c->elist,
+                               c->row_counts, c->wave_counts, c->divcheck, c->rowcell, c->msaa_keys, c->clip_keys, c->clip_flags};
+    for (void* p : render_ws) ws_free(c, p);      // (ws_free takes a null pointer)
     if (c->div_done) (void)hipEventDestroy(c->div_done);
-    if (c->rowcell) ws_free(c, c->rowcell);
-    if (c->msaa_keys) ws_free(c, c->msaa_keys);
-    if (c->clip_keys) ws_free(c, c->clip_keys);
-    if (c->clip_flags) ws_free(c, c->clip_flags);
     pool_give(c->telea_levels_host, nullptr, 64, -1);
     free_telea(c);
     free_telea_heap(c);
-    if (c->ni_ws) ws_free(c, c->ni_ws);
-    if (c->ffv1_ws) ws_free(c, c->ffv1_ws);
-    if (c->ffv1_dec_ws) ws_free(c, c->ffv1_dec_ws);
+    void* const other_ws[] = {c->ni_ws, c->ffv1_ws, c->ffv1_dec_ws};
+    for (void* p : other_ws) ws_free(c, p);
     delete c;
     return MDVT_OK;
 }
@@ -911,322 +895,250 @@ int mdvt_selftest(mdvt_ctx* c, int which, uint64_t seed, uint64_t* h_mismatches)
     return MDVT_OK;
 }
 
-int mdvt_render_stereo_batch(mdvt_ctx* c, int n_frames, const mdvt_frame_params* params, const mdvt_io* io, void* stream)
+// ---- The steps of mdvt_render_stereo_batch, in its order ---------------------------------------------------------------------
+struct BatchFlags { bool no_byte_mask, zout, want_bits, near_clip; };
+
+// Everything that is refused before the device is touched.
+static int validate_batch(mdvt_ctx* c, int n_frames, const mdvt_frame_params* params, const mdvt_io* io, BatchFlags& f)
 {
-    if (!c) return MDVT_ERR_INVALID_ARG;
     if (n_frames <= 0 || !params || !io) return fail(c, MDVT_ERR_INVALID_ARG, "n_frames/params/io invalid");
     if (!io->depth_rgb || !io->color_rgb || !io->left_rgb || !io->right_rgb)
         return fail(c, MDVT_ERR_INVALID_ARG, "depth_rgb, color_rgb and left/right rgb buffers are required");
-    if (c->cfg.samples == 4) {
-        const int rc = msaa_refusal(c, io);
-        if (rc != MDVT_OK) return rc;
-    }
-    const bool near_clip = c->near_clip && c->cfg.mode == MDVT_MODE_MESH;     // (points: a GL drops a point behind the plane, as the decree does)
-    if (near_clip) {
-        const int rc = msaa_refusal(c, io, "near-plane clipping (near_clip = 1)");
-        if (rc != MDVT_OK) return rc;
+    if (c->cfg.samples == 4) { if (int rc = msaa_refusal(c, io)) return rc; }
+    f.near_clip = c->near_clip && c->cfg.mode == MDVT_MODE_MESH;     // (points: a GL drops a point behind the plane, as the decree does)
+    if (f.near_clip) {
+        if (int rc = msaa_refusal(c, io, "near-plane clipping (near_clip = 1)")) return rc;
         // fan triangle f of source triangle d is drawn as 2 d + f: 4 (W - 1) (H - 1) ids in the 32 bits of a key
         if (c->W >= 2 && c->H >= 2 && 4 * (uint64_t)(c->W - 1) * (uint64_t)(c->H - 1) >= (uint64_t)0xFFFFFFFFu)
             return fail(c, MDVT_ERR_UNSUPPORTED, "near-plane clipping: a %d x %d frame has more fan triangles than its 32-bit draw ids can name", c->W, c->H);
     }
     // The byte masks may be left out (both NULL) by a caller that takes the packed mask instead -- where the compaction is fused
-    // into the render kernel (pure-shift point frames: checked per run below); everywhere else they are required.
-    const bool no_byte_mask = !io->left_mask && !io->right_mask && io->left_maskbits && io->right_maskbits;
-    if (!no_byte_mask && (!io->left_mask || !io->right_mask))
+    // into the render kernel (pure-shift point frames: checked per launch set in submit_run); everywhere else they are required.
+    f.no_byte_mask = !io->left_mask && !io->right_mask && io->left_maskbits && io->right_maskbits;
+    if (!f.no_byte_mask && (!io->left_mask || !io->right_mask))
         return fail(c, MDVT_ERR_INVALID_ARG, "left/right mask buffers are required (both may be NULL only when maskbits are given)");
     const int W = c->W, H = c->H;
     if (W < 2 || H < 2) return fail(c, MDVT_ERR_INVALID_ARG, "rendering needs at least a 2x2 frame");
     if (io->depth_pitch < (size_t)3 * W || io->color_pitch < (size_t)3 * W || io->rgb_pitch < (size_t)3 * W ||
-        (!no_byte_mask && io->mask_pitch < (size_t)W))
+        (!f.no_byte_mask && io->mask_pitch < (size_t)W))
         return fail(c, MDVT_ERR_INVALID_ARG, "a pitch is smaller than one row");   // sr:507 shape assert
-    const bool zout = io->left_depth || io->right_depth;
-    if (zout && io->zout_pitch < (size_t)4 * W) return fail(c, MDVT_ERR_INVALID_ARG, "zout_pitch smaller than one row");
+    f.zout = io->left_depth || io->right_depth;
+    if (f.zout && io->zout_pitch < (size_t)4 * W) return fail(c, MDVT_ERR_INVALID_ARG, "zout_pitch smaller than one row");
     if (io->left_seed || io->right_seed) {
         if (!io->left_seed || !io->right_seed) return fail(c, MDVT_ERR_INVALID_ARG, "seed images need both eyes");
         if (!c->cfg.remove_edges) return fail(c, MDVT_ERR_INVALID_ARG, "seed images need remove_edges (the infill-mask mode of sr:568-570)");
         if (io->seed_pitch < (size_t)3 * W) return fail(c, MDVT_ERR_INVALID_ARG, "seed_pitch smaller than one row");
     }
-    const bool want_bits = io->left_maskbits || io->right_maskbits;
-    if (want_bits) {
+    f.want_bits = io->left_maskbits || io->right_maskbits;
+    if (f.want_bits) {
         if (!io->left_maskbits || !io->right_maskbits) return fail(c, MDVT_ERR_INVALID_ARG, "maskbits need both eyes");
         if (io->maskbits_pitch < (size_t)4 * (((size_t)W + 31) / 32) || io->maskbits_pitch % 4 != 0 || io->maskbits_stride % 4 != 0 ||
             ((uintptr_t)io->left_maskbits % 4) || ((uintptr_t)io->right_maskbits % 4))
             return fail(c, MDVT_ERR_INVALID_ARG, "maskbits rows must be dword aligned and at least 4*ceil(W/32) bytes");
     }
-    DeviceGuard g(c->device);
-    hipStream_t s = (hipStream_t)stream;
+    return MDVT_OK;
+}
 
-    std::vector<FrameDev> fd((size_t)n_frames);
-    int general = 0;
-    for (int k = 0; k < n_frames; ++k) {
-        const int rc = fill_frame_dev(c, params[k], fd[(size_t)k]);
-        if (rc != MDVT_OK) return rc;
-        general |= fd[(size_t)k].general;
-        fd[(size_t)k].div_slot = -1;
-    }
-    if (c->cfg.samples == 4) return render_msaa(c, n_frames, fd, io, s);
-    // Pure-shift point frames: the disparity's division proven short per parameter set (FrameDev.div_slot).  A new set costs one
-    // launch of 65536 threads on this stream, once per context; clips have one set, or one per distinct field of view.
-    // The checks run on the stream of the call that brought their set in; a call on another stream (a pure-shift point render
-    // without hole counts uses no other workspace, so nothing else orders it after that call) first waits for the latest check,
-    // and with it for every earlier one and the table's fill: each check is recorded after a wait for the one before it, whichever
-    // stream that was on.
-    if (c->cfg.mode == MDVT_MODE_POINTS) {
-        bool ordered = false;
-        for (int k = 0; k < n_frames; ++k) {
-            FrameDev& f = fd[(size_t)k];
-            if (f.general) continue;
-            if (!ordered && c->div_done && c->div_stream != s) MDVT_HIP(c, hipStreamWaitEvent(s, c->div_done, 0));
-            ordered = true;
-            std::array<uint32_t, 3> key;
-            memcpy(&key[0], &f.mult, 4); memcpy(&key[1], &f.scale, 4); memcpy(&key[2], &f.dl, 4);
-            int slot = -1;
-            for (size_t q = c->div_keys.size(); q-- > 0;) if (c->div_keys[q] == key) { slot = (int)q; break; }
-            if (slot < 0 && c->div_keys.size() < (size_t)mdvt::kDivSlots) {
-                if (!c->divcheck) {
-                    MDVT_HIP(c, ws_malloc(c, (void**)&c->divcheck, mdvt::kDivSlots * sizeof(uint32_t), s));
-                    MDVT_HIP(c, hipMemsetAsync(c->divcheck, 0, mdvt::kDivSlots * sizeof(uint32_t), s));
-                }
-                if (!c->div_done) MDVT_HIP(c, hipEventCreateWithFlags(&c->div_done, hipEventDisableTiming));
-                slot = (int)c->div_keys.size();
-                MDVT_HIP(c, MDVT_GRID_CALL(c, launch_divcheck, f.mult, f.scale, f.dl, c->divcheck + slot, s));
-                MDVT_HIP(c, hipEventRecord(c->div_done, s));
-                c->div_stream = s;
-                c->div_keys.push_back(key);
+// Pure-shift point frames: the disparity's division proven short per parameter set (FrameDev.div_slot).  A new set costs one
+// launch of 65536 threads on this stream, once per context; clips have one set, or one per distinct field of view.
+// The checks run on the stream of the call that brought their set in; a call on another stream (a pure-shift point render
+// without hole counts uses no other workspace, so nothing else orders it after that call) first waits for the latest check,
+// and with it for every earlier one and the table's fill: each check is recorded after a wait for the one before it, whichever
+// stream that was on.
+static int assign_div_slots(mdvt_ctx* c, std::vector<FrameDev>& fd, hipStream_t s)
+{
+    bool ordered = false;
+    for (FrameDev& f : fd) {
+        if (f.general) continue;
+        if (!ordered && c->div_done && c->div_stream != s) MDVT_HIP(c, hipStreamWaitEvent(s, c->div_done, 0));
+        ordered = true;
+        std::array<uint32_t, 3> key;
+        memcpy(&key[0], &f.mult, 4); memcpy(&key[1], &f.scale, 4); memcpy(&key[2], &f.dl, 4);
+        int slot = -1;
+        for (size_t q = c->div_keys.size(); q-- > 0;) if (c->div_keys[q] == key) { slot = (int)q; break; }
+        if (slot < 0 && c->div_keys.size() < (size_t)mdvt::kDivSlots) {
+            if (!c->divcheck) {
+                MDVT_HIP(c, ws_malloc(c, (void**)&c->divcheck, mdvt::kDivSlots * sizeof(uint32_t), s));
+                MDVT_HIP(c, hipMemsetAsync(c->divcheck, 0, mdvt::kDivSlots * sizeof(uint32_t), s));
             }
-            f.div_slot = slot;
+            if (!c->div_done) MDVT_HIP(c, hipEventCreateWithFlags(&c->div_done, hipEventDisableTiming));
+            slot = (int)c->div_keys.size();
+            MDVT_HIP(c, MDVT_GRID_CALL(c, launch_divcheck, f.mult, f.scale, f.dl, c->divcheck + slot, s));
+            MDVT_HIP(c, hipEventRecord(c->div_done, s));
+            c->div_stream = s;
+            c->div_keys.push_back(key);
         }
+        f.div_slot = slot;
     }
-    // The arithmetic of a frame (pure shift or general) is its own property, never its batch
-    // neighbours': consecutive frames of one kind form a run, every run gets its own launches.
-    struct Run { int f0, f1, general, conv, craster; };  // general = "takes the global-key kernels"; conv = k_mesh_conv (mesh, convergence only);
-                                                         // craster = general, but every frame convergence-only: k_mesh_raster_conv
-    std::vector<Run> runs;
+    return MDVT_OK;
+}
 
-    const FrameDev* dfp = nullptr;
-    ParamSlot* slot = nullptr;
-    int rc = stage_params(c, fd, s, &dfp, &slot);
-    if (rc != MDVT_OK) return rc;
-
-    RenderPlan plan{};
-    plan.mode = c->cfg.mode;
-    plan.remove_edges = c->cfg.remove_edges;
-    plan.edge_points = c->cfg.remove_edges && c->cfg.edge_points;
-    plan.general = general;
-    plan.allow_conv = c->opt_mesh_conv ? 1 : 0;
-    if (tuning_build()) { const char* e = tuning_env(TUNE_MESH_CONV); plan.allow_conv = (e && e[0] == '1') ? 1 : 0; }   // (tests toggle it per call)
-    plan.vec4 = (W % 4 == 0) && aligned(io->depth_rgb, 4) && aligned(io->color_rgb, 4) && aligned(io->left_rgb, 4) &&
-                aligned(io->right_rgb, 4) && aligned(io->left_mask, 4) && aligned(io->right_mask, 4) &&
-                io->depth_pitch % 4 == 0 && io->color_pitch % 4 == 0 && io->rgb_pitch % 4 == 0 && io->mask_pitch % 4 == 0 &&
-                io->depth_stride % 4 == 0 && io->color_stride % 4 == 0 && io->rgb_stride % 4 == 0 && io->mask_stride % 4 == 0 &&
-                (!io->left_seed || (aligned(io->left_seed, 4) && aligned(io->right_seed, 4) && io->seed_pitch % 4 == 0 && io->seed_stride % 4 == 0)) &&
-                (!zout || ((!io->left_depth || aligned(io->left_depth, 16)) && (!io->right_depth || aligned(io->right_depth, 16)) &&
-                           io->zout_pitch % 16 == 0 && io->zout_stride % 16 == 0));
-
+// The arithmetic of a frame (pure shift or general) is its own property, never its batch
+// neighbours': consecutive frames of one kind form a run, every run gets its own launches.
+struct Run { int f0, f1, general, conv, craster; };  // general = "takes the global-key kernels"; conv = k_mesh_conv (mesh, convergence only);
+                                                     // craster = general, but every frame convergence-only: k_mesh_raster_conv
+static void build_runs(const mdvt_ctx* c, const RenderPlan& plan, const std::vector<FrameDev>& fd, std::vector<Run>& runs)
+{
+    const int W = c->W, H = c->H;
     // A pure-shift frame wider than the LDS row kernels can hold (10 240 px for points, ~4 300 for the mesh with edge
     // points) is rendered by the global-key kernels instead -- with its own pure-shift arithmetic (FrameDev.general
     // stays 0), so the pixels do not depend on which kernels ran.  MDVT_FORCE_GLOBAL=1 sends every frame that way (tests).
     const bool wide = !MDVT_GRID_CALL(c, render_fits_lds, plan, W) || tuning_env(TUNE_FORCE_GLOBAL) != nullptr;
-    if (wide) general = 1;
     bool conv_kernel = false;
     if (plan.mode == MDVT_MODE_MESH && !wide) {
         RenderArgs probe{};
         probe.W = W; probe.H = H;
         conv_kernel = MDVT_GRID_CALL(c, mesh_conv_supported, plan, probe);
     }
-    bool any_global = false, any_conv = false;
-    for (int k = 0; k < n_frames; ++k) {
+    for (int k = 0; k < (int)fd.size(); ++k) {
         const int cv = (conv_kernel && fd[(size_t)k].conv_band) ? 1 : 0;
         const int g = (!cv && (wide || fd[(size_t)k].general || fd[(size_t)k].erow_wild)) ? 1 : 0;
         const int cr = (g && !wide && plan.mode == MDVT_MODE_MESH && fd[(size_t)k].conv_band) ? 1 : 0;
-        any_global |= g != 0; any_conv |= cv != 0;
         if (runs.empty() || runs.back().general != g || runs.back().conv != cv || runs.back().craster != cr) runs.push_back({k, k + 1, g, cv, cr});
         else runs.back().f1 = k + 1;
     }
-    general = (any_global || any_conv) ? 1 : 0;          // some run uses the global workspace
-    const bool need_keys = any_global;
-    const bool need_ekeys = general && plan.edge_points;
-    const bool need_mesh_ws = any_global && plan.mode == MDVT_MODE_MESH;
-    // frames per launch set.  Point splat, general: two frames keep the 64-bit key buffers (33 MB per 1080p frame)
-    // inside the 256 MiB Infinity Cache between splat and resolve (measured +12 %); the mesh needs the slack of
-    // eight (rows full of slivers leave a long tail), and the edge filter alone streams, so 8 as well.
-    int tuned_chunk = 0;
-    if (const char* e = tuning_env(TUNE_WS_CHUNK)) { const int v = atoi(e); if (v > 0) tuned_chunk = v; }   // tuning hook
-    auto chunk_of = [&](const Run& r) {
-        const int n = r.f1 - r.f0;
-        if (!(r.general || plan.remove_edges || (r.conv && plan.edge_points))) return n;                  // no workspace: the whole run in one launch
-        // (points, general path: four slots -- one launch set of four frames, or banks of two (below); two slots until r04:
-        //  1080p convergence 26.7 k -> 28.2 k frames/s, 4K pose + contention 5.4 k -> 6.1 k)
-        int ws_chunk = (r.general && plan.mode == MDVT_MODE_POINTS) ? 4 : kWorkspaceChunk;
-        if (r.general && plan.mode == MDVT_MODE_MESH) {
-            ws_chunk = 2 * kWorkspaceChunk;      // 16: measured -4 % (convergence) / -11 % (pose) vs 8
-            // ~64 B/px per slot (z keys, tie side words, triangle queue; until r04 also 32 B/px of vertex records): 2.1 GB at 1080p,
-            // 8.5 GB at 4K; the queue's entry indices are 32-bit, so very large frames get fewer slots (4 entries per pixel and slot)
-            const size_t fit = (size_t)0xFFFFFFF0u / (4 * (size_t)W * (size_t)H);
-            if ((size_t)ws_chunk > fit) ws_chunk = fit < 1 ? 1 : (int)fit;
-            // ... and the slots have to fit the context's workspace budget (mdvt_config.workspace_mib, default 4 GiB: 16 slots at
-            // 1080p, 8 at 3840 x 2160 -- where 16 would be 8.5 GB): per slot and pixel 16 B of z keys, 16 B of tie side words,
-            // 32 B of triangle queue, with edge points 28 B of edge keys, their list and the vertex list, 3 B of filter flags
-            const size_t per_slot = (size_t)W * (size_t)H * (16 + 16 + 32 + (plan.edge_points ? 28 : 0) + (plan.remove_edges ? 3 : 0));
-            const size_t budget = (size_t)(c->cfg.workspace_mib ? c->cfg.workspace_mib : 4096u) << 20;
-            const size_t afford = budget / per_slot;
-            if ((size_t)ws_chunk > afford) ws_chunk = afford < 1 ? 1 : (int)afford;
-        }
-        // pure-shift mesh rows with edge removal: a launch is (frames x 135 bands) workgroups for 512 slots -- 8 frames
-        // leave the chip 30 % idle in the last wave of workgroups (476 -> see DESIGN.md); the workspace is 11 B/px per frame
-        // (points with edge removal likewise since r04: every launch set ends with k_edge_rows_exact, a handful of workgroups the
-        //  stream waits for -- once per 32 frames instead of once per 8)
-        if (!r.general) ws_chunk = 4 * kWorkspaceChunk;
-        if (tuned_chunk) ws_chunk = tuned_chunk;
-        if (r.general && ws_chunk > 32) ws_chunk = 32;        // one parity bit per z-key slot (uint32_t key_parity)
-        return n < ws_chunk ? n : ws_chunk;
-    };
-    int ws_frames = 0, count_frames = 0;
-    for (const Run& r : runs) {
-        const int ch = chunk_of(r);
-        if ((r.general || r.conv || plan.remove_edges) && ch > ws_frames) ws_frames = ch;
-        if (ch > count_frames) count_frames = ch;
-    }
-    if (ws_frames && (rc = ensure_workspace(c, ws_frames, need_keys, need_ekeys, plan.remove_edges, need_mesh_ws, s)) != MDVT_OK) return rc;
+}
 
-    RenderArgs a{};
-    a.depth = io->depth_rgb; a.depth_pitch = io->depth_pitch; a.depth_stride = io->depth_stride;
-    a.color = io->color_rgb; a.color_pitch = io->color_pitch; a.color_stride = io->color_stride;
-    a.rgb[0] = io->left_rgb; a.rgb[1] = io->right_rgb; a.rgb_pitch = io->rgb_pitch; a.rgb_stride = io->rgb_stride;
-    a.mask[0] = io->left_mask; a.mask[1] = io->right_mask; a.mask_pitch = io->mask_pitch; a.mask_stride = io->mask_stride;
-    a.zout[0] = io->left_depth; a.zout[1] = io->right_depth; a.zout_pitch = io->zout_pitch; a.zout_stride = io->zout_stride;
-    a.maskbits[0] = io->left_maskbits; a.maskbits[1] = io->right_maskbits;
-    a.maskbits_pitch = io->maskbits_pitch; a.maskbits_stride = io->maskbits_stride;
-    a.hole_counts = io->hole_counts;
-    a.seed[0] = io->left_seed; a.seed[1] = io->right_seed; a.seed_pitch = io->seed_pitch; a.seed_stride = io->seed_stride;
-    if (io->hole_counts) {
-        if (c->row_counts_frames < count_frames) {
-            if (c->row_counts) { MDVT_HIP(c, hipDeviceSynchronize()); ws_free(c, c->row_counts); ws_free(c, c->wave_counts); }     // (earlier submissions may still count into it)
-            c->row_counts = nullptr; c->wave_counts = nullptr; c->row_counts_frames = 0;
-            MDVT_HIP(c, ws_malloc(c, (void**)&c->row_counts, (size_t)count_frames * 2 * H * sizeof(uint32_t), s));
-            MDVT_HIP(c, ws_malloc(c, (void**)&c->wave_counts, (size_t)count_frames * H * 16 * sizeof(uint32_t), s));
-            c->row_counts_frames = count_frames;
-        }
-        a.row_counts = c->row_counts;
-        a.wave_counts = c->wave_counts;
+// frames per launch set.  Point splat, general: two frames keep the 64-bit key buffers (33 MB per 1080p frame)
+// inside the 256 MiB Infinity Cache between splat and resolve (measured +12 %); the mesh needs the slack of
+// eight (rows full of slivers leave a long tail), and the edge filter alone streams, so 8 as well.
+static int chunk_of(const mdvt_ctx* c, const RenderPlan& plan, const Run& r, int tuned_chunk)
+{
+    const int n = r.f1 - r.f0;
+    if (!(r.general || plan.remove_edges || (r.conv && plan.edge_points))) return n;                  // no workspace: the whole run in one launch
+    // (points, general path: four slots -- one launch set of four frames, or banks of two (submit_run); two slots until r04:
+    //  1080p convergence 26.7 k -> 28.2 k frames/s, 4K pose + contention 5.4 k -> 6.1 k)
+    int ws_chunk = (r.general && plan.mode == MDVT_MODE_POINTS) ? 4 : kWorkspaceChunk;
+    if (r.general && plan.mode == MDVT_MODE_MESH) {
+        ws_chunk = 2 * kWorkspaceChunk;      // 16: measured -4 % (convergence) / -11 % (pose) vs 8
+        // ~64 B/px per slot (z keys, tie side words, triangle queue; until r04 also 32 B/px of vertex records): 2.1 GB at 1080p,
+        // 8.5 GB at 4K; the queue's entry indices are 32-bit, so very large frames get fewer slots (4 entries per pixel and slot)
+        const size_t fit = queue_slots_max(c->W, c->H);
+        if ((size_t)ws_chunk > fit) ws_chunk = fit < 1 ? 1 : (int)fit;
+        // ... and the slots have to fit the context's workspace budget (mdvt_config.workspace_mib, default 4 GiB: 16 slots at
+        // 1080p, 8 at 3840 x 2160 -- where 16 would be 8.5 GB): per slot and pixel 16 B of z keys, 16 B of tie side words,
+        // 32 B of triangle queue, with edge points 28 B of edge keys, their list and the vertex list, 3 B of filter flags
+        ws_chunk = slots_afforded(c, nominal_slot_bytes(c->W, c->H, plan.edge_points, plan.remove_edges), ws_chunk);
     }
-    a.fp = dfp;
-    a.divcheck = c->divcheck;
-    a.edge_paint = c->cfg.edge_points != 2;
-    a.cull = c->cfg.cull;
-    if (c->cfg.mode == MDVT_MODE_MESH) { if ((rc = ensure_rowcell(c, s)) != MDVT_OK) return rc; a.rowcell = c->rowcell; }
-    a.W = W; a.H = H;
-    a.key_rgb = (uint32_t)c->cfg.key_rgb[0] | ((uint32_t)c->cfg.key_rgb[1] << 8) | ((uint32_t)c->cfg.key_rgb[2] << 16);
-    a.keys[0] = c->keys[0]; a.keys[1] = c->keys[1];
-    a.ekeys[0] = c->ekeys[0]; a.ekeys[1] = c->ekeys[1];
-    a.elist = c->elist; a.elist_count = c->elist ? c->elist + (size_t)c->ws_frames * 2 * (size_t)W * H : nullptr;
-    a.vlist = c->elist ? a.elist_count + (size_t)c->ws_frames * H : nullptr;
-    a.vlist_count = c->elist ? a.vlist + (size_t)c->ws_frames * (size_t)W * H : nullptr;
-    a.cbuf[0] = c->cbuf[0]; a.cbuf[1] = c->cbuf[1];
-    a.tri_invalid = c->tri_invalid; a.unused = c->unused;
-    if (c->bigq) {
-        a.bigq = c->bigq; a.bigq_cap = c->bigq_cap; a.bigq_count = c->bigq + (size_t)c->bigq_cap * mdvt::kBigRecDwords;
-        a.hugeq = a.bigq_count + 2 * (size_t)c->ws_frames * H + 8;      // (8-byte aligned: entries are uint2); two lists (banks, below)
-        a.tie_flag = a.hugeq + (size_t)c->huge_lists * (2 * (size_t)mdvt::kHugeCap + 2);
-        a.tie_tiles = a.tie_flag + c->ws_frames;
-        a.tie_words = (int32_t)mdvt::tie_words_of(W, H);
-        a.tie_tiles_x = (W + mdvt::kTieTile - 1) / mdvt::kTieTile;
-    }
-    a.ws_stride_px = (size_t)W * H;
-    a.ws_stride_tri = 2 * (size_t)(W - 1) * (H - 1);
+    // pure-shift mesh rows with edge removal: a launch is (frames x 135 bands) workgroups for 512 slots -- 8 frames
+    // leave the chip 30 % idle in the last wave of workgroups (476 -> see DESIGN.md); the workspace is 11 B/px per frame
+    // (points with edge removal likewise since r04: every launch set ends with k_edge_rows_exact, a handful of workgroups the
+    //  stream waits for -- once per 32 frames instead of once per 8)
+    if (!r.general) ws_chunk = 4 * kWorkspaceChunk;
+    if (tuned_chunk) ws_chunk = tuned_chunk;
+    if (r.general && ws_chunk > 32) ws_chunk = 32;        // one parity bit per z-key slot (uint32_t key_parity)
+    return n < ws_chunk ? n : ws_chunk;
+}
 
-    if (general) {
-        if (c->keys_dirty) {        // re-establish the EMPTY invariant the resolve pass normally maintains
-            const size_t bytes = (size_t)c->ws_frames * a.ws_stride_px * sizeof(unsigned long long);
-            for (int e = 0; e < 2; ++e) {
-                if (c->keys[e]) MDVT_HIP(c, hipMemsetAsync(c->keys[e], 0xFF, bytes, s));
-                if (c->ekeys[e]) MDVT_HIP(c, hipMemsetAsync(c->ekeys[e], 0xFF, bytes, s));
-            }
-            if (c->elist) MDVT_HIP(c, hipMemsetAsync(a.elist_count, 0, (size_t)c->ws_frames * H * sizeof(uint32_t), s));
-            c->key_parity = 0;
-        }
-        c->keys_dirty = true;
+// The hole counts' per-row and per-wave counters of `frames` frames in flight, grown on demand.
+static int ensure_count_buffers(mdvt_ctx* c, int frames, hipStream_t s)
+{
+    if (c->row_counts_frames >= frames) return MDVT_OK;
+    if (c->row_counts) { MDVT_HIP(c, hipDeviceSynchronize()); ws_free(c, c->row_counts); ws_free(c, c->wave_counts); }     // (earlier submissions may still count into it)
+    c->row_counts = nullptr; c->wave_counts = nullptr; c->row_counts_frames = 0;
+    MDVT_HIP(c, ws_malloc(c, (void**)&c->row_counts, (size_t)frames * 2 * c->H * sizeof(uint32_t), s));
+    MDVT_HIP(c, ws_malloc(c, (void**)&c->wave_counts, (size_t)frames * c->H * 16 * sizeof(uint32_t), s));
+    c->row_counts_frames = frames;
+    return MDVT_OK;
+}
+
+// An earlier general-path submission stopped between splat and resolve: re-establish the EMPTY invariant the resolve pass normally maintains.
+static int reset_dirty_keys(mdvt_ctx* c, const RenderWorkspaceLayout& L, hipStream_t s)
+{
+    for (int e = 0; e < 2; ++e) {
+        if (c->keys[e]) MDVT_HIP(c, hipMemsetAsync(c->keys[e], 0xFF, L.plane_bytes(), s));
+        if (c->ekeys[e]) MDVT_HIP(c, hipMemsetAsync(c->ekeys[e], 0xFF, L.plane_bytes(), s));
     }
-    for (const Run& r : runs) {
-      plan.general = r.general;
-      plan.conv = r.conv;
-      plan.conv_raster = r.craster;
-      int chunk = chunk_of(r);
-      // Posed / converged mesh frames in more than one launch set: the sets take turns on two halves ("banks") of the workspace slots
-      // and on two streams, a set starting when the vertex pass of the set before it is through -- the path's stages wait for
-      // different things (the vertex pass for its stores, the rasteriser for its atomics), and the next set's vertex pass and edge
-      // filter fill the rasteriser's waits: 32 frames of 1080p product default +3 %, mesh + convergence +4 %, mesh under a pose +7 %,
-      // 8 frames of 4K pose + contention (C4) +10 %; a run that fits ONE launch set stays as it is (16 frames: two sets of 8 lose 1.5 %).
-      // Points on the general path likewise (splat, then resolve: the next set's splat beside this set's resolve): C4 points +13 %.
-      const bool bankable = r.general && !r.conv && !want_bits && !io->hole_counts && tuning_env(TUNE_WS_CHUNK) == nullptr;
-      bool banks = bankable && chunk >= 2 && r.f1 - r.f0 > chunk;
-      int bank_slots = chunk / 2;
-      // r05: a posed mesh run that FITS one launch set is split into two sets on the two banks all the same when each half is large
-      // enough to fill the chip by itself (3 frames of 4K = 24.9 M pixels: 6 to 8 frames of C4's shape) -- since the vertex records went (64 B/px per slot, was 96) the
-      // 8 frames of C4 are one set of 8 slots, and its cell walk (VALU) and resolve (HBM) ran one after the other again
-      if (bankable && !banks && plan.mode == MDVT_MODE_MESH && r.f1 - r.f0 <= chunk && r.f1 - r.f0 >= 4 &&
-          (size_t)((r.f1 - r.f0) / 2) * (size_t)W * (size_t)H >= (size_t)3 * 3840 * 2160) {
-          banks = true;
-          bank_slots = (r.f1 - r.f0) / 2;
-      }
-      hipStream_t const s_call = s;
-      // (every way out of the bank loop joins the side stream back into the caller's: an error return must not leave the side
-      //  stream working on its half of the workspace -- and on the caller's output buffers -- behind the caller's back; advisor, r04)
-      struct BankJoin {
-          mdvt_ctx* c; hipStream_t s_call; bool armed;
-          ~BankJoin() {
-              if (!armed) return;
-              if (hipEventRecord(c->ev_join, c->side) != hipSuccess || hipStreamWaitEvent(s_call, c->ev_join, 0) != hipSuccess) (void)hipStreamSynchronize(c->side);
-          }
-      } bank_join{c, s_call, false};
-      if (banks) {
-          chunk = bank_slots;
-          if (!c->side) MDVT_HIP(c, bank_res_take(c));        // (process-wide: see bank_res_take)
-          MDVT_HIP(c, hipEventRecord(c->ev_start, s_call));            // (the inputs, the parameter block, the runs before this one)
-          MDVT_HIP(c, hipStreamWaitEvent(c->side, c->ev_start, 0));
-          bank_join.armed = true;
-      }
-      const RenderArgs a_all = a;
-      int set = 0;
-      for (int f0 = r.f0; f0 < r.f1; f0 += chunk, ++set) {
+    if (c->elist) MDVT_HIP(c, hipMemsetAsync(c->elist + L.elist_count_at(), 0, L.slots * L.H * sizeof(uint32_t), s));
+    c->key_parity = 0;
+    return MDVT_OK;
+}
+
+// Points RenderArgs at the workspace slots [slot0, ...) of a launch set: the whole workspace (slot0 = 0, bank 0) or a bank's half
+// (slot0 = bank * bank_slots).  Allocates nothing: the second bank's separate huge list is made by submit_run.
+static void bind_workspace(RenderArgs& a, const mdvt_ctx* c, const RenderWorkspaceLayout& L, int slot0, int bank, int bank_slots)
+{
+    const size_t s0 = (size_t)slot0;
+    auto at = [](auto* p, size_t off) -> decltype(p) { return p ? p + off : nullptr; };
+    for (int e = 0; e < 2; ++e) {
+        a.keys[e] = at(c->keys[e], s0 * L.npx);
+        a.ekeys[e] = at(c->ekeys[e], s0 * L.npx);
+        a.cbuf[e] = at(c->cbuf[e], s0 * L.npx);
+    }
+    a.elist = at(c->elist, s0 * L.elist_stride());
+    a.elist_count = at(c->elist, L.elist_count_at() + s0 * L.H);
+    a.vlist = at(c->elist, L.vlist_at() + s0 * L.npx);
+    a.vlist_count = at(c->elist, L.vlist_count_at() + s0);
+    a.tri_invalid = at(c->tri_invalid, s0 * L.ntri);
+    a.unused = at(c->unused, s0 * L.npx);
+    if (!c->bigq) return;
+    a.bigq = c->bigq + s0 * L.queue_stride(); a.bigq_cap = (uint32_t)L.bigq_cap();
+    a.bigq_count = c->bigq + L.counters_at() + L.bank_counters_at(bank, bank_slots);      // (counters and prefix sums of a set; 16-byte aligned)
+    // The second bank's own huge list: a separate allocation, made when banks are first used (r04: with both lists in the
+    // queue's block a 100 x 31 frame's block passed 2 MB and left the runtime's fragment cache -- see the workspace pool above).
+    a.hugeq = c->bigq + L.huge_at();      // (8-byte aligned: entries are uint2)
+    if (bank) a.hugeq = L.huge_lists == 2 ? a.hugeq + L.huge_list_dwords() : c->hugeq2;
+    a.tie_flag = c->bigq + L.tie_flag_at() + s0;
+    a.tie_tiles = c->bigq + L.tie_tiles_at() + s0 * L.tie_tiles_stride();
+    a.tie_words = (int32_t)L.tie_words; a.tie_tiles_x = (c->W + mdvt::kTieTile - 1) / mdvt::kTieTile;
+}
+
+// (every way out of the bank loop joins the side stream back into the caller's: an error return must not leave the side
+//  stream working on its half of the workspace -- and on the caller's output buffers -- behind the caller's back; advisor, r04)
+struct BankJoin {
+    mdvt_ctx* c; hipStream_t s_call; bool armed;
+    ~BankJoin() {
+        if (!armed) return;
+        if (hipEventRecord(c->ev_join, c->side) != hipSuccess || hipStreamWaitEvent(s_call, c->ev_join, 0) != hipSuccess) (void)hipStreamSynchronize(c->side);
+    }
+};
+
+// One run's launch sets of up to `chunk` frames; `base`: everything of RenderArgs but the workspace.
+static int submit_run(mdvt_ctx* c, RenderPlan plan, const Run& r, int chunk, const RenderArgs& base, const RenderWorkspaceLayout& L,
+               const std::vector<FrameDev>& fd, const BatchFlags& bf, hipStream_t s_call)
+{
+    const int W = c->W, H = c->H;
+    plan.general = r.general; plan.conv = r.conv; plan.conv_raster = r.craster;
+    // Posed / converged mesh frames in more than one launch set: the sets take turns on two halves ("banks") of the workspace slots
+    // and on two streams, a set starting when the vertex pass of the set before it is through -- the path's stages wait for
+    // different things (the vertex pass for its stores, the rasteriser for its atomics), and the next set's vertex pass and edge
+    // filter fill the rasteriser's waits: 32 frames of 1080p product default +3 %, mesh + convergence +4 %, mesh under a pose +7 %,
+    // 8 frames of 4K pose + contention (C4) +10 %; a run that fits ONE launch set stays as it is (16 frames: two sets of 8 lose 1.5 %).
+    // Points on the general path likewise (splat, then resolve: the next set's splat beside this set's resolve): C4 points +13 %.
+    const bool bankable = r.general && !r.conv && !bf.want_bits && !base.hole_counts && tuning_env(TUNE_WS_CHUNK) == nullptr;
+    bool banks = bankable && chunk >= 2 && r.f1 - r.f0 > chunk;
+    int bank_slots = chunk / 2;
+    // r05: a posed mesh run that FITS one launch set is split into two sets on the two banks all the same when each half is large
+    // enough to fill the chip by itself (3 frames of 4K = 24.9 M pixels: 6 to 8 frames of C4's shape) -- since the vertex records went (64 B/px per slot, was 96) the
+    // 8 frames of C4 are one set of 8 slots, and its cell walk (VALU) and resolve (HBM) ran one after the other again
+    if (bankable && !banks && plan.mode == MDVT_MODE_MESH && r.f1 - r.f0 <= chunk && r.f1 - r.f0 >= 4 &&
+        (size_t)((r.f1 - r.f0) / 2) * (size_t)W * (size_t)H >= (size_t)3 * 3840 * 2160) {
+        banks = true;
+        bank_slots = (r.f1 - r.f0) / 2;
+    }
+    BankJoin bank_join{c, s_call, false};
+    if (banks) {
+        chunk = bank_slots;
+        if (!c->side) MDVT_HIP(c, bank_res_take(c));        // (process-wide: see bank_res_take)
+        MDVT_HIP(c, hipEventRecord(c->ev_start, s_call));            // (the inputs, the parameter block, the runs before this one)
+        MDVT_HIP(c, hipStreamWaitEvent(c->side, c->ev_start, 0));
+        bank_join.armed = true;
+    }
+    int set = 0;
+    for (int f0 = r.f0; f0 < r.f1; f0 += chunk, ++set) {
         plan.n = (r.f1 - f0 < chunk) ? r.f1 - f0 : chunk;
         const int bank = banks ? (set & 1) : 0, slot0 = bank * bank_slots;
-        hipStream_t s = bank ? c->side : s_call;
+        hipStream_t const s_set = bank ? c->side : s_call;
+        if (bank && c->bigq && c->huge_lists != 2 && !c->hugeq2) MDVT_HIP(c, ws_malloc(c, (void**)&c->hugeq2, L.huge_list_dwords() * sizeof(uint32_t), s_set));
+        RenderArgs a = base;
+        bind_workspace(a, c, L, slot0, bank, bank_slots);
         if (banks) {
-            a = a_all;
-            const size_t px0 = (size_t)slot0 * a.ws_stride_px;
-            for (int e = 0; e < 2; ++e) {
-                a.keys[e] += px0;
-                if (a.cbuf[e]) a.cbuf[e] += px0;
-                if (a.ekeys[e]) a.ekeys[e] += px0;
-            }
-            if (a.elist) { a.elist += (size_t)slot0 * 2 * (size_t)W * H; a.elist_count += (size_t)slot0 * H; a.vlist += px0; a.vlist_count += slot0; }
-            if (a.tri_invalid) a.tri_invalid += (size_t)slot0 * a.ws_stride_tri;
-            if (a.unused) a.unused += px0;
-            if (a.bigq) {
-                a.bigq += (size_t)slot0 * H * (size_t)(4 * W) * mdvt::kBigRecDwords;
-                a.bigq_count += (size_t)bank * ((2 * (size_t)bank_slots * H + 2 + 3) & ~(size_t)3);      // (counters and prefix sums of a set; 16-byte aligned)
-                // The second bank's own huge list: a separate allocation, made when banks are first used (r04: with both lists in the
-                // queue's block a 100 x 31 frame's block passed 2 MB and left the runtime's fragment cache -- see the workspace pool above).
-                if (bank && c->huge_lists == 2) a.hugeq += 2 * (size_t)mdvt::kHugeCap + 2;
-                else if (bank) {
-                    if (!c->hugeq2) MDVT_HIP(c, ws_malloc(c, (void**)&c->hugeq2, (2 * (size_t)mdvt::kHugeCap + 2) * sizeof(uint32_t), s));
-                    a.hugeq = c->hugeq2;
-                }
-                a.tie_flag += slot0;
-                a.tie_tiles += (size_t)slot0 * 2 * a.tie_words;
-            }
-            if (set > 0) MDVT_HIP(c, hipStreamWaitEvent(s, c->ev_vert[bank ^ 1], 0));      // (the set before this one has projected its vertices / splatted its points)
+            if (set > 0) MDVT_HIP(c, hipStreamWaitEvent(s_set, c->ev_vert[bank ^ 1], 0));      // (the set before this one has projected its vertices / splatted its points)
             plan.after_vertices = c->ev_vert[bank];
         }
         a.frame0 = f0;
-        if (plan.remove_edges) {
-            MDVT_HIP(c, launch_zero_bytes(a.unused, (size_t)plan.n * a.ws_stride_px, s));
-            MDVT_HIP(c, launch_edge_filter(a.depth, a.depth_pitch, a.depth_stride, dfp, f0, plan.n, W, H,
-                                           plan.mode == MDVT_MODE_MESH, a.tri_invalid, a.ws_stride_tri,
-                                           a.unused, a.ws_stride_px, s));
-        }
-        if (no_byte_mask && !MDVT_GRID_CALL(c, points_fused_bits_applies, plan, a))
+        if (plan.remove_edges) { if (int rc = filter_edges(c, a, plan.n, a.tri_invalid, a.unused, s_set)) return rc; }
+        if (bf.no_byte_mask && !MDVT_GRID_CALL(c, points_fused_bits_applies, plan, a))
             return fail(c, MDVT_ERR_INVALID_ARG, "the byte masks may be NULL only where the mask compaction is fused into the render "
                         "(points mode, pure stereo shift, no edge removal, W %% 4 == 0, W <= 4096, dword-aligned image pointers, pitches and strides)");
         a.key_parity = c->key_parity >> slot0;
@@ -1235,23 +1147,92 @@ int mdvt_render_stereo_batch(mdvt_ctx* c, int n_frames, const mdvt_frame_params*
             for (int k = f0; k < f0 + plan.n; ++k)
                 if (fd[(size_t)k].erow_lo < fd[(size_t)k].erow_hi)
                     plan.edge_rows_max = std::max(plan.edge_rows_max, fd[(size_t)k].erow_hi - fd[(size_t)k].erow_lo + 1);
-        hipError_t e = MDVT_GRID_CALL(c, launch_render, plan, a, s);
+        hipError_t e = MDVT_GRID_CALL(c, launch_render, plan, a, s_set);
         plan.after_vertices = nullptr;
         if (r.general && e == hipSuccess) c->key_parity ^= (plan.n >= 32 ? 0xFFFFFFFFu : ((1u << plan.n) - 1u)) << slot0;   // these slots' next use has the other parity
         if (e == hipErrorNotSupported) return fail(c, MDVT_ERR_UNSUPPORTED, "render mode %d is not built yet", plan.mode);
         if (e != hipSuccess) return fail(c, MDVT_ERR_HIP, "render launch failed: %s", hipGetErrorString(e));
-        if ((want_bits || io->hole_counts) && !plan.fused_bits) MDVT_HIP(c, launch_pack_mask(a, plan.n, s));
-        if (io->hole_counts && !plan.fused_bits) MDVT_HIP(c, launch_reduce_counts(a, plan.n, s));
-      }
-      if (banks) {
-          a = a_all;
-          MDVT_HIP(c, hipEventRecord(c->ev_join, c->side));
-          MDVT_HIP(c, hipStreamWaitEvent(s_call, c->ev_join, 0));
-          bank_join.armed = false;
-      }
+        if ((bf.want_bits || a.hole_counts) && !plan.fused_bits) MDVT_HIP(c, launch_pack_mask(a, plan.n, s_set));
+        if (a.hole_counts && !plan.fused_bits) MDVT_HIP(c, launch_reduce_counts(a, plan.n, s_set));
     }
-    if (general) c->keys_dirty = false;
-    if (near_clip && (rc = render_near_clip_gate(c, n_frames, dfp, io, s)) != MDVT_OK) return rc;
+    if (banks) {
+        MDVT_HIP(c, hipEventRecord(c->ev_join, c->side));
+        MDVT_HIP(c, hipStreamWaitEvent(s_call, c->ev_join, 0));
+        bank_join.armed = false;
+    }
+    return MDVT_OK;
+}
+
+int mdvt_render_stereo_batch(mdvt_ctx* c, int n_frames, const mdvt_frame_params* params, const mdvt_io* io, void* stream)
+{
+    if (!c) return MDVT_ERR_INVALID_ARG;
+    BatchFlags bf{};
+    int rc = validate_batch(c, n_frames, params, io, bf);
+    if (rc != MDVT_OK) return rc;
+    DeviceGuard g(c->device);
+    hipStream_t const s = (hipStream_t)stream;
+    std::vector<FrameDev> fd((size_t)n_frames);
+    int any_general_frame = 0;
+    for (int k = 0; k < n_frames; ++k) {
+        if ((rc = fill_frame_dev(c, params[k], fd[(size_t)k])) != MDVT_OK) return rc;
+        any_general_frame |= fd[(size_t)k].general;
+        fd[(size_t)k].div_slot = -1;
+    }
+    if (c->cfg.samples == 4) return render_msaa(c, n_frames, fd, io, s);
+    if (c->cfg.mode == MDVT_MODE_POINTS && (rc = assign_div_slots(c, fd, s)) != MDVT_OK) return rc;
+
+    const FrameDev* dfp = nullptr;
+    ParamSlot* slot = nullptr;
+    if ((rc = stage_params(c, fd, s, &dfp, &slot)) != MDVT_OK) return rc;
+
+    RenderPlan plan{};
+    plan.mode = c->cfg.mode;
+    plan.remove_edges = c->cfg.remove_edges;
+    plan.edge_points = c->cfg.remove_edges && c->cfg.edge_points;
+    plan.general = any_general_frame;
+    plan.allow_conv = c->opt_mesh_conv ? 1 : 0;
+    if (tuning_build()) { const char* e = tuning_env(TUNE_MESH_CONV); plan.allow_conv = (e && e[0] == '1') ? 1 : 0; }   // (tests toggle it per call)
+    plan.vec4 = (c->W % 4 == 0) && aligned(io->depth_rgb, 4) && aligned(io->color_rgb, 4) && aligned(io->left_rgb, 4) &&
+                aligned(io->right_rgb, 4) && aligned(io->left_mask, 4) && aligned(io->right_mask, 4) &&
+                io->depth_pitch % 4 == 0 && io->color_pitch % 4 == 0 && io->rgb_pitch % 4 == 0 && io->mask_pitch % 4 == 0 &&
+                io->depth_stride % 4 == 0 && io->color_stride % 4 == 0 && io->rgb_stride % 4 == 0 && io->mask_stride % 4 == 0 &&
+                (!io->left_seed || (aligned(io->left_seed, 4) && aligned(io->right_seed, 4) && io->seed_pitch % 4 == 0 && io->seed_stride % 4 == 0)) &&
+                (!bf.zout || ((!io->left_depth || aligned(io->left_depth, 16)) && (!io->right_depth || aligned(io->right_depth, 16)) &&
+                              io->zout_pitch % 16 == 0 && io->zout_stride % 16 == 0));
+
+    std::vector<Run> runs;
+    build_runs(c, plan, fd, runs);
+    bool any_global = false, uses_global_ws = false;          // some run takes the global-key kernels / uses the global workspace
+    for (const Run& r : runs) { any_global |= r.general != 0; uses_global_ws |= r.general || r.conv; }
+    int tuned_chunk = 0;
+    if (const char* e = tuning_env(TUNE_WS_CHUNK)) { const int v = atoi(e); if (v > 0) tuned_chunk = v; }   // tuning hook
+    int ws_frames = 0, count_frames = 0;
+    for (const Run& r : runs) {
+        const int ch = chunk_of(c, plan, r, tuned_chunk);
+        if ((r.general || r.conv || plan.remove_edges) && ch > ws_frames) ws_frames = ch;
+        if (ch > count_frames) count_frames = ch;
+    }
+    if (ws_frames && (rc = ensure_workspace(c, ws_frames, any_global, uses_global_ws && plan.edge_points, plan.remove_edges,
+                                            any_global && plan.mode == MDVT_MODE_MESH, s)) != MDVT_OK) return rc;
+    RenderArgs base{};
+    bind_io(base, c, io, dfp);
+    base.zout[0] = io->left_depth; base.zout[1] = io->right_depth; base.zout_pitch = io->zout_pitch; base.zout_stride = io->zout_stride;
+    base.maskbits[0] = io->left_maskbits; base.maskbits[1] = io->right_maskbits;
+    base.maskbits_pitch = io->maskbits_pitch; base.maskbits_stride = io->maskbits_stride;
+    base.seed[0] = io->left_seed; base.seed[1] = io->right_seed; base.seed_pitch = io->seed_pitch; base.seed_stride = io->seed_stride;
+    if (io->hole_counts) {
+        if ((rc = ensure_count_buffers(c, count_frames, s)) != MDVT_OK) return rc;
+        base.row_counts = c->row_counts; base.wave_counts = c->wave_counts;
+    }
+    base.divcheck = c->divcheck; base.edge_paint = c->cfg.edge_points != 2; base.cull = c->cfg.cull;
+    if (c->cfg.mode == MDVT_MODE_MESH) { if ((rc = ensure_rowcell(c, s)) != MDVT_OK) return rc; base.rowcell = c->rowcell; }
+    const RenderWorkspaceLayout L = layout_of(c);
+    if (uses_global_ws && c->keys_dirty && (rc = reset_dirty_keys(c, L, s)) != MDVT_OK) return rc;
+    if (uses_global_ws) c->keys_dirty = true;
+    for (const Run& r : runs)
+        if ((rc = submit_run(c, plan, r, chunk_of(c, plan, r, tuned_chunk), base, L, fd, bf, s)) != MDVT_OK) return rc;
+    if (uses_global_ws) c->keys_dirty = false;
+    if (bf.near_clip && (rc = render_near_clip_gate(c, n_frames, dfp, io, s)) != MDVT_OK) return rc;
     MDVT_HIP(c, hipEventRecord(slot->done, s));
     return MDVT_OK;
 }
@@ -1288,50 +1269,14 @@ int mdvt_encode_depth(mdvt_ctx* c, const float* d_depth, size_t depth_pitch, uin
 
 int mdvt_release_cached_memory(int device)
 {
-    std::vector<DevBlock> out;
-    {
-        std::lock_guard<std::mutex> lock(g_dev_pool_mutex);
-        auto& pool = dev_pool();
-        for (size_t k = 0; k < pool.size();) {
-            if (device >= 0 && pool[k].tag != device) { ++k; continue; }
-            out.push_back(pool[k]);
-            dev_pool_idle()[pool[k].tag] -= pool[k].bytes;
-            pool.erase(pool.begin() + (long)k);
-        }
-    }
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess) count = 0;
-    for (const DevBlock& b : out) {
-        // (a block tagged for a GPU this process does not have -- the tuning build's MDVT_POOL_TAG -- lives on the current one)
-        DeviceGuard g(b.tag >= 0 && b.tag < count ? b.tag : 0);
-        (void)hipDeviceSynchronize();
-        (void)hipFree(b.p);
-    }
+    drain_dev_pool([&](const DevBlock& b) { return device < 0 || b.tag == device; });
     return MDVT_OK;
 }
 
 int mdvt_set_cached_memory_limit(uint64_t bytes_per_gpu)
 {
-    std::vector<DevBlock> out;
-    {
-        std::lock_guard<std::mutex> lock(g_dev_pool_mutex);
-        g_dev_pool_idle_cap = (size_t)bytes_per_gpu;
-        auto& pool = dev_pool();
-        for (size_t k = 0; k < pool.size();) {                                           // oldest first, per GPU
-            size_t& idle = dev_pool_idle()[pool[k].tag];
-            if (idle <= g_dev_pool_idle_cap) { ++k; continue; }
-            out.push_back(pool[k]);
-            idle -= pool[k].bytes;
-            pool.erase(pool.begin() + (long)k);
-        }
-    }
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess) count = 0;
-    for (const DevBlock& b : out) {
-        DeviceGuard g(b.tag >= 0 && b.tag < count ? b.tag : 0);
-        (void)hipDeviceSynchronize();
-        (void)hipFree(b.p);
-    }
+    const size_t cap = (size_t)bytes_per_gpu;
+    drain_dev_pool([](const DevBlock& b) { return dev_pool_idle()[b.tag] > g_dev_pool_idle_cap; }, &cap);      // per GPU, while its idle bytes pass the limit
     return MDVT_OK;
 }
 
@@ -1385,12 +1330,12 @@ int mdvt_debug_read(mdvt_ctx* c, int what, void* h_dst, uint64_t capacity, uint6
         info[0] = tag;
         return MDVT_OK;
     }
-    const size_t cap_dw = (size_t)c->bigq_cap * mdvt::kBigRecDwords;
+    const RenderWorkspaceLayout L = layout_of(c);
     info[0] = c->bigq ? c->bigq_bytes : 0;                                   // bytes of the queue block
-    info[1] = cap_dw;                                                        // dword offset of the segment counters
-    info[2] = (uint64_t)c->ws_frames * (uint64_t)c->H;                       // segments the block has room for
-    info[3] = cap_dw + 2 * (uint64_t)c->ws_frames * (uint64_t)c->H + 8;      // dword offset of the (first) huge list
-    info[4] = info[3] + (uint64_t)c->huge_lists * (2 * (uint64_t)mdvt::kHugeCap + 2);   // dword offset of the tie flags
+    info[1] = c->bigq_counters_at;                                           // dword offset of the segment counters (as the block was made)
+    info[2] = L.slots * L.H;                                                 // segments the block has room for
+    info[3] = info[1] + L.counter_words();                                   // dword offset of the (first) huge list
+    info[4] = info[3] + L.huge_lists * L.huge_list_dwords();                 // dword offset of the tie flags
     info[5] = (uint64_t)c->W; info[6] = (uint64_t)c->H; info[7] = (uint64_t)c->ws_frames;
     if (h_dst && c->bigq) {
         if (capacity < c->bigq_bytes) return fail(c, MDVT_ERR_INVALID_ARG, "mdvt_debug_read: %zu bytes needed", c->bigq_bytes);
@@ -1707,7 +1652,7 @@ static int finish_infill_mask(mdvt_ctx* c, const uint8_t* d_seed, const uint8_t*
         MDVT_HIP(c, pool_take(64, false, -1, &h, &d, &got));          // pinned, from the process-wide pool (see pool_take)
         c->telea_levels_host = (uint32_t*)h;
     }
-    const uint32_t key = (uint32_t)c->cfg.key_rgb[0] | ((uint32_t)c->cfg.key_rgb[1] << 8) | ((uint32_t)c->cfg.key_rgb[2] << 16);
+    const uint32_t key = packed_key_rgb(c);
     const mdvt::BlurKernel K = masked_blur_kernel();
     const int eyes = d_seed_right ? 2 : 1;
     const int fchunk = kTeleaChunk / eyes;                   // frames per pass: both eyes of a frame travel together
@@ -1781,7 +1726,7 @@ static int finish_infill_mask_heap(mdvt_ctx* c, const uint8_t* d_seed, const uin
         c->heap_images = images;
     }
     if (fchunk > c->heap_images / eyes) fchunk = c->heap_images / eyes;
-    const uint32_t key = (uint32_t)c->cfg.key_rgb[0] | ((uint32_t)c->cfg.key_rgb[1] << 8) | ((uint32_t)c->cfg.key_rgb[2] << 16);
+    const uint32_t key = packed_key_rgb(c);
     const mdvt::BlurKernel K = masked_blur_kernel();
     for (int f0 = 0; f0 < n_frames; f0 += fchunk) {
         const int nf = n_frames - f0 < fchunk ? n_frames - f0 : fchunk, n = nf * eyes;
@@ -1860,9 +1805,7 @@ int mdvt_encode_video_frames(mdvt_ctx* c, int width, int height, int slices_h, i
     const uint32_t cap = (uint32_t)(want_cap < limit ? want_cap : limit);
     const size_t slice_stride = ((size_t)cap + 15) & ~(size_t)15;
     const size_t per_frame = (size_t)spf * (slice_stride + sizeof(uint32_t)) + 256;
-    const size_t budget = (size_t)(c->cfg.workspace_mib ? c->cfg.workspace_mib : 4096u) << 20;
-    int fchunk = (int)(budget / per_frame > (size_t)n_frames ? (size_t)n_frames : budget / per_frame);
-    if (fchunk < 1) fchunk = 1;
+    const int fchunk = slots_afforded(c, per_frame, n_frames);
     const size_t head = 256;                                           // the running offset, alone on its line
     const size_t words = ((size_t)fchunk * spf * sizeof(uint32_t) + 255) & ~(size_t)255;
     const size_t need = head + words + (size_t)fchunk * spf * slice_stride;
@@ -1931,9 +1874,7 @@ int mdvt_decode_video_frames(mdvt_ctx* c, int width, int height, const uint8_t* 
     hipStream_t s = (hipStream_t)stream;
     const int spf = sc.nh * sc.nv;
     const size_t per_frame = (size_t)spf * 3 * sizeof(uint32_t);
-    const size_t budget = (size_t)(c->cfg.workspace_mib ? c->cfg.workspace_mib : 4096u) << 20;
-    int fchunk = (int)(budget / per_frame > (size_t)n_frames ? (size_t)n_frames : budget / per_frame);
-    if (fchunk < 1) fchunk = 1;
+    const int fchunk = slots_afforded(c, per_frame, n_frames);
     const size_t need = (size_t)fchunk * per_frame;
     if (c->ffv1_dec_bytes < need) {
         MDVT_HIP(c, hipDeviceSynchronize());                 // earlier submissions may still use the old workspace

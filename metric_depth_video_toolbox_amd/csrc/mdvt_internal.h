@@ -7,6 +7,7 @@
 #include <stddef.h>
 
 #include "mdvt.h"
+#include "mdvt_workspace.h"
 
 namespace mdvt {
 
@@ -138,10 +139,7 @@ hipError_t launch_edge_filter(const uint8_t* depth_rgb, size_t pitch, size_t str
                               uint8_t* unused, size_t unused_stride, hipStream_t s);
 
 constexpr int kDivSlots = 256;        // parameter sets (mult, scale, dl) a context keeps division checks for; later ones take the IEEE division
-constexpr int kTieTile = 32;          // pixels: side of the tiles whose "holds a pixel marked as tied" bits gate the second rasteriser pass of the general mesh path
-inline size_t tie_words_of(int W, int H) { return ((size_t)((W + kTieTile - 1) / kTieTile) * (size_t)((H + kTieTile - 1) / kTieTile) + 31) / 32; }
-constexpr int kHugeCap = 1 << 17;     // row-block entries of huge triangles per launch set (overflow: the queue kernel keeps the triangle)
-constexpr int kBigRecDwords = 2;     // a queued triangle: draw id, frame slot << 1 | eye
+// (kTieTile, tie_words_of, kHugeCap, kBigRecDwords: mdvt_workspace.h)
 
 struct RenderPlan {
     int mode;            // mdvt_mode

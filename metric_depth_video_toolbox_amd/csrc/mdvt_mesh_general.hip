@@ -829,7 +829,7 @@ hipError_t launch_mesh_raster_general(const RenderPlan& plan, const RenderArgs& 
 {
     RenderArgs a = a_in;
     const int nseg = plan.n * a.H;
-    a.bigq_coarse = a.bigq_count + nseg;                 // (nseg + 1 words follow the segment counters: mdvt_api.hip)
+    a.bigq_coarse = a.bigq_count + queue_coarse_at(plan.n, a.H);     // (nseg + 1 words follow the segment counters: mdvt_workspace.h)
     a.bigq_shift = queue_shift_for(nseg);
     const int ncoarse = (nseg + (1 << a.bigq_shift) - 1) >> a.bigq_shift;
     const dim3 grid_c(cell_blocks(a.W, a.H, rows_wg(plan.remove_edges ? 2 : 0, false)), 1, plan.n);
