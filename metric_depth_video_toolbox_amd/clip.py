@@ -996,10 +996,20 @@ def check_video_decoder(video_decoder: str, video: bool) -> str:
     return video_decoder
 
 
+def check_find_convergence(find_convergence: bool, convergence_mask_video, convergence_file) -> None:
+    """ValueError for --find_convergence together with --convergence_file, or a --convergence_mask_video without --find_convergence."""
+    if find_convergence and convergence_file is not None:
+        raise ValueError("--find_convergence writes the convergence file itself (<depth_video>_convergence_depths.json): "
+                         "not together with --convergence_file")
+    if convergence_mask_video is not None and not find_convergence:
+        raise ValueError("--convergence_mask_video is the mask of --find_convergence: give both")
+
+
 def run(depth_path: str, color_path: Optional[str], *, batch: int = 16, create_sbs_depth_video: bool = False,
         max_frames: int = -1, green_and_black_infill_mask: bool = False, backend: Optional[str] = None,
         normal_infill: bool = False, inpaint_order: str = "levels", multisample: Optional[dict] = None, near_clip: bool = False,
         video_encoder: str = "host", video_decoder: str = "host",
+        find_convergence: bool = False, convergence_mask_video: Optional[str] = None,
         **clip_kwargs):
     """File-level entry (what `python stereo_rerender.py --depth_video ...` is to the reference).
     Multi-process aware: under torchrun every rank renders its own contiguous frame range into its own output segment
@@ -1008,12 +1018,21 @@ def run(depth_path: str, color_path: Optional[str], *, batch: int = 16, create_s
     "device" (the .mkv outputs are FFV1-encoded on the GPU: the same bytes; refused for .npy outputs, which are not encoded).
     video_decoder: "host" (default) or "device" (the .mkv inputs' packets are copied to the GPU and decoded there, straight into
     the batch's input tensors: the same bytes; an input outside the device's stream class is read by the host decoder, with one
-    line on stderr; refused for .npy inputs, which are not decoded)."""
+    line on stderr; refused for .npy inputs, which are not decoded).
+    find_convergence: rank 0 first runs find_convergence_depth.find on the whole depth video (under convergence_mask_video's white
+    pixels, if given) and its side-car becomes the convergence_file -- what movie_2_3D.py:408-419 does between its steps 4 and 5;
+    refused together with a convergence_file."""
     from . import video_io
     video = video_io.is_matroska(depth_path)                 # the reference's own format (sr:326-341): outputs follow it
     check_video_encoder(video_encoder, video)
     check_video_decoder(video_decoder, video)
+    check_find_convergence(find_convergence, convergence_mask_video, clip_kwargs.get("convergence_file"))
     rank, world = D.init_process_group(backend or os.environ.get("MDVT_DIST_BACKEND"))
+    if find_convergence:
+        from . import find_convergence_depth as fcd
+        if rank == 0:                                        # (only rank 0 reads the side-car: load_clip_parameters below)
+            fcd.find(depth_path, convergence_mask_video, clip_kwargs.get("max_depth", 100), video_decoder=video_decoder)
+        clip_kwargs["convergence_file"] = fcd.sidecar_path(depth_path)
     depth = VideoFrames(depth_path) if video else np.load(depth_path, mmap_mode="r")
     if color_path is None:
         color = depth                                                                                  # sr:508-509

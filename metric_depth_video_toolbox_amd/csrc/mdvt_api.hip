@@ -4,6 +4,7 @@
 #include "mdvt_internal.h"
 #include "mdvt_ffv1_core.h"
 #include "mdvt_ffv1_decode.h"
+#include "mdvt_convergence.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -93,6 +94,10 @@ struct mdvt_ctx {
     // FFV1 decoding (mdvt_decode_video_frames): per slice of a pass its offset, payload bytes and cell claim
     uint8_t* ffv1_dec_ws = nullptr;
     size_t ffv1_dec_bytes = 0;
+    // convergence depths (mdvt_convergence_depths): per frame of a launch set its chunk sums; with a mask also the selection's ballot
+    // words, the selected codes and the unit counts
+    uint8_t* conv_ws = nullptr;
+    size_t conv_bytes = 0;
     // normal_infill / infill_using_mask_normals: about 16 B/px per image in flight
     uint8_t* ni_ws = nullptr;
     int ni_images = 0;
@@ -840,7 +845,7 @@ int mdvt_destroy(mdvt_ctx* c)
     pool_give(c->telea_levels_host, nullptr, 64, -1);
     free_telea(c);
     free_telea_heap(c);
-    void* const other_ws[] = {c->ni_ws, c->ffv1_ws, c->ffv1_dec_ws};
+    void* const other_ws[] = {c->ni_ws, c->ffv1_ws, c->ffv1_dec_ws, c->conv_ws};
     for (void* p : other_ws) ws_free(c, p);
     delete c;
     return MDVT_OK;
@@ -1898,6 +1903,82 @@ int mdvt_decode_video_frames(mdvt_ctx* c, int width, int height, const uint8_t* 
         a.claims = a.table + (size_t)2 * nf * spf;
         MDVT_HIP(c, hipMemsetAsync(a.claims, 0, (size_t)nf * spf * sizeof(uint32_t), s));
         MDVT_HIP(c, mdvt::launch_ffv1_decode(a, tab, s));
+    }
+    return MDVT_OK;
+}
+
+// Per-frame masked depth means (mdvt_convergence.hip).  Launch sets: as many frames as the ctx's workspace budget affords.
+int mdvt_convergence_depths(mdvt_ctx* c, int width, int height, const uint8_t* d_depth, size_t depth_pitch, size_t depth_stride, int depth_order,
+                            const uint8_t* d_mask, size_t mask_pitch, size_t mask_stride, int mask_order, int n_frames, int n_mask_frames,
+                            double max_depth, float* d_means, uint32_t* d_counts, void* stream)
+{
+    if (!c) return MDVT_ERR_INVALID_ARG;
+    if (!d_depth || !d_means) return fail(c, MDVT_ERR_INVALID_ARG, "NULL buffer");
+    if (width < 1 || height < 1) return fail(c, MDVT_ERR_INVALID_ARG, "bad frame size %d x %d", width, height);
+    if (depth_order != 0 && depth_order != 1) return fail(c, MDVT_ERR_INVALID_ARG, "depth_order must be 0 (RGB) or 1 (BGR), got %d", depth_order);
+    if (n_frames < 1) return fail(c, MDVT_ERR_INVALID_ARG, "n_frames must be >= 1");
+    if (n_mask_frames < 0 || n_mask_frames > n_frames) return fail(c, MDVT_ERR_INVALID_ARG, "n_mask_frames %d outside [0, n_frames = %d]", n_mask_frames, n_frames);
+    if (n_mask_frames > 0 && !d_mask) return fail(c, MDVT_ERR_INVALID_ARG, "n_mask_frames %d without a mask", n_mask_frames);
+    if (!(max_depth > 0.0)) return fail(c, MDVT_ERR_INVALID_ARG, "max_depth must be > 0");
+    if (depth_pitch < (size_t)width * 3u) return fail(c, MDVT_ERR_INVALID_ARG, "depth_pitch smaller than one row");
+    if (n_frames > 1 && depth_stride < depth_pitch * (size_t)height) return fail(c, MDVT_ERR_INVALID_ARG, "depth_stride smaller than one frame");
+    const bool with_mask = d_mask && n_mask_frames > 0;
+    if (with_mask) {
+        if (mask_order != 0 && mask_order != 1) return fail(c, MDVT_ERR_INVALID_ARG, "mask_order must be 0 (RGB) or 1 (BGR), got %d", mask_order);
+        if (mask_pitch < (size_t)width * 3u) return fail(c, MDVT_ERR_INVALID_ARG, "mask_pitch smaller than one row");
+        if (n_mask_frames > 1 && mask_stride < mask_pitch * (size_t)height) return fail(c, MDVT_ERR_INVALID_ARG, "mask_stride smaller than one frame");
+    }
+    if ((uint64_t)width * (uint64_t)height > ((uint64_t)1 << 28))
+        return fail(c, MDVT_ERR_UNSUPPORTED, "frame too large for the convergence depths (%d x %d)", width, height);
+    DeviceGuard g(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    const uint32_t npx = (uint32_t)width * (uint32_t)height;
+    const uint32_t nchunks = (npx + 8191u) / 8192u, nunits = (npx + 2047u) / 2048u;
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    // per frame of a set: the chunk sums; with a mask the ballot words (1 bit/px), the selected codes (2 B/px), unit counts and offsets, the count
+    const size_t bits_bytes = with_mask ? (size_t)nunits * 32 * sizeof(unsigned long long) : 0;
+    const size_t compact_stride = ((size_t)npx + 7) & ~(size_t)7;
+    const size_t compact_bytes = with_mask ? compact_stride * sizeof(uint16_t) : 0;
+    const size_t sums_bytes = up16((size_t)nchunks * sizeof(float));
+    const size_t unit_bytes = with_mask ? up16((size_t)nunits * sizeof(uint32_t)) : 0;
+    const size_t per_frame = bits_bytes + compact_bytes + sums_bytes + 2 * unit_bytes + (with_mask ? 16 : 0);
+    const int fchunk = slots_afforded(c, per_frame, n_frames < 4096 ? n_frames : 4096);
+    const size_t need = (size_t)fchunk * per_frame;
+    if (c->conv_bytes < need) {
+        MDVT_HIP(c, hipDeviceSynchronize());                 // earlier submissions may still use the old workspace
+        if (c->conv_ws) ws_free(c, c->conv_ws);
+        c->conv_ws = nullptr; c->conv_bytes = 0;
+        MDVT_HIP(c, ws_malloc(c, (void**)&c->conv_ws, need, s));
+        c->conv_bytes = need;
+    }
+    // rows without padding are one long row of npx pixels: no division per pixel, and the 12-byte loads need npx % 4 == 0 only
+    const uint32_t depth_W = depth_pitch == (size_t)width * 3u ? npx : (uint32_t)width;
+    const uint32_t mask_W = with_mask && mask_pitch == (size_t)width * 3u ? npx : (uint32_t)width;
+    auto vec_ok = [&](const uint8_t* p, uint32_t row, size_t pitch, size_t stride) {
+        return row % 4 == 0 && pitch % 4 == 0 && stride % 4 == 0 && (uintptr_t)p % 4 == 0;
+    };
+    mdvt::ConvergenceArgs a{};
+    a.depth_pitch = depth_pitch; a.depth_stride = depth_stride; a.depth_bgr = depth_order; a.depth_W = depth_W;
+    a.depth_vec = vec_ok(d_depth, depth_W, depth_pitch, depth_stride);
+    a.mask_pitch = mask_pitch; a.mask_stride = mask_stride; a.mask_bgr = mask_order; a.mask_W = mask_W;
+    a.mask_vec = with_mask && vec_ok(d_mask, mask_W, mask_pitch, mask_stride);
+    a.npx = npx; a.nchunks = nchunks; a.nunits = nunits;
+    a.div = (float)(4228250625.0 / max_depth);               // 255^4 / max_depth in double, rounded once (fcd:60)
+    a.compact_stride = compact_stride;
+    uint8_t* w = c->conv_ws;
+    a.bits = reinterpret_cast<unsigned long long*>(w); w += (size_t)fchunk * bits_bytes;
+    a.compact = reinterpret_cast<uint16_t*>(w); w += (size_t)fchunk * compact_bytes;
+    a.sums = reinterpret_cast<float*>(w); w += (size_t)fchunk * sums_bytes;
+    a.unit_cnt = reinterpret_cast<uint32_t*>(w); w += (size_t)fchunk * unit_bytes;
+    a.unit_off = reinterpret_cast<uint32_t*>(w); w += (size_t)fchunk * unit_bytes;
+    a.totals = reinterpret_cast<uint32_t*>(w);
+    for (int f0 = 0; f0 < n_frames; f0 += fchunk) {
+        a.n_frames = n_frames - f0 < fchunk ? n_frames - f0 : fchunk;
+        a.n_masked = n_mask_frames - f0 < 0 ? 0 : n_mask_frames - f0 < a.n_frames ? n_mask_frames - f0 : a.n_frames;
+        a.depth = d_depth + (size_t)f0 * depth_stride;
+        a.mask = a.n_masked ? d_mask + (size_t)f0 * mask_stride : nullptr;
+        a.means = d_means + f0; a.counts = d_counts ? d_counts + f0 : nullptr;
+        MDVT_HIP(c, mdvt::launch_convergence(a, s));
     }
     return MDVT_OK;
 }

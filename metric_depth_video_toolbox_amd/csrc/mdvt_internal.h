@@ -261,6 +261,21 @@ struct Ffv1DecodeArgs {
 size_t ffv1_decode_lds_bytes(int line_stride);                     // dynamic LDS of the slice kernel
 size_t ffv1_decode_static_lds_bytes();
 hipError_t launch_ffv1_decode(const Ffv1DecodeArgs& a, const Ffv1StateTables& tab, hipStream_t s);
+// mdvt_convergence.hip: per-frame masked depth means (mdvt_convergence_depths, include/mdvt_convergence.h)
+struct ConvergenceArgs {
+    const uint8_t* depth; size_t depth_pitch, depth_stride; int depth_bgr, depth_vec;     // the set's first frame; _vec: 12-byte loads are aligned
+    const uint8_t* mask; size_t mask_pitch, mask_stride; int mask_bgr, mask_vec;
+    uint32_t depth_W, mask_W;                                      // pixels per row; npx where the pitch is 3 * width (one long row)
+    uint32_t npx, nchunks, nunits;                                 // pixels, chunks of 8192 values and units of 2048 pixels of a frame
+    int n_frames, n_masked;                                        // frames of the set; its first n_masked have a mask frame
+    float div;                                                     // float(255^4 / max_depth)
+    unsigned long long* bits;                                      // workspace [n_masked][nunits][32]: the selection as ballot words
+    uint16_t* compact; size_t compact_stride;                      // workspace [n_masked][compact_stride]: the selected codes in order
+    float* sums;                                                   // workspace [n_frames][nchunks]
+    uint32_t *unit_cnt, *unit_off, *totals;                        // workspace [n_masked][nunits] twice, [n_masked]
+    float* means; uint32_t* counts;                                // the caller's, at the set's first frame; counts may be null
+};
+hipError_t launch_convergence(const ConvergenceArgs& a, hipStream_t s);
 hipError_t launch_selftest(int which, unsigned long long seed, unsigned long long* d_mism, hipStream_t s);
 hipError_t launch_coherence_test(uint32_t* blk, size_t dwords, uint32_t tag, uint32_t* d_xcc, uint32_t* d_out, hipStream_t s);     // (mdvt_selftest.hip; r05 diagnosis)
 

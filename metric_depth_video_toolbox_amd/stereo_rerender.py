@@ -748,6 +748,13 @@ def build_arg_parser():
                          "(README). Mesh mode: not with edge points, seed images or depth outputs: --infill_mask needs "
                          "--dont_place_points_in_edges and --green_and_black_infill_mask, and --do_basic_infill, --normal_infill, "
                          "--create_sbs_depth_video, --touchly0 / --touchly1 are refused")
+    ap.add_argument("--find_convergence", action="store_true",
+                    help="not a reference flag: first run find_convergence_depth on the depth video (movie_2_3D.py's step 4, on the "
+                         "GPU) and use the <depth_video>_convergence_depths.json it writes as the convergence file. Not with "
+                         "--convergence_file")
+    ap.add_argument("--convergence_mask_video", type=str, required=False,
+                    help="not a reference flag: with --find_convergence, the black and white mask video of the main focus area "
+                         "(find_convergence_depth's --mask_video)")
     for flag in ("--compressed", "--mask_video", "--save_background", "--load_background"):
         ap.add_argument(flag, nargs="?", const=True, default=None, help="reference flag outside the built hot path")
     return ap
@@ -773,6 +780,9 @@ def main(argv=None):
     from . import video_io
     clip.check_video_encoder(args.video_encoder, video_io.is_matroska(args.depth_video))
     clip.check_video_decoder(args.video_decoder, video_io.is_matroska(args.depth_video))
+    clip.check_find_convergence(args.find_convergence, args.convergence_mask_video, args.convergence_file)
+    if args.convergence_mask_video and not os.path.isfile(args.convergence_mask_video):
+        raise FileNotFoundError(f"Convergence mask video not found: {args.convergence_mask_video}")
     stats, final = clip.run(args.depth_video, args.color_video, batch=args.batch,
                             create_sbs_depth_video=args.create_sbs_depth_video, max_frames=args.max_frames,
                             green_and_black_infill_mask=args.green_and_black_infill_mask,
@@ -789,6 +799,8 @@ def main(argv=None):
                             multisample=multisample_kwargs(args), near_clip=bool(args.near_clip),
                             video_encoder=args.video_encoder,
                             **({"video_decoder": "device"} if args.video_decoder == "device" else {}),
+                            **({"find_convergence": True, "convergence_mask_video": args.convergence_mask_video}
+                               if args.find_convergence else {}),
                             touchly_max_depth=args.touchly_max_depth, touchly_min_depth=args.touchly_min_depth)
     if int(os.environ.get("RANK", "0")) == 0:
         frames, secs = float(stats[:, 0].sum()), float(stats[:, 1].max())
