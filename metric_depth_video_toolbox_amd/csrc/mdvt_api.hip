@@ -1,5 +1,5 @@
 // mdvt_api.hip -- the C ABI of include/mdvt.h: context, parameter preparation, launch sequencing.
-// Host code only; the kernels are in mdvt_kernels.hip.  Compiled with -ffp-contract=off (the f64
+// Host code only; the kernels are in the other *.hip units.  Compiled with -ffp-contract=off (the f64
 // composition of the eye matrices below is part of the arithmetic decree).
 #include "mdvt_internal.h"
 #include "mdvt_ffv1_core.h"

@@ -1,4 +1,4 @@
-// mdvt_device.h -- device-side helpers shared by the kernels in mdvt_kernels.hip.
+// mdvt_device.h -- device-side helpers shared by the kernel translation units (mdvt_kernels.hip, mdvt_mesh_*.hip, mdvt_formats.hip, ...).
 //
 // Arithmetic decree: every f32 expression below is one IEEE operation per node, the
 // translation unit is compiled with -ffp-contract=off and divisions are the correctly rounded ones --
@@ -56,6 +56,58 @@ __device__ __forceinline__ void store_px_bytes(uint8_t* row, int j, uint32_t px)
     uint8_t* p = row + 3 * (size_t)j;
     p[0] = (uint8_t)px; p[1] = (uint8_t)(px >> 8); p[2] = (uint8_t)(px >> 16);
 }
+
+// Row loads / stores of the row kernels and the streaming kernels: plain memory access, PX pixels of an interleaved row per call.
+template <int PX>   // pixels per thread-iteration: 4 (dwordx3 path) or 1 (byte path, any W / alignment)
+struct RowIO;
+
+template <>
+struct RowIO<4> {
+    static __device__ __forceinline__ void load(const uint8_t* row, int g, uint32_t (&px)[4])
+    {
+        const uint32_t* p = (const uint32_t*)row + 3 * (size_t)g;
+        unpack4(p[0], p[1], p[2], px);
+    }
+    // for data that is read exactly once (non-temporal: does not displace what the caches hold)
+    static __device__ __forceinline__ void load_nt(const uint8_t* row, int g, uint32_t (&px)[4])
+    {
+        const uint32_t* p = (const uint32_t*)row + 3 * (size_t)g;
+        unpack4(__builtin_nontemporal_load(p), __builtin_nontemporal_load(p + 1), __builtin_nontemporal_load(p + 2), px);
+    }
+    // outputs are written once and not read back by the library: non-temporal stores
+    static __device__ __forceinline__ void store_rgb(uint8_t* row, int g, const uint32_t (&px)[4])
+    {
+        uint32_t w0, w1, w2;
+        pack4(px, w0, w1, w2);
+        uint32_t* p = (uint32_t*)row + 3 * (size_t)g;
+        __builtin_nontemporal_store(w0, p); __builtin_nontemporal_store(w1, p + 1); __builtin_nontemporal_store(w2, p + 2);
+    }
+    static __device__ __forceinline__ void store_mask(uint8_t* row, int g, const uint32_t (&m)[4])
+    {
+        __builtin_nontemporal_store(m[0] | (m[1] << 8) | (m[2] << 16) | (m[3] << 24), (uint32_t*)row + g);
+    }
+    static __device__ __forceinline__ void store_z(float* row, int g, const float (&z)[4])
+    {
+        typedef float f32x4 __attribute__((ext_vector_type(4)));
+        const f32x4 v = {z[0], z[1], z[2], z[3]};
+        __builtin_nontemporal_store(v, (f32x4*)row + g);
+    }
+    static __device__ __forceinline__ void load_u8(const uint8_t* row, int g, uint32_t (&v)[4])
+    {
+        const uint32_t w = ((const uint32_t*)row)[g];
+        v[0] = w & 0xFF; v[1] = (w >> 8) & 0xFF; v[2] = (w >> 16) & 0xFF; v[3] = w >> 24;
+    }
+};
+
+template <>
+struct RowIO<1> {
+    static __device__ __forceinline__ void load(const uint8_t* row, int g, uint32_t (&px)[1]) { px[0] = load_px_bytes(row, g); }
+    static __device__ __forceinline__ void load_nt(const uint8_t* row, int g, uint32_t (&px)[1]) { px[0] = load_px_bytes(row, g); }
+    static __device__ __forceinline__ void store_rgb(uint8_t* row, int g, const uint32_t (&px)[1]) { store_px_bytes(row, g, px[0]); }
+    static __device__ __forceinline__ void store_mask(uint8_t* row, int g, const uint32_t (&m)[1]) { row[g] = (uint8_t)m[0]; }
+    static __device__ __forceinline__ void store_z(float* row, int g, const float (&z)[1]) { row[g] = z[0]; }
+    static __device__ __forceinline__ void load_u8(const uint8_t* row, int g, uint32_t (&v)[1]) { v[0] = row[g]; }
+};
 
 // ---- correctly rounded 1/x and a/b without the generic IEEE expansion ---------------------------
 // The decree asks for correctly rounded divisions.  hipcc's expansion (v_div_scale x2, v_rcp, 5 fma,

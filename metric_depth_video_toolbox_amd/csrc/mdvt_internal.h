@@ -1,5 +1,5 @@
-// mdvt_internal.h -- shared between the C-ABI host code (mdvt_api.hip) and the kernels
-// (mdvt_kernels.hip).  Not part of the public interface (that is include/mdvt.h).
+// mdvt_internal.h -- shared between the C-ABI host code (mdvt_api.hip) and the kernel
+// translation units (the other *.hip).  Not part of the public interface (that is include/mdvt.h).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -128,7 +128,7 @@ struct RenderArgs {
     int32_t debug_skip;          // ablation hook for tools/kbench.py (env MDVT_DEBUG_SKIP): 1 raster, 2 resolve, 4 staging
 };
 
-// launchers implemented in mdvt_kernels.hip; all return hipError_t from hipGetLastError()
+// launchers of mdvt_formats.hip (codec, zero_bytes) and mdvt_edge_filter.hip; all return hipError_t from hipGetLastError()
 hipError_t launch_decode_depth(const uint8_t* rgb, size_t rgb_pitch, float* out, size_t out_pitch, int W, int H,
                                float mult, float scale, hipStream_t s);
 hipError_t launch_encode_depth(const float* depth, size_t depth_pitch, uint8_t* rgb, size_t rgb_pitch, int W, int H,
@@ -172,7 +172,7 @@ struct MsaaArgs {
     int32_t mode, cull, pattern, resolve;     // mdvt_config: mode, cull, sample_pattern, sample_resolve
     uint32_t key_rgb;            // R | G<<8 | B<<16
 };
-// The rasterising translation units (mdvt_kernels.hip's render sections, mdvt_mesh_*.hip) are compiled once per sub-pixel grid;
+// The rasterising translation units (mdvt_kernels.hip, mdvt_mesh_*.hip) are compiled once per sub-pixel grid;
 // what they define is declared in mdvt_grid_decls.h, once per grid namespace (below, after the shared declarations).
 // (mdvt_normal_infill.hip; workspace: normal_infill_workspace_bytes(1, W, H))
 hipError_t launch_infill_normals(const uint8_t* color, size_t color_pitch, const uint8_t* hole, size_t hole_pitch,
@@ -180,6 +180,7 @@ hipError_t launch_infill_normals(const uint8_t* color, size_t color_pitch, const
                                  int max_steps, uint8_t* workspace, hipStream_t s);
 hipError_t launch_mark_lower_side(const uint8_t* img, size_t img_pitch, uint8_t* out, size_t out_pitch, int W, int H,
                                   int max_steps, uint8_t* workspace, hipStream_t s);
+// (mdvt_formats.hip)
 hipError_t launch_touchly_depth(const float* depth, size_t depth_pitch, uint8_t* rgb, size_t rgb_pitch, int W, int H,
                                 float tmax, float tmin, float k, int zero_is_far, hipStream_t s);
 hipError_t launch_equirect_remap(const uint8_t* src, size_t src_pitch, size_t src_stride, uint8_t* dst, size_t dst_pitch,
@@ -190,6 +191,7 @@ struct ImageSet {
     __host__ __device__ uint8_t* image(int im) const { return base + (size_t)(im % per_eye) * stride + (ptrdiff_t)(im / per_eye) * eye_offset; }
 };
 
+// mdvt_telea_levels.hip: the infill-mask completion in level order and the masked blur behind it
 struct TeleaWorkspace {              // per image pixel: stamp u16, T f32, work image u8x3, need u8, nlist u32 (14 B)
     uint16_t* stamp; float* T; uint8_t* img; uint8_t* need; uint32_t* nlist;
     uint32_t* counts;                // [max_rounds + 2], followed by
@@ -203,7 +205,7 @@ size_t telea_counter_words(int max_rounds);      // counts + offs + the strided 
 hipError_t launch_telea_init(const ImageSet& seed, const TeleaWorkspace& ws, int n, int W, int H, int max_rounds, uint32_t key_rgb,
                              uint32_t* h_levels, hipStream_t s);
 hipError_t launch_telea_rounds(const TeleaWorkspace& ws, int W, int H, int levels, uint32_t key_rgb, hipStream_t s);
-hipError_t launch_swap_rb(const ImageSet& src, const ImageSet& dst, int n, int W, int H, hipStream_t s);
+hipError_t launch_swap_rb(const ImageSet& src, const ImageSet& dst, int n, int W, int H, hipStream_t s);      // (mdvt_formats.hip)
 // mdvt_telea_heap.hip: the same completion in the heap order of cv2.inpaint, one workgroup per image (opt-in).  Workspace: one
 // block of telea_heap_image_bytes(W, H) per image (44 B/px), the work image at telea_heap_img_offset inside it (pitch 3 W).
 constexpr int kTeleaHeapMaxImages = 256;  // images per launch at most (one workgroup each: one per CU)

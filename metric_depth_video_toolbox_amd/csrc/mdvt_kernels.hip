@@ -1,9 +1,12 @@
-// mdvt_kernels.hip -- hand-written gfx950 (CDNA4) kernels of the stereo-rerender hot path.
+// mdvt_kernels.hip -- hand-written gfx950 (CDNA4) rasterising kernels of the stereo-rerender hot path that have no unit of their own.
 //
-// Replaces the NumPy + Open3D/OpenGL stages of the reference's frame loop (stereo_rerender.py:512-907):
-//   decode (dfh:63-75, 13-24) -> master scale (sr:541) -> unproject (dmt:1112-1133) -> eye/pose
-//   transform (sr:615-619, 724-725, 832-836) -> z-buffered render (dmt:1422-1572) -> colour-key hole
-//   mask (sr:740, 793) -> edge-point splat (sr:745-814).
+// Replaces the Open3D/OpenGL stage of the reference's frame loop (stereo_rerender.py:512-907): decode (dfh:63-75, 13-24) ->
+// master scale (sr:541) -> unproject (dmt:1112-1133) -> eye/pose transform (sr:615-619, 724-725, 832-836) -> z-buffered render
+// (dmt:1422-1572) -> colour-key hole mask (sr:740, 793) -> edge-point splat (sr:745-814).  Here: the points rows (k_points_rows,
+// k_points_rows_fast), the general points and the edge-point lists, the mesh rows (k_mesh_rows), the edge points placed after a
+// pure-shift render (k_edge_rows_pure / k_edge_rows_exact) and launch_render, which dispatches to these and to mdvt_mesh_*.hip.
+// Everything depends on the sub-pixel grid: one namespace MDVT_GRID, compiled once per grid and once with -DMDVT_TUNING (Makefile).
+// The kernels that depend on neither are in mdvt_formats.hip, mdvt_edge_filter.hip and mdvt_telea_levels.hip.
 //
 // The path is an HBM-bound gather/scatter: no MFMA.  What matters is (i) every HBM byte is read and
 // written once, coalesced (12 B/lane dwordx3 = 768 contiguous bytes per wave), (ii) the z-buffer
@@ -12,414 +15,11 @@
 //
 // Compiled with -ffp-contract=off: see the arithmetic decree in mdvt_device.h / DESIGN.md.
 #include "mdvt_device.h"
-#include "mdvt_telea_common.h"
 #include <type_traits>
 
-#include <vector>
-#include <stdio.h>
 #include <stdlib.h>
-#include <string.h>
 
 namespace mdvt {
-
-// Sections that do not depend on the sub-pixel grid are compiled once, with the default grid (-DMDVT_SUBPIX_BITS=8), into
-// namespace mdvt; the rasterising sections once per grid into mdvt::MDVT_GRID (mdvt_internal.h).
-#if MDVT_SUBPIX_BITS == 8
-// =================================================================================================
-// depth codec (dfh)
-// =================================================================================================
-
-__global__ void k_decode_depth(const uint8_t* __restrict__ rgb, size_t rgb_pitch, float* __restrict__ out,
-                               size_t out_pitch, int W, int H, float mult, float scale)
-{
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    const int i = blockIdx.y;
-    if (j >= W || i >= H) return;
-    const uint32_t px = load_px_bytes(rgb + (size_t)i * rgb_pitch, j);
-    float* orow = (float*)((uint8_t*)out + (size_t)i * out_pitch);
-    orow[j] = decode_z(code16_of(px), mult, scale);
-}
-
-// 4 pixels per thread: 12 B coalesced load, 16 B coalesced store.
-__global__ void k_decode_depth4(const uint8_t* __restrict__ rgb, size_t rgb_pitch, float* __restrict__ out,
-                                size_t out_pitch, int W4, int H, float mult, float scale)
-{
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    const int i = blockIdx.y;
-    if (g >= W4 || i >= H) return;
-    const uint32_t* src = (const uint32_t*)(rgb + (size_t)i * rgb_pitch) + 3 * (size_t)g;
-    uint32_t px[4];
-    unpack4(src[0], src[1], src[2], px);
-    float4 z;
-    z.x = decode_z(code16_of(px[0]), mult, scale);
-    z.y = decode_z(code16_of(px[1]), mult, scale);
-    z.z = decode_z(code16_of(px[2]), mult, scale);
-    z.w = decode_z(code16_of(px[3]), mult, scale);
-    ((float4*)((uint8_t*)out + (size_t)i * out_pitch))[g] = z;
-}
-
-hipError_t launch_decode_depth(const uint8_t* rgb, size_t rgb_pitch, float* out, size_t out_pitch, int W, int H,
-                               float mult, float scale, hipStream_t s)
-{
-    const bool vec = (W % 4 == 0) && (rgb_pitch % 4 == 0) && (out_pitch % 16 == 0) &&
-                     ((uintptr_t)rgb % 4 == 0) && ((uintptr_t)out % 16 == 0);
-    if (vec) {
-        const int W4 = W / 4;
-        dim3 grid((W4 + 255) / 256, H);
-        hipLaunchKernelGGL(k_decode_depth4, grid, dim3(256), 0, s, rgb, rgb_pitch, out, out_pitch, W4, H, mult, scale);
-    } else {
-        dim3 grid((W + 255) / 256, H);
-        hipLaunchKernelGGL(k_decode_depth, grid, dim3(256), 0, s, rgb, rgb_pitch, out, out_pitch, W, H, mult, scale);
-    }
-    return hipGetLastError();
-}
-
-// dfh:5-11: clip to [0,max] in f32, f64 multiply by 255^4/max, truncate to u32; dfh:53-55: R = G = byte 3,
-// B = byte 2.
-__global__ void k_encode_depth(const float* __restrict__ depth, size_t depth_pitch, uint8_t* __restrict__ rgb,
-                               size_t rgb_pitch, int W, int H, double multi, float fmax_depth, int bgr)
-{
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    const int i = blockIdx.y;
-    if (j >= W || i >= H) return;
-    float d = ((const float*)((const uint8_t*)depth + (size_t)i * depth_pitch))[j];
-    if (d > fmax_depth) d = fmax_depth;
-    if (d < 0.0f) d = 0.0f;
-    const double e = multi * (double)d;
-    const uint32_t code = (e >= 0.0 && e < 4294967296.0) ? (uint32_t)e : 0u;     // NaN -> 0
-    const uint32_t hi = code >> 24, lo = (code >> 16) & 0xFFu;
-    const uint32_t px = bgr ? (lo | (hi << 8) | (hi << 16)) : (hi | (hi << 8) | (lo << 16));
-    store_px_bytes(rgb + (size_t)i * rgb_pitch, j, px);
-}
-
-hipError_t launch_encode_depth(const float* depth, size_t depth_pitch, uint8_t* rgb, size_t rgb_pitch, int W, int H,
-                               double max_depth, int bgr, hipStream_t s)
-{
-    dim3 grid((W + 255) / 256, H);
-    hipLaunchKernelGGL(k_encode_depth, grid, dim3(256), 0, s, depth, depth_pitch, rgb, rgb_pitch, W, H,
-                       4228250625.0 / max_depth, (float)max_depth, bgr);
-    return hipGetLastError();
-}
-
-// =================================================================================================
-// 89-degree oblique-triangle filter (dmt:1283-1294, 1339-1344), f64 exactly as NumPy >= 2 evaluates it
-// =================================================================================================
-
-__device__ __forceinline__ bool tri_oblique(const double (&a)[3], const double (&b)[3], const double (&c)[3])
-{
-    const double e1x = b[0] - a[0], e1y = b[1] - a[1], e1z = b[2] - a[2];
-    const double e2x = c[0] - a[0], e2y = c[1] - a[1], e2z = c[2] - a[2];
-    const double nx = e1y * e2z - e1z * e2y;
-    const double ny = e1z * e2x - e1x * e2z;
-    const double nz = e1x * e2y - e1y * e2x;
-    const double vx = -((a[0] + b[0]) + c[0]) / 3.0;
-    const double vy = -((a[1] + b[1]) + c[1]) / 3.0;
-    const double vz = -((a[2] + b[2]) + c[2]) / 3.0;
-    const double dot = (nx * vx + ny * vy) + nz * vz;
-    const double len_n = sqrt((nx * nx + ny * ny) + nz * nz);
-    const double len_v = sqrt((vx * vx + vy * vy) + vz * vz);
-    const double cosine = dot / (len_n * len_v + 1e-15);
-    return cosine < 0x1.1df0b2b89dd37p-6;          // np.cos(np.radians(89.0))
-}
-
-// Division-free screening of the same test.  cos < c0  <=>  dot < c0 * (|n||v| + 1e-15); with the
-// unnormalised view vector vs = a+b+c (v = -vs/3) this is  -n.vs < c0 * |n| |vs|  up to the 1e-15 term.
-// Squaring removes the square roots.  The screening value carries ~1e-15 relative rounding error and
-// ignores the 1e-15 term, which moves the threshold by the relative amount 1e-15 / (|n||v|): a triangle with
-// |n||v| < 1e-8 (content nearer than ~0.3 m at 1080p: tiny triangles, tiny view vectors) is therefore NOT
-// decided here, nor is one whose margin is below kScreenMargin (5e-7 in linear terms, against <= 1e-7 from the
-// dropped term); both go through the exact formula.  Everything else provably gets the exact formula's decision.
-constexpr double kScreenMargin = 1e-6;
-constexpr double kScreenMinNNSS = 9e-16;          // (3 |n||v|)^2 for |n||v| = 1e-8
-
-// returns 0 = valid, 1 = oblique (removed), 2 = undecided
-__device__ __forceinline__ int tri_oblique_screen(const double (&a)[3], const double (&b)[3], const double (&c)[3])
-{
-    const double e1x = b[0] - a[0], e1y = b[1] - a[1], e1z = b[2] - a[2];
-    const double e2x = c[0] - a[0], e2y = c[1] - a[1], e2z = c[2] - a[2];
-    // (explicit fused multiply-adds: the screen only has to be accurate, not bit-identical to anything, and the
-    //  filter is bound by the f64 VALU rate -- the exact path below keeps the decree's one-rounding-per-node form)
-    const double nx = fma(e1y, e2z, -(e1z * e2y));
-    const double ny = fma(e1z, e2x, -(e1x * e2z));
-    const double nz = fma(e1x, e2y, -(e1y * e2x));
-    const double sx = (a[0] + b[0]) + c[0], sy = (a[1] + b[1]) + c[1], sz = (a[2] + b[2]) + c[2];
-    const double d = -fma(nz, sz, fma(ny, sy, nx * sx));               // 3 * dot
-    const double nn = fma(nz, nz, fma(ny, ny, nx * nx));
-    const double ss = fma(sz, sz, fma(sy, sy, sx * sx));               // 9 * |v|^2
-    const double c0 = 0x1.1df0b2b89dd37p-6;
-    const double rhs = (c0 * c0) * (nn * ss);                          // (c0 |n| |vs|)^2
-    if (!(nn * ss > kScreenMinNNSS)) return 2;                         // degenerate / zero depth / tiny: exact path
-    const double lhs = d * fabs(d);                                    // signed square
-    const double tol = kScreenMargin * rhs;
-    if (lhs < rhs - tol) return 1;
-    if (lhs > rhs + tol) return 0;
-    return 2;
-}
-
-// f32 pre-screen of the same test (r04), from the closed form of a triangle whose vertices are P_k = z_k (u_k, v_k, 1) on the
-// grid's rays u in {a, a + px}, v in {b, b + py}:  n = (P1 - P0) x (P2 - P0) and n . P_k = z0 z1 z2 det(r0, r1, r2) = -px py z0 z1 z2
-// for both triangles of a cell, so with s = P0 + P1 + P2 (the view vector is -s / 3)
-//     3 dot = -n . s = 3 px py z0 z1 z2 > 0,    tri1 (A, B, C): nx = py zA (zC - zB), ny = px zC (zB - zA),
-//                                               tri2 (A, C, D): nx = py zC (zD - zA), ny = px zA (zC - zD),
-//     nz = -(a nx + b ny) - px py z1 z2   (from n . P0),
-// and the test cos < cos 89 is  (3 dot)^2 < c0^2 |n|^2 |s|^2.  No difference of nearly equal PRODUCTS is left (the generic
-// cross product of the edge vectors cancels ~4 digits): every factor is an input or one f32 subtraction of inputs, |n|^2 and
-// |s|^2 are sums of squares, and nz's one cancellation is bounded by eps (|a nx| + |b ny| + ...) <= eps (|a| + |b| + 1) |n|.
-// With |a|, |b| <= 64 both sides are good to ~1e-5 relative in f32, the f64 formula of the reference's order differs from
-// the exact value by ~1e-15, its 1e-15 term moves the threshold by < 1e-7 when (3 |n||v|)^2 > 9e-16: a margin of 1e-3
-// decides the same way for sure.  The rest -- a fraction of a per cent of the triangles -- takes the f64 screen and, inside
-// its own margin, the exact formula.  returns 0 = valid, 1 = oblique (removed), 2 = undecided
-__device__ __forceinline__ int tri_oblique_screen_f32(float a, float b, float pp, float z0, float t12 /* pp z1 z2 */,
-                                                      float nx, float ny, float sx, float sy, float sz)
-{
-    // (explicit fused multiply-adds: the screen only has to be accurate, not bit-identical to anything)
-    const float nz = -__builtin_fmaf(a, nx, __builtin_fmaf(b, ny, t12));
-    const float nn = __builtin_fmaf(nz, nz, __builtin_fmaf(ny, ny, nx * nx));
-    const float ss = __builtin_fmaf(sz, sz, __builtin_fmaf(sy, sy, sx * sx));
-    const float d3 = (3.0f * z0) * t12;
-    const float lhs = d3 * d3;
-    const float nnss = nn * ss;
-    const float rhs = 0x1.3f61d0p-12f * nnss;                           // cos^2 89 degrees (f32: 6e-8 relative, inside the margin)
-    // (no branches: 0 = valid, 1 = oblique (removed), 2 = undecided -- degenerate / zero depth / tiny / NaN / inside the margin)
-    const bool ok = nnss > 1.0e-15f;
-    const bool rem = ok && lhs < rhs * 0.999f, val = ok && lhs > rhs * 1.001f;
-    return rem ? 1 : (val ? 0 : 2);
-}
-
-struct CellRaysF32 { float a, a1, b, b1, px, py; bool ok; };     // the f32 pre-screen's view of the cell's rays (ok: all within +-64)
-__device__ __forceinline__ CellRaysF32 cell_rays_f32(double x0r, double x1r, double y0r, double y1r)
-{
-    CellRaysF32 r;
-    r.a = (float)x0r; r.b = (float)y0r; r.a1 = (float)x1r; r.b1 = (float)y1r;
-    r.px = (float)(x1r - x0r); r.py = (float)(y1r - y0r);
-    r.ok = fabsf(r.a) <= 64.0f && fabsf(r.b) <= 64.0f && fabsf(r.a1) <= 64.0f && fabsf(r.b1) <= 64.0f;
-    return r;
-}
-
-// f32 pre-screen of both triangles of a cell: s1 | s2 << 2, each 0 = valid, 1 = oblique (removed), 2 = undecided
-__device__ __forceinline__ uint32_t edge_filter_prescreen(const CellRaysF32& r, float zA, float zB, float zC, float zD)
-{
-    if (!r.ok) return 2u | (2u << 2);
-    // tri1 = (A, B, C) = rays (a, b), (a, b'), (a', b');  tri2 = (A, C, D) = (a, b), (a', b'), (a', b)
-    const float pp = r.px * r.py;
-    const int s1 = tri_oblique_screen_f32(r.a, r.b, pp, zA, (pp * zB) * zC, (r.py * zA) * (zC - zB), (r.px * zC) * (zB - zA),
-                                          __builtin_fmaf(r.a1, zC, r.a * (zA + zB)), __builtin_fmaf(r.b1, zB + zC, r.b * zA), (zA + zB) + zC);
-    const int s2 = tri_oblique_screen_f32(r.a, r.b, pp, zA, (pp * zC) * zD, (r.py * zC) * (zD - zA), (r.px * zA) * (zC - zD),
-                                          __builtin_fmaf(r.a1, zC + zD, r.a * zA), __builtin_fmaf(r.b1, zC, r.b * (zA + zD)), (zA + zC) + zD);
-    return (uint32_t)s1 | ((uint32_t)s2 << 2);
-}
-
-// Both triangles of cell (i, j): bit 0 = tri1 (A, B, C) removed, bit 1 = tri2 (A, C, D) removed.  `pre` = edge_filter_prescreen's
-// verdict; x0r.. are the cell's ray coordinates (g - c) * (1 / f) in f64 (the f64 screen; the exact path recomputes the vertices
-// in the reference's own order).
-__device__ __forceinline__ uint32_t edge_filter_cell(const FrameDev& f, int i, int j, int of_by_one, double x0r, double x1r, double y0r,
-                                                     double y1r, uint32_t pre, float zA, float zB, float zC, float zD)
-{
-    int s1 = (int)(pre & 3u), s2 = (int)(pre >> 2);
-    if (s1 == 2 || s2 == 2) {
-        asm volatile("; f64 screen" ::: "memory");
-        const double dA = (double)zA, dB = (double)zB, dC = (double)zC, dD = (double)zD;
-        const double A[3] = {x0r * dA, y0r * dA, dA};
-        const double B[3] = {x0r * dB, y1r * dB, dB};
-        const double Cc[3] = {x1r * dC, y1r * dC, dC};
-        const double D[3] = {x1r * dD, y0r * dD, dD};
-        if (s1 == 2) s1 = tri_oblique_screen(A, B, Cc);      // tri1 = (v[i,j], v[i+1,j], v[i+1,j+1])
-        if (s2 == 2) s2 = tri_oblique_screen(A, Cc, D);      // tri2 = (v[i,j], v[i+1,j+1], v[i,j+1])
-    }
-    if (s1 == 2 || s2 == 2) {
-        // exact path: the reference's own evaluation order (dmt:1127-1128, 1283-1294)
-        double Ae[3], Be[3], Ce[3], De[3];
-        vertex_f64(f, i, j, of_by_one, zA, Ae);
-        vertex_f64(f, i + 1, j, of_by_one, zB, Be);
-        vertex_f64(f, i + 1, j + 1, of_by_one, zC, Ce);
-        vertex_f64(f, i, j + 1, of_by_one, zD, De);
-        if (s1 == 2) s1 = tri_oblique(Ae, Be, Ce) ? 1 : 0;
-        if (s2 == 2) s2 = tri_oblique(Ae, Ce, De) ? 1 : 0;
-    }
-    return (s1 == 1 ? 1u : 0u) | (s2 == 1 ? 2u : 0u);
-}
-
-__device__ __forceinline__ void edge_filter_mark_unused(uint8_t* u, int W, int i, int j, uint32_t inv)
-{
-    const size_t a = (size_t)i * W + j;
-    u[a] = 1;                          // A
-    u[a + W + 1] = 1;                  // C
-    if (inv & 1u) u[a + W] = 1;        // B
-    if (inv & 2u) u[a + 1] = 1;        // D
-}
-
-// One thread per grid cell: both triangles of the cell.  `unused` must be zeroed beforehand.  (Any width / alignment.)
-// NOTE f.sx / f.sy hold the mesh grid scale only when the frame was prepared for mesh mode; the host
-// passes scale factors explicitly so the filter can be run standalone for either grid.
-__global__ void __launch_bounds__(128) k_edge_filter(const uint8_t* __restrict__ depth_rgb, size_t pitch, size_t stride,
-                              const FrameDev* __restrict__ fp, int frame0, int W, int H, int of_by_one,
-                              float sx, float sy,
-                              uint8_t* __restrict__ tri_invalid, size_t tri_stride,
-                              uint8_t* __restrict__ unused, size_t unused_stride)
-{
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    const int i = blockIdx.y;
-    const int fr = blockIdx.z;
-    if (j >= W - 1 || i >= H - 1) return;
-    const uint8_t* r0 = depth_rgb + (size_t)(frame0 + fr) * stride + (size_t)i * pitch;
-    const uint8_t* r1 = r0 + pitch;
-    const uint32_t pA = load_px_bytes(r0, j), pD = load_px_bytes(r0, j + 1);
-    const uint32_t pB = load_px_bytes(r1, j), pC = load_px_bytes(r1, j + 1);
-    FrameDev f = fp[frame0 + fr];
-    f.sx = sx; f.sy = sy;
-    const float zA = decode_z(code16_of(pA), f.mult, f.scale);
-    const float zD = decode_z(code16_of(pD), f.mult, f.scale);
-    const float zB = decode_z(code16_of(pB), f.mult, f.scale);
-    const float zC = decode_z(code16_of(pC), f.mult, f.scale);
-    // screening vertices: the same unprojection with a reciprocal instead of the two divisions
-    const double rfx = f.rKd[0], rfy = f.rKd[1];
-    const double x0 = (of_by_one ? (double)((float)j * f.sx) : (double)j) - f.Kd[2];
-    const double x1 = (of_by_one ? (double)((float)(j + 1) * f.sx) : (double)(j + 1)) - f.Kd[2];
-    const double y0 = (of_by_one ? (double)((float)i * f.sy) : (double)i) - f.Kd[3];
-    const double y1 = (of_by_one ? (double)((float)(i + 1) * f.sy) : (double)(i + 1)) - f.Kd[3];
-    const double x0r = x0 * rfx, x1r = x1 * rfx, y0r = y0 * rfy, y1r = y1 * rfy;
-    const uint32_t inv = edge_filter_cell(f, i, j, of_by_one, x0r, x1r, y0r, y1r, edge_filter_prescreen(cell_rays_f32(x0r, x1r, y0r, y1r), zA, zB, zC, zD), zA, zB, zC, zD);
-    const size_t ncell = (size_t)(W - 1) * (H - 1);
-    const size_t cell = (size_t)i * (W - 1) + j;
-    if (tri_invalid) {
-        uint8_t* t = tri_invalid + (size_t)fr * tri_stride;
-        t[cell] = inv & 1u;
-        t[ncell + cell] = (inv >> 1) & 1u;
-    }
-    if (unused && inv) edge_filter_mark_unused(unused + (size_t)fr * unused_stride, W, i, j, inv);
-}
-
-// The same for dword-addressable rows (W % 4 == 0, 4-byte aligned base / pitch / stride): a thread takes FOUR cells of a
-// row -- five pixels of two rows as 2 x 4 dwords instead of 2 x 10 byte loads, the eight validity bytes as two dword stores.
-// (r04: with the f32 pre-screen no f64 instruction runs on ordinary content, and the one-cell kernel turned out to be bound
-// by its byte accesses, not by the f64 rate its design assumed: 10.4 -> see DESIGN.md us per 1080p frame.)
-typedef uint32_t u32_unaligned_t __attribute__((aligned(1)));
-__global__ void __launch_bounds__(128) k_edge_filter4(const uint8_t* __restrict__ depth_rgb, size_t pitch, size_t stride,
-                              const FrameDev* __restrict__ fp, int frame0, int W, int H, int of_by_one,
-                              float sx, float sy,
-                              uint8_t* __restrict__ tri_invalid, size_t tri_stride,
-                              uint8_t* __restrict__ unused, size_t unused_stride)
-{
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    const int i = blockIdx.y;
-    const int fr = blockIdx.z;
-    const int j0 = 4 * g;
-    if (j0 >= W - 1 || i >= H - 1) return;
-    const uint32_t* r0 = (const uint32_t*)(depth_rgb + (size_t)(frame0 + fr) * stride + (size_t)i * pitch) + 3 * g;
-    const uint32_t* r1 = (const uint32_t*)((const uint8_t*)r0 + pitch);
-    const bool five = j0 + 4 < W;                          // (the last group of a row has no fifth pixel -- and no fourth cell)
-    uint32_t p0[5], p1[5];
-    unpack4(r0[0], r0[1], r0[2], *(uint32_t(*)[4])p0);
-    unpack4(r1[0], r1[1], r1[2], *(uint32_t(*)[4])p1);
-    p0[4] = five ? r0[3] & 0xFFFFFFu : 0u;
-    p1[4] = five ? r1[3] & 0xFFFFFFu : 0u;
-    FrameDev f = fp[frame0 + fr];
-    f.sx = sx; f.sy = sy;
-    float z0[5], z1[5];
-#pragma unroll
-    for (int q = 0; q < 5; ++q) {
-        z0[q] = decode_z(code16_of(p0[q]), f.mult, f.scale);
-        z1[q] = decode_z(code16_of(p1[q]), f.mult, f.scale);
-    }
-    const double rfx = f.rKd[0], rfy = f.rKd[1];
-    const double y0r = ((of_by_one ? (double)((float)i * f.sy) : (double)i) - f.Kd[3]) * rfy;
-    const double y1r = ((of_by_one ? (double)((float)(i + 1) * f.sy) : (double)(i + 1)) - f.Kd[3]) * rfy;
-    double xr[5];
-#pragma unroll
-    for (int q = 0; q < 5; ++q) xr[q] = ((of_by_one ? (double)((float)(j0 + q) * f.sx) : (double)(j0 + q)) - f.Kd[2]) * rfx;
-    const int ncells = five ? 4 : 3;
-    float fx[5];
-    const float fb = (float)y0r, fb1 = (float)y1r, fpy = (float)(y1r - y0r);
-    bool rays_ok = fabsf(fb) <= 64.0f && fabsf(fb1) <= 64.0f;
-#pragma unroll
-    for (int q = 0; q < 5; ++q) { fx[q] = (float)xr[q]; rays_ok = rays_ok && fabsf(fx[q]) <= 64.0f; }
-    uint32_t w1 = 0, w2 = 0, any = 0;
-    uint32_t inv[4] = {0, 0, 0, 0}, pre[4] = {0, 0, 0, 0};
-    // all eight triangles through the f32 pre-screen first (straight-line code); the f64 paths behind ONE branch
-    uint32_t und = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        if (q < ncells) {
-            CellRaysF32 r;
-            r.a = fx[q]; r.a1 = fx[q + 1]; r.b = fb; r.b1 = fb1; r.px = (float)(xr[q + 1] - xr[q]); r.py = fpy;
-            r.ok = rays_ok;
-            pre[q] = edge_filter_prescreen(r, z0[q], z1[q], z1[q + 1], z0[q + 1]);
-        }
-        und |= pre[q] & 0xAu;                                // (a 2 in either field)
-        inv[q] = (pre[q] & 1u) | ((pre[q] >> 1) & 2u);       // decided: 1 -> removed
-    }
-    if (und) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            if (pre[q] & 0xAu) inv[q] = edge_filter_cell(f, i, j0 + q, of_by_one, xr[q], xr[q + 1], y0r, y1r, pre[q], z0[q], z1[q], z1[q + 1], z0[q + 1]);
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        w1 |= (inv[q] & 1u) << (8 * q);
-        w2 |= ((inv[q] >> 1) & 1u) << (8 * q);
-        any |= inv[q];
-    }
-    const size_t ncell = (size_t)(W - 1) * (H - 1);
-    const size_t cell = (size_t)i * (W - 1) + j0;
-    if (tri_invalid) {
-        uint8_t* t = tri_invalid + (size_t)fr * tri_stride;
-        if (five) {
-            *(u32_unaligned_t*)(t + cell) = w1;
-            *(u32_unaligned_t*)(t + ncell + cell) = w2;
-        } else {
-#pragma unroll
-            for (int q = 0; q < 3; ++q) { t[cell + q] = (w1 >> (8 * q)) & 1u; t[ncell + cell + q] = (w2 >> (8 * q)) & 1u; }
-        }
-    }
-    if (unused && any) {
-        uint8_t* u = unused + (size_t)fr * unused_stride;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) if (inv[q]) edge_filter_mark_unused(u, W, i, j0 + q, inv[q]);
-    }
-}
-
-// Zero `bytes` bytes at `p` (any alignment): 16-byte stores over the aligned body, byte stores at its two ends.  Replaces the per-set
-// hipMemsetAsync of the 89-degree filter's flag plane (two runtime fill launches, 13 us per 16 MB): one launch; measured, a single
-// product-default frame per call 148.9 -> 146.7 us, 32 frames per call unchanged (the fills hid behind the other bank's walk).
-__global__ void __launch_bounds__(256) k_zero_bytes(uint8_t* p, size_t bytes)
-{
-    const size_t head = min(bytes, (size_t)((16u - (uint32_t)((uintptr_t)p & 15u)) & 15u));
-    const size_t body = (bytes - head) >> 4, tail0 = head + (body << 4);
-    uint4* q = reinterpret_cast<uint4*>(p + head);
-    const size_t t = (size_t)blockIdx.x * 256u + threadIdx.x, nt = (size_t)gridDim.x * 256u;
-    for (size_t k = t; k < body; k += nt) q[k] = make_uint4(0u, 0u, 0u, 0u);
-    if (t < head) p[t] = 0;
-    if (t < bytes - tail0) p[tail0 + t] = 0;
-}
-hipError_t launch_zero_bytes(void* p, size_t bytes, hipStream_t s)
-{
-    if (!bytes) return hipSuccess;
-    const size_t blocks = (bytes / 16 + 255) / 256;
-    hipLaunchKernelGGL(k_zero_bytes, dim3((unsigned)(blocks < 1 ? 1 : (blocks > 8192 ? 8192 : blocks))), dim3(256), 0, s, (uint8_t*)p, bytes);
-    return hipGetLastError();
-}
-
-hipError_t launch_edge_filter(const uint8_t* depth_rgb, size_t pitch, size_t stride, const FrameDev* fp, int frame0,
-                              int n, int W, int H, int of_by_one, uint8_t* tri_invalid, size_t tri_stride,
-                              uint8_t* unused, size_t unused_stride, hipStream_t s)
-{
-    const float sx = of_by_one ? (float)(((double)W + 1.0) / (double)W) : 1.0f;
-    const float sy = of_by_one ? (float)(((double)H + 1.0) / (double)H) : 1.0f;
-    const bool dwords = W % 4 == 0 && W >= 8 && pitch % 4 == 0 && stride % 4 == 0 && ((uintptr_t)depth_rgb % 4) == 0;
-    if (dwords) {
-        dim3 grid((W / 4 + 127) / 128, H - 1, n);
-        hipLaunchKernelGGL(k_edge_filter4, grid, dim3(128), 0, s, depth_rgb, pitch, stride, fp, frame0, W, H, of_by_one,
-                           sx, sy, tri_invalid, tri_stride, unused, unused_stride);
-    } else {
-        dim3 grid((W - 1 + 127) / 128, H - 1, n);
-        hipLaunchKernelGGL(k_edge_filter, grid, dim3(128), 0, s, depth_rgb, pitch, stride, fp, frame0, W, H, of_by_one,
-                           sx, sy, tri_invalid, tri_stride, unused, unused_stride);
-    }
-    return hipGetLastError();
-}
-
-#endif  // grid-independent sections
-
 namespace MDVT_GRID {
 // =================================================================================================
 // POINT MODE, pure stereo shift: one workgroup per (frame,row), z-buffer in LDS
@@ -432,57 +32,6 @@ namespace MDVT_GRID {
 // whose unsigned minimum is "nearest Z, ties to the lower source column" -- and it carries the
 // colour, so the resolve phase is a plain LDS read (no gather, no second pass over the inputs).
 // HBM traffic = algorithmic bytes: 6 B/px in, 8 B/px out (+8 B/px with the optional depth planes).
-
-template <int PX>   // pixels per thread-iteration: 4 (dwordx3 path) or 1 (byte path, any W / alignment)
-struct RowIO;
-
-template <>
-struct RowIO<4> {
-    static __device__ __forceinline__ void load(const uint8_t* row, int g, uint32_t (&px)[4])
-    {
-        const uint32_t* p = (const uint32_t*)row + 3 * (size_t)g;
-        unpack4(p[0], p[1], p[2], px);
-    }
-    // for data that is read exactly once (non-temporal: does not displace what the caches hold)
-    static __device__ __forceinline__ void load_nt(const uint8_t* row, int g, uint32_t (&px)[4])
-    {
-        const uint32_t* p = (const uint32_t*)row + 3 * (size_t)g;
-        unpack4(__builtin_nontemporal_load(p), __builtin_nontemporal_load(p + 1), __builtin_nontemporal_load(p + 2), px);
-    }
-    // outputs are written once and not read back by the library: non-temporal stores
-    static __device__ __forceinline__ void store_rgb(uint8_t* row, int g, const uint32_t (&px)[4])
-    {
-        uint32_t w0, w1, w2;
-        pack4(px, w0, w1, w2);
-        uint32_t* p = (uint32_t*)row + 3 * (size_t)g;
-        __builtin_nontemporal_store(w0, p); __builtin_nontemporal_store(w1, p + 1); __builtin_nontemporal_store(w2, p + 2);
-    }
-    static __device__ __forceinline__ void store_mask(uint8_t* row, int g, const uint32_t (&m)[4])
-    {
-        __builtin_nontemporal_store(m[0] | (m[1] << 8) | (m[2] << 16) | (m[3] << 24), (uint32_t*)row + g);
-    }
-    static __device__ __forceinline__ void store_z(float* row, int g, const float (&z)[4])
-    {
-        typedef float f32x4 __attribute__((ext_vector_type(4)));
-        const f32x4 v = {z[0], z[1], z[2], z[3]};
-        __builtin_nontemporal_store(v, (f32x4*)row + g);
-    }
-    static __device__ __forceinline__ void load_u8(const uint8_t* row, int g, uint32_t (&v)[4])
-    {
-        const uint32_t w = ((const uint32_t*)row)[g];
-        v[0] = w & 0xFF; v[1] = (w >> 8) & 0xFF; v[2] = (w >> 16) & 0xFF; v[3] = w >> 24;
-    }
-};
-
-template <>
-struct RowIO<1> {
-    static __device__ __forceinline__ void load(const uint8_t* row, int g, uint32_t (&px)[1]) { px[0] = load_px_bytes(row, g); }
-    static __device__ __forceinline__ void load_nt(const uint8_t* row, int g, uint32_t (&px)[1]) { px[0] = load_px_bytes(row, g); }
-    static __device__ __forceinline__ void store_rgb(uint8_t* row, int g, const uint32_t (&px)[1]) { store_px_bytes(row, g, px[0]); }
-    static __device__ __forceinline__ void store_mask(uint8_t* row, int g, const uint32_t (&m)[1]) { row[g] = (uint8_t)m[0]; }
-    static __device__ __forceinline__ void store_z(float* row, int g, const float (&z)[1]) { row[g] = z[0]; }
-    static __device__ __forceinline__ void load_u8(const uint8_t* row, int g, uint32_t (&v)[1]) { v[0] = row[g]; }
-};
 
 // FLAGS bit 0: optional depth planes, bit 1: `unused` vertices are not drawn (remove_edges),
 // bit 2: edge points splatted into holes.
@@ -1702,934 +1251,6 @@ __global__ void __launch_bounds__(TPB) k_mesh_rows(RenderArgs a)
     }
 }
 
-}  // namespace MDVT_GRID
-
-#if MDVT_SUBPIX_BITS == 8
-using MDVT_GRID::RowIO;      // (the row loads / stores of the points section: plain memory access, nothing of the grid in them)
-// =================================================================================================
-// MESH MODE, general (pose / convergence): triangles rasterised into global 64-bit z keys
-// =================================================================================================
-//   key = ~bits(1/Z') << 32 | draw id (pass << 31 | i << 16 | j): the 64-bit minimum is "nearest, then first drawn" = GL_LESS
-//   with the reference's draw order (dmt:1243-1254).  The colour travels beside it: EVERY fragment also leaves
-//   draw id << 32 | rgb in a side buffer with a plain 64-bit store.  Fragments of one pixel overwrite each other in no
-//   particular order, so the resolve pass takes the side buffer's colour only if its id is the winner's -- always the
-//   case for the ~97 % of pixels that received one fragment -- and otherwise shades the winner from its id (three vertex
-//   records read back).  Measured and rejected: (1) shading every pixel in the resolve (deferred shading proper): the
-//   three 16-byte gathers per pixel make the resolve pass HBM-bound at 58 us per 1080p frame against 26; (2) storing the
-//   colour only when the fragment takes the pixel: the returning atomic that needs stalls the rasteriser (product
-//   default 2508 us per 16 frames against 2392 for (1)).
-
-// (Stage 1, the vertex records: computed by the rasterisers themselves since r05 -- mdvt_mesh_general.hip, vertex_records.)
-
-// (infill_using_normals and mark_lower_side: mdvt_normal_infill.hip)
-
-// Touchly inverse-depth plane (sr:549-551, 689-691, 825-829).
-__global__ void __launch_bounds__(256) k_touchly_depth(const float* __restrict__ depth, size_t depth_pitch,
-                                                       uint8_t* __restrict__ rgb, size_t rgb_pitch, int W, int H,
-                                                       float tmax, float tmin, float k, int zero_is_far)
-{
-    const int x = blockIdx.x * blockDim.x + threadIdx.x;
-    const int y = blockIdx.y;
-    if (x >= W) return;
-    const float d = ((const float*)((const uint8_t*)depth + (size_t)y * depth_pitch))[x];
-    const float v = rintf(fmaxf(0.0f, fminf(d, tmax) - tmin) * k);
-    uint32_t q = (uint32_t)v & 0xFFu;                       // .astype(np.uint8)
-    if (zero_is_far && q == 0) q = 255;                     // sr:690 / 827
-    q = 255u - q;                                           // Touchly uses reverse depth
-    store_px_bytes(rgb + (size_t)y * rgb_pitch, x, q | (q << 8) | (q << 16));
-}
-
-hipError_t launch_touchly_depth(const float* depth, size_t depth_pitch, uint8_t* rgb, size_t rgb_pitch, int W, int H,
-                                float tmax, float tmin, float k, int zero_is_far, hipStream_t s)
-{
-    dim3 grid((W + 255) / 256, H);
-    hipLaunchKernelGGL(k_touchly_depth, grid, dim3(256), 0, s, depth, depth_pitch, rgb, rgb_pitch, W, H, tmax, tmin, k, zero_is_far);
-    return hipGetLastError();
-}
-
-// =================================================================================================
-// VR180: convert_to_equirectangular (sr:25-86) = cv2.remap(INTER_LINEAR, BORDER_CONSTANT 0) through
-// separable lookup tables
-// =================================================================================================
-// One thread = PX output pixels of one row of one image.  Coordinates are rounded to 1/32 px (half to even),
-// the four taps get the integer weights (32-fx)(32-fy)*32 ... (sum 2^15), taps outside the image are 0, the
-// result is (sum + 2^14) >> 15.  A table entry of -1 marks an angle outside the input fov: the pixel is black.
-__device__ __forceinline__ uint32_t remap_tap4(const uint8_t* __restrict__ src, size_t pitch, int W, int H,
-                                               int ix, int iy, int fx, int fy)
-{
-    const int w00 = (32 - fx) * (32 - fy) * 32, w10 = fx * (32 - fy) * 32, w01 = (32 - fx) * fy * 32, w11 = fx * fy * 32;
-    const bool x0 = ix >= 0 && ix < W, x1 = ix + 1 >= 0 && ix + 1 < W;
-    const bool y0 = iy >= 0 && iy < H, y1 = iy + 1 >= 0 && iy + 1 < H;
-    const uint32_t p00 = (x0 && y0) ? load_px_bytes(src + (size_t)iy * pitch, ix) : 0u;
-    const uint32_t p10 = (x1 && y0 && w10) ? load_px_bytes(src + (size_t)iy * pitch, ix + 1) : 0u;
-    const uint32_t p01 = (x0 && y1 && w01) ? load_px_bytes(src + (size_t)(iy + 1) * pitch, ix) : 0u;
-    const uint32_t p11 = (x1 && y1 && w11) ? load_px_bytes(src + (size_t)(iy + 1) * pitch, ix + 1) : 0u;
-    uint32_t out = 0;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const int sh = 8 * c;
-        const int acc = w00 * (int)((p00 >> sh) & 0xFF) + w10 * (int)((p10 >> sh) & 0xFF) +
-                        w01 * (int)((p01 >> sh) & 0xFF) + w11 * (int)((p11 >> sh) & 0xFF);
-        out |= (uint32_t)((acc + (1 << 14)) >> 15) << sh;
-    }
-    return out;
-}
-
-template <int PX>
-__global__ void __launch_bounds__(256) k_equirect_remap(const uint8_t* __restrict__ src, size_t src_pitch, size_t src_stride,
-                                                        uint8_t* __restrict__ dst, size_t dst_pitch, size_t dst_stride,
-                                                        int W, int H, const float* __restrict__ mx, const float* __restrict__ my)
-{
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    const int y = blockIdx.y;
-    if (g >= W / PX) return;
-    const uint8_t* simg = src + (size_t)blockIdx.z * src_stride;
-    uint8_t* drow = dst + (size_t)blockIdx.z * dst_stride + (size_t)y * dst_pitch;
-    const float fyv = my[y];
-    uint32_t out[PX];
-    if (fyv == -1.0f) {
-#pragma unroll
-        for (int q = 0; q < PX; ++q) out[q] = 0u;
-    } else {
-        const int sy = (int)rintf(fyv * 32.0f);
-#pragma unroll
-        for (int q = 0; q < PX; ++q) {
-            const float fxv = mx[g * PX + q];
-            if (fxv == -1.0f) { out[q] = 0u; continue; }
-            const int sx = (int)rintf(fxv * 32.0f);
-            out[q] = remap_tap4(simg, src_pitch, W, H, sx >> 5, sy >> 5, sx & 31, sy & 31);
-        }
-    }
-    RowIO<PX>::store_rgb(drow, g, out);
-}
-
-hipError_t launch_equirect_remap(const uint8_t* src, size_t src_pitch, size_t src_stride, uint8_t* dst, size_t dst_pitch,
-                                 size_t dst_stride, int n, int W, int H, const float* mx, const float* my, hipStream_t s)
-{
-    const bool vec4 = W % 4 == 0 && ((uintptr_t)dst % 4 == 0) && dst_pitch % 4 == 0 && dst_stride % 4 == 0;
-    if (vec4) {
-        dim3 grid((W / 4 + 255) / 256, H, n);
-        hipLaunchKernelGGL((k_equirect_remap<4>), grid, dim3(256), 0, s, src, src_pitch, src_stride, dst, dst_pitch, dst_stride, W, H, mx, my);
-    } else {
-        dim3 grid((W + 255) / 256, H, n);
-        hipLaunchKernelGGL((k_equirect_remap<1>), grid, dim3(256), 0, s, src, src_pitch, src_stride, dst, dst_pitch, dst_stride, W, H, mx, my);
-    }
-    return hipGetLastError();
-}
-
-// =================================================================================================
-// infill-mask completion (sr:803-808, 114-153): level-synchronous Telea inpaint + masked Gaussian
-// =================================================================================================
-// State per image: stamp u16 (0 known from the start, 0xFFFF unknown, r = filled in round r), T f32 (written by the fill pass only: known pixels read as 0), the work
-// image (seed copy, filled in place).  Round r reads only pixels with stamp < r, so the in-place writes of the
-// same round (stamp = r) are never observed: one launch = one Jacobi step, no double buffering.
-constexpr uint16_t kTeleaUnknown = 0xFFFFu;
-constexpr uint32_t kTeleaNeedBit = 0x8000u;        // from the list scatter on: top bit of a level word = "this pixel's estimate is needed"
-constexpr uint32_t kTeleaLevelMask = 0x7FFFu;      // (levels stay below 32767: max_rounds <= 32766)
-#ifndef MDVT_NC_STRIDE
-#define MDVT_NC_STRIDE 32
-#endif
-// The per-level counters of needed pixels take the appends of every workgroup of a launch: atomics on one address serialise at
-// ~4 ns each, and neighbouring levels' counters in one cache line queue behind each other -- one counter per 128-byte line.
-constexpr uint32_t kNcStride = MDVT_NC_STRIDE;
-
-// The level of a pixel -- the round in which the level-synchronous front reaches it -- is its 4-connected distance to the
-// nearest known pixel: an L1 distance transform, two separable passes (A) instead of one dependent launch per level.
-// Then, level by level, so that the expensive estimate only runs where the result can reach a hole:
-//   A  k_telea_dt_rows / k_telea_dt_cols   stamp = L1 distance to the nearest known pixel (0 = known), capped at max_rounds;
-//                                   per image last_round = the level of its deepest key-coloured pixel (later levels
-//                                   are never needed) and remaining = key-coloured pixels beyond max_rounds;
-//      (level sizes: last sweep of the transform) / k_telea_scan / k_telea_sort   offsets, and the key-coloured pixels
-//                                   of level r appended to nlist[offs[r] ..) -- the first needed pixels of each level.
-//   B  k_telea_need    r = R .. 2   which estimates are needed: key-coloured pixels, and every pixel of a lower
-//                                   level that a needed pixel reads (its radius-3 disc and their 4-neighbours) -- which
-//                                   also closes the set under "T of a pixel needs T of its lower 4-neighbours".  The launch
-//                                   for level r walks the needed pixels of that level only (complete by then: levels are
-//                                   1-Lipschitz, so they were all marked by levels r+1 .. r+5) and appends what it marks to
-//                                   the lists of levels r-5 .. r-1; a pixel is appended by whoever sets its need flag first.
-//   C  k_telea_fill    r = 1 .. R   T (FastMarching_solve over the four quadrants) and Telea's estimate for the needed
-//                                   pixels of level r, reading levels < r.
-// A black (non-hole) pixel that no key-coloured pixel depends on is never estimated -- it returns to black at
-// sr:807 anyway -- which removes ~90 % of the estimates (and T solves) of a front that also grows outwards from the
-// holes.  R (the deepest level any image needs) is read back by the host after pass A: passes B and C are launched
-// for exactly the levels that exist (round 1 launched all max_rounds levels of all three passes, 768 launches of which
-// ~620 found nothing to do).
-struct TeleaArgs {
-    uint16_t* stamp; float* T; uint8_t* img;      // [n][H*W] / [n][H*W*3]
-    uint8_t* need;                                // [n][H*W] 1 = this pixel's estimate is needed (and it is in nlist)
-    uint32_t* nlist;                              // the needed pixels of each level; level r owns [offs[r], offs[r] + counts[r])
-    uint32_t* counts;                             // [max_rounds + 2] level sizes (all pixels of the level: the capacity of its nlist part)
-    uint32_t* offs;                               // [max_rounds + 2] level offsets into nlist
-    uint32_t* ncounts;                            // [max_rounds + 2] needed pixels per level so far
-    uint32_t* remaining;                          // [n] key-coloured pixels not reached yet
-    uint32_t* last_round;                         // [n]
-    int W, H, n;
-    uint32_t key_rgb;
-};
-
-constexpr int kDtInf = 1 << 20;          // "no known pixel in this direction" (any real distance is < 2^17)
-
-// T is zeroed with a memset beforehand; this pass writes 0 (known) / 0xFFFF (to fill) stamps, the need flags (key-coloured
-// pixels) and the work image.
-template <int PX>
-__global__ void __launch_bounds__(128) k_telea_init(ImageSet seed, TeleaArgs a)
-{
-    const int g = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, im = blockIdx.z;
-    const int W = a.W, H = a.H;
-    if (g * PX >= W) return;
-    const size_t o = (size_t)im * W * H + (size_t)y * W + (size_t)g * PX;
-    uint32_t px[PX];
-    RowIO<PX>::load(seed.image(im) + (size_t)y * seed.pitch, g, px);
-    uint32_t st = 0, nd = 0;
-#pragma unroll
-    for (int q = 0; q < PX; ++q) {
-        const bool green = px[q] == a.key_rgb;
-        if (green || px[q] == 0u) {                                        // sr:803-805: key-coloured or black = to inpaint
-            if (PX == 4) { if (q < 2) st |= (uint32_t)kTeleaUnknown << (16 * q); }
-            else a.stamp[o + q] = kTeleaUnknown;
-        } else if (PX != 4) a.stamp[o + q] = 0;
-        if (PX == 4) nd |= (green ? 1u : 0u) << (8 * q); else a.need[o + q] = green ? 1 : 0;
-    }
-    if (PX == 4) {
-        uint32_t st1 = 0;
-#pragma unroll
-        for (int q = 2; q < 4; ++q) if (px[q] == a.key_rgb || px[q] == 0u) st1 |= (uint32_t)kTeleaUnknown << (16 * (q - 2));
-        *reinterpret_cast<uint2*>(a.stamp + o) = make_uint2(st, st1);
-        *reinterpret_cast<uint32_t*>(a.need + o) = nd;
-    }
-    RowIO<PX>::store_rgb(a.img + 3 * ((size_t)im * W * H + (size_t)y * W), g, px);
-}
-
-// Pass A, rows: stamp[x] = distance to the nearest known pixel of the same row (0xFFFF: none), in place.  One workgroup per
-// (row, image); a thread owns a contiguous segment, the nearest known pixels outside it come from a block-wide scan.
-__global__ void __launch_bounds__(256) k_telea_dt_rows(uint16_t* __restrict__ stamp, int W, int H)
-{
-    __shared__ int sl[256], sf[256];
-    uint16_t* d = stamp + ((size_t)blockIdx.y * H + blockIdx.x) * W;
-    const int t = threadIdx.x;
-    const int seg = (W + 255) / 256, x0 = min(t * seg, W), x1 = min(x0 + seg, W);
-    int last = -kDtInf, first = kDtInf;
-    for (int x = x0; x < x1; ++x)
-        if (d[x] == 0) { last = x; if (first == kDtInf) first = x; }
-    sl[t] = last; sf[t] = first;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {            // inclusive prefix max of `last`, inclusive suffix min of `first`
-        const int vl = t >= off ? sl[t - off] : -kDtInf, vf = t + off < 256 ? sf[t + off] : kDtInf;
-        __syncthreads();
-        sl[t] = max(sl[t], vl); sf[t] = min(sf[t], vf);
-        __syncthreads();
-    }
-    int run = t > 0 ? sl[t - 1] : -kDtInf;                // nearest known pixel left of the segment
-    for (int x = x0; x < x1; ++x) {
-        if (d[x] == 0) run = x;
-        const int v = x - run;
-        d[x] = (uint16_t)(v < 0xFFFF ? v : 0xFFFF);
-    }
-    run = t < 255 ? sf[t + 1] : kDtInf;                   // ... and right of it
-    for (int x = x1 - 1; x >= x0; --x) {
-        if (d[x] == 0) run = x;
-        const int v = run - x;
-        if (v < (int)d[x]) d[x] = (uint16_t)v;
-    }
-}
-
-// The same with 16-byte row accesses: a thread owns 8 * VEC consecutive pixels (W % 8 == 0, W <= 2048 * VEC).
-template <int VEC>
-__global__ void __launch_bounds__(256) k_telea_dt_rows_vec(uint16_t* __restrict__ stamp, int W, int H)
-{
-    __shared__ int sl[256], sf[256];
-    uint16_t* d = stamp + ((size_t)blockIdx.y * H + blockIdx.x) * W;
-    const int t = threadIdx.x;
-    constexpr int N = 8 * VEC;
-    const int x0 = t * N;
-    uint32_t w[4 * VEC];
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) {
-        uint4 q = make_uint4(~0u, ~0u, ~0u, ~0u);                       // past the row end: "unknown", never a zero
-        if (x0 + 8 * v < W) q = *reinterpret_cast<const uint4*>(d + x0 + 8 * v);
-        w[4 * v] = q.x; w[4 * v + 1] = q.y; w[4 * v + 2] = q.z; w[4 * v + 3] = q.w;
-    }
-    auto val = [&](int k) { return (w[k >> 1] >> (16 * (k & 1))) & 0xFFFFu; };
-    int last = -kDtInf, first = kDtInf;
-#pragma unroll
-    for (int k = 0; k < N; ++k)
-        if (val(k) == 0u) { last = x0 + k; if (first == kDtInf) first = x0 + k; }
-    sl[t] = last; sf[t] = first;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {            // inclusive prefix max of `last`, inclusive suffix min of `first`
-        const int vl = t >= off ? sl[t - off] : -kDtInf, vf = t + off < 256 ? sf[t + off] : kDtInf;
-        __syncthreads();
-        sl[t] = max(sl[t], vl); sf[t] = min(sf[t], vf);
-        __syncthreads();
-    }
-    int out[N];
-    int run = t > 0 ? sl[t - 1] : -kDtInf;
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        if (val(k) == 0u) run = x0 + k;
-        out[k] = min(x0 + k - run, 0xFFFF);
-    }
-    run = t < 255 ? sf[t + 1] : kDtInf;
-#pragma unroll
-    for (int k = N - 1; k >= 0; --k) {
-        if (val(k) == 0u) run = x0 + k;
-        out[k] = min(out[k], run - (x0 + k));
-    }
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) {
-        if (x0 + 8 * v >= W) continue;
-        uint4 q;
-        q.x = (uint32_t)out[8 * v] | ((uint32_t)out[8 * v + 1] << 16); q.y = (uint32_t)out[8 * v + 2] | ((uint32_t)out[8 * v + 3] << 16);
-        q.z = (uint32_t)out[8 * v + 4] | ((uint32_t)out[8 * v + 5] << 16); q.w = (uint32_t)out[8 * v + 6] | ((uint32_t)out[8 * v + 7] << 16);
-        *reinterpret_cast<uint4*>(d + x0 + 8 * v) = q;
-    }
-}
-
-constexpr int kLevelBins = 4096;      // levels counted / slotted in LDS; deeper ones go straight to the global counters
-
-// Pass A, columns: the two sweeps of the L1 transform (down: D[y] = min(D[y-1] + 1, d[y]); up the same from below), in
-// place.  One workgroup = 64 columns x 16 row segments; the value entering a segment comes from a scan over the segments'
-// exit values.  The last sweep also caps the level at max_rounds and collects, per image, the deepest key-coloured level
-// (last_round) and the number of key-coloured pixels beyond the cap (remaining).
-__global__ void __launch_bounds__(1024) k_telea_dt_cols(TeleaArgs a, uint32_t max_rounds)
-{
-    __shared__ int ex[16][64], carry[16][64];
-    __shared__ uint32_t s_rem, s_max;
-    __shared__ uint32_t hist[kLevelBins];          // the level sizes (every reached pixel), added to a.counts at the end
-    const int W = a.W, H = a.H;
-    const int cx = threadIdx.x & 63, sg = threadIdx.x >> 6;
-    const int x = blockIdx.x * 64 + cx, im = blockIdx.y;
-    const bool act = x < W;
-    const int seglen = (H + 15) / 16, y0 = min(sg * seglen, H), y1 = min(y0 + seglen, H);
-    const size_t base = (size_t)im * W * H + (act ? x : 0);
-    uint16_t* d = a.stamp + base;
-    if (threadIdx.x == 0) { s_rem = 0u; s_max = 0u; }
-    for (int b = threadIdx.x; b < kLevelBins; b += 1024) hist[b] = 0u;
-    auto val = [&](int y) { const int v = d[(size_t)y * W]; return v == 0xFFFF ? kDtInf : v; };
-    auto put = [&](int y, int v) { d[(size_t)y * W] = (uint16_t)(v < 0xFFFF ? v : 0xFFFF); };
-    // ---- down ----
-    int run = kDtInf;
-    if (act) for (int y = y0; y < y1; ++y) run = min(run + 1, val(y));
-    ex[sg][cx] = run;
-    __syncthreads();
-    if (sg == 0) {
-        int c = kDtInf;
-        for (int q = 0; q < 16; ++q) {
-            carry[q][cx] = c;
-            const int len = min((q + 1) * seglen, H) - min(q * seglen, H);
-            c = min(ex[q][cx], c + len);
-        }
-    }
-    __syncthreads();
-    run = carry[sg][cx];
-    if (act) for (int y = y0; y < y1; ++y) { run = min(run + 1, val(y)); put(y, run); }
-    __syncthreads();            // (a column's segments are all in this workgroup: its writes above are visible below)
-    // ---- up ----
-    run = kDtInf;
-    if (act) for (int y = y1 - 1; y >= y0; --y) run = min(run + 1, val(y));
-    ex[sg][cx] = run;
-    __syncthreads();
-    if (sg == 0) {
-        int c = kDtInf;
-        for (int q = 15; q >= 0; --q) {
-            carry[q][cx] = c;
-            const int len = min((q + 1) * seglen, H) - min(q * seglen, H);
-            c = min(ex[q][cx], c + len);
-        }
-    }
-    __syncthreads();
-    run = carry[sg][cx];
-    uint32_t rem = 0, lmax = 0;
-    if (act) {
-        const uint8_t* key = a.need + base;
-        for (int y = y1 - 1; y >= y0; --y) {
-            run = min(run + 1, val(y));
-            const bool reached = run <= (int)max_rounds;
-            d[(size_t)y * W] = reached ? (uint16_t)run : kTeleaUnknown;
-            if (reached && run >= 1) { if (run < kLevelBins) atomicAdd(&hist[run], 1u); else atomicAdd(&a.counts[run], 1u); }
-            if (key[(size_t)y * W]) { if (reached) lmax = max(lmax, (uint32_t)run); else ++rem; }
-        }
-    }
-    if (rem) atomicAdd(&s_rem, rem);
-    if (lmax) atomicMax(&s_max, lmax);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        if (s_rem) atomicAdd(&a.remaining[im], s_rem);
-        if (s_max) atomicMax(&a.last_round[im], s_max);
-    }
-    for (int b = threadIdx.x; b < kLevelBins; b += 1024)
-        if (hist[b]) atomicAdd(&a.counts[b], hist[b]);
-}
-
-// The same with a column segment held in registers between the sweeps (H <= 16 * SEG): the stamps are read once and
-// written once instead of four times and twice.
-template <int SEG>
-__global__ void __launch_bounds__(1024) k_telea_dt_cols_reg(TeleaArgs a, uint32_t max_rounds)
-{
-    __shared__ int ex[16][64], carry[16][64];
-    __shared__ uint32_t s_rem, s_max;
-    __shared__ uint32_t hist[kLevelBins];          // the level sizes (every reached pixel), added to a.counts at the end
-    const int W = a.W, H = a.H;
-    const int cx = threadIdx.x & 63, sg = threadIdx.x >> 6;
-    const int x = blockIdx.x * 64 + cx, im = blockIdx.y;
-    const bool act = x < W;
-    const int seglen = (H + 15) / 16, y0 = min(sg * seglen, H), y1 = min(y0 + seglen, H);
-    const int len = act ? y1 - y0 : 0;
-    const size_t base = (size_t)im * W * H + (act ? x : 0);
-    uint16_t* d = a.stamp + base;
-    if (threadIdx.x == 0) { s_rem = 0u; s_max = 0u; }
-    for (int b = threadIdx.x; b < kLevelBins; b += 1024) hist[b] = 0u;
-    int v[SEG];
-#pragma unroll
-    for (int k = 0; k < SEG; ++k) {
-        v[k] = kDtInf;
-        if (k < len) { const int q = d[(size_t)(y0 + k) * W]; v[k] = q == 0xFFFF ? kDtInf : q; }
-    }
-    // ---- down ----
-    int run = kDtInf;
-#pragma unroll
-    for (int k = 0; k < SEG; ++k) if (k < len) run = min(run + 1, v[k]);
-    ex[sg][cx] = run;
-    __syncthreads();
-    if (sg == 0) {
-        int c = kDtInf;
-        for (int q = 0; q < 16; ++q) {
-            carry[q][cx] = c;
-            const int l = min((q + 1) * seglen, H) - min(q * seglen, H);
-            c = min(ex[q][cx], c + l);
-        }
-    }
-    __syncthreads();
-    run = carry[sg][cx];
-#pragma unroll
-    for (int k = 0; k < SEG; ++k) if (k < len) { run = min(run + 1, v[k]); v[k] = run; }
-    __syncthreads();
-    // ---- up ----
-    run = kDtInf;
-#pragma unroll
-    for (int k = SEG - 1; k >= 0; --k) if (k < len) run = min(run + 1, v[k]);
-    ex[sg][cx] = run;
-    __syncthreads();
-    if (sg == 0) {
-        int c = kDtInf;
-        for (int q = 15; q >= 0; --q) {
-            carry[q][cx] = c;
-            const int l = min((q + 1) * seglen, H) - min(q * seglen, H);
-            c = min(ex[q][cx], c + l);
-        }
-    }
-    __syncthreads();
-    run = carry[sg][cx];
-    uint32_t rem = 0, lmax = 0;
-    const uint8_t* key = a.need + base;
-#pragma unroll
-    for (int k = SEG - 1; k >= 0; --k) {
-        if (k >= len) continue;
-        run = min(run + 1, v[k]);
-        const bool reached = run <= (int)max_rounds;
-        d[(size_t)(y0 + k) * W] = reached ? (uint16_t)run : kTeleaUnknown;
-        if (reached && run >= 1) { if (run < kLevelBins) atomicAdd(&hist[run], 1u); else atomicAdd(&a.counts[run], 1u); }
-        if (key[(size_t)(y0 + k) * W]) { if (reached) lmax = max(lmax, (uint32_t)run); else ++rem; }
-    }
-    if (rem) atomicAdd(&s_rem, rem);
-    if (lmax) atomicMax(&s_max, lmax);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        if (s_rem) atomicAdd(&a.remaining[im], s_rem);
-        if (s_max) atomicMax(&a.last_round[im], s_max);
-    }
-    for (int b = threadIdx.x; b < kLevelBins; b += 1024)
-        if (hist[b]) atomicAdd(&a.counts[b], hist[b]);
-}
-
-// counts[0] = the deepest level any image needs (the host reads it back: passes B and C get exactly that many launches)
-__global__ void k_telea_rmax(TeleaArgs a)
-{
-    uint32_t m = 0;
-    for (int im = 0; im < a.n; ++im) m = max(m, a.last_round[im]);
-    a.counts[0] = m;
-}
-
-// The first entries of the level lists: the key-coloured pixels.  (The level sizes -- every reached pixel of a level, the room
-// its list may need -- are counted by the last sweep of the distance transform.)  A workgroup takes a 64 x 64 tile of one
-// image -- so that the pixels of a level stay together tile by tile in the list, and the half-waves that later work through
-// consecutive list entries read overlapping 9 x 9 neighbourhoods --; levels below kLevelBins are slotted in LDS first (one
-// global atomic per occupied level and workgroup), deeper ones directly.
-constexpr int kSortTile = 64;
-
-__global__ void __launch_bounds__(256) k_telea_sort(TeleaArgs a)
-{
-    __shared__ uint32_t hist[kLevelBins];
-    __shared__ uint32_t slot[kLevelBins];
-    const int im = blockIdx.y;
-    const uint32_t lr = a.last_round[im];
-    if (lr == 0u) return;                                   // nothing key-coloured (or nothing reachable): nothing to do
-    const uint32_t npx = (uint32_t)a.W * (uint32_t)a.H;
-    const int tiles_x = (a.W + kSortTile - 1) / kSortTile;
-    const int tx0 = (int)(blockIdx.x % tiles_x) * kSortTile, ty0 = (int)(blockIdx.x / tiles_x) * kSortTile;
-    // a thread takes four consecutive pixels of a row (one dword of need flags where the row allows it): 16 threads per tile
-    // row, 16 rows per step, 4 steps
-    const int lx = (threadIdx.x & 15) * 4, ly0 = threadIdx.x >> 4;
-    const uint16_t* st = a.stamp + (size_t)im * npx;
-    const uint8_t* nd = a.need + (size_t)im * npx;
-    const bool dwords = (a.W & 3) == 0;                     // (then every row starts on a dword of the flag plane)
-    for (int b = threadIdx.x; b < kLevelBins; b += 256) hist[b] = 0u;
-    __syncthreads();
-    constexpr int kSteps = kSortTile / 16;
-    uint32_t lv[kSteps][4];
-#pragma unroll
-    for (int k = 0; k < kSteps; ++k) {
-        const int px = tx0 + lx, py = ty0 + ly0 + 16 * k;
-        const uint32_t o = (uint32_t)py * (uint32_t)a.W + (uint32_t)px;
-        uint32_t flags = 0;
-        if (py < a.H) {
-            if (dwords && px + 3 < a.W) flags = *reinterpret_cast<const uint32_t*>(nd + o);
-            else {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) if (px + q < a.W && nd[o + q]) flags |= 1u << (8 * q);
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            lv[k][q] = 0u;
-            if ((flags >> (8 * q)) & 0xFFu) {               // key-coloured (~4 % of the pixels): only those look their level up
-                const uint32_t sv = st[o + q];
-                if (sv >= 1u && sv <= lr) {
-                    lv[k][q] = sv;
-                    a.stamp[(size_t)im * npx + o + q] = (uint16_t)(sv | kTeleaNeedBit);      // needed from the start
-                    if (sv < (uint32_t)kLevelBins) atomicAdd(&hist[sv], 1u);
-                }
-            }
-        }
-    }
-    __syncthreads();
-    for (int b = threadIdx.x; b < kLevelBins; b += 256) {
-        const uint32_t c = hist[b];
-        if (!c) continue;
-        slot[b] = atomicAdd(&a.ncounts[(uint32_t)b * kNcStride], c); hist[b] = 0u;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < kSteps; ++k)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const uint32_t l = lv[k][q];
-            if (!l) continue;
-            const uint32_t e = (uint32_t)im * npx + (uint32_t)(ty0 + ly0 + 16 * k) * (uint32_t)a.W + (uint32_t)(tx0 + lx + q);
-            const uint32_t pos = l < (uint32_t)kLevelBins ? slot[l] + atomicAdd(&hist[l], 1u) : atomicAdd(&a.ncounts[l * kNcStride], 1u);
-            a.nlist[a.offs[l] + pos] = e;
-        }
-}
-
-// offs[r] = counts[1] + ... + counts[r-1] for r = 1 .. n_levels + 1 (level 1 starts at 0).  One workgroup.
-__global__ void __launch_bounds__(1024) k_telea_scan(TeleaArgs a, int n_levels)
-{
-    __shared__ uint32_t part[1024];
-    const int t = threadIdx.x, n = n_levels + 1;             // entries 1 .. n
-    const int per = (n + 1023) / 1024, lo = min(1 + t * per, n + 1), hi = min(lo + per, n + 1);
-    uint32_t sum = 0;
-    for (int k = lo; k < hi; ++k) sum += a.counts[k];
-    part[t] = sum;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        const uint32_t v = t >= off ? part[t - off] : 0u;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    uint32_t run = part[t] - sum;
-    for (int k = lo; k < hi; ++k) { a.offs[k] = run; run += a.counts[k]; }
-}
-
-// (telea_solve and kNeedOffsets, the read set of an estimate: mdvt_telea_common.h)
-constexpr int kNeedLanes = 8;            // lanes sharing the 56 offsets of one needed pixel
-constexpr int kNeedStage = 512;          // newly marked pixels a workgroup collects per target level before it appends them
-
-__global__ void __launch_bounds__(256) k_telea_need(TeleaArgs a, uint32_t r)
-{
-    __shared__ uint32_t stage[5][kNeedStage];
-    __shared__ uint32_t cnt[5], base[5];
-    const uint32_t count = a.ncounts[r * kNcStride], off = a.offs[r];
-    constexpr uint32_t per_block = 256 / kNeedLanes;
-    // XCD-aware dealing (workgroup b runs on XCD b % 8, each XCD has its own L2): every XCD walks one contiguous eighth of the
-    // level's list -- neighbouring entries are neighbouring pixels, whose 9 x 9 windows share their cache lines
-    const uint32_t xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3, nslot = gridDim.x >> 3;
-    const uint32_t per_xcd = (count + 7u) >> 3, lo_x = xcd * per_xcd, hi_x = min(lo_x + per_xcd, count);
-    if (lo_x + slot * per_block >= hi_x) return;                       // (workgroup-uniform)
-    const int W = a.W, H = a.H;
-    const uint32_t npx = (uint32_t)W * (uint32_t)H;
-    if (threadIdx.x < 5) cnt[threadIdx.x] = 0u;
-    __syncthreads();
-    const int sub = threadIdx.x & (kNeedLanes - 1);
-    // (from the list scatter on, "needed" is the top bit of a pixel's level word: one load tells level and flag)
-    uint32_t* stamp_words = reinterpret_cast<uint32_t*>(a.stamp);
-    uint32_t idx = lo_x + slot * per_block + threadIdx.x / kNeedLanes;
-    uint32_t e_next = idx < hi_x ? a.nlist[off + idx] : 0u;
-    for (; idx < hi_x; idx += nslot * per_block) {
-        const uint32_t e = e_next, im = e / npx, o = e - im * npx;
-        if (idx + nslot * per_block < hi_x) e_next = a.nlist[off + idx + nslot * per_block];     // (in flight during this entry)
-        const int y = (int)(o / (uint32_t)W), x = (int)(o - (uint32_t)y * (uint32_t)W);
-        const size_t ib = (size_t)im * npx;
-        // three rounds with everything of a round in flight together (a loop over the lane's offsets with the flag test, the
-        // atomic and the append inside is seven dependent round trips to L2 per entry: the floor of a level's launch)
-        constexpr int kPer = (56 + kNeedLanes - 1) / kNeedLanes;
-        static_assert(kPer * kNeedLanes >= 56, "every offset has a lane");
-        uint32_t uu[kPer], su[kPer], old[kPer];
-        bool want[kPer];
-#pragma unroll
-        for (int k = 0; k < kPer; ++k) {
-            const int q = sub + k * kNeedLanes;
-            const int xx = x + kNeedOffsets.dx[q < kNeedOffsets.n ? q : 0], yy = y + kNeedOffsets.dy[q < kNeedOffsets.n ? q : 0];
-            const bool in = q < kNeedOffsets.n && xx >= 0 && xx < W && yy >= 0 && yy < H;
-            uu[k] = in ? (uint32_t)(ib + (size_t)yy * W + xx) : e;           // (the entry itself: level r, never marked)
-            const uint32_t sw = a.stamp[uu[k]];
-            su[k] = sw & kTeleaLevelMask;
-            want[k] = su[k] != 0u && su[k] < r && !(sw & kTeleaNeedBit);
-        }
-#pragma unroll
-        for (int k = 0; k < kPer; ++k) {
-            const uint32_t bit = kTeleaNeedBit << (16u * (uu[k] & 1u));
-            old[k] = bit;                                                      // "already set"
-            if (want[k]) old[k] = atomicOr(stamp_words + (uu[k] >> 1), bit);
-        }
-#pragma unroll
-        for (int k = 0; k < kPer; ++k) {
-            if (old[k] & (kTeleaNeedBit << (16u * (uu[k] & 1u)))) continue;    // flag was set: somebody else appends (or has appended) it
-            const uint32_t d = r - 1u - su[k];
-            const uint32_t pos = d < 5u ? atomicAdd(&cnt[d], 1u) : (uint32_t)kNeedStage;
-            if (pos < (uint32_t)kNeedStage) stage[d][pos] = uu[k];
-            else a.nlist[a.offs[su[k]] + atomicAdd(&a.ncounts[su[k] * kNcStride], 1u)] = uu[k];
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < 5) {
-        const uint32_t n = min(cnt[threadIdx.x], (uint32_t)kNeedStage);
-        cnt[threadIdx.x] = n;
-        base[threadIdx.x] = n ? a.offs[r - 1u - threadIdx.x] + atomicAdd(&a.ncounts[(r - 1u - threadIdx.x) * kNcStride], n) : 0u;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int d = 0; d < 5; ++d)
-        for (uint32_t i = threadIdx.x; i < cnt[d]; i += 256) a.nlist[base[d] + i] = stage[d][i];
-}
-
-// Pass C, lane-parallel: one half-wave (32 lanes) per needed pixel, lane j < 28 = disc pixel j.  The 9 x 9 neighbourhood is
-// fetched once into LDS, coalesced along its rows; T comes from four lanes solving one quadrant each; every lane weighs
-// its own disc pixel; the 10 running sums (Ia, Jx, Jy per channel and the weight) are then added up in the oracle's order
-// j = 0..27 by 10 lanes reading the terms back from LDS -- the same left-to-right f32 chain as the oracle's loop, so the
-// result is bit-identical to it (telea_tile_estimate, mdvt_telea_common.h).  (The level's latency is what bounds the deep levels,
-// instruction issue the first ones.)
-__global__ void __launch_bounds__(256) k_telea_fill(TeleaArgs a, uint32_t r)
-{
-    const uint32_t off = a.offs[r];
-    const int W = a.W, H = a.H;
-    const uint32_t npx = (uint32_t)W * (uint32_t)H;
-    __shared__ __attribute__((aligned(16))) float red[8][10][kRedStride];
-    __shared__ uint32_t wcol[8][81];
-    __shared__ float wt[8][81];
-    __shared__ uint8_t wkn[8][84];
-    const int lane32 = threadIdx.x & 31, hw = threadIdx.x >> 5;
-    const uint32_t nneed = a.ncounts[r * kNcStride];
-    const DiscPixel dp = kDisc[lane32];
-    const int qv = 4 + ((lane32 & 1) ? 9 : -9), qh = 4 * 9 + 4 + ((lane32 & 2) ? 1 : -1);     // this lane's quadrant: cells (0, +-1) and (+-1, 0)
-    // every entry of nlist is a pixel to estimate: they are dealt round-robin to all half-waves of the grid
-    // (XCD-aware dealing as in the need pass: one contiguous eighth of the list per XCD)
-    const uint32_t xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3, nslot = gridDim.x >> 3;
-    const uint32_t per_xcd = (nneed + 7u) >> 3, lo_x = xcd * per_xcd, hi_x = min(lo_x + per_xcd, nneed);
-    // Software pipeline over a half-wave's pixels: the neighbourhood of pixel i + 1 (loads into registers) and the list index of
-    // pixel i + 2 are in flight while pixel i is worked out from LDS -- pixels of one level never read each other's results.
-    struct Cells { uint32_t c[3]; float t[3]; uint32_t sv[3]; bool inb[3]; };
-    auto fetch = [&](uint32_t e, Cells& p) {
-        const uint32_t im = e / npx, o = e - im * npx;
-        const int y = (int)(o / (uint32_t)W), x = (int)(o - (uint32_t)y * (uint32_t)W);
-        const size_t ib = (size_t)im * npx;
-        const uint16_t* stamp = a.stamp + ib;
-        const float* Tm = a.T + ib;
-        const uint8_t* img = a.img + 3 * ib;
-#pragma unroll
-        for (int it = 0; it < 3; ++it) {
-            const int q = min(lane32 + 32 * it, 80);                  // (lanes past cell 80 repeat it: their values are not committed)
-            const int wy = q / 9, wx = q - 9 * wy;
-            const int xx = x - 4 + wx, yy = y - 4 + wy;
-            p.inb[it] = xx >= 0 && xx < W && yy >= 0 && yy < H;
-            const size_t oo = (size_t)(p.inb[it] ? yy : y) * W + (p.inb[it] ? xx : x);
-            __builtin_memcpy(&p.c[it], img + 3 * oo, 4);              // unaligned dword: the work image is padded by 4 bytes
-            p.sv[it] = stamp[oo];
-            p.t[it] = Tm[oo];
-        }
-    };
-    auto commit = [&](const Cells& p) {
-#pragma unroll
-        for (int it = 0; it < 3; ++it) {
-            const int q = lane32 + 32 * it;
-            if (q >= 81) continue;
-            const uint32_t sv = p.sv[it] & kTeleaLevelMask;           // (an unreached pixel, 0xFFFF, stays beyond every level)
-            wcol[hw][q] = p.c[it] & 0xFFFFFFu;
-            wt[hw][q] = sv == 0u ? 0.0f : p.t[it];                    // T = 0 at every originally known pixel (nobody writes it there)
-            wkn[hw][q] = (p.inb[it] && sv < r) ? 1 : 0;
-        }
-    };
-    const uint32_t stride = nslot * 8;
-    uint32_t k = lo_x + slot * 8 + hw;
-    uint32_t e_cur = k < hi_x ? a.nlist[off + k] : 0u;
-    uint32_t e_next = k + stride < hi_x ? a.nlist[off + k + stride] : 0u;
-    Cells cells;
-    if (k < hi_x) fetch(e_cur, cells);
-    for (; k < hi_x; k += stride) {                                                         // half-wave uniform
-        const uint32_t e = e_cur, im = e / npx, o = e - im * npx;
-        const size_t ib = (size_t)im * npx;
-        commit(cells);
-        e_cur = e_next;
-        if (k + stride < hi_x) fetch(e_cur, cells);
-        if (k + 2 * stride < hi_x) e_next = a.nlist[off + k + 2 * stride];
-        __builtin_amdgcn_wave_barrier();                   // LDS is in order within a wave: the reads below see these writes
-        const uint8_t* kn = wkn[hw];
-        const float* tt = wt[hw];
-        const uint32_t* cc = wcol[hw];
-        const uint32_t out = telea_tile_estimate(kn, tt, cc, red[hw], dp, lane32, qv, qh, [&](float t) { if (lane32 == 0) a.T[e] = t; });
-        if (lane32 == 0) store_px_bytes(a.img + 3 * ib, (int)o, out);
-    }
-}
-
-// sr:807: only the key-coloured pixels take the inpainted value, black ones go back to black; then masked_blur.
-// Both in one pass: the 36 taps read the work image and zero it on the fly where the seed was black.
-struct BlurSrc { const uint8_t* ibase; const uint8_t* sbase; size_t img_pitch, seed_pitch; bool masked; };
-
-__device__ __forceinline__ uint32_t blur_px(const BlurSrc& b, int x, int y)
-{
-    uint32_t c = load_px_bytes(b.ibase + (size_t)y * b.img_pitch, x);
-    if (b.masked && load_px_bytes(b.sbase + (size_t)y * b.seed_pitch, x) == 0u) c = 0u;
-    return c;
-}
-
-// The 6 x 6 correlation around a non-black pixel (a black pixel stays black whatever surrounds it, sr:151).
-__device__ __forceinline__ uint32_t masked_blur_pixel(const BlurSrc& b, int x, int y, int W, int H, const BlurKernel& K)
-{
-    float acc[3] = {0.0f, 0.0f, 0.0f}, wsum = 0.0f;
-    uint32_t centre = 0;
-#pragma unroll
-    for (int ky = 0; ky < 6; ++ky) {
-        const int sy = y + ky - 3;
-        if (sy < 0 || sy >= H) continue;
-#pragma unroll
-        for (int kx = 0; kx < 6; ++kx) {
-            const int sx = x + kx - 3;
-            if (sx < 0 || sx >= W) continue;
-            const uint32_t px = blur_px(b, sx, sy);
-            const float k = K.k[6 * ky + kx];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) acc[c] = acc[c] + k * (float)((px >> (8 * c)) & 0xFF);
-            if (px) wsum = wsum + k;
-            if (ky == 3 && kx == 3) centre = px;
-        }
-    }
-    uint32_t o = 0;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        float v = (wsum == 0.0f || centre == 0u) ? 0.0f : acc[c] / wsum;
-        v = fminf(fmaxf(v, 0.0f), 255.0f);
-        o |= (uint32_t)v << (8 * c);
-    }
-    return o;
-}
-
-__device__ __forceinline__ BlurSrc blur_src(const ImageSet& imgs, const ImageSet& seeds, int im, uint32_t key_rgb)
-{
-    return BlurSrc{imgs.image(im), seeds.base ? seeds.image(im) : nullptr, imgs.pitch, seeds.pitch, seeds.base != nullptr && key_rgb != 0u};
-}
-
-__global__ void __launch_bounds__(256) k_masked_blur(ImageSet imgs, ImageSet seeds, ImageSet outs, int W, int H, BlurKernel K,
-                                                     uint32_t key_rgb)
-{
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, im = blockIdx.z;
-    if (x >= W) return;
-    const BlurSrc b = blur_src(imgs, seeds, im, key_rgb);
-    uint8_t* orow = outs.image(im) + (size_t)y * outs.pitch;
-    if (blur_px(b, x, y) == 0u) { store_px_bytes(orow, x, 0u); return; }
-    store_px_bytes(orow, x, masked_blur_pixel(b, x, y, W, H, K));
-}
-
-// The same in two passes, for images that are mostly black (an infill mask is: ~4 % of its pixels are not, in strips a few
-// pixels wide -- a wave of 64 consecutive pixels that meets one runs all 36 taps for a handful of lanes): the first pass
-// writes the black pixels and lists the columns of the others row by row (a counter per image row: one counter for the whole
-// pass serialised 3 * 10^5 atomics on one address, 1.2 ms), the second gives every lane of a row's wave a listed pixel.
-template <int PX>      // 4: rows addressable as dwords (12 bytes per lane), 1: any width / alignment
-__global__ void __launch_bounds__(128) k_masked_blur_scan(ImageSet imgs, ImageSet seeds, ImageSet outs, int W, int H, uint32_t key_rgb,
-                                                          uint32_t* __restrict__ list, uint32_t* __restrict__ row_count)
-{
-    const int g = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, im = blockIdx.z;
-    uint32_t c[PX];
-#pragma unroll
-    for (int q = 0; q < PX; ++q) c[q] = 0u;
-    const bool in = g * PX < W;
-    uint8_t* orow = outs.image(im) + (size_t)y * outs.pitch;
-    if (in) {
-        uint8_t* irow = imgs.image(im) + (size_t)y * imgs.pitch;
-        RowIO<PX>::load(irow, g, c);
-        if (seeds.base && key_rgb != 0u) {
-            uint32_t sd[PX];
-            RowIO<PX>::load(seeds.image(im) + (size_t)y * seeds.pitch, g, sd);
-#pragma unroll
-            for (int q = 0; q < PX; ++q)
-                if (sd[q] == 0u && c[q] != 0u) {           // an estimate nobody keeps (sr:807): black in the work image too, so that the
-                    c[q] = 0u;                              // second pass reads one image per tap instead of two
-                    store_px_bytes(irow, g * PX + q, 0u);
-                }
-        }
-        bool any = false;
-#pragma unroll
-        for (int q = 0; q < PX; ++q) any |= c[q] != 0u;
-        if (!any) { const uint32_t z[PX] = {}; RowIO<PX>::store_rgb(orow, g, z); }
-        else {
-#pragma unroll
-            for (int q = 0; q < PX; ++q) if (c[q] == 0u) store_px_bytes(orow, g * PX + q, 0u);
-        }
-    }
-    u64 m[PX];
-    uint32_t total = 0;
-#pragma unroll
-    for (int q = 0; q < PX; ++q) { m[q] = __ballot(c[q] != 0u); total += (uint32_t)__popcll(m[q]); }
-    if (total) {
-        const size_t row = (size_t)im * H + y;
-        const int lane = threadIdx.x & 63;
-        uint32_t base = 0;
-        if (lane == 0) base = atomicAdd(&row_count[row], total);
-        base = __shfl(base, 0);
-#pragma unroll
-        for (int q = 0; q < PX; ++q) {
-            if (c[q] != 0u) list[row * (size_t)W + base + (uint32_t)__popcll(m[q] & ((1ull << lane) - 1ull))] = (uint32_t)(g * PX + q);
-            base += (uint32_t)__popcll(m[q]);
-        }
-    }
-}
-
-__global__ void __launch_bounds__(64) k_masked_blur_list(ImageSet imgs, ImageSet seeds, ImageSet outs, int W, int H, BlurKernel K,
-                                                         uint32_t key_rgb, const uint32_t* __restrict__ list, const uint32_t* __restrict__ row_count)
-{
-    const int y = blockIdx.x, im = blockIdx.y;
-    const size_t row = (size_t)im * H + y;
-    const uint32_t n = row_count[row];
-    if (n == 0u) return;
-    const BlurSrc b{imgs.image(im), nullptr, imgs.pitch, 0, false};          // (the scan pass has merged the seed's black pixels into the work image)
-    uint8_t* orow = outs.image(im) + (size_t)y * outs.pitch;
-    for (uint32_t k = threadIdx.x; k < n; k += 64) {
-        const int x = (int)list[row * (size_t)W + k];
-        store_px_bytes(orow, x, masked_blur_pixel(b, x, y, W, H, K));
-    }
-}
-
-size_t telea_counter_words(int max_rounds) { return (2 + (size_t)kNcStride) * ((size_t)max_rounds + 2); }
-
-static TeleaArgs telea_args(const TeleaWorkspace& ws, int n, int W, int H, uint32_t key_rgb)
-{
-    return TeleaArgs{ws.stamp, ws.T, ws.img, ws.need, ws.nlist, ws.counts, ws.offs, ws.ncounts, ws.remaining, ws.last_round, W, H, n, key_rgb};
-}
-
-// Per-call part: reset the counters, copy the seeds into the work image, pass A (levels by distance transform, level
-// lists by counting sort).  h_levels (pinned host word) receives the deepest level any image needs -- the call waits for
-// it, once per pass, so that passes B and C can be launched for exactly the levels that exist.
-hipError_t launch_telea_init(const ImageSet& seed, const TeleaWorkspace& ws, int n, int W, int H, int max_rounds, uint32_t key_rgb,
-                             uint32_t* h_levels, hipStream_t s)
-{
-    const TeleaArgs a = telea_args(ws, n, W, H, key_rgb);
-    hipError_t e = hipMemsetAsync(ws.remaining, 0, (size_t)kTeleaMaxImages * sizeof(uint32_t), s);
-    if (e != hipSuccess) return e;
-    if ((e = hipMemsetAsync(ws.last_round, 0, (size_t)kTeleaMaxImages * sizeof(uint32_t), s)) != hipSuccess) return e;
-    e = hipMemsetAsync(ws.counts, 0, (2 + (size_t)kNcStride) * ((size_t)max_rounds + 2) * sizeof(uint32_t), s);      // counts, offs and ncounts (adjacent)
-    if (e != hipSuccess) return e;
-    if (W % 4 == 0 && (((uintptr_t)seed.base | seed.pitch | seed.stride | (size_t)seed.eye_offset) & 3) == 0)
-        hipLaunchKernelGGL(k_telea_init<4>, dim3((W / 4 + 127) / 128, H, n), dim3(128), 0, s, seed, a);
-    else
-        hipLaunchKernelGGL(k_telea_init<1>, dim3((W + 127) / 128, H, n), dim3(128), 0, s, seed, a);
-    if (W % 8 == 0 && W <= 2048) hipLaunchKernelGGL(k_telea_dt_rows_vec<1>, dim3(H, n), dim3(256), 0, s, ws.stamp, W, H);
-    else if (W % 8 == 0 && W <= 4096) hipLaunchKernelGGL(k_telea_dt_rows_vec<2>, dim3(H, n), dim3(256), 0, s, ws.stamp, W, H);
-    else hipLaunchKernelGGL(k_telea_dt_rows, dim3(H, n), dim3(256), 0, s, ws.stamp, W, H);
-    if (H <= 16 * 68) hipLaunchKernelGGL(k_telea_dt_cols_reg<68>, dim3((W + 63) / 64, n), dim3(1024), 0, s, a, (uint32_t)max_rounds);
-    else hipLaunchKernelGGL(k_telea_dt_cols, dim3((W + 63) / 64, n), dim3(1024), 0, s, a, (uint32_t)max_rounds);
-    hipLaunchKernelGGL(k_telea_rmax, dim3(1), dim3(1), 0, s, a);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    int R = max_rounds;
-    if (h_levels) {       // (NULL: the asynchronous form -- every level up to max_rounds gets its launches; the ones that do not exist have empty lists)
-        if ((e = hipMemcpyAsync(h_levels, ws.counts, sizeof(uint32_t), hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
-        if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
-        R = (int)*h_levels;
-        if (R == 0) return hipSuccess;
-    }
-    if ((e = hipMemsetAsync(ws.counts, 0, sizeof(uint32_t), s)) != hipSuccess) return e;         // counts[0] carried R; level 0 is empty
-    const dim3 grid_s((unsigned)(((W + kSortTile - 1) / kSortTile) * ((H + kSortTile - 1) / kSortTile)), n);
-    hipLaunchKernelGGL(k_telea_scan, dim3(1), dim3(1024), 0, s, a, R);
-    hipLaunchKernelGGL(k_telea_sort, grid_s, dim3(256), 0, s, a);
-    return hipGetLastError();
-}
-
-// Passes B and C: one launch per existing level each (a captured HIP graph replays them no faster: the ~4 us between
-// dependent kernels is the device's, not the host's; one cooperative launch with grid-wide barriers is 3 x slower).
-hipError_t launch_telea_rounds(const TeleaWorkspace& ws, int W, int H, int levels, uint32_t key_rgb, hipStream_t s)
-{
-    const TeleaArgs a = telea_args(ws, kTeleaMaxImages, W, H, key_rgb);
-    // both passes wait on memory, not on arithmetic (PMC: `need` spends 90 % of its wave cycles waiting): a grid large enough
-    // for one entry per thread takes 7.1 -> 5.8 ms off a 32-image pass compared with 512 workgroups looping
-    int nb = 2048;
-    if (const char* e = tuning_env(TUNE_TELEA_BLOCKS)) { const int v = atoi(e); if (v > 0) nb = (v + 7) & ~7; }      // tuning hook (a multiple of 8: XCDs)
-    const dim3 grid(nb), block(256);
-    for (int r = levels; r >= 2; --r) hipLaunchKernelGGL(k_telea_need, grid, block, 0, s, a, (uint32_t)r);
-    for (int r = 1; r <= levels; ++r) hipLaunchKernelGGL(k_telea_fill, dim3(4 * nb), block, 0, s, a, (uint32_t)r);
-    if (tuning_env(TUNE_TELEA_DUMP)) {         // tuning hook: level sizes / needed pixels of this pass on stderr
-        std::vector<uint32_t> c(levels + 2), nc((size_t)(levels + 2) * kNcStride);
-        hipError_t e = hipStreamSynchronize(s);
-        if (e == hipSuccess) e = hipMemcpy(c.data(), ws.counts, c.size() * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(nc.data(), ws.ncounts, nc.size() * 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) return e;
-        for (int r = 1; r <= levels; ++r) fprintf(stderr, "level %d count %u need %u\n", r, c[r], nc[(size_t)r * kNcStride]);
-    }
-    return hipGetLastError();
-}
-
-hipError_t launch_masked_blur(const ImageSet& img, const ImageSet* seed, const ImageSet& out, int n, int W, int H,
-                              const BlurKernel& K, uint32_t key_rgb, hipStream_t s, uint32_t* list, uint32_t* count)
-{
-    const dim3 grid((W + 255) / 256, H, n), block(256);
-    const ImageSet none{nullptr, 0, 0, 0, 1};
-    if (list && count && tuning_env(TUNE_BLUR_ONE_PASS) == nullptr) {          // list: n * W * H entries, count: n * H row counters
-        hipError_t e = hipMemsetAsync(count, 0, (size_t)n * H * sizeof(uint32_t), s);
-        if (e != hipSuccess) return e;
-        auto dwords = [](const ImageSet& i) { return !i.base || (((uintptr_t)i.base | i.pitch | i.stride | (size_t)i.eye_offset) & 3) == 0; };
-        if (W % 4 == 0 && dwords(img) && dwords(out) && (!seed || dwords(*seed)))
-            hipLaunchKernelGGL(k_masked_blur_scan<4>, dim3((W / 4 + 127) / 128, H, n), dim3(128), 0, s, img, seed ? *seed : none, out, W, H, key_rgb, list, count);
-        else
-            hipLaunchKernelGGL(k_masked_blur_scan<1>, dim3((W + 127) / 128, H, n), dim3(128), 0, s, img, seed ? *seed : none, out, W, H, key_rgb, list, count);
-        hipLaunchKernelGGL(k_masked_blur_list, dim3(H, n), dim3(64), 0, s, img, seed ? *seed : none, out, W, H, K, key_rgb, list, count);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(k_masked_blur, grid, block, 0, s, img, seed ? *seed : none, out, W, H, K, key_rgb);
-    return hipGetLastError();
-}
-
-// cv2.cvtColor(BGR2RGB / RGB2BGR) of interleaved u8 frames (sr:493, 505, 928, 941): bytes 0 and 2 of every pixel swap.
-template <int PX>
-__global__ void __launch_bounds__(256) k_swap_rb(ImageSet src, ImageSet dst, int W, int H)
-{
-    const int g = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, im = blockIdx.z;
-    if (g >= W / PX) return;
-    uint32_t px[PX];
-    RowIO<PX>::load_nt(src.image(im) + (size_t)y * src.pitch, g, px);
-#pragma unroll
-    for (int q = 0; q < PX; ++q) px[q] = (px[q] & 0x00FF00u) | ((px[q] >> 16) & 0xFFu) | ((px[q] & 0xFFu) << 16);
-    RowIO<PX>::store_rgb(dst.image(im) + (size_t)y * dst.pitch, g, px);
-}
-
-hipError_t launch_swap_rb(const ImageSet& src, const ImageSet& dst, int n, int W, int H, hipStream_t s)
-{
-    const bool vec4 = W % 4 == 0 && ((uintptr_t)src.base % 4 == 0) && ((uintptr_t)dst.base % 4 == 0) && src.pitch % 4 == 0 &&
-                      dst.pitch % 4 == 0 && src.stride % 4 == 0 && dst.stride % 4 == 0;
-    if (vec4) hipLaunchKernelGGL((k_swap_rb<4>), dim3((W / 4 + 255) / 256, H, n), dim3(256), 0, s, src, dst, W, H);
-    else hipLaunchKernelGGL((k_swap_rb<1>), dim3((W + 255) / 256, H, n), dim3(256), 0, s, src, dst, W, H);
-    return hipGetLastError();
-}
-
-#endif  // grid-independent sections
-
-namespace MDVT_GRID {
 // =================================================================================================
 // launch plumbing
 // =================================================================================================

@@ -1,5 +1,5 @@
 // mdvt_telea_common.h -- the parts of Telea's estimate (cv2.inpaint INPAINT_TELEA, radius 3) that the level-synchronous
-// completion (k_telea_fill, mdvt_kernels.hip) and the heap-order completion (k_telea_heap, mdvt_telea_heap.hip) share: the
+// completion (k_telea_fill, mdvt_telea_levels.hip) and the heap-order completion (k_telea_heap, mdvt_telea_heap.hip) share: the
 // quadrant solve of FastMarching_solve, the read set of an estimate, the disc with its distance factors and the estimate of
 // one pixel from its 9 x 9 neighbourhood in LDS.  One copy of the arithmetic, so that both orders are bit-exact against the
 // same oracle expressions (orc_telea_pixel).
