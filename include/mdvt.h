@@ -12,6 +12,8 @@
  *     passed as void*; NULL = the default stream).
  *   - every image pointer is DEVICE memory owned by the caller (e.g. torch.Tensor.data_ptr());
  *     the library never frees or retains it beyond the stream-ordered work of the call.
+ *   - pitches, strides and offsets (size_t, uint64_t) are honoured at their full 64-bit width -- rows, frames, packets and the
+ *     buffers of one call may lie more than 4 GiB apart -- except where an entry point names a limit.
  *   - calls are asynchronous w.r.t. the host on the given stream.
  *   - return 0 (MDVT_OK) or a negative mdvt_status; mdvt_last_error() gives the text.
  *   - one ctx per (device, stream) user; a ctx is not thread-safe, distinct ctxs are independent.  The entry points that use
