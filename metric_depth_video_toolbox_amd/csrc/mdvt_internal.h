@@ -1,5 +1,5 @@
-// mdvt_internal.h -- shared between the C-ABI host code (mdvt_api.hip) and the kernel
-// translation units (the other *.hip).  Not part of the public interface (that is include/mdvt.h).
+// mdvt_internal.h -- shared between the C-ABI host code (mdvt_context.hip, mdvt_api_render.hip, mdvt_api.hip; what only they
+// share is mdvt_context.h) and the kernel translation units (the other *.hip).  Not part of the public interface (that is include/mdvt.h).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -32,7 +32,7 @@ constexpr float kNear = 1e-4f;
 // Rasteriser sub-pixel grid (GL_SUBPIXEL_BITS) and the clamp applied before snapping (DESIGN.md "Arithmetic decree").
 // The rasterising translation units are compiled once per supported grid (Makefile): 8 bits, what desktop GPUs report
 // and the default of mdvt_config.subpixel_bits, and 4 bits, the grid of the GL the fixtures of tests/golden/render_gl_*.npz
-// were rendered with.  Everything they define lives in namespace mdvt::MDVT_GRID; mdvt_api.hip picks per context.
+// were rendered with.  Everything they define lives in namespace mdvt::MDVT_GRID; the host code picks per context (MDVT_GRID_CALL).
 #ifndef MDVT_SUBPIX_BITS
 #define MDVT_SUBPIX_BITS 8
 #endif

@@ -90,7 +90,7 @@ __global__ void __launch_bounds__(kMsaaTPB) k_msaa_raster(const MsaaArgs a)
         const int py0 = max(0, floordiv_subpix(t.minY) - 1), py1 = min(H - 1, floordiv_subpix(t.maxY) + 1);
         if (px0 > px1 || py0 > py1) continue;
         const float ra = rcp_exact((float)t.area2);
-        const bool whole = (px1 - px0 + 1) * (py1 - py0 + 1) <= kMsaaSmallBox;      // (W H < 2^31: mdvt_api.hip)
+        const bool whole = (px1 - px0 + 1) * (py1 - py0 + 1) <= kMsaaSmallBox;      // (W H < 2^31: mdvt_api_render.hip)
         for (int py = py0; py <= py1; ++py) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) {

@@ -1,5 +1,5 @@
 // mdvt_workspace.h -- the layout of the render workspace (general path / edge filter), stated once for ensure_workspace, bind_workspace
-// and mdvt_debug_read (mdvt_api.hip) and launch_mesh_raster_general.  Plain C++17 without HIP: tests/workspace_layout_host.cpp checks it.
+// and mdvt_debug_read (mdvt_api_render.hip) and launch_mesh_raster_general.  Plain C++17 without HIP: tests/workspace_layout_host.cpp checks it.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
