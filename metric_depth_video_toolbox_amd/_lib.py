@@ -35,6 +35,9 @@ DECODE_SYMBOLS = ("mdvt_decode_video_frames", "mdvt_ffv1_decode_supported")
 # the entry point include/mdvt_convergence.h declares (per-frame convergence depths), listed apart from mdvt.h's in the same way
 CONVERGENCE_SYMBOLS = ("mdvt_convergence_depths",)
 
+# the entry points include/mdvt_metric_align.h declares (relative depth to metric depth codes), listed apart in the same way
+METRIC_ALIGN_SYMBOLS = ("mdvt_scale_shift_fit", "mdvt_metric_depth_codes")
+
 
 class MdvtError(RuntimeError):
     def __init__(self, code: int, text: str):
@@ -164,6 +167,12 @@ def load():
     L.mdvt_convergence_depths.restype = C.c_int
     L.mdvt_convergence_depths.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t, C.c_size_t, C.c_int, vp, C.c_size_t, C.c_size_t, C.c_int,
                                          C.c_int, C.c_int, C.c_double, vp, vp, vp]
+    L.mdvt_scale_shift_fit.restype = C.c_int
+    L.mdvt_scale_shift_fit.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_int,
+                                       vp, C.c_size_t, C.c_size_t, vp, vp]
+    L.mdvt_metric_depth_codes.restype = C.c_int
+    L.mdvt_metric_depth_codes.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, C.c_size_t, vp, C.c_int, C.c_double, C.c_int, C.c_int,
+                                          vp, C.c_size_t, C.c_size_t, C.c_int, vp, C.c_size_t, C.c_size_t, vp]
     _libs[variant] = L
     return L
 

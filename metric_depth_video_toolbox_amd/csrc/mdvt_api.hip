@@ -1,10 +1,11 @@
 // mdvt_api.hip -- the entry points of the C ABI of include/mdvt.h beside the render (mdvt_api_render.hip) and the context
-// (mdvt_context.hip): formats, equirect, blur, the infills, both infill-mask completions, FFV1 in both directions, convergence depths.
+// (mdvt_context.hip): formats, equirect, blur, the infills, both infill-mask completions, FFV1 in both directions, convergence depths, the metric alignment.
 // Host code only; the kernels are in the other *.hip units.
 #include "mdvt_context.h"
 #include "mdvt_ffv1_core.h"
 #include "mdvt_ffv1_decode.h"
 #include "mdvt_convergence.h"
+#include "mdvt_metric_align.h"
 
 #include <math.h>
 
@@ -583,5 +584,95 @@ int mdvt_convergence_depths(mdvt_ctx* c, int width, int height, const uint8_t* d
     return MDVT_OK;
 }
 
-}  // extern "C"
+// The scale-and-shift fit (mdvt_metric_align.hip).  Launch sets of kFitSetChunks chunks; the totals travel in the scratch block.
+int mdvt_scale_shift_fit(mdvt_ctx* c, int width, int height, int n_frames, const float* d_pred, size_t pred_pitch, size_t pred_stride,
+                         const float* d_target, size_t target_pitch, size_t target_stride, int target_is_depth,
+                         const uint8_t* d_mask, size_t mask_pitch, size_t mask_stride, float* d_out, void* stream)
+{
+    if (!c) return MDVT_ERR_INVALID_ARG;
+    if (!d_pred || !d_target || !d_out) return fail(c, MDVT_ERR_INVALID_ARG, "NULL buffer");
+    if (width < 1 || height < 1) return fail(c, MDVT_ERR_INVALID_ARG, "bad plane size %d x %d", width, height);
+    if (n_frames < 1) return fail(c, MDVT_ERR_INVALID_ARG, "n_frames must be >= 1");
+    if (target_is_depth != 0 && target_is_depth != 1) return fail(c, MDVT_ERR_INVALID_ARG, "target_is_depth must be 0 or 1, got %d", target_is_depth);
+    if (pred_pitch < (size_t)width * 4u || target_pitch < (size_t)width * 4u) return fail(c, MDVT_ERR_INVALID_ARG, "pitch smaller than one row");
+    if (d_mask && mask_pitch < (size_t)width) return fail(c, MDVT_ERR_INVALID_ARG, "mask_pitch smaller than one row");
+    if (n_frames > 1 && (pred_stride < pred_pitch * (size_t)height || target_stride < target_pitch * (size_t)height ||
+                         (d_mask && mask_stride < mask_pitch * (size_t)height)))
+        return fail(c, MDVT_ERR_INVALID_ARG, "stride smaller than one plane");
+    const uint64_t n64 = (uint64_t)n_frames * (uint64_t)width * (uint64_t)height;
+    if (n64 >= ((uint64_t)1 << 31)) return fail(c, MDVT_ERR_UNSUPPORTED, "too many values for one fit (%d x %d x %d)", n_frames, width, height);
+    DeviceGuard g(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    const uint32_t n = (uint32_t)n64, nchunks = (n + 8191u) / 8192u;
+    const uint32_t set = nchunks < mdvt::kFitSetChunks ? nchunks : mdvt::kFitSetChunks;
+    // 32 B of running totals, then the [5][set] chunk sums of a launch set
+    const size_t need = 32 + (size_t)5 * set * sizeof(float);
+    MDVT_HIP(c, scratch_reserve(c, c->scratch[SCR_FIT], need, s));
+    auto plane = [&](const void* p, size_t pitch, size_t stride, size_t size) {
+        mdvt::FitPlane pl{};
+        pl.p = static_cast<const uint8_t*>(p); pl.pitch = pitch; pl.stride = n_frames > 1 ? stride : 0; pl.n = n;
+        const size_t align = 4 * size;                           // four values
+        const bool dense = pitch == (size_t)width * size && (n_frames == 1 || stride == pitch * (size_t)height);
+        pl.W = dense ? n : (uint32_t)width;
+        pl.HW = dense ? n : (uint32_t)width * (uint32_t)height;
+        pl.vec = (uintptr_t)p % align == 0 && (dense || (width % 4 == 0 && pitch % align == 0 && (n_frames == 1 || stride % align == 0)));
+        return pl;
+    };
+    mdvt::FitArgs a{};
+    a.pred = plane(d_pred, pred_pitch, pred_stride, 4);
+    a.target = plane(d_target, target_pitch, target_stride, 4);
+    if (d_mask) a.mask = plane(d_mask, mask_pitch, mask_stride, 1);
+    a.target_is_depth = target_is_depth; a.n = n;
+    a.state = c->scratch[SCR_FIT].as<float>(); a.sums = a.state + 8; a.sums_stride = set; a.out = d_out;
+    for (uint32_t c0 = 0; c0 < nchunks; c0 += mdvt::kFitSetChunks) {
+        a.chunk0 = c0;
+        a.nchunks_set = nchunks - c0 < mdvt::kFitSetChunks ? nchunks - c0 : mdvt::kFitSetChunks;
+        a.first_set = c0 == 0; a.last_set = c0 + a.nchunks_set == nchunks;
+        MDVT_HIP(c, mdvt::launch_scale_shift_fit(a, s));
+    }
+    return MDVT_OK;
+}
 
+// Relative planes to metric depth codes (mdvt_metric_align.hip).
+int mdvt_metric_depth_codes(mdvt_ctx* c, int in_w, int in_h, int n_frames, const float* d_rel, size_t rel_pitch, size_t rel_stride,
+                            const float* d_scale_shift, int style, double max_depth, int out_w, int out_h,
+                            uint8_t* d_codes, size_t codes_pitch, size_t codes_stride, int order,
+                            float* d_depth, size_t depth_pitch, size_t depth_stride, void* stream)
+{
+    if (!c) return MDVT_ERR_INVALID_ARG;
+    if (!d_rel || !d_scale_shift || !d_codes) return fail(c, MDVT_ERR_INVALID_ARG, "NULL buffer");
+    if (in_w < 1 || in_h < 1 || out_w < 1 || out_h < 1) return fail(c, MDVT_ERR_INVALID_ARG, "bad size %d x %d -> %d x %d", in_w, in_h, out_w, out_h);
+    if (n_frames < 1) return fail(c, MDVT_ERR_INVALID_ARG, "n_frames must be >= 1");
+    if (style != 0 && style != 1) return fail(c, MDVT_ERR_INVALID_ARG, "style must be 0 or 1, got %d", style);
+    if (order != 0 && order != 1) return fail(c, MDVT_ERR_INVALID_ARG, "order must be 0 (RGB) or 1 (BGR), got %d", order);
+    if (!(max_depth > 0.0)) return fail(c, MDVT_ERR_INVALID_ARG, "max_depth must be > 0");
+    if (rel_pitch < (size_t)in_w * 4u) return fail(c, MDVT_ERR_INVALID_ARG, "rel_pitch smaller than one row");
+    if (codes_pitch < (size_t)out_w * 3u) return fail(c, MDVT_ERR_INVALID_ARG, "codes_pitch smaller than one row");
+    if (d_depth && depth_pitch < (size_t)out_w * 4u) return fail(c, MDVT_ERR_INVALID_ARG, "depth_pitch smaller than one row");
+    if (n_frames > 1 && (rel_stride < rel_pitch * (size_t)in_h || codes_stride < codes_pitch * (size_t)out_h ||
+                         (d_depth && depth_stride < depth_pitch * (size_t)out_h)))
+        return fail(c, MDVT_ERR_INVALID_ARG, "stride smaller than one frame");
+    if ((uint64_t)out_w * (uint64_t)out_h >= ((uint64_t)1 << 31))
+        return fail(c, MDVT_ERR_UNSUPPORTED, "output frame too large (%d x %d)", out_w, out_h);
+    DeviceGuard g(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (n_frames == 1) rel_stride = codes_stride = depth_stride = 0;
+    mdvt::MetricCodesArgs a{};
+    a.rel = reinterpret_cast<const uint8_t*>(d_rel); a.rel_pitch = rel_pitch; a.rel_stride = rel_stride; a.in_w = in_w; a.in_h = in_h;
+    a.rel_vec = (uintptr_t)d_rel % 16 == 0 && rel_pitch % 16 == 0 && rel_stride % 16 == 0;
+    a.scale_shift = d_scale_shift; a.style = style; a.fmax = (float)max_depth; a.multi = 4228250625.0 / max_depth;
+    a.out_w = out_w; a.out_h = out_h; a.resize = in_w != out_w || in_h != out_h;
+    a.ratio_x = (double)in_w / (double)out_w; a.ratio_y = (double)in_h / (double)out_h;
+    a.codes = d_codes; a.codes_pitch = codes_pitch; a.codes_stride = codes_stride; a.bgr = order;
+    a.codes_vec = (uintptr_t)d_codes % 4 == 0 && codes_pitch % 4 == 0 && codes_stride % 4 == 0;
+    a.depth = reinterpret_cast<uint8_t*>(d_depth); a.depth_pitch = depth_pitch; a.depth_stride = depth_stride;
+    a.depth_vec = d_depth && (uintptr_t)d_depth % 16 == 0 && depth_pitch % 16 == 0 && depth_stride % 16 == 0;
+    a.gw = ((uint32_t)out_w + 3u) / 4u; a.groups = a.gw * (uint32_t)out_h;
+    for (int f0 = 0; f0 < n_frames; f0 += 32768) {               // (the grid's second dimension holds the frames)
+        a.frame0 = f0;
+        MDVT_HIP(c, mdvt::launch_metric_codes(a, n_frames - f0 < 32768 ? n_frames - f0 : 32768, s));
+    }
+    return MDVT_OK;
+}
+
+}  // extern "C"

@@ -51,6 +51,7 @@ enum ScratchId {
     SCR_FFV1,                         // mdvt_encode_video_frames: the running packet offset, then per slice of a pass its size word and scratch
     SCR_FFV1_DEC,                     // mdvt_decode_video_frames: per slice of a pass its offset, payload bytes and cell claim
     SCR_CONV,                         // mdvt_convergence_depths: per frame of a launch set its chunk sums; with a mask also the ballot words, codes and unit counts
+    SCR_FIT,                          // mdvt_scale_shift_fit: the running totals (32 B), then per chunk of a launch set its five sums
     SCR_COUNT
 };
 

@@ -25,12 +25,13 @@
 //                   thread 0, summed by a thread each, combined by thread 0)
 //   k_conv_mean     one wave per frame: the chunk sums in order, the division, the NaN of an empty selection, the count
 #include "mdvt_internal.h"
+#include "mdvt_pairwise.h"
 
 namespace mdvt {
 namespace {
 
-constexpr int kChunk = 8192;          // NumPy's ufunc buffer, in elements
-constexpr int kLeaf = 128;            // the pairwise routine's block
+using pairwise::kChunk;               // NumPy's ufunc buffer, in elements
+using pairwise::kLeaf;                // the pairwise routine's block
 constexpr int kUnit = 2048;           // pixels a wave selects / compacts
 constexpr int kGroup = 256;           // pixels of one step of a wave: four per lane
 
@@ -169,34 +170,11 @@ struct Staged {
     }
 };
 
-// NumPy's pairwise routine for n <= 128 values from i0 on
-__device__ float leaf_sum(const Staged& v, int i0, int n)
-{
-    if (n < 8) {
-        float r = 0.f;
-        for (int i = 0; i < n; ++i) r += v(i0 + i);
-        return r;
-    }
-    float r[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) r[k] = v(i0 + k);
-    int i = 8;
-    for (; i < n - (n % 8); i += 8) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) r[k] += v(i0 + i + k);
-    }
-    float res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; ++i) res += v(i0 + i);
-    return res;
-}
-
 __global__ void __launch_bounds__(kReduceThreads) k_conv_reduce(ConvergenceArgs a)
 {
     __shared__ uint32_t s_code[kChunk / 2 + kLeafPad * (kChunk / kLeaf)];
-    __shared__ float s_leaf_sum[128], s_val[16];
-    __shared__ uint16_t s_leaf_at[128], s_leaf_n[128], s_at[16], s_n[16];
-    __shared__ uint8_t s_leaf_depth[128], s_depth[16];
-    __shared__ int s_leaves;
+    __shared__ pairwise::Shape s_shape;
+    __shared__ float s_val[4];
     const int tid = (int)threadIdx.x;
     const uint32_t c = blockIdx.x;
     const int f = (int)blockIdx.y;
@@ -253,44 +231,12 @@ __global__ void __launch_bounds__(kReduceThreads) k_conv_reduce(ConvergenceArgs 
         if (tid == 0) a.sums[(size_t)f * a.nchunks + c] = (s_val[0] + s_val[1]) + (s_val[2] + s_val[3]);
         return;
     }
-    // the general shape.  Thread 0 lists the leaves left to right with their depths (a stack of at most 8 pending right halves) ...
-    if (tid == 0) {
-        int sp = 0, nl = 0;
-        s_at[0] = 0; s_n[0] = (uint16_t)n; s_depth[0] = 0; sp = 1;
-        while (sp > 0) {
-            --sp;
-            const int at = s_at[sp], m = s_n[sp], d = s_depth[sp];
-            if (m <= kLeaf) {
-                s_leaf_at[nl] = (uint16_t)at; s_leaf_n[nl] = (uint16_t)m; s_leaf_depth[nl] = (uint8_t)d;
-                ++nl;
-            } else {
-                int m2 = m / 2;
-                m2 -= m2 % 8;
-                s_at[sp] = (uint16_t)(at + m2); s_n[sp] = (uint16_t)(m - m2); s_depth[sp] = (uint8_t)(d + 1);
-                s_at[sp + 1] = (uint16_t)at; s_n[sp + 1] = (uint16_t)m2; s_depth[sp + 1] = (uint8_t)(d + 1);
-                sp += 2;
-            }
-        }
-        s_leaves = nl;                                           // at most 128: a leaf of a split node holds at least 64 values
-    }
+    // the general shape (mdvt_pairwise.h): thread 0 lists the leaves, a thread each sums them, thread 0 joins them
+    if (tid == 0) pairwise::shape_list(s_shape, n);
     __syncthreads();
-    // ... a thread each sums them ...
-    if (tid < s_leaves) s_leaf_sum[tid] = leaf_sum(v, s_leaf_at[tid], s_leaf_n[tid]);
+    pairwise::shape_leaves(s_shape, v, tid);
     __syncthreads();
-    // ... and thread 0 joins neighbours of equal depth, which is the tree: every inner node has two children
-    if (tid == 0) {
-        int sp = 0;
-        for (int j = 0; j < s_leaves; ++j) {
-            s_val[sp] = s_leaf_sum[j]; s_depth[sp] = s_leaf_depth[j];
-            ++sp;
-            while (sp >= 2 && s_depth[sp - 1] == s_depth[sp - 2]) {
-                s_val[sp - 2] = s_val[sp - 2] + s_val[sp - 1];
-                --s_depth[sp - 2];
-                --sp;
-            }
-        }
-        a.sums[(size_t)f * a.nchunks + c] = s_val[0];
-    }
+    if (tid == 0) a.sums[(size_t)f * a.nchunks + c] = pairwise::shape_join(s_shape);
 }
 
 __global__ void __launch_bounds__(64) k_conv_mean(ConvergenceArgs a)

@@ -278,6 +278,33 @@ struct ConvergenceArgs {
     float* means; uint32_t* counts;                                // the caller's, at the set's first frame; counts may be null
 };
 hipError_t launch_convergence(const ConvergenceArgs& a, hipStream_t s);
+// mdvt_metric_align.hip: the scale-and-shift fit and the metric depth codes (include/mdvt_metric_align.h)
+constexpr uint32_t kFitSetChunks = 1024;                           // chunks of 8192 elements per launch set of the fit
+struct FitPlane {
+    const uint8_t* p; size_t pitch, stride;                        // the first plane; bytes between rows and between planes
+    uint32_t W, HW, n;                                             // values per row and per plane, and in all; W = HW = n where nothing is padded (one long row)
+    int vec;                                                       // four values from a multiple of 4 on are one aligned 16-byte (mask: 4-byte) load
+};
+struct FitArgs {
+    FitPlane pred, target, mask;                                   // mask.p null: none
+    int target_is_depth;
+    uint32_t n, chunk0, nchunks_set;                               // elements in all; the set's first chunk and its chunks (<= kFitSetChunks)
+    int first_set, last_set;
+    float* sums; uint32_t sums_stride;                             // workspace [5][sums_stride]: the chunk sums of a set, sum by sum
+    float* state;                                                  // workspace [5]: the totals up to this set
+    float* out;                                                    // the caller's 8 floats
+};
+hipError_t launch_scale_shift_fit(const FitArgs& a, hipStream_t s);
+struct MetricCodesArgs {
+    const uint8_t* rel; size_t rel_pitch, rel_stride; int in_w, in_h, rel_vec;
+    const float* scale_shift; int style; float fmax; double multi; // float(max_depth), 255^4 / max_depth
+    int out_w, out_h, resize; double ratio_x, ratio_y;             // in / out per axis
+    uint8_t* codes; size_t codes_pitch, codes_stride; int bgr, codes_vec;
+    uint8_t* depth; size_t depth_pitch, depth_stride; int depth_vec;          // null: no depth planes
+    uint32_t gw, groups;                                           // groups of four pixels per output row and per image
+    int frame0;                                                    // the launch's first frame
+};
+hipError_t launch_metric_codes(const MetricCodesArgs& a, int n_frames, hipStream_t s);
 hipError_t launch_selftest(int which, unsigned long long seed, unsigned long long* d_mism, hipStream_t s);
 hipError_t launch_coherence_test(uint32_t* blk, size_t dwords, uint32_t tag, uint32_t* d_xcc, uint32_t* d_out, hipStream_t s);     // (mdvt_selftest.hip; r05 diagnosis)
 
