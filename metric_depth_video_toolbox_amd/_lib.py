@@ -38,6 +38,9 @@ CONVERGENCE_SYMBOLS = ("mdvt_convergence_depths",)
 # the entry points include/mdvt_metric_align.h declares (relative depth to metric depth codes), listed apart in the same way
 METRIC_ALIGN_SYMBOLS = ("mdvt_scale_shift_fit", "mdvt_metric_depth_codes")
 
+# the entry points include/mdvt_infill_adapter.h declares (the frames around an in-painting model), listed apart in the same way
+INFILL_ADAPTER_SYMBOLS = ("mdvt_adapter_prepare_eye", "mdvt_lhm_moments", "mdvt_lhm_apply", "mdvt_adapter_composite_eye")
+
 
 class MdvtError(RuntimeError):
     def __init__(self, code: int, text: str):
@@ -173,6 +176,16 @@ def load():
     L.mdvt_metric_depth_codes.restype = C.c_int
     L.mdvt_metric_depth_codes.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, C.c_size_t, vp, C.c_int, C.c_double, C.c_int, C.c_int,
                                           vp, C.c_size_t, C.c_size_t, C.c_int, vp, C.c_size_t, C.c_size_t, vp]
+    st = C.c_size_t
+    L.mdvt_adapter_prepare_eye.restype = C.c_int
+    L.mdvt_adapter_prepare_eye.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, st, st, vp, st, st, C.c_int, C.c_int, vp, st, st, vp, st, st, vp, vp]
+    L.mdvt_lhm_moments.restype = C.c_int
+    L.mdvt_lhm_moments.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, st, st, vp, st, st, vp, vp]
+    L.mdvt_lhm_apply.restype = C.c_int
+    L.mdvt_lhm_apply.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, st, st, vp, vp, st, st, vp]
+    L.mdvt_adapter_composite_eye.restype = C.c_int
+    L.mdvt_adapter_composite_eye.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, st, st, vp, st, st, vp, st, st,
+                                             vp, st, st, vp, st, st, vp]
     _libs[variant] = L
     return L
 

@@ -1,11 +1,12 @@
 // mdvt_api.hip -- the entry points of the C ABI of include/mdvt.h beside the render (mdvt_api_render.hip) and the context
-// (mdvt_context.hip): formats, equirect, blur, the infills, both infill-mask completions, FFV1 in both directions, convergence depths, the metric alignment.
+// (mdvt_context.hip): formats, equirect, blur, the infills, both infill-mask completions, FFV1 in both directions, convergence depths, the metric alignment, the infill adapter.
 // Host code only; the kernels are in the other *.hip units.
 #include "mdvt_context.h"
 #include "mdvt_ffv1_core.h"
 #include "mdvt_ffv1_decode.h"
 #include "mdvt_convergence.h"
 #include "mdvt_metric_align.h"
+#include "mdvt_infill_adapter.h"
 
 #include <math.h>
 
@@ -671,6 +672,177 @@ int mdvt_metric_depth_codes(mdvt_ctx* c, int in_w, int in_h, int n_frames, const
     for (int f0 = 0; f0 < n_frames; f0 += 32768) {               // (the grid's second dimension holds the frames)
         a.frame0 = f0;
         MDVT_HIP(c, mdvt::launch_metric_codes(a, n_frames - f0 < 32768 ? n_frames - f0 : 32768, s));
+    }
+    return MDVT_OK;
+}
+
+}  // extern "C"
+
+// ---- the infill adapter (mdvt_infill_adapter.hip; include/mdvt_infill_adapter.h) ----
+
+namespace {
+
+// cv2.getGaussianKernel(15, 0) as the header restates it: sigma = 0.3 * ((15 - 1) * 0.5 - 1) + 0.8 = 2.6; exp in f64, the weights added
+// from the first on, scaled by 1 / sum, rounded once to f32
+mdvt::AdapterGauss adapter_gauss()
+{
+    double g[15], sum = 0.0;
+    const double sigma = 2.6, scale2 = -0.5 / (sigma * sigma);
+    for (int i = 0; i < 15; ++i) { const double x = (double)(i - 7); g[i] = exp(scale2 * x * x); sum += g[i]; }
+    sum = 1.0 / sum;
+    mdvt::AdapterGauss K;
+    for (int i = 0; i < 15; ++i) K.w[i] = (float)(g[i] * sum);
+    return K;
+}
+
+// What the two calls on side-by-side frames refuse: the layouts of the colour and mask frames (width 2 * ew) and the sizes.
+int check_adapter_sbs(mdvt_ctx* c, int ew, int eh, int n, int eye, const void* d_color, size_t color_pitch, size_t color_stride,
+                      const void* d_mask, size_t mask_pitch, size_t mask_stride, int mw, int mh)
+{
+    if (!d_color || !d_mask) return fail(c, MDVT_ERR_INVALID_ARG, "NULL buffer");
+    if (ew < 1 || eh < 1 || mw < 1 || mh < 1) return fail(c, MDVT_ERR_INVALID_ARG, "bad size: eye %d x %d, model %d x %d", ew, eh, mw, mh);
+    if (n < 1) return fail(c, MDVT_ERR_INVALID_ARG, "n_frames must be >= 1");
+    if (eye != 0 && eye != 1) return fail(c, MDVT_ERR_INVALID_ARG, "eye must be 0 (left) or 1 (right), got %d", eye);
+    if (color_pitch < (size_t)6 * ew || mask_pitch < (size_t)6 * ew) return fail(c, MDVT_ERR_INVALID_ARG, "pitch smaller than one side-by-side row");
+    if (n > 1 && (color_stride < color_pitch * (size_t)eh || mask_stride < mask_pitch * (size_t)eh))
+        return fail(c, MDVT_ERR_INVALID_ARG, "stride smaller than one frame");
+    return MDVT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mdvt_adapter_prepare_eye(mdvt_ctx* c, int eye_w, int eye_h, int n_frames, int eye,
+                             const uint8_t* d_color, size_t color_pitch, size_t color_stride,
+                             const uint8_t* d_mask, size_t mask_pitch, size_t mask_stride, int model_w, int model_h,
+                             uint8_t* d_image, size_t image_pitch, size_t image_stride,
+                             uint8_t* d_model_mask, size_t model_mask_pitch, size_t model_mask_stride, uint32_t* d_hole_counts, void* stream)
+{
+    if (!c) return MDVT_ERR_INVALID_ARG;
+    if (!d_image || !d_model_mask || !d_hole_counts) return fail(c, MDVT_ERR_INVALID_ARG, "NULL buffer");
+    if (const int rc = check_adapter_sbs(c, eye_w, eye_h, n_frames, eye, d_color, color_pitch, color_stride, d_mask, mask_pitch, mask_stride, model_w, model_h)) return rc;
+    if (image_pitch < (size_t)3 * model_w || model_mask_pitch < (size_t)model_w) return fail(c, MDVT_ERR_INVALID_ARG, "pitch smaller than one model row");
+    if (n_frames > 1 && (image_stride < image_pitch * (size_t)model_h || model_mask_stride < model_mask_pitch * (size_t)model_h))
+        return fail(c, MDVT_ERR_INVALID_ARG, "stride smaller than one model frame");
+    if ((uintptr_t)d_hole_counts % 4) return fail(c, MDVT_ERR_INVALID_ARG, "d_hole_counts must be 4-byte aligned");
+    if (model_h > 65535) return fail(c, MDVT_ERR_UNSUPPORTED, "model frame too tall (%d rows)", model_h);
+    DeviceGuard g(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (n_frames == 1) color_stride = mask_stride = image_stride = model_mask_stride = 0;
+    MDVT_HIP(c, hipMemsetAsync(d_hole_counts, 0, (size_t)n_frames * sizeof(uint32_t), s));
+    mdvt::AdapterPrepareArgs a{};
+    a.mirror = eye == 0;
+    a.rs = mdvt::adapter_resize(eye_w, eye_h, model_w, model_h);
+    a.image_pitch = image_pitch; a.image_stride = image_stride; a.mmask_pitch = model_mask_pitch; a.mmask_stride = model_mask_stride;
+    for (int f0 = 0; f0 < n_frames; f0 += 32768) {               // (the grid's third dimension holds the frames)
+        a.color = {d_color + (size_t)eye * 3 * eye_w + (size_t)f0 * color_stride, color_pitch, color_stride};
+        a.mask = {d_mask + (size_t)eye * 3 * eye_w + (size_t)f0 * mask_stride, mask_pitch, mask_stride};
+        a.image = d_image + (size_t)f0 * image_stride; a.mmask = d_model_mask + (size_t)f0 * model_mask_stride; a.holes = d_hole_counts + f0;
+        MDVT_HIP(c, mdvt::launch_adapter_prepare(a, n_frames - f0 < 32768 ? n_frames - f0 : 32768, s));
+    }
+    return MDVT_OK;
+}
+
+int mdvt_lhm_moments(mdvt_ctx* c, int width, int height, int n_frames, const uint8_t* d_rgb, size_t pitch, size_t stride,
+                     const uint8_t* d_mask, size_t mask_pitch, size_t mask_stride, uint64_t* d_out, void* stream)
+{
+    if (!c) return MDVT_ERR_INVALID_ARG;
+    if (!d_rgb || !d_out) return fail(c, MDVT_ERR_INVALID_ARG, "NULL buffer");
+    if (width < 1 || height < 1) return fail(c, MDVT_ERR_INVALID_ARG, "bad frame size %d x %d", width, height);
+    if (n_frames < 1) return fail(c, MDVT_ERR_INVALID_ARG, "n_frames must be >= 1");
+    if (pitch < (size_t)3 * width || (d_mask && mask_pitch < (size_t)width)) return fail(c, MDVT_ERR_INVALID_ARG, "pitch smaller than one row");
+    if (n_frames > 1 && (stride < pitch * (size_t)height || (d_mask && mask_stride < mask_pitch * (size_t)height)))
+        return fail(c, MDVT_ERR_INVALID_ARG, "stride smaller than one frame");
+    if ((uintptr_t)d_out % 8) return fail(c, MDVT_ERR_INVALID_ARG, "d_out must be 8-byte aligned");
+    DeviceGuard g(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (n_frames == 1) stride = mask_stride = 0;
+    MDVT_HIP(c, hipMemsetAsync(d_out, 0, (size_t)n_frames * 10 * sizeof(uint64_t), s));
+    mdvt::LhmMomentsArgs a{};
+    a.W = width; a.H = height;
+    const size_t one_row = height == 1 ? 0 : ~(size_t)0;           // (the pitch of a single row is never used)
+    a.vec = (((uintptr_t)d_rgb | (pitch & one_row) | stride) & 3) == 0 && (!d_mask || (((uintptr_t)d_mask | (mask_pitch & one_row) | mask_stride) & 3) == 0);
+    for (int f0 = 0; f0 < n_frames; f0 += 32768) {
+        a.img = {d_rgb + (size_t)f0 * stride, pitch, stride};
+        a.mask = {d_mask ? d_mask + (size_t)f0 * mask_stride : nullptr, mask_pitch, mask_stride};
+        a.out = reinterpret_cast<unsigned long long*>(d_out) + (size_t)f0 * 10;
+        MDVT_HIP(c, mdvt::launch_lhm_moments(a, n_frames - f0 < 32768 ? n_frames - f0 : 32768, s));
+    }
+    return MDVT_OK;
+}
+
+int mdvt_lhm_apply(mdvt_ctx* c, int width, int height, int n_frames, const uint8_t* d_rgb, size_t pitch, size_t stride,
+                   const double* d_params, uint8_t* d_out, size_t out_pitch, size_t out_stride, void* stream)
+{
+    if (!c) return MDVT_ERR_INVALID_ARG;
+    if (!d_rgb || !d_params || !d_out) return fail(c, MDVT_ERR_INVALID_ARG, "NULL buffer");
+    if (width < 1 || height < 1) return fail(c, MDVT_ERR_INVALID_ARG, "bad frame size %d x %d", width, height);
+    if (n_frames < 1) return fail(c, MDVT_ERR_INVALID_ARG, "n_frames must be >= 1");
+    if (pitch < (size_t)3 * width || out_pitch < (size_t)3 * width) return fail(c, MDVT_ERR_INVALID_ARG, "pitch smaller than one row");
+    if (n_frames > 1 && (stride < pitch * (size_t)height || out_stride < out_pitch * (size_t)height))
+        return fail(c, MDVT_ERR_INVALID_ARG, "stride smaller than one frame");
+    if ((uintptr_t)d_params % 8) return fail(c, MDVT_ERR_INVALID_ARG, "d_params must be 8-byte aligned");
+    if (height > 65535) return fail(c, MDVT_ERR_UNSUPPORTED, "frame too tall (%d rows)", height);
+    DeviceGuard g(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (n_frames == 1) stride = out_stride = 0;
+    mdvt::LhmApplyArgs a{};
+    a.W = width; a.H = height; a.out_pitch = out_pitch; a.out_stride = out_stride;
+    const size_t one_row = height == 1 ? 0 : ~(size_t)0;           // (the pitch of a single row is never used)
+    a.vec = (((uintptr_t)d_rgb | (pitch & one_row) | stride | (uintptr_t)d_out | (out_pitch & one_row) | out_stride) & 3) == 0;
+    for (int f0 = 0; f0 < n_frames; f0 += 32768) {
+        a.img = {d_rgb + (size_t)f0 * stride, pitch, stride};
+        a.params = d_params + (size_t)f0 * 15; a.out = d_out + (size_t)f0 * out_stride;
+        MDVT_HIP(c, mdvt::launch_lhm_apply(a, n_frames - f0 < 32768 ? n_frames - f0 : 32768, s));
+    }
+    return MDVT_OK;
+}
+
+int mdvt_adapter_composite_eye(mdvt_ctx* c, int eye_w, int eye_h, int n_frames, int eye,
+                               const uint8_t* d_model, int model_w, int model_h, size_t model_pitch, size_t model_stride,
+                               const uint8_t* d_color, size_t color_pitch, size_t color_stride,
+                               const uint8_t* d_mask, size_t mask_pitch, size_t mask_stride,
+                               uint8_t* d_pasted, size_t pasted_pitch, size_t pasted_stride,
+                               uint8_t* d_blended, size_t blended_pitch, size_t blended_stride, void* stream)
+{
+    if (!c) return MDVT_ERR_INVALID_ARG;
+    if (!d_model || !d_pasted || !d_blended) return fail(c, MDVT_ERR_INVALID_ARG, "NULL buffer");
+    if (const int rc = check_adapter_sbs(c, eye_w, eye_h, n_frames, eye, d_color, color_pitch, color_stride, d_mask, mask_pitch, mask_stride, model_w, model_h)) return rc;
+    if (model_pitch < (size_t)3 * model_w) return fail(c, MDVT_ERR_INVALID_ARG, "pitch smaller than one model row");
+    if (pasted_pitch < (size_t)6 * eye_w || blended_pitch < (size_t)6 * eye_w) return fail(c, MDVT_ERR_INVALID_ARG, "pitch smaller than one side-by-side row");
+    if (n_frames > 1 && (model_stride < model_pitch * (size_t)model_h || pasted_stride < pasted_pitch * (size_t)eye_h || blended_stride < blended_pitch * (size_t)eye_h))
+        return fail(c, MDVT_ERR_INVALID_ARG, "stride smaller than one frame");
+    if (eye_w < 8 || eye_h < 8) return fail(c, MDVT_ERR_UNSUPPORTED, "eye of %d x %d: the 15-tap Gaussian's reflection needs 8 x 8", eye_w, eye_h);
+    if (eye_h > 65535) return fail(c, MDVT_ERR_UNSUPPORTED, "eye too tall (%d rows)", eye_h);
+    if (mask_pitch >= (1u << 24) || (unsigned long long)mask_pitch * eye_h > 0xFFFFFFFFull)
+        return fail(c, MDVT_ERR_UNSUPPORTED, "mask frame too large for the march's 32-bit offsets (pitch %zu, %d rows)", mask_pitch, eye_h);
+    DeviceGuard g(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    // one frame at a time through: the listed-pixel workspace of the march | the row-blurred plane (f32) | the marks image | the grown plane
+    const size_t npx = (size_t)eye_w * eye_h;
+    const size_t ni = (mdvt::normal_infill_workspace_bytes(1, eye_w, eye_h) + 255) & ~(size_t)255;
+    MDVT_HIP(c, scratch_reserve(c, c->scratch[SCR_ADAPTER], ni + 8 * npx, s));
+    uint8_t* const ws = c->scratch[SCR_ADAPTER].p;
+    float* const hblur = reinterpret_cast<float*>(ws + ni);
+    uint8_t* const marks = ws + ni + 4 * npx;
+    uint8_t* const grown = marks + 3 * npx;
+    mdvt::AdapterCompositeArgs a{};
+    a.mirror = eye == 0;
+    a.rs = mdvt::adapter_resize(model_w, model_h, eye_w, eye_h);
+    a.grown = grown; a.hblur = hblur; a.pasted_pitch = pasted_pitch; a.blended_pitch = blended_pitch;
+    a.g = adapter_gauss();
+    const size_t at = (size_t)eye * 3 * eye_w;
+    for (int f = 0; f < n_frames; ++f) {
+        const size_t k = n_frames > 1 ? (size_t)f : 0;
+        const uint8_t* mask = d_mask + k * mask_stride + at;
+        MDVT_HIP(c, launch_mark_lower_side(mask, mask_pitch, marks, (size_t)3 * eye_w, eye_w, eye_h, 30, ws, s));           // scr:172-175
+        MDVT_HIP(c, mdvt::launch_grow_marks(marks, (size_t)3 * eye_w, grown, eye_w, eye_h, s));                             // scr:177-178
+        a.model = {d_model + k * model_stride, model_pitch, 0};
+        a.color = {d_color + k * color_stride + at, color_pitch, 0};
+        a.mask = {mask, mask_pitch, 0};
+        a.pasted = d_pasted + k * pasted_stride + at; a.blended = d_blended + k * blended_stride + at;
+        MDVT_HIP(c, mdvt::launch_adapter_composite(a, s));
     }
     return MDVT_OK;
 }

@@ -305,6 +305,46 @@ struct MetricCodesArgs {
     int frame0;                                                    // the launch's first frame
 };
 hipError_t launch_metric_codes(const MetricCodesArgs& a, int n_frames, hipStream_t s);
+// mdvt_normal_infill.hip: the six cross dilations of normal_infill (bni:112) on their own.  marks: an image as mdvt_mark_lower_side
+// writes it ((0,0,255) at a mark); grown: H rows of W bytes without padding, zeroed here, 1 within L1 distance 6 of a mark.
+hipError_t launch_grow_marks(const uint8_t* marks, size_t marks_pitch, uint8_t* grown, int W, int H, hipStream_t s);
+// mdvt_infill_adapter.hip: the frame preparation, colour match and compositing around an in-painting model (include/mdvt_infill_adapter.h)
+struct AdapterImage { const uint8_t* p; size_t pitch, stride; };   // frame k at p + k * stride; u8 RGB rows unless said otherwise
+struct AdapterResize { int in_w, in_h, out_w, out_h, mode; double rx, ry; };     // mode 0 copy, 1 the 2 x 2 area mean, 2 linear; rx, ry = in / out
+AdapterResize adapter_resize(int in_w, int in_h, int out_w, int out_h);
+struct AdapterPrepareArgs {
+    AdapterImage color, mask;                                      // the eye's half of the side-by-side frames (p at the eye's first column)
+    int mirror;                                                    // the eye is read right to left
+    AdapterResize rs;                                              // eye -> model
+    uint8_t* image; size_t image_pitch, image_stride;              // the model's image
+    uint8_t* mmask; size_t mmask_pitch, mmask_stride;              // the model's mask, one byte per pixel
+    uint32_t* holes;                                               // [n], zeroed before the launch
+};
+hipError_t launch_adapter_prepare(const AdapterPrepareArgs& a, int n, hipStream_t s);
+constexpr uint32_t kMomentsWiden = 65536;                          // pixels a lane may sum in 32 bits: 65536 * 255 * 255 < 2^32
+struct LhmMomentsArgs {
+    AdapterImage img, mask;                                        // mask.p null: every pixel counts; else one byte per pixel, 0 = counts
+    int W, H, vec;                                                 // vec: four pixels are three aligned dwords (mask: one)
+    unsigned long long* out;                                       // [n][10], zeroed before the launch
+};
+hipError_t launch_lhm_moments(const LhmMomentsArgs& a, int n, hipStream_t s);
+struct LhmApplyArgs {
+    AdapterImage img; int W, H, vec;
+    const double* params;                                          // [n][15]: A row-major, mu_x, mu_r
+    uint8_t* out; size_t out_pitch, out_stride;
+};
+hipError_t launch_lhm_apply(const LhmApplyArgs& a, int n, hipStream_t s);
+struct AdapterGauss { float w[15]; };                              // cv2.getGaussianKernel(15, 0) rounded to f32 (built on the host in f64)
+struct AdapterCompositeArgs {
+    AdapterImage model; int mirror; AdapterResize rs;              // one model frame -> eye
+    AdapterImage color, mask;                                      // the eye's half of one side-by-side frame
+    const uint8_t* grown;                                          // [eh][ew] 0 / 1
+    float* hblur;                                                  // [eh][ew] the horizontal pass
+    uint8_t* pasted; size_t pasted_pitch;                          // the eye's half of the two outputs
+    uint8_t* blended; size_t blended_pitch;
+    AdapterGauss g;
+};
+hipError_t launch_adapter_composite(const AdapterCompositeArgs& a, hipStream_t s);
 hipError_t launch_selftest(int which, unsigned long long seed, unsigned long long* d_mism, hipStream_t s);
 hipError_t launch_coherence_test(uint32_t* blk, size_t dwords, uint32_t tag, uint32_t* d_xcc, uint32_t* d_out, hipStream_t s);     // (mdvt_selftest.hip; r05 diagnosis)
 

@@ -299,10 +299,8 @@ __device__ __forceinline__ void ni_stage_requests_and_marks(const NiArgs& a, int
 }
 
 // STAGE 5, a mark: its diamond of L1 radius 6 = six passes of the 4-neighbour cross (bni:112)
-__device__ __forceinline__ void ni_stage_grow(const NiArgs& a, int im, int mx, int my)
+__device__ __forceinline__ void ni_grow_diamond(uint8_t* g, int W, int H, int mx, int my)
 {
-    const int W = a.W, H = a.H;
-    uint8_t* g = a.grown + (size_t)im * H * W;
     for (int ey = -kGrowR; ey <= kGrowR; ++ey) {
         const int yy = my + ey;
         if (yy < 0 || yy >= H) continue;
@@ -310,6 +308,12 @@ __device__ __forceinline__ void ni_stage_grow(const NiArgs& a, int im, int mx, i
         const int x0 = max(mx - r, 0), x1 = min(mx + r, W - 1);
         for (int xx = x0; xx <= x1; ++xx) g[(size_t)yy * W + xx] = 1;
     }
+}
+
+__device__ __forceinline__ void ni_stage_grow(const NiArgs& a, int im, int mx, int my)
+{
+    const int W = a.W, H = a.H;
+    ni_grow_diamond(a.grown + (size_t)im * H * W, W, H, mx, my);
     uint8_t* coarse = a.coarse + (size_t)(2 * im + 1) * a.tiles_x * a.tiles_y;  // the tiles under the diamond's bounding box
     const int tx0 = max(mx - kGrowR, 0) / kTileW, tx1 = min(mx + kGrowR, W - 1) / kTileW;
     const int ty0 = max(my - kGrowR, 0) / kTileH, ty1 = min(my + kGrowR, H - 1) / kTileH;
@@ -653,6 +657,14 @@ __global__ void __launch_bounds__(256) k_solo_run(SoloArgs a)
     }
 }
 
+// The marks of an image written by k_solo_run<1> grown by the six cross dilations of stage 5 (a thread per pixel; marks are few).
+__global__ void __launch_bounds__(256) k_grow_marks(const uint8_t* marks, size_t pitch, uint8_t* grown, int W, int H)
+{
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x >= W) return;
+    if (marks[(size_t)y * pitch + 3 * (size_t)x + 2] != 0) ni_grow_diamond(grown, W, H, x, y);
+}
+
 struct NiLayout { uint32_t cap_a, cap_b; int tiles_x, tiles_y; size_t ncoarse, bytes_lists, bytes_zero, bytes_total; };
 
 // cap_a covers both shapes of k_ni_prep (128 threads x 4 px or x 1 px per workgroup)
@@ -741,6 +753,14 @@ hipError_t launch_mark_lower_side(const uint8_t* img, size_t img_pitch, uint8_t*
     SoloArgs a{};
     a.src = img; a.src_pitch = img_pitch; a.out = out; a.out_pitch = out_pitch; a.W = W; a.H = H; a.max_steps = max_steps;
     return solo_launch(1, a, workspace, s);
+}
+
+hipError_t launch_grow_marks(const uint8_t* marks, size_t marks_pitch, uint8_t* grown, int W, int H, hipStream_t s)
+{
+    hipError_t e = hipMemsetAsync(grown, 0, (size_t)W * H, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_grow_marks, dim3((W + 255) / 256, H), dim3(256), 0, s, marks, marks_pitch, grown, W, H);
+    return hipGetLastError();
 }
 
 hipError_t launch_normal_infill(const ImageSet& img, const ImageSet& mask, const ImageSet& out, uint8_t* workspace, int n, int W, int H,

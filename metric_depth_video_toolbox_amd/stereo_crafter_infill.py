@@ -1,0 +1,423 @@
+"""Device-side mirror of the reference's stereo_crafter_infill.py ("scr"; movie_2_3D.py's default --infill_engine): the same
+names and argument meaning, on PyTorch-ROCm tensors through libmdvt_hip.so (include/mdvt_infill_adapter.h).  No CPU fallback.
+
+    transfer_lhm_video_refmask(video, reference, reference_mask)     infill_common.py:52-130, on device tensors
+    deal_with_frame_chunk(...)                                       scr:91-190, one chunk of side-by-side frames
+    process_pair(sbs_color, sbs_mask, generate)                      scr:192-274, on the clip driver's outputs
+    python -m metric_depth_video_toolbox_amd.stereo_crafter_infill --sbs_color_video X.mkv --sbs_mask_video Y.mkv
+
+The in-painting model is a callable, THE GENERATOR CONTRACT:
+
+    generate(frames, masks, fps) -> frames
+
+frames: uint8 CUDA tensor [T, 768, 1024, 3] (RGB; the left eye mirrored), masks: uint8 CUDA tensor [T, 768, 1024] (255 = fill here),
+fps: the clip's frame rate.  Returns a uint8 CUDA tensor of the shape of `frames`, produced on the current stream.  `--generator
+pkg.module:callable` names one; the default, `stereocrafter`, wraps StereoCrafter's pipeline with the reference's arguments
+(scr:57-82) and needs StereoCrafter, diffusers and transformers, none of which this project ships or tests against.
+
+Everything around the model runs on the device: the eyes are split, mirrored and resized (mdvt_adapter_prepare_eye), the model's
+colours matched to its input (mdvt_lhm_moments -> the float64 host algebra of lhm_params on 30 integers per frame -> mdvt_lhm_apply),
+the frames resized back, pasted under the mask and blended along the holes' lower side (mdvt_adapter_composite_eye).  The colour
+match follows the reference's single_precision=False; its default float32 path differs from that in a few per cent of the values by
+1 (include/mdvt_infill_adapter.h).
+
+The chunk schedule is the reference's (scr:218-266): 25 frames per chunk; after a chunk the buffer keeps six frames -- three pasted
+frames with their masks, then three untouched ones; a chunk writes from its index 3 unless it is the first and stops 3 short unless
+it is the last; the last call runs on whatever is buffered.  One difference, on purpose: the reference pairs the masks of the frames
+T-6 .. T-4 with the pasted frames T-9 .. T-7 (its list of written frames is three short, scr:148, 251-253); here the pasted frames
+T-6 .. T-4 go with their own masks.  Those three frames are context for the generator only and are never written again.
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import importlib
+import os
+
+import numpy as np
+
+from . import _lib
+from .basic_nomal_infill import _fetch, _is_txt, _video_parts, pairs_from_arguments
+
+MODEL_W, MODEL_H = 1024, 768              # scr:95-96
+FRAMES_CHUNK, OVERLAP = 25, 6             # scr:222, 250-257
+EPS = 1e-5                                # ic:57
+
+
+def _frames4(t, channels=3):
+    import torch
+    ok = t.is_cuda and t.dtype == torch.uint8 and t.dim() == 3 + (channels == 3) and t.stride(-1) == 1
+    if channels == 3:
+        ok = ok and t.shape[-1] == 3 and t.stride(-2) == 3
+    assert ok, f"uint8 CUDA [N,H,W{',3' if channels == 3 else ''}] with packed pixels expected"
+    return t
+
+
+def _stream(t):
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+
+
+def _context(t):
+    from .depth_frames_helper import _ctx
+    return _ctx(t.device.index or 0, 16, 16)
+
+
+def prepare_eye(sbs_color, sbs_mask, eye: int, model_size=(MODEL_W, MODEL_H)):
+    """scr:101-126 for one eye (0 = left, read mirrored; 1 = right) of uint8 CUDA [N,H,2W,3] colour and infill-mask frames ->
+    (image [N,mh,mw,3], mask [N,mh,mw], hole counts int32 [N]), all on the device."""
+    import torch
+    _frames4(sbs_color), _frames4(sbs_mask)
+    assert sbs_color.shape == sbs_mask.shape and sbs_color.shape[2] % 2 == 0
+    N, H, W2 = (int(v) for v in sbs_color.shape[:3])
+    mw, mh = model_size
+    image = torch.empty((N, mh, mw, 3), dtype=torch.uint8, device=sbs_color.device)
+    mask = torch.empty((N, mh, mw), dtype=torch.uint8, device=sbs_color.device)
+    counts = torch.empty((N,), dtype=torch.int32, device=sbs_color.device)
+    ctx = _context(sbs_color)
+    ctx.check(_lib.load().mdvt_adapter_prepare_eye(
+        ctx.handle, W2 // 2, H, N, int(eye), sbs_color.data_ptr(), sbs_color.stride(1), sbs_color.stride(0),
+        sbs_mask.data_ptr(), sbs_mask.stride(1), sbs_mask.stride(0), mw, mh, image.data_ptr(), image.stride(1), image.stride(0),
+        mask.data_ptr(), mask.stride(1), mask.stride(0), counts.data_ptr(), _stream(sbs_color)))
+    return image, mask, counts
+
+
+def lhm_moments(frames, mask=None, out=None):
+    """mdvt_lhm_moments: per frame of uint8 CUDA [N,H,W,3] the ten exact integer moments (count, sums, second moments) over the
+    pixels whose mask byte is 0 (all without a mask) -> int64 CUDA [N,10]."""
+    import torch
+    _frames4(frames)
+    N, H, W = (int(v) for v in frames.shape[:3])
+    if mask is not None:
+        _frames4(mask, 1)
+        assert tuple(mask.shape) == (N, H, W)
+    if out is None:
+        out = torch.empty((N, 10), dtype=torch.int64, device=frames.device)
+    assert out.is_contiguous() and out.dtype == torch.int64 and tuple(out.shape) == (N, 10)
+    ctx = _context(frames)
+    ctx.check(_lib.load().mdvt_lhm_moments(
+        ctx.handle, W, H, N, frames.data_ptr(), frames.stride(1), frames.stride(0),
+        mask.data_ptr() if mask is not None else None, mask.stride(1) if mask is not None else 0, mask.stride(0) if mask is not None else 0,
+        out.data_ptr(), _stream(frames)))
+    return out
+
+
+def _mean_cov(m):
+    """Ten integer moments -> (mu, cov + eps on the diagonal) in float64; the covariance's numerator is formed exactly in integers."""
+    n, s1 = int(m[0]), [int(v) for v in m[1:4]]
+    q = [int(v) for v in m[4:10]]
+    s2 = [[q[0], q[1], q[2]], [q[1], q[3], q[4]], [q[2], q[4], q[5]]]
+    mu = np.array(s1, dtype=np.float64) / n
+    den = float(n) * max(n - 1, 1)
+    cov = np.array([[float(n * s2[i][j] - s1[i] * s1[j]) / den for j in range(3)] for i in range(3)], dtype=np.float64)
+    cov = 0.5 * (cov + cov.T)
+    cov[np.arange(3), np.arange(3)] += EPS
+    return mu, cov
+
+
+def lhm_params(mom_x, mom_r, mom_r_all):
+    """The host algebra of the colour match (ic:100-125), float64, per frame: the moments of the video frame, of the reference's
+    kept pixels and of all the reference's pixels (used where fewer than 3 are kept, ic:113-114) -> [N,15] float64: A row-major,
+    mu_x, mu_r."""
+    out = np.empty((len(mom_x), 15), dtype=np.float64)
+    for k in range(len(mom_x)):
+        mu_x, cov_x = _mean_cov(mom_x[k])
+        eval_x, evec_x = np.linalg.eigh(cov_x)
+        invsqrt_x = (evec_x * (1.0 / np.sqrt(np.clip(eval_x, EPS, None)))) @ evec_x.T
+        mu_r, cov_r = _mean_cov(mom_r[k] if int(mom_r[k][0]) >= 3 else mom_r_all[k])
+        eval_r, evec_r = np.linalg.eigh(cov_r)
+        sqrt_r = (evec_r * np.sqrt(np.clip(eval_r, 0, None))) @ evec_r.T
+        out[k, :9] = (sqrt_r @ invsqrt_x).reshape(9)
+        out[k, 9:12] = mu_x
+        out[k, 12:] = mu_r
+    return out
+
+
+def lhm_apply(frames, params, out=None):
+    """mdvt_lhm_apply: uint8 CUDA [N,H,W,3] and float64 CUDA [N,15] -> the matched frames."""
+    import torch
+    _frames4(frames)
+    N, H, W = (int(v) for v in frames.shape[:3])
+    assert params.is_cuda and params.dtype == torch.float64 and tuple(params.shape) == (N, 15) and params.is_contiguous()
+    if out is None:
+        out = torch.empty((N, H, W, 3), dtype=torch.uint8, device=frames.device)
+    _frames4(out)
+    ctx = _context(frames)
+    ctx.check(_lib.load().mdvt_lhm_apply(ctx.handle, W, H, N, frames.data_ptr(), frames.stride(1), frames.stride(0), params.data_ptr(),
+                                         out.data_ptr(), out.stride(1), out.stride(0), _stream(frames)))
+    return out
+
+
+def transfer_lhm_video_refmask(video, reference, reference_mask=None):
+    """infill_common.transfer_lhm_video_refmask (ic:52-130) with single_precision=False, on uint8 CUDA tensors: video [T,H,W,3],
+    reference [H,W,3] or [T,H,W,3], reference_mask None, [H,W] or [T,H,W] (0 = the pixel counts).  One small read-back (the
+    3 x T x 10 moments) per call."""
+    import torch
+    assert video.dim() == 4, "video must be (T,H,W,C)"
+    T = int(video.shape[0])
+    if reference.dim() == 3:
+        reference = reference.unsqueeze(0).expand(T, -1, -1, -1).contiguous()
+    assert reference.shape == video.shape, "reference must be (H,W,C) or (T,H,W,C) of the video's size"
+    mom = torch.empty((3, T, 10), dtype=torch.int64, device=video.device)
+    lhm_moments(video, None, out=mom[0])
+    lhm_moments(reference, None, out=mom[2])
+    if reference_mask is None:
+        mom[1].copy_(mom[2])
+    else:
+        if reference_mask.dim() == 2:
+            reference_mask = reference_mask.unsqueeze(0).expand(T, -1, -1).contiguous()
+        lhm_moments(reference, reference_mask, out=mom[1])
+    m = mom.cpu().numpy()
+    params = torch.from_numpy(lhm_params(m[0], m[1], m[2])).to(video.device)
+    return lhm_apply(video, params)
+
+
+def composite_eye(model_frames, sbs_color, sbs_mask, eye: int, pasted, blended):
+    """scr:151-188 for one eye: the model's frames (uint8 CUDA [N,mh,mw,3]) resized back, pasted under the mask into that eye's half
+    of `pasted` and blended along the holes' lower side into that eye's half of `blended` (both uint8 CUDA [N,H,2W,3])."""
+    for t in (model_frames, sbs_color, sbs_mask, pasted, blended):
+        _frames4(t)
+    N, H, W2 = (int(v) for v in sbs_color.shape[:3])
+    assert sbs_mask.shape == sbs_color.shape == pasted.shape == blended.shape and int(model_frames.shape[0]) == N
+    ctx = _context(sbs_color)
+    ctx.check(_lib.load().mdvt_adapter_composite_eye(
+        ctx.handle, W2 // 2, H, N, int(eye), model_frames.data_ptr(), int(model_frames.shape[2]), int(model_frames.shape[1]),
+        model_frames.stride(1), model_frames.stride(0), sbs_color.data_ptr(), sbs_color.stride(1), sbs_color.stride(0),
+        sbs_mask.data_ptr(), sbs_mask.stride(1), sbs_mask.stride(0), pasted.data_ptr(), pasted.stride(1), pasted.stride(0),
+        blended.data_ptr(), blended.stride(1), blended.stride(0), _stream(sbs_color)))
+
+
+def deal_with_frame_chunk(keep_first_three: bool, color, mask, keep_last_three: bool, fps: float, generate, model_size=(MODEL_W, MODEL_H)):
+    """scr:91-190 on a chunk of uint8 CUDA [T,H,2W,3] colour and mask frames.  Returns (first, pasted, blended): the chunk's index of
+    the first frame it writes and the pasted and blended frames from there to the last one it writes (scr:147-148)."""
+    import torch
+    T = int(color.shape[0])
+    start = 0 if keep_first_three else 3
+    end = T if keep_last_three else T - 3
+    n = max(end - start, 0)
+    pasted = torch.empty((n,) + tuple(color.shape[1:]), dtype=torch.uint8, device=color.device)
+    blended = torch.empty_like(pasted)
+    for eye in (0, 1):                                             # scr:133-145: the left eye first
+        image, mmask, counts = prepare_eye(color, mask, eye, model_size)
+        if int(counts.sum().item()) == 0:                          # scr:134, 141
+            frames = image
+        else:
+            frames = generate(image, mmask, fps)
+            if not (torch.is_tensor(frames) and frames.is_cuda and frames.dtype == torch.uint8 and frames.shape == image.shape):
+                raise TypeError(f"the generator must return a uint8 CUDA tensor of shape {tuple(image.shape)}")
+            frames = transfer_lhm_video_refmask(frames.contiguous(), image, mmask)
+        if n:
+            composite_eye(frames[start:end], color[start:end], mask[start:end], eye, pasted, blended)
+    return start, pasted, blended
+
+
+def chunk_schedule(n_frames: int):
+    """The calls of scr:218-266 for a clip of n_frames: [(first, last, frame of the buffer's index 0, buffered frames, (a, b))], where
+    [a, b) are the clip's frames the call writes."""
+    if n_frames < 1:
+        raise ValueError("a clip needs at least one frame")
+    calls, first, base, held = [], True, 0, 0
+    for t in range(n_frames):
+        held += 1
+        if held >= FRAMES_CHUNK:
+            start = 0 if first else 3
+            calls.append((first, False, base, held, (base + start, base + held - 3)))
+            first, base, held = False, base + held - OVERLAP, OVERLAP
+    start = 0 if first else 3
+    calls.append((first, True, base, held, (base + start, base + held)))
+    return calls
+
+
+def process_pair(sbs_color_video_path: str, sbs_mask_video_path: str, generate, max_frames: int = -1, batch: int = 8, device=None, *,
+                 video_decoder: str = "host", video_encoder: str = "host", model_size=(MODEL_W, MODEL_H)):
+    """scr:192-274.  `.mkv` inputs give `<sbs_color>_infilled.mkv` at the colour video's frame rate, frame dumps (`.npy`, uint8
+    [N,H,2W,3]) give `<sbs_color>_infilled.npy`; either is written under its `_tmp_infilled` name and renamed once every frame is in.
+    A mask clip shorter than the colour clip means black masks for the rest (scr:234-237).  Returns the output path."""
+    import torch
+    from .clip import VideoSink, check_video_decoder, check_video_encoder, open_output, verify_and_move
+    if not (os.path.isfile(sbs_color_video_path) or os.path.isfile(sbs_color_video_path + ".index.json")):
+        raise Exception(f"input sbs_color_video does not exist: {sbs_color_video_path}")
+    if not (os.path.isfile(sbs_mask_video_path) or os.path.isfile(sbs_mask_video_path + ".index.json")):
+        raise Exception(f"input sbs_mask_video does not exist: {sbs_mask_video_path}")
+    color = open_output(sbs_color_video_path)
+    mask = open_output(sbs_mask_video_path)
+    video = bool(_video_parts(color))
+    check_video_decoder(video_decoder, video)
+    check_video_encoder(video_encoder, video)
+    try:
+        assert color.ndim == 4 and color.shape[-1] == 3 and color.dtype == np.uint8, "uint8 [N, H, 2W, 3] expected"
+        assert color.shape[1:] == mask.shape[1:], "mask and color video not same resolution"      # scr:210
+        if color.shape[2] % 2:
+            raise ValueError(f"side-by-side frames need an even width, got {color.shape[2]}")
+        if max_frames == 0:
+            raise ValueError("max_frames = 0: ask for -1 (all) or a positive count")
+        n = color.shape[0] if max_frames == -1 else min(color.shape[0], max_frames)
+        if n < 1:
+            raise ValueError(f"{sbs_color_video_path} has no frames")
+    except Exception:
+        for frames in (color, mask):
+            for p, _ in _video_parts(frames):
+                p.close()
+        raise
+    batch = max(1, int(batch))
+    ext = ".mkv" if video else ".npy"
+    tmp, final = sbs_color_video_path + "_tmp_infilled" + ext, sbs_color_video_path + "_infilled" + ext      # scr:213-214
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    H, W2 = int(color.shape[1]), int(color.shape[2])
+    ctx, fps = None, 30.0
+    if video:
+        fps = _video_parts(color)[0][0].fps or 30.0
+        out = VideoSink(tmp, W2, H, fps, encoder=video_encoder)
+        if video_decoder == "device" or video_encoder == "device":
+            ctx = _lib.Context(dev.index, 16, 16)
+        if video_decoder == "device":
+            for name, frames in (("sbs_color_video", color), ("sbs_mask_video", mask)):
+                for p, _ in _video_parts(frames):
+                    p.use_device_decoder(name)
+    else:
+        out = np.lib.format.open_memmap(tmp, mode="w+", dtype=np.uint8, shape=(n, H, W2, 3))
+    dec_ctx = ctx if video_decoder == "device" else None
+
+    def store(d_out, a):
+        if not video:
+            out[a:a + len(d_out)] = d_out.cpu().numpy()
+        elif video_encoder == "device":
+            out.append_packets(out.enqueue(ctx, d_out), a)
+        else:
+            out.write_from(d_out.cpu().numpy(), a, len(d_out))
+
+    try:
+        with torch.cuda.device(dev):
+            buf_c = torch.empty((FRAMES_CHUNK, H, W2, 3), dtype=torch.uint8, device=dev)
+            buf_m = torch.zeros_like(buf_c)
+            read = 0
+            for first, last, base, held, (wa, wb) in chunk_schedule(n):
+                have = read - base                                 # the overlap is in the buffer already
+                while have < held:
+                    k = min(batch, held - have)
+                    buf_c[have:have + k] = _fetch(color, read, read + k, dev, dec_ctx)
+                    got = max(0, min(read + k, mask.shape[0]) - read)
+                    if got:
+                        buf_m[have:have + got] = _fetch(mask, read, read + got, dev, dec_ctx)
+                    buf_m[have + got:have + k] = 0                 # scr:234-237
+                    have += k
+                    read += k
+                start, pasted, blended = deal_with_frame_chunk(first, buf_c[:held], buf_m[:held], last, fps, generate, model_size)
+                assert base + start == wa and len(blended) == wb - wa
+                if wb > wa:
+                    store(blended, wa)
+                if not last:                                       # scr:250-257
+                    keep_c = torch.cat([pasted[held - OVERLAP - start:held - 3 - start], buf_c[held - 3:held]])
+                    keep_m = buf_m[held - OVERLAP:held].clone()
+                    buf_c[:OVERLAP], buf_m[:OVERLAP] = keep_c, keep_m
+        if video:
+            out.close()
+        else:
+            out.flush()
+    finally:
+        if ctx is not None:
+            ctx.close()
+        for frames in (color, mask):
+            for p, _ in _video_parts(frames):
+                p.close()
+    del out
+    verify_and_move(tmp, n, final)
+    return final
+
+
+class StereoCrafterGenerator:
+    """The default generator: StereoCrafter's in-painting pipeline with the reference's arguments (scr:57-82, 291-325).  Needs the
+    StereoCrafter checkout, diffusers and transformers and their weights; UNTESTED here (none of them is available to this project)."""
+
+    def __init__(self, num_inference_steps: int = 5, img2vid_path: str = "weights/stable-video-diffusion-img2vid-xt-1-1",
+                 unet_path: str = "StereoCrafter/weights/StereoCrafter"):
+        try:
+            import torch
+            from diffusers import AutoencoderKLTemporalDecoder, UNetSpatioTemporalConditionModel
+            from transformers import CLIPVisionModelWithProjection
+            from StereoCrafter.pipelines.stereo_video_inpainting import StableVideoDiffusionInpaintingPipeline, tensor2vid
+        except ImportError as e:
+            raise RuntimeError(f"the stereocrafter generator needs StereoCrafter, diffusers and transformers ({e}); "
+                               "install them or name another model with --generator pkg.module:callable") from None
+        half = dict(torch_dtype=torch.float16)
+        encoder = CLIPVisionModelWithProjection.from_pretrained(img2vid_path, subfolder="image_encoder", variant="fp16", **half)
+        vae = AutoencoderKLTemporalDecoder.from_pretrained(img2vid_path, subfolder="vae", variant="fp16", **half)
+        unet = UNetSpatioTemporalConditionModel.from_pretrained(unet_path, subfolder="unet_diffusers", low_cpu_mem_usage=True, **half)
+        for m in (encoder, vae, unet):
+            m.requires_grad_(False)
+        self.pipeline = StableVideoDiffusionInpaintingPipeline.from_pretrained(img2vid_path, image_encoder=encoder, vae=vae, unet=unet,
+                                                                              **half).to("cuda")
+        self.tensor2vid, self.steps = tensor2vid, int(num_inference_steps)
+
+    def __call__(self, frames, masks, fps):
+        import torch
+        x = frames.permute(0, 3, 1, 2).float() / 255.0
+        m = masks.float() / 255.0
+        latents = self.pipeline(frames=x, frames_mask=m, height=x.shape[2], width=x.shape[3], num_frames=len(x), output_type="latent",
+                                min_guidance_scale=1.01, max_guidance_scale=1.01, decode_chunk_size=8, fps=fps, motion_bucket_id=127,
+                                noise_aug_strength=0.0, num_inference_steps=self.steps).frames[0].unsqueeze(0)
+        decoded = self.pipeline.decode_latents(latents, num_frames=latents.shape[1], decode_chunk_size=2)
+        video = self.tensor2vid(decoded, self.pipeline.image_processor, output_type="np")[0]
+        return torch.from_numpy((video * 255).astype(np.uint8)).to(frames.device)
+
+
+def load_generator(spec: str, num_inference_steps: int = 5):
+    """`stereocrafter` (the default model) or `pkg.module:callable`."""
+    if spec == "stereocrafter":
+        return StereoCrafterGenerator(num_inference_steps)
+    mod, sep, name = spec.partition(":")
+    if not sep or not mod or not name:
+        raise ValueError(f"--generator must be 'stereocrafter' or 'pkg.module:callable', got {spec!r}")
+    fn = getattr(importlib.import_module(mod), name, None)
+    if not callable(fn):
+        raise ValueError(f"{spec}: {mod} has no callable {name!r}")
+    return fn
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description="StereoCrafter infill script (FFV1 .mkv videos, or frame dumps)")
+    p.add_argument("--sbs_color_video", type=str, required=True, help="side by side stereo video rendered with point clouds in the masked area (.mkv, or a .npy frame dump), or a .txt list of them")
+    p.add_argument("--sbs_mask_video", type=str, required=True, help="side by side stereo video mask, or the matching .txt list")
+    p.add_argument("--max_frames", default=-1, type=int, help="quit after max_frames nr of frames", required=False)
+    p.add_argument("--num_inference_steps", default=5, type=int, help="number of diffusion steps of the stereocrafter generator. More look better but is slower", required=False)
+    p.add_argument("--generator", default="stereocrafter", type=str,
+                   help="not a reference flag: the in-painting model, 'stereocrafter' (default) or pkg.module:callable with "
+                        "generate(frames, masks, fps) -> frames on uint8 CUDA tensors [T,768,1024,3] and [T,768,1024]")
+    p.add_argument("--batch", default=8, type=int, help="not a reference flag: frames per read from the input")
+    p.add_argument("--video_decoder", choices=("host", "device"), default="host",
+                   help="not a reference flag: where the .mkv inputs are FFV1-decoded -- 'host' (default) or 'device' (on the GPU, the same bytes). Not with .npy inputs")
+    p.add_argument("--video_encoder", choices=("host", "device"), default="host",
+                   help="not a reference flag: where the .mkv output is FFV1-encoded -- 'host' (default) or 'device' (on the GPU, the same bytes). Not with .npy inputs")
+    return p
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    if args.max_frames == 0:
+        raise SystemExit("--max_frames 0: ask for -1 (all) or a positive count")
+    pairs = pairs_from_arguments(args.sbs_color_video, args.sbs_mask_video)
+    for c_path, m_path in pairs:
+        for what, path in (("sbs_color_video", c_path), ("sbs_mask_video", m_path)):
+            if not _is_txt(args.sbs_color_video) and not (os.path.isfile(path) or os.path.isfile(path + ".index.json")):
+                raise SystemExit(f"input {what} does not exist: {path}")
+    try:
+        generate = load_generator(args.generator, args.num_inference_steps)
+    except (RuntimeError, ValueError, ImportError) as e:
+        raise SystemExit(str(e))
+    kw = dict(batch=args.batch, video_decoder=args.video_decoder, video_encoder=args.video_encoder)
+    if _is_txt(args.sbs_color_video):
+        # (the reference runs two clips at a time with the model serialised, scr:343-354; here the clips follow each other)
+        print(f"Batch mode: {len(pairs)} pairs")
+        for c_path, m_path in pairs:
+            try:
+                print("Done. Wrote:", process_pair(c_path, m_path, generate, args.max_frames, **kw))
+            except Exception as e:                                # scr:352-354: surface the error, keep the other clips going
+                print(f"[ERROR] A clip failed: {e}")
+        return 0
+    print("Done. Wrote:", process_pair(*pairs[0], generate, args.max_frames, **kw))
+    return 0
+
+
+if __name__ == "__main__":
+    import sys
+    sys.exit(main())
