@@ -220,6 +220,34 @@ def retry_after_release(alloc):
         return alloc()
 
 
+def device_index(dev) -> int:
+    """The GPU that `dev` (a torch.device, or an int already) names: `cuda` without an index is the current device, not GPU 0."""
+    if isinstance(dev, int):
+        return dev
+    import torch
+    return torch.cuda.current_device() if dev.index is None else dev.index
+
+
+def stream_arg(dev, stream=None):
+    """The void* of `stream`, or of the current stream of `dev`, as the library's entry points take it."""
+    import torch
+    return C.c_void_p((torch.cuda.current_stream(dev) if stream is None else stream).cuda_stream)
+
+
+_shared = {}
+
+
+def shared_context(device, W: int = 16, H: int = 16) -> "Context":
+    """The process-wide context of a GPU (a torch.device or an index) and render size, for the entry points that keep no state in
+    it (for most of them the size is irrelevant: 16 x 16).  A context belongs to the library that made it, so MDVT_LIB_VARIANT
+    is part of the key."""
+    key = (device_index(device), int(W), int(H), os.environ.get("MDVT_LIB_VARIANT", ""))
+    ctx = _shared.get(key)
+    if ctx is None:
+        ctx = _shared[key] = Context(*key[:3])
+    return ctx
+
+
 def exported_symbols():
     """Names from SYMBOLS that the loaded library actually exports (used by the CPU-only tests)."""
     L = load()
@@ -245,20 +273,24 @@ class Context:
         if rc != MDVT_OK:
             raise MdvtError(rc, (self._L.mdvt_last_error(self._h) or b"").decode())
 
+    def call(self, name: str, *args):
+        """`name`(this context, *args) of the library that made the context; a negative status raises MdvtError."""
+        self.check(getattr(self._L, name)(self._h, *args))
+
     def workspace_bytes(self) -> int:
         """Device memory the context owns right now (mdvt_workspace_bytes)."""
         n = C.c_uint64()
-        self.check(self._L.mdvt_workspace_bytes(self._h, C.byref(n)))
+        self.call("mdvt_workspace_bytes", C.byref(n))
         return int(n.value)
 
     def debug_read_queue_block(self):
         """(bytes of the general mesh path's queue block as a uint32 array, info[8]) -- tuning library only (mdvt_debug_read)."""
         import numpy as np
         info = (C.c_uint64 * 8)()
-        self.check(self._L.mdvt_debug_read(self._h, 0, None, 0, info))
+        self.call("mdvt_debug_read", 0, None, 0, info)
         buf = np.zeros(int(info[0]) // 4, dtype=np.uint32)
         if buf.size:
-            self.check(self._L.mdvt_debug_read(self._h, 0, buf.ctypes.data_as(C.c_void_p), buf.nbytes, info))
+            self.call("mdvt_debug_read", 0, buf.ctypes.data_as(C.c_void_p), buf.nbytes, info)
         return buf, [int(v) for v in info]
 
     def debug_coherence(self):
@@ -267,14 +299,14 @@ class Context:
         import numpy as np
         info = (C.c_uint64 * 8)()
         out = np.zeros(80, dtype=np.uint32)
-        self.check(self._L.mdvt_debug_read(self._h, 1, out.ctypes.data_as(C.c_void_p), out.nbytes, info))
+        self.call("mdvt_debug_read", 1, out.ctypes.data_as(C.c_void_p), out.nbytes, info)
         return out
 
     def debug_pools(self):
         """mdvt_debug_read(what = 2), tuning library: idle blocks of the two process-wide pools as this context's GPU sees them ->
         dict(param_mine, param_other, ws_mine, ws_other, tag)."""
         info = (C.c_uint64 * 8)()
-        self.check(self._L.mdvt_debug_read(self._h, 2, None, 0, info))
+        self.call("mdvt_debug_read", 2, None, 0, info)
         return dict(param_mine=int(info[0]), param_other=int(info[1]), ws_mine=int(info[2]), ws_other=int(info[3]), tag=int(info[4]))
 
     def close(self):

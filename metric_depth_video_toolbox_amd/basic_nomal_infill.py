@@ -10,17 +10,16 @@ files the clip driver writes (`<depth>_stereo.mkv`, `<depth>_stereo.mkv_infillma
 `<sbs_color>_infilled.mkv` (the reference appends `_infilled.mkv` to the colour video's full name, bni:141), optionally decoded
 and encoded on the GPU (--video_decoder / --video_encoder device).  With the `.npy` dumps the clip driver writes for `.npy`
 inputs (uint8 [N, H, 2W, 3], RGB order) the output is `<sbs_color>_infilled.npy`.  Either is written under its `_tmp_infilled`
-name and renamed once every frame is in (depth_frames_helper.verify_and_move, dfh:163-179).
+name and renamed once every frame is in (clip_io.verify_and_move, dfh:163-179).
 """
 from __future__ import annotations
 
 import argparse
-import ctypes as C
-import os
 
 import numpy as np
 
 from . import _lib
+from .clip_io import ClipInputs, ClipOutput, check_video_decoder, check_video_encoder, video_parts
 
 
 def _packed(t):
@@ -33,7 +32,6 @@ def normal_infill(img, infill_mask, out=None):
     holes filled.  Unlike the reference, `img` itself is left untouched (the reference blackens and refills it in place
     and returns a new array; its caller only uses the returned one, basic_nomal_infill.py:186)."""
     import torch
-    from .depth_frames_helper import _ctx
     for t in (img, infill_mask):
         assert t.is_cuda and t.dtype == torch.uint8 and t.dim() in (3, 4) and t.shape[-1] == 3 and _packed(t), \
             "uint8 CUDA [H,W,3] or [N,H,W,3] with packed RGB pixels"
@@ -44,12 +42,10 @@ def normal_infill(img, infill_mask, out=None):
     if out is None:
         out = torch.empty(tuple(img.shape), dtype=torch.uint8, device=img.device)
     assert out.shape == img.shape and out.is_cuda and out.dtype == torch.uint8 and _packed(out)
-    ctx = _ctx(img.device.index or 0, W, H)
-    s = torch.cuda.current_stream(img.device)
     stride = (lambda t: t.stride(0) if batched else 0)
-    ctx.check(_lib.load().mdvt_normal_infill(ctx.handle, img.data_ptr(), img.stride(-3), stride(img),
-                                             infill_mask.data_ptr(), infill_mask.stride(-3), stride(infill_mask),
-                                             out.data_ptr(), out.stride(-3), stride(out), N, C.c_void_p(s.cuda_stream)))
+    _lib.shared_context(img.device, W, H).call("mdvt_normal_infill", img.data_ptr(), img.stride(-3), stride(img),
+                                               infill_mask.data_ptr(), infill_mask.stride(-3), stride(infill_mask),
+                                               out.data_ptr(), out.stride(-3), stride(out), N, _lib.stream_arg(img.device))
     return out
 
 
@@ -65,108 +61,46 @@ def normal_infill_sbs(sbs, sbs_mask, out=None):
     return out
 
 
-def _video_parts(frames):
-    """[(VideoFrames, first frame)] of an opened output that is one video or per-rank video segments; [] for frame dumps."""
-    from .clip import SegmentedFrames, VideoFrames
-    if isinstance(frames, VideoFrames):
-        return [(frames, 0)]
-    if isinstance(frames, SegmentedFrames) and all(isinstance(p, VideoFrames) for p in frames.parts):
-        return list(zip(frames.parts, frames.bounds[:-1]))
-    return []
-
-
-def _fetch(frames, a: int, b: int, dev, dec_ctx):
-    """Frames [a, b) as a uint8 CUDA tensor.  Videos switched to the device decoder hand over their packets (decoded on the
-    device, straight into the tensor); everything else is read on the host and copied."""
-    import torch
-    parts = _video_parts(frames)
-    if dec_ctx is None or not parts or not all(p.device_decode for p, _ in parts):
-        return torch.from_numpy(np.array(frames[a:b])).to(dev)
-    from . import ffv1_device
-    H, W = int(frames.shape[1]), int(frames.shape[2])
-    out = torch.empty((b - a, H, W, 3), dtype=torch.uint8, device=dev)
-    for p, b0 in parts:
-        lo, hi = max(a, b0), min(b, b0 + len(p))
-        if lo < hi:
-            ffv1_device.enqueue_decode(dec_ctx, p.read_packets(lo - b0, hi - lo), p.config, W, H, out=out[lo - a:hi - a]).collect()
-    return out
-
-
 def process_pair(sbs_color_video_path: str, sbs_mask_video_path: str, max_frames: int = -1, batch: int = 8, device=None, *,
                  video_decoder: str = "host", video_encoder: str = "host"):
     """basic_nomal_infill.process_pair (basic_nomal_infill.py:124-236).  `.mkv` inputs (the reference's format: `<x>_stereo.mkv`
     and `<x>_stereo.mkv_infillmask.mkv`, bni:129-145) give `<sbs_color>_infilled.mkv` at the colour video's frame rate, frame
     dumps give `<sbs_color>_infilled.npy`; either is written under its `_tmp_infilled` name and renamed once every frame is in.
     A mask clip shorter than the colour clip means "no holes" for the remaining frames (basic_nomal_infill.py:165-167).
-    video_decoder / video_encoder: "host" (default) or "device" for .mkv files (the same bytes; clip.check_video_decoder /
+    video_decoder / video_encoder: "host" (default) or "device" for .mkv files (the same bytes; clip_io.check_video_decoder /
     check_video_encoder refuse "device" for frame dumps).  Returns the output path."""
     import torch
-    from .clip import VideoSink, check_video_decoder, check_video_encoder, open_output, verify_and_move
-    # (a clip rendered by several ranks exists as per-rank segments + index: open_output reads either form)
-    if not (os.path.isfile(sbs_color_video_path) or os.path.isfile(sbs_color_video_path + ".index.json")):
-        raise Exception(f"input sbs_color_video does not exist: {sbs_color_video_path}")
-    if not (os.path.isfile(sbs_mask_video_path) or os.path.isfile(sbs_mask_video_path + ".index.json")):
-        raise Exception(f"input sbs_mask_video does not exist: {sbs_mask_video_path}")
-    color = open_output(sbs_color_video_path)
-    mask = open_output(sbs_mask_video_path)
-    video = bool(_video_parts(color))
-    check_video_decoder(video_decoder, video)
-    check_video_encoder(video_encoder, video)
-    assert color.ndim == 4 and color.shape[-1] == 3 and color.dtype == np.uint8, "uint8 [N, H, 2W, 3] expected"
-    assert color.shape[1:] == mask.shape[1:], "mask and color video not same resolution"
-    if color.shape[2] % 2:
-        raise ValueError(f"side-by-side frames need an even width, got {color.shape[2]}")     # (the reference gives the right eye the odd column: bni:180-181)
-    if max_frames == 0:
-        raise ValueError("max_frames = 0: the reference still processes one frame (bni:226-228); ask for -1 (all) or a positive count")
-    n = color.shape[0] if max_frames == -1 else min(color.shape[0], max_frames)
-    batch = max(1, int(batch))
-    ext = ".mkv" if video else ".npy"
-    tmp, final = sbs_color_video_path + "_tmp_infilled" + ext, sbs_color_video_path + "_infilled" + ext      # bni:140-141
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-    ctx = None
-    if video:
-        fps = _video_parts(color)[0][0].fps or 30.0                                      # bni:134: the colour video's frame rate
-        out = VideoSink(tmp, int(color.shape[2]), int(color.shape[1]), fps, encoder=video_encoder)
-        if video_decoder == "device" or video_encoder == "device":
-            ctx = _lib.Context(dev.index, 16, 16)
-        if video_decoder == "device":
-            for name, frames in (("sbs_color_video", color), ("sbs_mask_video", mask)):
-                for p, _ in _video_parts(frames):
-                    p.use_device_decoder(name)
-    else:
-        out = np.lib.format.open_memmap(tmp, mode="w+", dtype=np.uint8, shape=(n,) + tuple(color.shape[1:]))
-    dec_ctx = ctx if video_decoder == "device" else None
-    try:
-        with torch.cuda.device(dev):
+    with ClipInputs() as inp:
+        # (a clip rendered by several ranks exists as per-rank segments + index: run_output reads either form)
+        color = inp.open(sbs_color_video_path, "sbs_color_video", Exception(f"input sbs_color_video does not exist: {sbs_color_video_path}"), True)
+        mask = inp.open(sbs_mask_video_path, "sbs_mask_video", Exception(f"input sbs_mask_video does not exist: {sbs_mask_video_path}"), True)
+        video = bool(video_parts(color))
+        check_video_decoder(video_decoder, video)
+        check_video_encoder(video_encoder, video)
+        assert color.ndim == 4 and color.shape[-1] == 3 and color.dtype == np.uint8, "uint8 [N, H, 2W, 3] expected"
+        assert color.shape[1:] == mask.shape[1:], "mask and color video not same resolution"
+        if color.shape[2] % 2:
+            raise ValueError(f"side-by-side frames need an even width, got {color.shape[2]}")     # (the reference gives the right eye the odd column: bni:180-181)
+        if max_frames == 0:
+            raise ValueError("max_frames = 0: the reference still processes one frame (bni:226-228); ask for -1 (all) or a positive count")
+        n = color.shape[0] if max_frames == -1 else min(color.shape[0], max_frames)
+        batch = max(1, int(batch))
+        ext = ".mkv" if video else ".npy"
+        tmp, final = sbs_color_video_path + "_tmp_infilled" + ext, sbs_color_video_path + "_infilled" + ext      # bni:140-141
+        fps = (video_parts(color)[0][0].fps or 30.0) if video else None                      # bni:134: the colour video's frame rate
+        inp.on_device(torch.device("cuda", torch.cuda.current_device() if device is None else device), video_decoder, video_encoder)
+        with ClipOutput(tmp, final, n, color.shape[1:], fps, video_encoder, inp.ctx) as out, torch.cuda.device(inp.dev):
             for a in range(0, n, batch):
                 b = min(a + batch, n)
-                d_color = _fetch(color, a, b, dev, dec_ctx)
+                d_color = inp.fetch(color, a, b)
                 have = max(0, min(b, mask.shape[0]) - a)
                 if have == b - a:
-                    d_mask = _fetch(mask, a, b, dev, dec_ctx)
+                    d_mask = inp.fetch(mask, a, b)
                 else:
-                    d_mask = torch.zeros((b - a,) + tuple(color.shape[1:]), dtype=torch.uint8, device=dev)
+                    d_mask = torch.zeros((b - a,) + tuple(color.shape[1:]), dtype=torch.uint8, device=inp.dev)
                     if have:
-                        d_mask[:have] = _fetch(mask, a, a + have, dev, dec_ctx)
-                d_out = normal_infill_sbs(d_color, d_mask)
-                if not video:
-                    out[a:b] = d_out.cpu().numpy()
-                elif video_encoder == "device":
-                    out.append_packets(out.enqueue(ctx, d_out), a)
-                else:
-                    out.write_from(d_out.cpu().numpy(), a, b - a)
-        if video:
-            out.close()
-        else:
-            out.flush()
-    finally:
-        if ctx is not None:
-            ctx.close()
-        for frames in (color, mask):
-            for p, _ in _video_parts(frames):
-                p.close()
-    del out
-    verify_and_move(tmp, n, final)
+                        d_mask[:have] = inp.fetch(mask, a, a + have)
+                out.store(normal_infill_sbs(d_color, d_mask), a)
     return final
 
 

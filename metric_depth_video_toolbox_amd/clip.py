@@ -43,12 +43,15 @@ from __future__ import annotations
 import json
 import math
 import os
-import threading
 from typing import Optional
 
 import numpy as np
 
 from . import distributed as D
+# (the file side lives in clip_io.py; its names stay importable from here)
+from .clip_io import (VIDEO_DECODERS, VIDEO_ENCODERS, SegmentedFrames, VideoFrames, VideoSink, _RawFrames, _remove_segments,  # noqa: F401
+                      _usable_cores, check_video_decoder, check_video_encoder, frames_in, merge_output, npy_shape, open_output,
+                      segment_path, verify_and_move)
 from .stereo_rerender import StereoRerenderer, curve_fit, fill_nan_with_closest
 
 
@@ -196,245 +199,6 @@ def _post_touchly1(r, clip, scales, d_depth_in, d_color_in, d_sbs, d_mask, d_z, 
             d_post[f, :H] = img
             touchly_depth(d_z[f, :, :W], clip.touchly_max_depth, clip.touchly_min_depth, zero_is_far=True, out=d_post[f, H:])
     return d_post[:n]
-
-
-class _RawFrames:
-    """Frame dumps that live in a file (np.load(..., mmap_mode=...) / open_memmap arrays) are read and written with
-    pread / pwrite straight between the file and the pinned staging buffers: one kernel copy per batch and direction,
-    no page-fault storm through a mapping and no intermediate NumPy array.  Anything else (plain arrays, lists) is
-    indexed the ordinary way."""
-
-    def __init__(self, arr, writable: bool):
-        self.arr = arr
-        self.fd = -1
-        if isinstance(arr, (VideoFrames, VideoSink)):           # a video file: its own decode / encode-and-append
-            self.read_into = arr.read_into if isinstance(arr, VideoFrames) else None
-            self.write_from = arr.write_from if isinstance(arr, VideoSink) else None
-            return
-        if isinstance(arr, np.memmap) and arr.flags["C_CONTIGUOUS"] and getattr(arr, "filename", None) and arr.ndim >= 2:
-            # A slice of a memmap (depth[k:]) is still an np.memmap with the parent's filename AND the parent's `offset`:
-            # the file position of its first byte is the root mapping's offset plus the distance of the data pointers.
-            root = arr
-            while isinstance(getattr(root, "base", None), np.memmap):
-                root = root.base
-            try:
-                delta = int(arr.__array_interface__["data"][0]) - int(root.__array_interface__["data"][0])
-                if delta < 0 or len(arr) == 0:
-                    raise OSError("not a forward slice of its mapping")
-                self.fd = os.open(str(arr.filename), os.O_RDWR if writable else os.O_RDONLY)
-                self.base = int(root.offset) + delta
-                self.frame_bytes = int(arr[0].nbytes)
-            except (OSError, KeyError, TypeError):
-                self.fd = -1
-
-    def read_into(self, dst: np.ndarray, a: int, n: int):
-        if self.fd < 0:
-            dst[...] = self.arr[a:a + n]
-            return
-        mv = memoryview(dst).cast("B")
-        off, done, total = self.base + a * self.frame_bytes, 0, n * self.frame_bytes
-        while done < total:
-            got = os.preadv(self.fd, [mv[done:total]], off + done)
-            if got <= 0:
-                raise IOError("short read from a frame dump")
-            done += got
-
-    def write_from(self, src: np.ndarray, a: int, n: int):
-        if self.fd < 0:
-            self.arr[a:a + n] = src
-            return
-        mv = memoryview(src).cast("B")
-        off, done, total = self.base + a * self.frame_bytes, 0, n * self.frame_bytes
-        while done < total:
-            done += os.pwritev(self.fd, [mv[done:total]], off + done)
-
-    def close(self):
-        if self.fd >= 0:
-            os.close(self.fd)
-            self.fd = -1
-
-
-class VideoFrames:
-    """An FFV1-in-Matroska file as the read-only [N, H, W, 3] uint8 frame array render_clip / open_output expect (RGB order).
-    Reads go through a small pool of decoders: a sequential reader continues where its decoder stands, anything else is a
-    seek (free in an intra-only stream; an inter-coded one -- FFmpeg's default, a key frame every 12 -- decodes forward from the
-    last key frame, so it gets ONE decoder and all the slice threads instead of several decoders leap-frogging)."""
-
-    def __init__(self, path: str, readers: int = 2):
-        from . import video_io
-        first = video_io.VideoReader(path)
-        self.path, self.fps, self.info = path, first.fps, first.info
-        self.shape = (first.frames, first.height, first.width, 3)
-        self.dtype, self.ndim = np.dtype(np.uint8), 4
-        n = max(1, int(readers)) if first.info.intra else 1
-        cores = _usable_cores()
-        first.threads = max(1, cores // (2 * n)) if n > 1 else 0
-        self._readers = [first] + [video_io.VideoReader(path, threads=first.threads) for _ in range(n - 1)]
-        self._pos = [0] * n
-        self._busy = [False] * n
-        self._cv = threading.Condition()
-        # render_clip decodes this file's frames on the device (use_device_decoder): it asks for packets, not for frames
-        self.device_decode = False
-        self._packet_reader = None
-
-    def __len__(self):
-        return self.shape[0]
-
-    def use_device_decoder(self, name: str = "input") -> bool:
-        """Switches render_clip's reads of this file to the device decoder (ffv1_device) if the stream is in its class; if not,
-        says so on stderr and leaves the host decoder in charge (files the reference made must keep working)."""
-        import sys
-        from . import ffv1_device
-        self.config = self._readers[0].config_record()
-        why = ffv1_device.supported(self.info, self.config)
-        if why is not None:
-            print(f"video_decoder device: {name} {self.path} is decoded on the host ({why})", file=sys.stderr)
-            return False
-        self.device_decode = True
-        return True
-
-    def read_packets(self, a: int, n: int):
-        """The stored FFV1 packets of frames a ... a + n - 1 (a reader of its own: packets are not decoded, so nothing is shared
-        with the decoders' positions)."""
-        with self._cv:
-            if self._packet_reader is None:
-                from . import video_io
-                self._packet_reader = [video_io.VideoReader(self.path, threads=1), -1, threading.Lock()]
-        r = self._packet_reader
-        with r[2]:
-            if r[1] != a:
-                r[0].seek(a)
-            out = []
-            for i in range(n):
-                pkt = r[0].next_packet()
-                if pkt is None:
-                    r[1] = -1
-                    raise IOError(f"{self.path}: ends at frame {a + i}")
-                out.append(pkt)
-            r[1] = a + n
-        return out
-
-    def read_into(self, dst: np.ndarray, a: int, n: int):
-        with self._cv:
-            while True:
-                free = [k for k in range(len(self._readers)) if not self._busy[k]]
-                if free:
-                    k = next((k for k in free if self._pos[k] == a), None)
-                    if k is None:
-                        behind = [k for k in free if self._pos[k] <= a]
-                        k = max(behind, key=lambda q: self._pos[q]) if behind else free[0]
-                    self._busy[k] = True
-                    break
-                self._cv.wait()
-        try:
-            r = self._readers[k]
-            if self._pos[k] != a:
-                r.seek(a)
-            for i in range(n):
-                if not r.read_into(dst[i]):
-                    raise IOError(f"{self.path}: ends at frame {a + i}")
-            self._pos[k] = a + n
-        except BaseException:
-            self._pos[k] = -1 << 60         # unknown position: the next use seeks
-            raise
-        finally:
-            with self._cv:
-                self._busy[k] = False
-                self._cv.notify()
-
-    def __getitem__(self, idx):
-        if isinstance(idx, slice):
-            lo, hi, step = idx.indices(len(self))
-            if step != 1:
-                return np.stack([self[t] for t in range(lo, hi, step)]) if hi > lo else np.empty((0,) + self.shape[1:], np.uint8)
-            out = np.empty((max(0, hi - lo),) + self.shape[1:], np.uint8)
-            if hi > lo:
-                self.read_into(out, lo, hi - lo)
-            return out
-        t = int(idx)
-        if t < 0:
-            t += len(self)
-        out = np.empty((1,) + self.shape[1:], np.uint8)
-        self.read_into(out, t, 1)
-        return out[0]
-
-    def __array__(self, dtype=None, copy=None):
-        a = self[0:len(self)]
-        return a if dtype is None else a.astype(dtype)
-
-    def close(self):
-        for r in self._readers:
-            r.close()
-        if self._packet_reader is not None:
-            self._packet_reader[0].close()
-
-
-VIDEO_ENCODERS = ("host", "device")
-VIDEO_DECODERS = ("host", "device")
-
-
-class VideoSink:
-    """An output video being written: render_clip's store threads hand it frame sub-ranges in any order (write_from), each
-    thread encodes its frames itself (one FFV1 packet per frame, slices on one thread: the parallelism is across frames) and
-    the packets are appended in frame order.  Grey frames (the hole mask) are written as R = G = B.
-    encoder="device": render_clip enqueues the encode of each batch on the device right after the frames are made (enqueue:
-    mdvt_encode_video_frames, the same bytes) and its store stage appends the packets (append_packets); only the packet bytes
-    leave the device.  write_from stays available in both modes (host encode)."""
-
-    def __init__(self, path: str, width: int, height: int, fps: float, grey: bool = False, slices=(4, 4), bgr: bool = False,
-                 encoder: str = "host"):
-        import threading
-        from . import video_io
-        if encoder not in VIDEO_ENCODERS:
-            raise ValueError(f"encoder must be one of {VIDEO_ENCODERS}, got {encoder!r}")
-        self._vio, self.bgr, self.device = video_io, bgr, encoder == "device"
-        self.slices = (min(slices[0], width), min(slices[1], height))
-        self._w = video_io.VideoWriter(path, width, height, fps, slices=self.slices)
-        self.path, self.grey, self.shape_hw = path, grey, (height, width)
-        self._pending, self._next, self._lock = {}, 0, threading.Lock()
-        self.host_frames = 0             # device mode: frames the device flagged, re-encoded on the host (reported by close)
-
-    def _append(self, t: int, pkt: bytes):
-        with self._lock:
-            self._pending[t] = pkt
-            while self._next in self._pending:
-                self._w.write_packet(self._pending.pop(self._next))
-                self._next += 1
-
-    def write_from(self, src: np.ndarray, a: int, n: int):
-        for i in range(n):
-            f = src[i]
-            if self.grey:
-                f = np.repeat(f[..., None], 3, axis=-1)
-            pkt, _ = self._vio.encode_frame(f, slices=self.slices, threads=1, bgr=self.bgr)
-            self._append(a + i, pkt)
-
-    def enqueue(self, ctx, frames):
-        """Enqueues the device encode of frames ([n, H, W, 3] or grey [n, H, W] on the current stream) -> ffv1_device.PendingPackets."""
-        from . import ffv1_device
-        return ffv1_device.enqueue(ctx, frames, slices=self.slices, bgr=self.bgr)
-
-    def append_packets(self, pending, a: int):
-        """The packets of an enqueue()d batch (its stream work done), as frames a, a + 1, ...  Frames the device flagged are
-        encoded on the host."""
-        for i, pkt in enumerate(pending.collect()):
-            self._append(a + i, pkt)
-        if pending.host_frames:
-            with self._lock:
-                self.host_frames += pending.host_frames
-
-    def close(self) -> int:
-        with self._lock:
-            if self._pending:
-                missing = self._next
-                self._pending.clear()
-                self._w.close()
-                raise RuntimeError(f"{self.path}: frame {missing} was never written")
-            if self.host_frames:
-                import warnings
-                warnings.warn(f"{self.path}: {self.host_frames} frame(s) had a slice past its device capacity and were encoded on "
-                              "the host (same bytes)")
-            return self._w.close()
 
 
 def render_clip(depth_frames, color_frames, out_sbs, out_mask, clip: D.ClipParameters, *, lo: int = 0,
@@ -764,38 +528,7 @@ def render_clip(depth_frames, color_frames, out_sbs, out_mask, clip: D.ClipParam
     return hi - lo, dt, holes
 
 
-def npy_shape(path: str):
-    """Shape recorded in a .npy header (no mapping: an empty segment cannot be mapped)."""
-    with open(path, "rb") as fh:
-        major, _ = np.lib.format.read_magic(fh)
-        shape, _, _ = (np.lib.format.read_array_header_1_0 if major == 1 else np.lib.format.read_array_header_2_0)(fh)
-    return shape
-
-
-def frames_in(path: str) -> int:
-    """Frames in an output file of either kind (a .npy header, or the frames indexed in a Matroska file: what the reference asks
-    cv2.CAP_PROP_FRAME_COUNT for, dfh:169)."""
-    from . import video_io
-    if video_io.is_matroska(path):
-        with video_io.VideoReader(path) as r:
-            return r.frames
-    return npy_shape(path)[0]
-
-
-def verify_and_move(tmp_path: str, expected_frames: int, final_path: str):
-    """The reference's tmp -> final protocol (dfh:163-179): rename only if the frame count matches."""
-    got = frames_in(tmp_path)
-    if got != expected_frames:
-        raise RuntimeError(f"{tmp_path}: {got} frames written, expected {expected_frames}; left in place")
-    os.replace(tmp_path, final_path)
-
-
 OUTPUT_KINDS = {"sbs": "", "mask": "_holemask", "depth": "_depth", "infill": "_infillmask", "infilled": "_infilled"}
-
-
-def segment_path(path: str, rank: int, world: int) -> str:
-    """File of rank `rank`'s output segment: `<path>` itself for a single rank, else `<path>.rank<r>of<R><ext of path>`."""
-    return path if world == 1 else f"{path}.rank{rank}of{world}{os.path.splitext(path)[1] or '.npy'}"
 
 
 def plan_outputs(depth_path: str, clip: D.ClipParameters, world: int, *, create_sbs_depth_video: bool = False,
@@ -825,134 +558,6 @@ def plan_outputs(depth_path: str, clip: D.ClipParameters, world: int, *, create_
             for k, shp in shapes.items()}
 
 
-class SegmentedFrames:
-    """Read-only view of an output written as per-rank segments: indexable like the single [N, ...] array."""
-
-    def __init__(self, parts, bounds):
-        self.parts, self.bounds = parts, bounds          # bounds[k] = first frame of part k; bounds[-1] = N
-        self.shape = (bounds[-1],) + tuple(parts[0].shape[1:])
-        self.dtype = parts[0].dtype
-        self.ndim = len(self.shape)
-
-    def __len__(self):
-        return self.bounds[-1]
-
-    def __getitem__(self, idx):
-        if isinstance(idx, slice):
-            lo, hi, step = idx.indices(len(self))
-            if step != 1:
-                return np.stack([self[t] for t in range(lo, hi, step)])
-            out = [p[max(lo, b0) - b0:min(hi, b1) - b0] for p, b0, b1 in zip(self.parts, self.bounds[:-1], self.bounds[1:])
-                   if max(lo, b0) < min(hi, b1)]
-            return np.concatenate(out) if out else np.empty((0,) + self.shape[1:], self.dtype)
-        t = int(idx)
-        if t < 0:
-            t += len(self)
-        k = int(np.searchsorted(self.bounds, t, side="right")) - 1
-        return self.parts[k][t - self.bounds[k]]
-
-    def __array__(self, dtype=None, copy=None):
-        a = self[0:len(self)]
-        return a if dtype is None else a.astype(dtype)
-
-
-def open_output(path: str, mmap_mode: Optional[str] = "r"):
-    """An output of run(): the single dump `<path>` or the per-rank segments named by `<path>.index.json` (run() leaves only the
-    form it wrote; should both exist -- files copied together by hand -- the newer one is taken)."""
-    from . import video_io
-
-    def one(f, mapped=True):
-        return VideoFrames(f, readers=1) if video_io.is_matroska(f) else np.load(f, mmap_mode=mmap_mode if mapped else None)
-    ip = path + ".index.json"
-    if os.path.exists(path) and not (os.path.exists(ip) and os.path.getmtime(ip) > os.path.getmtime(path)):
-        return one(path)
-    with open(path + ".index.json") as fh:
-        idx = json.load(fh)
-    here = os.path.dirname(path)
-    parts = [one(os.path.join(here, s["file"]), s["hi"] > s["lo"]) for s in idx["segments"]]
-    bounds = [s["lo"] for s in idx["segments"]] + [idx["frames"]]
-    for p, s in zip(parts, idx["segments"]):
-        if p.shape[0] != s["hi"] - s["lo"]:
-            raise RuntimeError(f"{s['file']}: {p.shape[0]} frames, the index says {s['hi'] - s['lo']}")
-    return SegmentedFrames(parts, bounds)
-
-
-def _remove_segments(path: str, keep=()):
-    """Remove `<path>.index.json` and the segment files it names (an earlier multi-rank run's form of the output), except the
-    files named in `keep` (base names: the segments the run that calls this has just written)."""
-    ip = path + ".index.json"
-    if not os.path.exists(ip):
-        return
-    try:
-        with open(ip) as fh:
-            idx = json.load(fh)
-        for s in idx.get("segments", []):
-            if s["file"] in keep:
-                continue
-            f = os.path.join(os.path.dirname(path), s["file"])
-            if os.path.exists(f):
-                os.remove(f)
-    finally:
-        os.remove(ip)
-
-
-def merge_output(path: str, remove_segments: bool = True) -> str:
-    """Concatenate the segments of `<path>.index.json` into the single dump `<path>` (tmp -> final rename)."""
-    seg = open_output(path)
-    if not isinstance(seg, SegmentedFrames):
-        return path
-    if isinstance(seg.parts[0], VideoFrames):
-        # video segments: the packets are copied as they are (every segment was written with the same size and slice counts)
-        from . import video_io
-        tmp = path + ".merge_tmp.mkv"
-        first = video_io.VideoReader(seg.parts[0].path)
-        H, W = first.height, first.width
-        sl = (min(4, W), min(4, H))                    # VideoSink's slice grid
-        if first.info.slices != sl[0] * sl[1]:
-            raise RuntimeError(f"{seg.parts[0].path}: {first.info.slices} slices per frame, not one of this driver's segments")
-        first.close()
-        with video_io.VideoWriter(tmp, W, H, seg.parts[0].fps, slices=sl) as w:
-            for part in seg.parts:
-                with video_io.VideoReader(part.path) as r:
-                    while True:
-                        pkt = r.next_packet()
-                        if pkt is None:
-                            break
-                        w.write_packet(pkt)
-        for part in seg.parts:
-            part.close()
-    else:
-        tmp = path + ".merge_tmp.npy"
-        out = np.lib.format.open_memmap(tmp, mode="w+", dtype=seg.dtype, shape=seg.shape)
-        for p, b0 in zip(seg.parts, seg.bounds[:-1]):
-            out[b0:b0 + p.shape[0]] = p
-        out.flush()
-        del out
-    os.replace(tmp, path)
-    if remove_segments:
-        with open(path + ".index.json") as fh:
-            idx = json.load(fh)
-        for s in idx["segments"]:
-            os.remove(os.path.join(os.path.dirname(path), s["file"]))
-        os.remove(path + ".index.json")
-    return path
-
-
-def _usable_cores() -> int:
-    """Cores this process may use: affinity mask capped by the cgroup CPU quota."""
-    try:
-        n = len(os.sched_getaffinity(0))
-    except AttributeError:
-        n = os.cpu_count() or 1
-    try:
-        q, per = open("/sys/fs/cgroup/cpu.max").read().split()[:2]
-        if q != "max":
-            n = max(1, min(n, int(float(q) / float(per))))
-    except Exception:
-        pass
-    return n
-
-
 def pin_to_gpu_numa_node(device_index: int) -> Optional[int]:
     """Restrict this process (and the I/O threads it starts afterwards) to the CPUs of the NUMA node its GPU hangs off:
     the pinned staging buffers and the page-cache copies of a rank then stay on the memory controller next to its PCIe
@@ -975,25 +580,6 @@ def pin_to_gpu_numa_node(device_index: int) -> Optional[int]:
         return node
     except Exception:
         return None
-
-
-def check_video_encoder(video_encoder: str, video: bool):
-    """ValueError unless video_encoder is "host" or "device", and "device" only where the outputs are .mkv files."""
-    if video_encoder not in VIDEO_ENCODERS:
-        raise ValueError(f"video_encoder must be one of {VIDEO_ENCODERS}, got {video_encoder!r}")
-    if video_encoder == "device" and not video:
-        raise ValueError("--video_encoder device encodes .mkv outputs: with a .npy depth input the outputs are raw .npy dumps, "
-                         "which are not encoded (use the default --video_encoder host)")
-
-
-def check_video_decoder(video_decoder: str, video: bool) -> str:
-    """ValueError unless video_decoder is "host" or "device", and "device" only where the inputs are .mkv files."""
-    if video_decoder not in VIDEO_DECODERS:
-        raise ValueError(f"video_decoder must be one of {VIDEO_DECODERS}, got {video_decoder!r}")
-    if video_decoder == "device" and not video:
-        raise ValueError("--video_decoder device decodes .mkv inputs: a .npy input is a raw frame dump, which is not decoded "
-                         "(use the default --video_decoder host)")
-    return video_decoder
 
 
 def check_find_convergence(find_convergence: bool, convergence_mask_video, convergence_file) -> None:

@@ -6,19 +6,7 @@ argument meaning), operating on PyTorch-ROCm tensors through the HIP kernels.  N
 """
 from __future__ import annotations
 
-import ctypes as C
-
 from . import _lib
-
-_ctx_cache = {}
-
-
-def _ctx(device_index: int, W: int, H: int):
-    import os
-    key = (device_index, W, H, os.environ.get("MDVT_LIB_VARIANT", ""))      # a context belongs to the library that made it
-    if key not in _ctx_cache:
-        _ctx_cache[key] = _lib.Context(device_index, W, H)
-    return _ctx_cache[key]
 
 
 def decode_rgb_depth_frame(rgb, max_depth, bit16=True, depth_scale: float = 1.0, out=None):
@@ -31,10 +19,8 @@ def decode_rgb_depth_frame(rgb, max_depth, bit16=True, depth_scale: float = 1.0,
     H, W = int(rgb.shape[0]), int(rgb.shape[1])
     if out is None:
         out = torch.empty((H, W), dtype=torch.float32, device=rgb.device)
-    ctx = _ctx(rgb.device.index or 0, W, H)
-    s = torch.cuda.current_stream(rgb.device)
-    ctx.check(_lib.load().mdvt_decode_depth(ctx.handle, rgb.data_ptr(), 3 * W, out.data_ptr(), 4 * W,
-                                            float(max_depth), float(depth_scale), C.c_void_p(s.cuda_stream)))
+    _lib.shared_context(rgb.device, W, H).call("mdvt_decode_depth", rgb.data_ptr(), 3 * W, out.data_ptr(), 4 * W,
+                                               float(max_depth), float(depth_scale), _lib.stream_arg(rgb.device))
     return out
 
 
@@ -46,10 +32,8 @@ def encode_depth_frame(depth, max_depth, bgr: bool = True, out=None):
     H, W = int(depth.shape[0]), int(depth.shape[1])
     if out is None:
         out = torch.empty((H, W, 3), dtype=torch.uint8, device=depth.device)
-    ctx = _ctx(depth.device.index or 0, W, H)
-    s = torch.cuda.current_stream(depth.device)
-    ctx.check(_lib.load().mdvt_encode_depth(ctx.handle, depth.data_ptr(), 4 * W, out.data_ptr(), 3 * W,
-                                            float(max_depth), int(bool(bgr)), C.c_void_p(s.cuda_stream)))
+    _lib.shared_context(depth.device, W, H).call("mdvt_encode_depth", depth.data_ptr(), 4 * W, out.data_ptr(), 3 * W,
+                                                 float(max_depth), int(bool(bgr)), _lib.stream_arg(depth.device))
     return out
 
 
@@ -66,8 +50,7 @@ def swap_rb(frames, out=None):
     if out is None:
         out = torch.empty(tuple(frames.shape), dtype=torch.uint8, device=frames.device)
     assert out.shape == frames.shape and out.stride(-1) == 1 and out.stride(-2) == 3
-    ctx = _ctx(frames.device.index or 0, W, H)
-    s = torch.cuda.current_stream(frames.device)
-    ctx.check(_lib.load().mdvt_swap_rb(ctx.handle, frames.data_ptr(), frames.stride(-3), frames.stride(0) if batched else 0,
-                                       out.data_ptr(), out.stride(-3), out.stride(0) if batched else 0, N, C.c_void_p(s.cuda_stream)))
+    _lib.shared_context(frames.device, W, H).call("mdvt_swap_rb", frames.data_ptr(), frames.stride(-3), frames.stride(0) if batched else 0,
+                                                  out.data_ptr(), out.stride(-3), out.stride(0) if batched else 0, N,
+                                                  _lib.stream_arg(frames.device))
     return out

@@ -128,23 +128,19 @@ def enqueue(ctx: "_lib.Context", frames, slices=(4, 4), bgr: bool = False, slice
     offsets = torch.empty(N, dtype=torch.int64, device=dev)
     sizes = torch.empty(N, dtype=torch.int32, device=dev)
     s = stream if stream is not None else torch.cuda.current_stream(dev)
-    ctx.check(ctx._L.mdvt_encode_video_frames(ctx.handle, W, H, nh, nv, C.c_void_p(frames.data_ptr()), frames.stride(1),
-                                             frames.stride(0), ch, 1 if bgr else 0, N, int(slice_capacity),
-                                             C.c_void_p(packets.data_ptr()), int(packets_cap), C.c_void_p(offsets.data_ptr()),
-                                             C.c_void_p(sizes.data_ptr()), C.c_void_p(s.cuda_stream)))
+    ctx.call("mdvt_encode_video_frames", W, H, nh, nv, C.c_void_p(frames.data_ptr()), frames.stride(1),
+             frames.stride(0), ch, 1 if bgr else 0, N, int(slice_capacity),
+             C.c_void_p(packets.data_ptr()), int(packets_cap), C.c_void_p(offsets.data_ptr()),
+             C.c_void_p(sizes.data_ptr()), _lib.stream_arg(dev, s))
     done = torch.cuda.Event()
     done.record(s)
     return PendingPackets(frames, (nh, nv), bgr, packets, offsets, sizes, done)
 
 
-_contexts = {}
-
-
-def _context(device: int) -> "_lib.Context":
-    ctx = _contexts.get(device)
-    if ctx is None:
-        ctx = _contexts[device] = _lib.Context(device, 16, 16)      # (the render size is irrelevant to the encoder)
-    return ctx
+def _context(device) -> "_lib.Context":
+    """The shared 16 x 16 context of a GPU (the render size is irrelevant to the codec): _lib.shared_context under the name the
+    tests of this module know."""
+    return _lib.shared_context(device)
 
 
 def encode_frames_on_device(frames, slices=(4, 4), bgr: bool = False, slice_capacity: int = 0,
@@ -153,9 +149,7 @@ def encode_frames_on_device(frames, slices=(4, 4), bgr: bool = False, slice_capa
     padded): the same bytes as video_io.encode_frame(frame, slices, bgr) per frame, grey frames as R = G = B.  The defaults
     leave the host nothing to do short of a slice past twice its raw size (enqueue + collect report such frames)."""
     check_frames(frames, slices)
-    p = enqueue(_context(frames.device.index if frames.device.index is not None else 0), frames, slices, bgr, slice_capacity,
-                packets_cap)
-    return p.collect()
+    return enqueue(_context(frames.device), frames, slices, bgr, slice_capacity, packets_cap).collect()
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -280,10 +274,10 @@ def enqueue_decode(ctx: "_lib.Context", packets, config: bytes, width: int, heig
     s.wait_event(copied)
     for t in (d_blob, d_meta, d_sizes, status):
         t.record_stream(s)
-    ctx.check(ctx._L.mdvt_decode_video_frames(ctx.handle, W, H, config, len(config), C.c_void_p(d_blob.data_ptr()), total,
-                                             C.c_void_p(d_meta.data_ptr()), C.c_void_p(d_sizes.data_ptr()), N,
-                                             C.c_void_p(out.data_ptr()), out.stride(1), out.stride(0) if N > 1 else out.stride(1) * H,
-                                             1 if bgr else 0, C.c_void_p(status.data_ptr()), C.c_void_p(s.cuda_stream)))
+    ctx.call("mdvt_decode_video_frames", W, H, config, len(config), C.c_void_p(d_blob.data_ptr()), total,
+             C.c_void_p(d_meta.data_ptr()), C.c_void_p(d_sizes.data_ptr()), N,
+             C.c_void_p(out.data_ptr()), out.stride(1), out.stride(0) if N > 1 else out.stride(1) * H,
+             1 if bgr else 0, C.c_void_p(status.data_ptr()), _lib.stream_arg(dev, s))
     done = torch.cuda.Event()
     done.record(s)
     return PendingFrames(staged.packets, config, W, H, bgr, out, status, done, (staged, d_blob, d_meta, d_sizes))
@@ -294,8 +288,6 @@ def decode_frames_on_device(packets, config: bytes, width: int, height: int, *, 
     """-> (frames, status): the N x H x W x 3 uint8 CUDA frames video_io.VideoReader gives for these packets (RGB, or BGR with
     bgr=True; into `out`, whose rows and frames may be padded) and the device's status words (numpy uint32 [N]; a nonzero word:
     that frame was decoded on the host instead)."""
-    if out is not None:
-        device = out.device.index if out.device.index is not None else 0
-    p = enqueue_decode(_context(device), packets, config, width, height, bgr, out, stream)
+    p = enqueue_decode(_context(device if out is None else out.device), packets, config, width, height, bgr, out, stream)
     frames = p.collect()
     return frames, p.flags

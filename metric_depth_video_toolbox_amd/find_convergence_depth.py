@@ -10,13 +10,13 @@ summation is reproduced by the kernels of csrc/mdvt_convergence.hip (include/mdv
 from __future__ import annotations
 
 import argparse
-import ctypes as C
 import json
 import os
 
 import numpy as np
 
 from . import _lib
+from .clip_io import ClipInputs, check_video_decoder, video_parts
 
 SIDECAR_SUFFIX = "_convergence_depths.json"             # fcd:41
 
@@ -36,7 +36,6 @@ def convergence_depths(depth_frames, mask_frames=None, max_depth=100, *, bgr: bo
     frame selects nothing); with counts=True also the uint32-valued int32 tensor [N] of the selected pixels.  Only enqueues, on `stream`
     (default: the current stream of the frames' device)."""
     import torch
-    from . import ffv1_device
     _check_frames(depth_frames, "depth_frames")
     N, H, W = (int(v) for v in depth_frames.shape[:3])
     if N < 1:
@@ -52,16 +51,15 @@ def convergence_depths(depth_frames, mask_frames=None, max_depth=100, *, bgr: bo
         if M > N:
             raise ValueError(f"{M} mask frames for {N} depth frames")
     dev = depth_frames.device
-    ctx = ffv1_device._context(dev.index or 0)              # (the render size is irrelevant here too)
     s = torch.cuda.current_stream(dev) if stream is None else stream
     with torch.cuda.stream(s):
         means = torch.empty(N, dtype=torch.float32, device=dev)
         n_sel = torch.empty(N, dtype=torch.int32, device=dev) if counts else None
     order = 1 if bgr else 0
-    ctx.check(_lib.load().mdvt_convergence_depths(
-        ctx.handle, W, H, depth_frames.data_ptr(), depth_frames.stride(1), depth_frames.stride(0), order,
+    _lib.shared_context(dev).call(                          # (the render size is irrelevant here too)
+        "mdvt_convergence_depths", W, H, depth_frames.data_ptr(), depth_frames.stride(1), depth_frames.stride(0), order,
         mask_frames.data_ptr() if M else None, mask_frames.stride(1) if M else 0, mask_frames.stride(0) if M else 0, order,
-        N, M, float(max_depth), means.data_ptr(), n_sel.data_ptr() if counts else None, C.c_void_p(s.cuda_stream)))
+        N, M, float(max_depth), means.data_ptr(), n_sel.data_ptr() if counts else None, _lib.stream_arg(dev, s))
     return (means, n_sel) if counts else means
 
 
@@ -74,10 +72,7 @@ def sidecar_text(depths) -> str:
     return json.dumps([float(v) for v in depths])
 
 
-def _open(path: str):
-    from . import video_io
-    from .clip import VideoFrames
-    frames = VideoFrames(path) if video_io.is_matroska(path) else np.load(path, mmap_mode="r")
+def _check_dump(frames, path: str):
     if frames.ndim != 4 or frames.shape[3] != 3 or frames.dtype != np.uint8:
         raise ValueError(f"{path}: uint8 [N, H, W, 3] expected")
     return frames
@@ -88,51 +83,34 @@ def find(depth_path: str, mask_path=None, max_depth=100, *, batch: int = 64, max
     under the white pixels (gray > 240) of the mask video where one is given.  Writes `<depth_video>_convergence_depths.json` (under a
     temporary name, renamed when complete) and returns the list of Python floats.  A mask video of another size raises ValueError; a
     shorter one prints the reference's "Failed to read mask video frame" (once) and the remaining frames use every pixel.
-    video_decoder: "host" (default) or "device" for .mkv files (clip.check_video_decoder)."""
+    video_decoder: "host" (default) or "device" for .mkv files (clip_io.check_video_decoder)."""
     import torch
-    from . import video_io
-    from .basic_nomal_infill import _fetch
-    from .clip import VideoFrames, check_video_decoder
-    if not os.path.isfile(depth_path):
-        raise FileNotFoundError(f"Depth video not found: {depth_path}")                      # fcd:24-25
-    if mask_path is not None and not os.path.isfile(mask_path):
-        raise FileNotFoundError(f"Mask video not found: {mask_path}")                        # fcd:29-30
-    check_video_decoder(video_decoder, video_io.is_matroska(depth_path))
-    if not (float(max_depth) > 0):
-        raise ValueError("max_depth must be > 0")
-    depth = _open(depth_path)
-    mask = _open(mask_path) if mask_path is not None else None
-    opened = [f for f in (depth, mask) if isinstance(f, VideoFrames)]
-    ctx = None
-    try:
-        if mask is not None and tuple(mask.shape[1:3]) != tuple(depth.shape[1:3]):
+    with ClipInputs() as inp:
+        depth = inp.open(depth_path, "depth video", FileNotFoundError(f"Depth video not found: {depth_path}"))             # fcd:24-25
+        mask = None if mask_path is None else \
+            inp.open(mask_path, "mask video", FileNotFoundError(f"Mask video not found: {mask_path}"))                     # fcd:29-30
+        check_video_decoder(video_decoder, bool(video_parts(depth)))
+        if not (float(max_depth) > 0):
+            raise ValueError("max_depth must be > 0")
+        _check_dump(depth, depth_path)
+        if mask is not None and tuple(_check_dump(mask, mask_path).shape[1:3]) != tuple(depth.shape[1:3]):
             raise ValueError(f"Mask video and depth video must have the same dimensions "
                              f"(Mask: {mask.shape[2]}x{mask.shape[1]} vs Depth {depth.shape[2]}x{depth.shape[1]}).")
         n = depth.shape[0] if max_frames < 0 else min(depth.shape[0], max_frames)
         n_mask = min(n, mask.shape[0]) if mask is not None else 0
         batch = max(1, int(batch))
-        dev = torch.device("cuda", torch.cuda.current_device())
-        if video_decoder == "device":
-            ctx = _lib.Context(dev.index, 16, 16)
-            for name, f in (("depth video", depth), ("mask video", mask)):
-                if isinstance(f, VideoFrames):
-                    f.use_device_decoder(name)
+        inp.on_device(torch.device("cuda", torch.cuda.current_device()), video_decoder)
         parts = []
-        with torch.cuda.device(dev):
+        with torch.cuda.device(inp.dev):
             for a in range(0, n, batch):
                 b = min(a + batch, n)
-                d_depth = _fetch(depth, a, b, dev, ctx)
+                d_depth = inp.fetch(depth, a, b)
                 have = max(0, min(b, n_mask) - a)
-                d_mask = _fetch(mask, a, a + have, dev, ctx) if have else None
+                d_mask = inp.fetch(mask, a, a + have) if have else None
                 parts.append(convergence_depths(d_depth, d_mask, max_depth))
             means = torch.cat(parts).cpu().numpy() if parts else np.empty(0, np.float32)
         if mask is not None and n_mask < n:
             print("Failed to read mask video frame")                                         # fcd:71
-    finally:
-        if ctx is not None:
-            ctx.close()
-        for f in opened:
-            f.close()
     depths = [float(v) for v in means]                                                       # fcd:78
     out = sidecar_path(depth_path)
     with open(out + ".tmp", "w") as fh:

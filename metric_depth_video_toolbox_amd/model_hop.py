@@ -15,7 +15,6 @@ unless a state dict is supplied.
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional
 
 from . import _lib
@@ -61,14 +60,12 @@ def depth_to_rgb_code(depth, max_depth: float, out=None):
     N, H, W = (int(v) for v in depth.shape)
     if out is None:
         out = torch.empty((N, H, W, 3), dtype=torch.uint8, device=depth.device)
-    from .depth_frames_helper import _ctx
-    s = torch.cuda.current_stream(depth.device)
+    s = _lib.stream_arg(depth.device)
     group = max(1, 32767 // H)                      # a context takes at most 32767 rows
     for a in range(0, N, group):
         n = min(group, N - a)
-        ctx = _ctx(depth.device.index or 0, W, n * H)
-        ctx.check(_lib.load().mdvt_encode_depth(ctx.handle, depth[a].data_ptr(), 4 * W, out[a].data_ptr(), 3 * W,
-                                                float(max_depth), 0, C.c_void_p(s.cuda_stream)))
+        _lib.shared_context(depth.device, W, n * H).call("mdvt_encode_depth", depth[a].data_ptr(), 4 * W, out[a].data_ptr(), 3 * W,
+                                                         float(max_depth), 0, s)
     return out
 
 

@@ -30,14 +30,14 @@ T-6 .. T-4 go with their own masks.  Those three frames are context for the gene
 from __future__ import annotations
 
 import argparse
-import ctypes as C
 import importlib
 import os
 
 import numpy as np
 
 from . import _lib
-from .basic_nomal_infill import _fetch, _is_txt, _video_parts, pairs_from_arguments
+from .basic_nomal_infill import pairs_from_arguments
+from .clip_io import ClipInputs, ClipOutput, check_video_decoder, check_video_encoder, video_parts
 
 MODEL_W, MODEL_H = 1024, 768              # scr:95-96
 FRAMES_CHUNK, OVERLAP = 25, 6             # scr:222, 250-257
@@ -53,16 +53,6 @@ def _frames4(t, channels=3):
     return t
 
 
-def _stream(t):
-    import torch
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
-def _context(t):
-    from .depth_frames_helper import _ctx
-    return _ctx(t.device.index or 0, 16, 16)
-
-
 def prepare_eye(sbs_color, sbs_mask, eye: int, model_size=(MODEL_W, MODEL_H)):
     """scr:101-126 for one eye (0 = left, read mirrored; 1 = right) of uint8 CUDA [N,H,2W,3] colour and infill-mask frames ->
     (image [N,mh,mw,3], mask [N,mh,mw], hole counts int32 [N]), all on the device."""
@@ -74,11 +64,10 @@ def prepare_eye(sbs_color, sbs_mask, eye: int, model_size=(MODEL_W, MODEL_H)):
     image = torch.empty((N, mh, mw, 3), dtype=torch.uint8, device=sbs_color.device)
     mask = torch.empty((N, mh, mw), dtype=torch.uint8, device=sbs_color.device)
     counts = torch.empty((N,), dtype=torch.int32, device=sbs_color.device)
-    ctx = _context(sbs_color)
-    ctx.check(_lib.load().mdvt_adapter_prepare_eye(
-        ctx.handle, W2 // 2, H, N, int(eye), sbs_color.data_ptr(), sbs_color.stride(1), sbs_color.stride(0),
+    _lib.shared_context(sbs_color.device).call(
+        "mdvt_adapter_prepare_eye", W2 // 2, H, N, int(eye), sbs_color.data_ptr(), sbs_color.stride(1), sbs_color.stride(0),
         sbs_mask.data_ptr(), sbs_mask.stride(1), sbs_mask.stride(0), mw, mh, image.data_ptr(), image.stride(1), image.stride(0),
-        mask.data_ptr(), mask.stride(1), mask.stride(0), counts.data_ptr(), _stream(sbs_color)))
+        mask.data_ptr(), mask.stride(1), mask.stride(0), counts.data_ptr(), _lib.stream_arg(sbs_color.device))
     return image, mask, counts
 
 
@@ -94,11 +83,10 @@ def lhm_moments(frames, mask=None, out=None):
     if out is None:
         out = torch.empty((N, 10), dtype=torch.int64, device=frames.device)
     assert out.is_contiguous() and out.dtype == torch.int64 and tuple(out.shape) == (N, 10)
-    ctx = _context(frames)
-    ctx.check(_lib.load().mdvt_lhm_moments(
-        ctx.handle, W, H, N, frames.data_ptr(), frames.stride(1), frames.stride(0),
+    _lib.shared_context(frames.device).call(
+        "mdvt_lhm_moments", W, H, N, frames.data_ptr(), frames.stride(1), frames.stride(0),
         mask.data_ptr() if mask is not None else None, mask.stride(1) if mask is not None else 0, mask.stride(0) if mask is not None else 0,
-        out.data_ptr(), _stream(frames)))
+        out.data_ptr(), _lib.stream_arg(frames.device))
     return out
 
 
@@ -142,9 +130,8 @@ def lhm_apply(frames, params, out=None):
     if out is None:
         out = torch.empty((N, H, W, 3), dtype=torch.uint8, device=frames.device)
     _frames4(out)
-    ctx = _context(frames)
-    ctx.check(_lib.load().mdvt_lhm_apply(ctx.handle, W, H, N, frames.data_ptr(), frames.stride(1), frames.stride(0), params.data_ptr(),
-                                         out.data_ptr(), out.stride(1), out.stride(0), _stream(frames)))
+    _lib.shared_context(frames.device).call("mdvt_lhm_apply", W, H, N, frames.data_ptr(), frames.stride(1), frames.stride(0), params.data_ptr(),
+                                            out.data_ptr(), out.stride(1), out.stride(0), _lib.stream_arg(frames.device))
     return out
 
 
@@ -179,12 +166,11 @@ def composite_eye(model_frames, sbs_color, sbs_mask, eye: int, pasted, blended):
         _frames4(t)
     N, H, W2 = (int(v) for v in sbs_color.shape[:3])
     assert sbs_mask.shape == sbs_color.shape == pasted.shape == blended.shape and int(model_frames.shape[0]) == N
-    ctx = _context(sbs_color)
-    ctx.check(_lib.load().mdvt_adapter_composite_eye(
-        ctx.handle, W2 // 2, H, N, int(eye), model_frames.data_ptr(), int(model_frames.shape[2]), int(model_frames.shape[1]),
+    _lib.shared_context(sbs_color.device).call(
+        "mdvt_adapter_composite_eye", W2 // 2, H, N, int(eye), model_frames.data_ptr(), int(model_frames.shape[2]), int(model_frames.shape[1]),
         model_frames.stride(1), model_frames.stride(0), sbs_color.data_ptr(), sbs_color.stride(1), sbs_color.stride(0),
         sbs_mask.data_ptr(), sbs_mask.stride(1), sbs_mask.stride(0), pasted.data_ptr(), pasted.stride(1), pasted.stride(0),
-        blended.data_ptr(), blended.stride(1), blended.stride(0), _stream(sbs_color)))
+        blended.data_ptr(), blended.stride(1), blended.stride(0), _lib.stream_arg(sbs_color.device))
 
 
 def deal_with_frame_chunk(keep_first_three: bool, color, mask, keep_last_three: bool, fps: float, generate, model_size=(MODEL_W, MODEL_H)):
@@ -234,17 +220,12 @@ def process_pair(sbs_color_video_path: str, sbs_mask_video_path: str, generate, 
     [N,H,2W,3]) give `<sbs_color>_infilled.npy`; either is written under its `_tmp_infilled` name and renamed once every frame is in.
     A mask clip shorter than the colour clip means black masks for the rest (scr:234-237).  Returns the output path."""
     import torch
-    from .clip import VideoSink, check_video_decoder, check_video_encoder, open_output, verify_and_move
-    if not (os.path.isfile(sbs_color_video_path) or os.path.isfile(sbs_color_video_path + ".index.json")):
-        raise Exception(f"input sbs_color_video does not exist: {sbs_color_video_path}")
-    if not (os.path.isfile(sbs_mask_video_path) or os.path.isfile(sbs_mask_video_path + ".index.json")):
-        raise Exception(f"input sbs_mask_video does not exist: {sbs_mask_video_path}")
-    color = open_output(sbs_color_video_path)
-    mask = open_output(sbs_mask_video_path)
-    video = bool(_video_parts(color))
-    check_video_decoder(video_decoder, video)
-    check_video_encoder(video_encoder, video)
-    try:
+    with ClipInputs() as inp:
+        color = inp.open(sbs_color_video_path, "sbs_color_video", Exception(f"input sbs_color_video does not exist: {sbs_color_video_path}"), True)
+        mask = inp.open(sbs_mask_video_path, "sbs_mask_video", Exception(f"input sbs_mask_video does not exist: {sbs_mask_video_path}"), True)
+        video = bool(video_parts(color))
+        check_video_decoder(video_decoder, video)
+        check_video_encoder(video_encoder, video)
         assert color.ndim == 4 and color.shape[-1] == 3 and color.dtype == np.uint8, "uint8 [N, H, 2W, 3] expected"
         assert color.shape[1:] == mask.shape[1:], "mask and color video not same resolution"      # scr:210
         if color.shape[2] % 2:
@@ -254,40 +235,14 @@ def process_pair(sbs_color_video_path: str, sbs_mask_video_path: str, generate, 
         n = color.shape[0] if max_frames == -1 else min(color.shape[0], max_frames)
         if n < 1:
             raise ValueError(f"{sbs_color_video_path} has no frames")
-    except Exception:
-        for frames in (color, mask):
-            for p, _ in _video_parts(frames):
-                p.close()
-        raise
-    batch = max(1, int(batch))
-    ext = ".mkv" if video else ".npy"
-    tmp, final = sbs_color_video_path + "_tmp_infilled" + ext, sbs_color_video_path + "_infilled" + ext      # scr:213-214
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-    H, W2 = int(color.shape[1]), int(color.shape[2])
-    ctx, fps = None, 30.0
-    if video:
-        fps = _video_parts(color)[0][0].fps or 30.0
-        out = VideoSink(tmp, W2, H, fps, encoder=video_encoder)
-        if video_decoder == "device" or video_encoder == "device":
-            ctx = _lib.Context(dev.index, 16, 16)
-        if video_decoder == "device":
-            for name, frames in (("sbs_color_video", color), ("sbs_mask_video", mask)):
-                for p, _ in _video_parts(frames):
-                    p.use_device_decoder(name)
-    else:
-        out = np.lib.format.open_memmap(tmp, mode="w+", dtype=np.uint8, shape=(n, H, W2, 3))
-    dec_ctx = ctx if video_decoder == "device" else None
-
-    def store(d_out, a):
-        if not video:
-            out[a:a + len(d_out)] = d_out.cpu().numpy()
-        elif video_encoder == "device":
-            out.append_packets(out.enqueue(ctx, d_out), a)
-        else:
-            out.write_from(d_out.cpu().numpy(), a, len(d_out))
-
-    try:
-        with torch.cuda.device(dev):
+        batch = max(1, int(batch))
+        ext = ".mkv" if video else ".npy"
+        tmp, final = sbs_color_video_path + "_tmp_infilled" + ext, sbs_color_video_path + "_infilled" + ext      # scr:213-214
+        H, W2 = int(color.shape[1]), int(color.shape[2])
+        fps = (video_parts(color)[0][0].fps or 30.0) if video else 30.0
+        inp.on_device(torch.device("cuda", torch.cuda.current_device() if device is None else device), video_decoder, video_encoder)
+        dev = inp.dev
+        with ClipOutput(tmp, final, n, (H, W2, 3), fps if video else None, video_encoder, inp.ctx) as out, torch.cuda.device(dev):
             buf_c = torch.empty((FRAMES_CHUNK, H, W2, 3), dtype=torch.uint8, device=dev)
             buf_m = torch.zeros_like(buf_c)
             read = 0
@@ -295,33 +250,21 @@ def process_pair(sbs_color_video_path: str, sbs_mask_video_path: str, generate, 
                 have = read - base                                 # the overlap is in the buffer already
                 while have < held:
                     k = min(batch, held - have)
-                    buf_c[have:have + k] = _fetch(color, read, read + k, dev, dec_ctx)
+                    buf_c[have:have + k] = inp.fetch(color, read, read + k)
                     got = max(0, min(read + k, mask.shape[0]) - read)
                     if got:
-                        buf_m[have:have + got] = _fetch(mask, read, read + got, dev, dec_ctx)
+                        buf_m[have:have + got] = inp.fetch(mask, read, read + got)
                     buf_m[have + got:have + k] = 0                 # scr:234-237
                     have += k
                     read += k
                 start, pasted, blended = deal_with_frame_chunk(first, buf_c[:held], buf_m[:held], last, fps, generate, model_size)
                 assert base + start == wa and len(blended) == wb - wa
                 if wb > wa:
-                    store(blended, wa)
+                    out.store(blended, wa)
                 if not last:                                       # scr:250-257
                     keep_c = torch.cat([pasted[held - OVERLAP - start:held - 3 - start], buf_c[held - 3:held]])
                     keep_m = buf_m[held - OVERLAP:held].clone()
                     buf_c[:OVERLAP], buf_m[:OVERLAP] = keep_c, keep_m
-        if video:
-            out.close()
-        else:
-            out.flush()
-    finally:
-        if ctx is not None:
-            ctx.close()
-        for frames in (color, mask):
-            for p, _ in _video_parts(frames):
-                p.close()
-    del out
-    verify_and_move(tmp, n, final)
     return final
 
 
@@ -396,16 +339,17 @@ def main(argv=None):
     if args.max_frames == 0:
         raise SystemExit("--max_frames 0: ask for -1 (all) or a positive count")
     pairs = pairs_from_arguments(args.sbs_color_video, args.sbs_mask_video)
+    listed = args.sbs_color_video.lower().endswith(".txt")        # (the rule of pairs_from_arguments, scr:343)
     for c_path, m_path in pairs:
         for what, path in (("sbs_color_video", c_path), ("sbs_mask_video", m_path)):
-            if not _is_txt(args.sbs_color_video) and not (os.path.isfile(path) or os.path.isfile(path + ".index.json")):
+            if not listed and not (os.path.isfile(path) or os.path.isfile(path + ".index.json")):
                 raise SystemExit(f"input {what} does not exist: {path}")
     try:
         generate = load_generator(args.generator, args.num_inference_steps)
     except (RuntimeError, ValueError, ImportError) as e:
         raise SystemExit(str(e))
     kw = dict(batch=args.batch, video_decoder=args.video_decoder, video_encoder=args.video_encoder)
-    if _is_txt(args.sbs_color_video):
+    if listed:
         # (the reference runs two clips at a time with the model serialised, scr:343-354; here the clips follow each other)
         print(f"Batch mode: {len(pairs)} pairs")
         for c_path, m_path in pairs:

@@ -69,7 +69,6 @@ def infill_using_normals(color_img, hole_mask, normal_map, max_steps=400, out=No
     color_img uint8 [H,W,3], hole_mask bool/uint8 [H,W] (True = fill), normal_map float32 [H,W,3] whose XY
     components give the march direction.  All CUDA tensors; returns a new uint8 [H,W,3] tensor."""
     import torch
-    from .depth_frames_helper import _ctx
     assert color_img.is_cuda and color_img.dtype == torch.uint8 and color_img.dim() == 3 and color_img.shape[2] == 3
     H, W = int(color_img.shape[0]), int(color_img.shape[1])
     color_img = color_img.contiguous()
@@ -78,11 +77,9 @@ def infill_using_normals(color_img, hole_mask, normal_map, max_steps=400, out=No
     assert tuple(hole.shape) == (H, W) and tuple(normal.shape) == (H, W, 3)
     if out is None:
         out = torch.empty_like(color_img)
-    ctx = _ctx(color_img.device.index or 0, W, H)
-    s = torch.cuda.current_stream(color_img.device)
-    ctx.check(_lib.load().mdvt_infill_using_normals(ctx.handle, color_img.data_ptr(), 3 * W, hole.data_ptr(), W,
-                                                    normal.data_ptr(), 12 * W, out.data_ptr(), 3 * W, int(max_steps),
-                                                    C.c_void_p(s.cuda_stream)))
+    _lib.shared_context(color_img.device, W, H).call("mdvt_infill_using_normals", color_img.data_ptr(), 3 * W, hole.data_ptr(), W,
+                                                     normal.data_ptr(), 12 * W, out.data_ptr(), 3 * W, int(max_steps),
+                                                     _lib.stream_arg(color_img.device))
     return out
 
 
@@ -93,7 +90,6 @@ def infill_using_mask_normals(img, hole_mask, infill_mask, max_steps=400, out=No
     (one half of side-by-side frames).  out None: a filled copy of img is returned; out given (may be img itself): filled in
     place after img has been copied into it."""
     import torch
-    from .depth_frames_helper import _ctx
     assert img.is_cuda and img.dtype == torch.uint8 and img.dim() in (3, 4) and img.shape[-1] == 3
     assert infill_mask.shape == img.shape and infill_mask.dtype == torch.uint8 and tuple(hole_mask.shape) == tuple(img.shape[:-1])
     if hole_mask.dtype == torch.bool:
@@ -108,13 +104,11 @@ def infill_using_mask_normals(img, hole_mask, infill_mask, max_steps=400, out=No
     batched = img.dim() == 4
     N = int(img.shape[0]) if batched else 1
     H, W = int(img.shape[-3]), int(img.shape[-2])
-    ctx = _ctx(img.device.index or 0, W, H)
-    s = torch.cuda.current_stream(img.device)
     stride = (lambda t: t.stride(0) if batched else 0)
-    ctx.check(_lib.load().mdvt_infill_using_mask_normals(ctx.handle, out.data_ptr(), out.stride(-3), stride(out),
-                                                         hole_mask.data_ptr(), hole_mask.stride(-2), stride(hole_mask),
-                                                         infill_mask.data_ptr(), infill_mask.stride(-3), stride(infill_mask),
-                                                         N, int(max_steps), C.c_void_p(s.cuda_stream)))
+    _lib.shared_context(img.device, W, H).call("mdvt_infill_using_mask_normals", out.data_ptr(), out.stride(-3), stride(out),
+                                               hole_mask.data_ptr(), hole_mask.stride(-2), stride(hole_mask),
+                                               infill_mask.data_ptr(), infill_mask.stride(-3), stride(infill_mask),
+                                               N, int(max_steps), _lib.stream_arg(img.device))
     return out
 
 
@@ -123,17 +117,14 @@ def touchly_depth(depth, touchly_max_depth=5, touchly_min_depth=0, zero_is_far=F
     variant used after a render, sr:689-691 / 825-829).  --touchly1 without a pose file is
     vconcat([color_frame, touchly_depth(decode(depth_rgb) * scale)]) (sr:548-552)."""
     import torch
-    from .depth_frames_helper import _ctx
     assert depth.is_cuda and depth.dtype == torch.float32 and depth.dim() == 2 and depth.stride(1) == 1   # rows may be strided
     H, W = int(depth.shape[0]), int(depth.shape[1])
     if out is None:
         out = torch.empty((H, W, 3), dtype=torch.uint8, device=depth.device)
     assert out.is_contiguous()
-    ctx = _ctx(depth.device.index or 0, W, H)
-    s = torch.cuda.current_stream(depth.device)
-    ctx.check(_lib.load().mdvt_touchly_depth(ctx.handle, depth.data_ptr(), 4 * depth.stride(0), out.data_ptr(), 3 * W,
-                                             float(touchly_max_depth), float(touchly_min_depth), int(bool(zero_is_far)),
-                                             C.c_void_p(s.cuda_stream)))
+    _lib.shared_context(depth.device, W, H).call("mdvt_touchly_depth", depth.data_ptr(), 4 * depth.stride(0), out.data_ptr(), 3 * W,
+                                                 float(touchly_max_depth), float(touchly_min_depth), int(bool(zero_is_far)),
+                                                 _lib.stream_arg(depth.device))
     return out
 
 
@@ -157,7 +148,6 @@ def convert_to_equirectangular(image, input_fov=100, out=None):
     centred and everything outside the input fov black.  Rows / images may be strided views (e.g. one eye of a
     side-by-side buffer); pixels must be packed RGB."""
     import torch
-    from .depth_frames_helper import _ctx
     assert image.is_cuda and image.dtype == torch.uint8 and image.dim() in (3, 4) and image.shape[-1] == 3
     assert image.stride(-1) == 1 and image.stride(-2) == 3, "pixels must be packed RGB"
     batched = image.dim() == 4
@@ -166,17 +156,14 @@ def convert_to_equirectangular(image, input_fov=100, out=None):
     if out is None:
         out = torch.empty(tuple(image.shape), dtype=torch.uint8, device=image.device)
     assert out.shape == image.shape and out.stride(-1) == 1 and out.stride(-2) == 3 and out.data_ptr() != image.data_ptr()
-    dev = image.device.index or 0
-    key = (dev, W, H, float(input_fov))
+    key = (_lib.device_index(image.device), W, H, float(input_fov))
     if key not in _equirect_cache:
         mx, my = equirect_tables(W, H, input_fov)
         _equirect_cache[key] = (torch.from_numpy(mx).to(image.device), torch.from_numpy(my).to(image.device))
     tx, ty = _equirect_cache[key]
-    ctx = _ctx(dev, W, H)
-    s = torch.cuda.current_stream(image.device)
-    ctx.check(_lib.load().mdvt_equirect_remap(ctx.handle, image.data_ptr(), image.stride(-3), image.stride(0) if batched else 0,
-                                              out.data_ptr(), out.stride(-3), out.stride(0) if batched else 0, N,
-                                              tx.data_ptr(), ty.data_ptr(), C.c_void_p(s.cuda_stream)))
+    _lib.shared_context(image.device, W, H).call("mdvt_equirect_remap", image.data_ptr(), image.stride(-3), image.stride(0) if batched else 0,
+                                                 out.data_ptr(), out.stride(-3), out.stride(0) if batched else 0, N,
+                                                 tx.data_ptr(), ty.data_ptr(), _lib.stream_arg(image.device))
     return out
 
 
@@ -184,17 +171,14 @@ def masked_blur(img, out=None):
     """Device version of the reference's masked_blur(img, ksize=(6,6), sigma=0) (sr:114-153): a 6x6 Gaussian that
     ignores pure black pixels.  uint8 CUDA [H,W,3] (rows may be strided) -> uint8 [H,W,3]."""
     import torch
-    from .depth_frames_helper import _ctx
     assert img.is_cuda and img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == 3
     assert img.stride(2) == 1 and img.stride(1) == 3, "pixels must be packed RGB"
     H, W = int(img.shape[0]), int(img.shape[1])
     if out is None:
         out = torch.empty((H, W, 3), dtype=torch.uint8, device=img.device)
     assert out.shape == img.shape and out.stride(2) == 1 and out.stride(1) == 3
-    ctx = _ctx(img.device.index or 0, W, H)
-    s = torch.cuda.current_stream(img.device)
-    ctx.check(_lib.load().mdvt_masked_blur(ctx.handle, img.data_ptr(), img.stride(0), out.data_ptr(), out.stride(0),
-                                           C.c_void_p(s.cuda_stream)))
+    _lib.shared_context(img.device, W, H).call("mdvt_masked_blur", img.data_ptr(), img.stride(0), out.data_ptr(), out.stride(0),
+                                               _lib.stream_arg(img.device))
     return out
 
 
@@ -260,7 +244,7 @@ class PreparedRender:
     """One pre-validated submission: launch() = one mdvt_render_stereo_batch call on a stream."""
 
     def __init__(self, renderer, n, params_arr, io, results, keepalive, device):
-        self._fn = renderer._L.mdvt_render_stereo_batch
+        self._fn = renderer.ctx._L.mdvt_render_stereo_batch      # (bound once: launch() is the benchmark's per-batch call)
         self._check = renderer.ctx.check
         self._h = renderer.ctx.handle
         self._n, self._arr, self._io, self._ioref = n, params_arr, io, C.byref(io)
@@ -426,14 +410,14 @@ class StereoRerenderer:
         cfg.max_depth = float(self.max_depth)
         for k in range(3):
             cfg.key_rgb[k] = self.key_rgb[k]
-        self.ctx.check(self._L.mdvt_set_config(self.ctx.handle, C.byref(cfg)))
+        self.ctx.call("mdvt_set_config", C.byref(cfg))
         self.near_clip = bool(near_clip)
-        self.ctx.check(self._L.mdvt_set_near_clip(self.ctx.handle, int(self.near_clip)))
+        self.ctx.call("mdvt_set_near_clip", int(self.near_clip))
         self._cfg, self._ctx2, self._side = cfg, None, None      # (finish_infill_mask_sbs's second context, made on first use)
 
     @property
     def _L(self):
-        return _lib.load()
+        return self.ctx._L
 
     # -- per-frame scalars (sr:515-541, 563-566, 707-721) -------------------------------------
     def frame_params(self, xfov=None, yfov=None, convergence_distance=None, transformation=None, vr180=False):
@@ -552,19 +536,19 @@ class StereoRerenderer:
         s = torch.cuda.current_stream(seed_sbs.device)
 
         if order == "heap":
-            self.ctx.check(self._L.mdvt_finish_infill_mask_heap_stereo(
-                self.ctx.handle, seed_sbs.data_ptr(), seed_sbs.data_ptr() + 3 * W, seed_sbs.stride(1), seed_sbs.stride(0),
+            self.ctx.call(
+                "mdvt_finish_infill_mask_heap_stereo", seed_sbs.data_ptr(), seed_sbs.data_ptr() + 3 * W, seed_sbs.stride(1), seed_sbs.stride(0),
                 out.data_ptr(), out.data_ptr() + 3 * W, out.stride(1), out.stride(0), N, rem.data_ptr() if rem is not None else None,
-                C.c_void_p(s.cuda_stream)))
+                C.c_void_p(s.cuda_stream))
             res = out[0] if single else out
             return (res, rem) if want_remaining else res
 
         def one_pass(ctx, a, b, stream, r):
             sd, o = seed_sbs[a:b], out[a:b]
-            ctx.check(self._L.mdvt_finish_infill_mask_stereo(
-                ctx.handle, sd.data_ptr(), sd.data_ptr() + 3 * W, sd.stride(1), sd.stride(0),
+            ctx.call(
+                "mdvt_finish_infill_mask_stereo", sd.data_ptr(), sd.data_ptr() + 3 * W, sd.stride(1), sd.stride(0),
                 o.data_ptr(), o.data_ptr() + 3 * W, o.stride(1), o.stride(0), b - a, int(max_rounds),
-                r.data_ptr() if r is not None else None, C.c_void_p(stream.cuda_stream)))
+                r.data_ptr() if r is not None else None, C.c_void_p(stream.cuda_stream))
 
         if N >= self.FINISH_SPLIT_FRAMES:
             # Two halves, two contexts, two streams (r04): the completion is ~260 dependent launches per pass whose marking half
@@ -576,7 +560,7 @@ class StereoRerenderer:
                 self._side = torch.cuda.Stream(device=seed_sbs.device)
             # (the configuration of the first context as it is now -- its key colour decides which pixels are filled -- not as it
             #  was when the second one was made: a caller may have changed it on the live context since)
-            self._ctx2.check(self._L.mdvt_set_config(self._ctx2.handle, C.byref(self._cfg)))
+            self._ctx2.call("mdvt_set_config", C.byref(self._cfg))
             h = N // 2
             # (the counters of both halves are allocated on the caller's stream BEFORE the side stream waits for it, and
             #  the second half's tensor is recorded on the side stream: the fill and the library's writes are ordered, and the
@@ -615,17 +599,15 @@ class StereoRerenderer:
             out = torch.empty(tuple(seed.shape), dtype=torch.uint8, device=seed.device)
         assert out.shape == seed.shape and out.stride(-1) == 1 and out.stride(-2) == 3
         rem = torch.empty(N, dtype=torch.int32, device=seed.device) if want_remaining else None
-        s = torch.cuda.current_stream(seed.device)
+        s = _lib.stream_arg(seed.device)
         if order == "heap":
-            self.ctx.check(self._L.mdvt_finish_infill_mask_heap(
-                self.ctx.handle, seed.data_ptr(), seed.stride(-3), seed.stride(0) if batched else 0, out.data_ptr(),
-                out.stride(-3), out.stride(0) if batched else 0, N, rem.data_ptr() if rem is not None else None,
-                C.c_void_p(s.cuda_stream)))
+            self.ctx.call(
+                "mdvt_finish_infill_mask_heap", seed.data_ptr(), seed.stride(-3), seed.stride(0) if batched else 0, out.data_ptr(),
+                out.stride(-3), out.stride(0) if batched else 0, N, rem.data_ptr() if rem is not None else None, s)
             return (out, rem) if want_remaining else out
-        self.ctx.check(self._L.mdvt_finish_infill_mask(
-            self.ctx.handle, seed.data_ptr(), seed.stride(-3), seed.stride(0) if batched else 0, out.data_ptr(),
-            out.stride(-3), out.stride(0) if batched else 0, N, int(max_rounds), rem.data_ptr() if rem is not None else None,
-            C.c_void_p(s.cuda_stream)))
+        self.ctx.call(
+            "mdvt_finish_infill_mask", seed.data_ptr(), seed.stride(-3), seed.stride(0) if batched else 0, out.data_ptr(),
+            out.stride(-3), out.stride(0) if batched else 0, N, int(max_rounds), rem.data_ptr() if rem is not None else None, s)
         return (out, rem) if want_remaining else out
 
     @staticmethod
@@ -654,10 +636,8 @@ class StereoRerenderer:
         if of_by_one is None:
             of_by_one = self.mode == _lib.MODE_MESH
         K = (C.c_double * 9)(*[params.K[k] for k in range(9)])
-        s = stream if stream is not None else torch.cuda.current_stream(dev)
-        self.ctx.check(self._L.mdvt_edge_filter(self.ctx.handle, depth_rgb.data_ptr(), 3 * W, K, params.depth_scale,
-                                                int(of_by_one), tri.data_ptr(), unused.data_ptr(),
-                                                C.c_void_p(s.cuda_stream)))
+        self.ctx.call("mdvt_edge_filter", depth_rgb.data_ptr(), 3 * W, K, params.depth_scale,
+                      int(of_by_one), tri.data_ptr(), unused.data_ptr(), _lib.stream_arg(dev, stream))
         return tri, unused
 
     def edge_point_pixels(self, depth_rgb, params, how: int = 0, stream=None):
@@ -668,9 +648,8 @@ class StereoRerenderer:
         H, W = self.H, self.W
         assert tuple(depth_rgb.shape) == (H, W, 3) and depth_rgb.is_cuda and depth_rgb.is_contiguous()
         px = torch.empty((H * W, 2, 2), dtype=torch.int32, device=depth_rgb.device)
-        s = stream if stream is not None else torch.cuda.current_stream(depth_rgb.device)
-        self.ctx.check(self._L.mdvt_edge_point_pixels(self.ctx.handle, C.byref(params), depth_rgb.data_ptr(), 3 * W, int(how),
-                                                      px.data_ptr(), C.c_void_p(s.cuda_stream)))
+        self.ctx.call("mdvt_edge_point_pixels", C.byref(params), depth_rgb.data_ptr(), 3 * W, int(how),
+                      px.data_ptr(), _lib.stream_arg(depth_rgb.device, stream))
         return px
 
     def close(self, release_cached_memory: bool = False):

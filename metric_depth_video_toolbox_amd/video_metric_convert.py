@@ -13,12 +13,12 @@ kernels are csrc/mdvt_metric_align.hip).  No CPU fallback.
 from __future__ import annotations
 
 import argparse
-import ctypes as C
 import os
 
 import numpy as np
 
-from . import _lib
+from . import _lib, video_io
+from .clip_io import ClipInputs, ClipOutput, check_video_decoder, check_video_encoder
 
 ENGINES = {"vda": 0, "depthcrafter": 1}                  # engine -> reconstruction style (include/mdvt_metric_align.h)
 FIT_FRAMES = 32                                          # vmc:107
@@ -60,17 +60,6 @@ def _planes(t, name: str, dtypes, like=None):
     return t
 
 
-def _device_index(dev) -> int:
-    """The GPU a tensor's device names: `cuda` without an index is the current device, not GPU 0."""
-    import torch
-    return torch.cuda.current_device() if dev.index is None else dev.index
-
-
-def _context(dev):
-    from . import ffv1_device
-    return ffv1_device._context(_device_index(dev))         # (the render size is irrelevant here too)
-
-
 def compute_scale_and_shift_full(prediction, target, mask=None, *, target_is_depth: bool = False, stream=None) -> Fit:
     """vmc:17-41: the least-squares scale and shift with target ~ scale * prediction + shift over all values of the float32 CUDA
     tensors [N, H, W] (or [H, W]; rows and frames may be strided), under an optional bool / uint8 mask of the same shape (a byte v
@@ -88,14 +77,13 @@ def compute_scale_and_shift_full(prediction, target, mask=None, *, target_is_dep
     if N * H * W >= 1 << 31:
         raise ValueError(f"{N} x {H} x {W} values are more than one fit takes (2^31 - 1)")
     dev = p.device
-    ctx = _context(dev)
     s = torch.cuda.current_stream(dev) if stream is None else stream
     with torch.cuda.stream(s):
         out = torch.empty(8, dtype=torch.float32, device=dev)
-    ctx.check(_lib.load().mdvt_scale_shift_fit(
-        ctx.handle, W, H, N, p.data_ptr(), 4 * p.stride(1), 4 * p.stride(0), t.data_ptr(), 4 * t.stride(1), 4 * t.stride(0),
+    _lib.shared_context(dev).call(                          # (the render size is irrelevant here too)
+        "mdvt_scale_shift_fit", W, H, N, p.data_ptr(), 4 * p.stride(1), 4 * p.stride(0), t.data_ptr(), 4 * t.stride(1), 4 * t.stride(0),
         int(bool(target_is_depth)), m.data_ptr() if m is not None else None, m.stride(1) if m is not None else 0,
-        m.stride(0) if m is not None else 0, out.data_ptr(), C.c_void_p(s.cuda_stream)))
+        m.stride(0) if m is not None else 0, out.data_ptr(), _lib.stream_arg(dev, s))
     return Fit(out)
 
 
@@ -123,7 +111,7 @@ def metric_depth_codes(relative, fit, max_depth, *, style: int = 0, out_size=Non
     ow, oh = (W, H) if out_size is None else (int(out_size[0]), int(out_size[1]))
     v = fit.values if isinstance(fit, Fit) else fit
     if not isinstance(v, torch.Tensor) or not v.is_cuda or v.dtype != torch.float32 or v.dim() != 1 or v.numel() not in (2, 8) \
-            or not v.is_contiguous() or _device_index(v.device) != _device_index(x.device):
+            or not v.is_contiguous() or _lib.device_index(v.device) != _lib.device_index(x.device):
         raise ValueError("fit must be a Fit, or a contiguous float32 CUDA tensor of 8 floats (a fit's) or of 2 (scale, shift)")
     ss = v[5:7] if v.numel() == 8 else v
     dev = x.device
@@ -131,16 +119,15 @@ def metric_depth_codes(relative, fit, max_depth, *, style: int = 0, out_size=Non
     if out is not None:
         from . import ffv1_device
         ffv1_device.check_out(out, N, oh, ow)
-        if _device_index(out.device) != _device_index(dev):
+        if _lib.device_index(out.device) != _lib.device_index(dev):
             raise ValueError(f"out is on {out.device}, the relative depth on {dev}")
     with torch.cuda.stream(s):
         codes = torch.empty((N, oh, ow, 3), dtype=torch.uint8, device=dev) if out is None else out
         depth = torch.empty((N, oh, ow), dtype=torch.float32, device=dev) if want_depth else None
-    ctx = _context(dev)
-    ctx.check(_lib.load().mdvt_metric_depth_codes(
-        ctx.handle, W, H, N, x.data_ptr(), 4 * x.stride(1), 4 * x.stride(0), ss.data_ptr(), int(style), float(max_depth), ow, oh,
+    _lib.shared_context(dev).call(
+        "mdvt_metric_depth_codes", W, H, N, x.data_ptr(), 4 * x.stride(1), 4 * x.stride(0), ss.data_ptr(), int(style), float(max_depth), ow, oh,
         codes.data_ptr(), codes.stride(1), codes.stride(0), int(bool(bgr)),
-        depth.data_ptr() if want_depth else None, 4 * ow, 4 * ow * oh, C.c_void_p(s.cuda_stream)))
+        depth.data_ptr() if want_depth else None, 4 * ow, 4 * ow * oh, _lib.stream_arg(dev, s))
     return (codes, depth) if want_depth else codes
 
 
@@ -208,23 +195,12 @@ def output_paths(color_video: str):
     return color_video + "_tmp_depth.mkv", color_video + "_depth.mkv"
 
 
-def _open_frames(path: str, what: str):
-    from . import video_io
-    from .clip import VideoFrames
-    if not os.path.isfile(path):
-        raise FileNotFoundError(f"{what} not found: {path}")
-    return VideoFrames(path) if video_io.is_matroska(path) else np.load(path, mmap_mode="r")
-
-
 def run(color_video: str, relative_depth: str, depth_video=None, metric_depth=None, max_depth=100, *, max_frames: int = -1,
         engine: str = "vda", batch: int = 16, video_encoder: str = "host", video_decoder: str = "host") -> str:
     """The script: relative_depth (a float32 [N, h, w] .npy dump, where the reference runs the model) is fitted against the RGB-coded
     depth_video (.mkv or a uint8 frame dump) or the float32 metric_depth dump, and `<color_video>_depth.mkv` is written at the
     colour video's size and frame rate (tmp -> rename, vmc:146-149).  Returns its path."""
     import torch
-    from . import video_io
-    from .basic_nomal_infill import _fetch
-    from .clip import VideoFrames, VideoSink, check_video_decoder, check_video_encoder, verify_and_move
     if engine not in ENGINES:
         raise ValueError(f"engine must be one of {tuple(ENGINES)}, got {engine!r}")
     if not (float(max_depth) > 0):
@@ -232,9 +208,10 @@ def run(color_video: str, relative_depth: str, depth_video=None, metric_depth=No
     if (depth_video is None) == (metric_depth is None):
         raise ValueError("give exactly one of --depth_video (RGB-coded reference) and --metric_depth (float32 dump)")
     check_video_encoder(video_encoder, True)
-    ref_path = depth_video if depth_video is not None else metric_depth
-    check_video_decoder(video_decoder, depth_video is not None and video_io.is_matroska(depth_video))
-    for path, what in ((color_video, "Color video"), (relative_depth, "Relative depth"), (ref_path, "Reference depth")):
+    coded = depth_video is not None
+    ref_path = depth_video if coded else metric_depth
+    check_video_decoder(video_decoder, coded and video_io.is_matroska(depth_video))
+    for path, what in ((color_video, "Color video"), (relative_depth, "Relative depth")):
         if not os.path.isfile(path):
             raise FileNotFoundError(f"{what} not found: {path}")
     if not video_io.is_matroska(color_video):
@@ -242,12 +219,9 @@ def run(color_video: str, relative_depth: str, depth_video=None, metric_depth=No
     rel = np.load(relative_depth, mmap_mode="r")
     if rel.ndim != 3 or rel.dtype != np.float32:
         raise ValueError(f"{relative_depth}: float32 [N, h, w] expected")
-    ref = _open_frames(ref_path, "Reference depth")
-    opened = [ref] if isinstance(ref, VideoFrames) else []
-    ctx = out = None
     tmp, final = output_paths(color_video)
-    try:
-        coded = depth_video is not None
+    with ClipInputs() as inp:
+        ref = inp.open(ref_path, "depth_video", FileNotFoundError(f"Reference depth not found: {ref_path}"))
         if coded and not (ref.ndim == 4 and ref.shape[3] == 3 and ref.dtype == np.uint8):
             raise ValueError(f"{ref_path}: uint8 [N, H, W, 3] expected")
         if not coded and not (ref.ndim == 3 and ref.dtype == np.float32):
@@ -264,44 +238,18 @@ def run(color_video: str, relative_depth: str, depth_video=None, metric_depth=No
         if n_fit < 1:
             raise ValueError(f"{ref_path} holds no frame")
         batch = max(1, int(batch))
-        dev = torch.device("cuda", torch.cuda.current_device())
-        if video_decoder == "device" or video_encoder == "device":
-            ctx = _lib.Context(dev.index, 16, 16)
-        if video_decoder == "device" and opened:
-            ref.use_device_decoder("depth_video")
+        inp.on_device(torch.device("cuda", torch.cuda.current_device()), video_decoder, video_encoder)
+        dev = inp.dev
         with torch.cuda.device(dev):
             d_rel = torch.from_numpy(np.ascontiguousarray(rel[:n_fit])).to(dev)
-            d_ref = _fetch(ref, 0, n_fit, dev, ctx if video_decoder == "device" else None) if coded \
-                else torch.from_numpy(np.ascontiguousarray(ref[:n_fit])).to(dev)
+            d_ref = inp.fetch(ref, 0, n_fit) if coded else torch.from_numpy(np.ascontiguousarray(ref[:n_fit])).to(dev)
             fit = fit_reference(d_rel, d_ref, max_depth, engine=engine)
             scale, shift = fit.scale_shift()
             print("scale:", scale, "shift:", shift)                                          # vmc:129
-            out = VideoSink(tmp, W, H, fps, encoder=video_encoder)
-            for a in range(0, n, batch):
-                b = min(a + batch, n)
-                d_rel = torch.from_numpy(np.ascontiguousarray(rel[a:b])).to(dev)
-                codes = metric_depth_codes(d_rel, fit, max_depth, style=ENGINES[engine], out_size=(W, H))
-                if video_encoder == "device":
-                    out.append_packets(out.enqueue(ctx, codes), a)
-                else:
-                    out.write_from(codes.cpu().numpy(), a, b - a)
-            out.close()
-            out = None
-    except BaseException:
-        if out is not None:                                  # a failure between open and close: no half-written tmp file stays
-            try:
-                out.close()
-            except Exception:
-                pass
-            if os.path.exists(tmp):
-                os.remove(tmp)
-        raise
-    finally:
-        if ctx is not None:
-            ctx.close()
-        for f in opened:
-            f.close()
-    verify_and_move(tmp, n, final)
+            with ClipOutput(tmp, final, n, (H, W, 3), fps, video_encoder, inp.ctx) as out:
+                for a in range(0, n, batch):
+                    d_rel = torch.from_numpy(np.ascontiguousarray(rel[a:min(a + batch, n)])).to(dev)
+                    out.store(metric_depth_codes(d_rel, fit, max_depth, style=ENGINES[engine], out_size=(W, H)), a)
     return final
 
 

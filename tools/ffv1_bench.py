@@ -50,12 +50,12 @@ def main(argv=None):
     if a.decode:
         return decode_main(a)
     import torch
-    from metric_depth_video_toolbox_amd import ffv1_device, video_io
+    from metric_depth_video_toolbox_amd import _lib, ffv1_device, video_io
     rng = np.random.default_rng(1)
     pool = ThreadPoolExecutor(a.host_threads)
 
     def device(frames, slices):
-        p = ffv1_device.enqueue(ffv1_device._context(0), frames, slices=slices)
+        p = ffv1_device.enqueue(_lib.shared_context(0), frames, slices=slices)
         pkts = p.collect()
         if p.host_frames:
             raise SystemExit(f"{p.host_frames} of {len(pkts)} frames were flagged by the device and re-encoded on the host "
@@ -97,10 +97,10 @@ def main(argv=None):
 def decode_main(a):
     import tempfile
     import torch
-    from metric_depth_video_toolbox_amd import clip, ffv1_device, video_io
+    from metric_depth_video_toolbox_amd import _lib, clip, ffv1_device, video_io
     rng = np.random.default_rng(1)
     pool = ThreadPoolExecutor(a.host_threads)
-    ctx = ffv1_device._context(0)
+    ctx = _lib.shared_context(0)
     rows = []
     nmax = max(int(v) for v in a.frames.split(","))
     tmp = tempfile.mkdtemp(prefix="ffv1_bench_")
