@@ -32,6 +32,9 @@ SYMBOLS = ("mdvt_version", "mdvt_create", "mdvt_destroy", "mdvt_last_error", "md
 # the entry points include/mdvt_ffv1_decode.h declares (the device FFV1 decoder): bound like the others, listed apart from mdvt.h's
 DECODE_SYMBOLS = ("mdvt_decode_video_frames", "mdvt_ffv1_decode_supported")
 
+# the entry points include/mdvt_ffv1_stream_decode.h declares (inter-coded and Golomb-Rice FFV1 streams), listed apart in the same way
+STREAM_DECODE_SYMBOLS = ("mdvt_decode_video_stream", "mdvt_ffv1_stream_decode_supported", "mdvt_ffv1_packet_is_key")
+
 # the entry point include/mdvt_convergence.h declares (per-frame convergence depths), listed apart from mdvt.h's in the same way
 CONVERGENCE_SYMBOLS = ("mdvt_convergence_depths",)
 
@@ -167,6 +170,13 @@ def load():
                                           C.c_size_t, C.c_int, vp, vp]
     L.mdvt_ffv1_decode_supported.restype = C.c_char_p
     L.mdvt_ffv1_decode_supported.argtypes = [C.c_char_p, C.c_size_t]
+    L.mdvt_decode_video_stream.restype = C.c_int
+    L.mdvt_decode_video_stream.argtypes = [vp, C.c_int, C.c_int, C.c_char_p, C.c_size_t, vp, C.c_uint64, vp, vp, C.c_int, C.c_int, vp,
+                                          C.c_size_t, C.c_size_t, C.c_int, vp, vp]
+    L.mdvt_ffv1_stream_decode_supported.restype = C.c_char_p
+    L.mdvt_ffv1_stream_decode_supported.argtypes = [C.c_char_p, C.c_size_t]
+    L.mdvt_ffv1_packet_is_key.restype = C.c_int
+    L.mdvt_ffv1_packet_is_key.argtypes = [C.c_char_p, C.c_size_t]
     L.mdvt_convergence_depths.restype = C.c_int
     L.mdvt_convergence_depths.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t, C.c_size_t, C.c_int, vp, C.c_size_t, C.c_size_t, C.c_int,
                                          C.c_int, C.c_int, C.c_double, vp, vp, vp]

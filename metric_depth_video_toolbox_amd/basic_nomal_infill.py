@@ -19,7 +19,7 @@ import argparse
 import numpy as np
 
 from . import _lib
-from .clip_io import ClipInputs, ClipOutput, check_video_decoder, check_video_encoder, video_parts
+from .clip_io import VIDEO_DECODERS, ClipInputs, ClipOutput, check_video_decoder, check_video_encoder, video_parts
 
 
 def _packed(t):
@@ -132,10 +132,11 @@ def build_parser():
     p.add_argument("--sbs_mask_video", type=str, required=True, help="side by side infill mask video (.mkv, or a .npy frame dump), or the matching .txt list")
     p.add_argument("--max_frames", default=-1, type=int, help="quit after max_frames nr of frames", required=False)
     p.add_argument("--batch", default=8, type=int, help="not a reference flag: frames per device batch")
-    p.add_argument("--video_decoder", choices=("host", "device"), default="host",
+    p.add_argument("--video_decoder", choices=VIDEO_DECODERS, default="host",
                    help="not a reference flag: where the .mkv inputs are FFV1-decoded -- 'host' (default) or 'device' (on the GPU, the "
                         "same bytes; only the compressed packets are copied to the device; a stream the device does not decode is "
-                        "read on the host). Not with .npy inputs")
+                        "read on the host) or 'device_all' (as 'device', and Golomb-Rice or inter-coded FFV1, FFmpeg's default, is "
+                        "decoded on the GPU as well). Not with .npy inputs")
     p.add_argument("--video_encoder", choices=("host", "device"), default="host",
                    help="not a reference flag: where the .mkv output is FFV1-encoded -- 'host' (default) or 'device' (on the GPU, the "
                         "same bytes). Not with .npy inputs")

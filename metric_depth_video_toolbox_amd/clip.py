@@ -311,6 +311,24 @@ def render_clip(depth_frames, color_frames, out_sbs, out_mask, clip: D.ClipParam
         dec_ctx = Context(r.device, 16, 16)
     dec_host_frames = [0]
 
+    def packets_of(frames, a, n):
+        """(the packets the device decodes for frames a ... a + n - 1, first_out) -- first_out None: mdvt_decode_video_frames, one
+        packet per frame; else mdvt_decode_video_stream, the packets from the key frame in front of frame a on --, or None when the
+        file's key frames turn out to lie too far apart: it is read on the host from then on."""
+        if not frames.device_decode:
+            return None
+        if not frames.stream_decode:
+            return frames.read_packets(a, n), None
+        got = frames.read_stream_packets(a, n)
+        if got is None:
+            frames.host_after_far_key_frame()
+        return got
+
+    def enqueue_packets(pk, frames, out, stream):
+        if pk[1] is None:
+            return ffv1_device.enqueue_decode(dec_ctx, pk[0], frames.config, W, H, out=out, stream=stream)
+        return ffv1_device.enqueue_decode_stream(dec_ctx, pk[0], frames.config, W, H, first_out=pk[1], out=out, stream=stream)
+
     f_depth, f_color = _RawFrames(depth_frames, False), _RawFrames(color_frames, False)
     f_sbs, f_mask = _RawFrames(out_sbs, True), _RawFrames(out_mask, True)
     f_zrgb = _RawFrames(out_depth_rgb, True) if out_depth_rgb is not None else None
@@ -324,23 +342,19 @@ def render_clip(depth_frames, color_frames, out_sbs, out_mask, clip: D.ClipParam
         st["in_done"].synchronize()                 # the H2D copies that last read these pinned buffers are done
         t_l1 = time.perf_counter()
         st["p_d"] = st["p_c"] = None
-        if same_video and dec_d:                    # one video, decoded once on the device
-            st["p_d"] = depth_frames.read_packets(a, n)
-            jobs = []
-        elif same_video:                            # sr:508-509 on one video: decode it once
-            for j in fan(f_depth.read_into, st["h_d"][:n].numpy(), a, n, 2):
-                j.result()
-            np.copyto(st["h_c"][:n].numpy(), st["h_d"][:n].numpy())
-            jobs = []
+        jobs = []
+        if same_video:                              # one video, decoded once: on the device, or on the host (sr:508-509)
+            st["p_d"] = packets_of(depth_frames, a, n) if dec_d else None
+            if st["p_d"] is None:
+                for j in fan(f_depth.read_into, st["h_d"][:n].numpy(), a, n, 2):
+                    j.result()
+                np.copyto(st["h_c"][:n].numpy(), st["h_d"][:n].numpy())
         else:
-            jobs = []
-            if dec_c:
-                st["p_c"] = color_frames.read_packets(a, n)
-            else:
+            st["p_c"] = packets_of(color_frames, a, n) if dec_c else None
+            if st["p_c"] is None:
                 jobs += fan(f_color.read_into, st["h_c"][:n].numpy(), a, n, 2)
-            if dec_d:
-                st["p_d"] = depth_frames.read_packets(a, n)
-            else:
+            st["p_d"] = packets_of(depth_frames, a, n) if dec_d else None
+            if st["p_d"] is None:
                 jobs += fan(f_depth.read_into, st["h_d"][:n].numpy(), a, n, 2)
         for j in jobs:
             j.result()
@@ -434,19 +448,19 @@ def render_clip(depth_frames, color_frames, out_sbs, out_mask, clip: D.ClipParam
             s_in.wait_event(st["render_done"])      # device inputs free again
             pend = []
             if st["p_d"] is not None:               # packets -> device -> frames, straight into the batch's input tensors
-                pend.append(ffv1_device.enqueue_decode(dec_ctx, st["p_d"], depth_frames.config, W, H, out=st["d_d"][:n], stream=s_in))
+                pend.append(enqueue_packets(st["p_d"], depth_frames, st["d_d"][:n], s_in))
             else:
                 st["d_d"][:n].copy_(st["h_d"][:n], non_blocking=True)
             if st["p_c"] is not None:
-                pend.append(ffv1_device.enqueue_decode(dec_ctx, st["p_c"], color_frames.config, W, H, out=st["d_c"][:n], stream=s_in))
-            elif same_video and dec_d:
+                pend.append(enqueue_packets(st["p_c"], color_frames, st["d_c"][:n], s_in))
+            elif same_video and st["p_d"] is not None:
                 st["d_c"][:n].copy_(st["d_d"][:n], non_blocking=True)
             else:
                 st["d_c"][:n].copy_(st["h_c"][:n], non_blocking=True)
             for p in pend:                          # a frame the device flagged is decoded on the host (or raises the host's error)
                 p.collect()
                 dec_host_frames[0] += p.host_frames
-            if same_video and dec_d and pend[0].host_frames:
+            if same_video and pend and pend[0].host_frames:
                 st["d_c"][:n].copy_(st["d_d"][:n], non_blocking=True)
             st["p_d"] = st["p_c"] = None
             st["in_done"].record(s_in)
@@ -604,7 +618,9 @@ def run(depth_path: str, color_path: Optional[str], *, batch: int = 16, create_s
     "device" (the .mkv outputs are FFV1-encoded on the GPU: the same bytes; refused for .npy outputs, which are not encoded).
     video_decoder: "host" (default) or "device" (the .mkv inputs' packets are copied to the GPU and decoded there, straight into
     the batch's input tensors: the same bytes; an input outside the device's stream class is read by the host decoder, with one
-    line on stderr; refused for .npy inputs, which are not decoded).
+    line on stderr; refused for .npy inputs, which are not decoded) or "device_all" (as "device", and inputs of the stream decoder's
+    class -- Golomb-Rice or range coder with inter frames, FFmpeg's default -- are decoded on the GPU too, each batch from the key
+    frame in front of it).
     find_convergence: rank 0 first runs find_convergence_depth.find on the whole depth video (under convergence_mask_video's white
     pixels, if given) and its side-car becomes the convergence_file -- what movie_2_3D.py:408-419 does between its steps 4 and 5;
     refused together with a convergence_file."""
@@ -624,10 +640,10 @@ def run(depth_path: str, color_path: Optional[str], *, batch: int = 16, create_s
         color = depth                                                                                  # sr:508-509
     else:
         color = VideoFrames(color_path) if video_io.is_matroska(color_path) else np.load(color_path, mmap_mode="r")
-    if video_decoder == "device":
-        depth.use_device_decoder("depth video")
+    if video_decoder in ("device", "device_all"):
+        depth.use_device_decoder("depth video", video_decoder)
         if color is not depth and isinstance(color, VideoFrames):
-            color.use_device_decoder("color video")
+            color.use_device_decoder("color video", video_decoder)
     if depth.ndim != 4 or depth.shape[3] != 3 or depth.dtype != np.uint8:
         raise ValueError("depth dump must be uint8 [N, H, W, 3]")
     if color.shape != depth.shape:

@@ -76,7 +76,9 @@ class VideoFrames:
     seek (free in an intra-only stream; an inter-coded one -- FFmpeg's default, a key frame every 12 -- decodes forward from the
     last key frame, so it gets ONE decoder and all the slice threads instead of several decoders leap-frogging)."""
 
-    def __init__(self, path: str, readers: int = 2):
+    def __init__(self, path: str, readers: int = 2, threads: Optional[int] = None):
+        """threads: slice threads per reader (default: the usable cores shared among the readers; an inter-coded file's one reader
+        gets one per slice, capped at the cores)."""
         from . import video_io
         first = video_io.VideoReader(path)
         self.path, self.fps, self.info = path, first.fps, first.info
@@ -84,30 +86,61 @@ class VideoFrames:
         self.dtype, self.ndim = np.dtype(np.uint8), 4
         n = max(1, int(readers)) if first.info.intra else 1
         cores = _usable_cores()
-        first.threads = max(1, cores // (2 * n)) if n > 1 else 0
+        first.threads = int(threads) if threads is not None else max(1, cores // (2 * n)) if n > 1 else 0
         self._readers = [first] + [video_io.VideoReader(path, threads=first.threads) for _ in range(n - 1)]
         self._pos = [0] * n
         self._busy = [False] * n
         self._cv = threading.Condition()
         # render_clip decodes this file's frames on the device (use_device_decoder): it asks for packets, not for frames
         self.device_decode = False
+        # ... with mdvt_decode_video_stream (inter-coded / Golomb-Rice files, video_decoder "device_all"): read_stream_packets
+        self.stream_decode = False
         self._packet_reader = None
 
     def __len__(self):
         return self.shape[0]
 
-    def use_device_decoder(self, name: str = "input") -> bool:
+    def use_device_decoder(self, name: str = "input", video_decoder: str = "device") -> bool:
         """Switches render_clip's reads of this file to the device decoder (ffv1_device) if the stream is in its class; if not,
-        says so on stderr and leaves the host decoder in charge (files the reference made must keep working)."""
+        says so on stderr and leaves the host decoder in charge (files the reference made must keep working).  "device_all" also
+        takes the stream decoder's class (Golomb-Rice, inter frames: what FFmpeg and OpenCV write by default) to the device."""
         import sys
         from . import ffv1_device
         self.config = self._readers[0].config_record()
+        self.decoder_name = name
         why = ffv1_device.supported(self.info, self.config)
+        if why is not None and video_decoder == "device_all":
+            why = ffv1_device.stream_supported(self.info, self.config)
+            self.stream_decode = why is None
         if why is not None:
-            print(f"video_decoder device: {name} {self.path} is decoded on the host ({why})", file=sys.stderr)
+            print(f"video_decoder {video_decoder}: {name} {self.path} is decoded on the host ({why})", file=sys.stderr)
             return False
         self.device_decode = True
         return True
+
+    def read_stream_packets(self, a: int, n: int):
+        """For a file of the stream decoder's class: (the packets from the last key frame at or before frame a up to frame
+        a + n - 1, the index of frame a among them = mdvt_decode_video_stream's first_out).  The key frame is looked for at most
+        KEY_SCAN_FRAMES frames back (two bytes read per frame: VideoReader.packet_is_key); None when there is none that near: the
+        caller gives the file to the host reader (host_after_far_key_frame)."""
+        self.read_packets(a, 0)                              # (makes the packet reader)
+        r = self._packet_reader
+        lo = max(0, a - KEY_SCAN_FRAMES)
+        k = a
+        with r[2]:
+            while not r[0].packet_is_key(k):
+                if k == lo:
+                    return None
+                k -= 1
+        return self.read_packets(k, a - k + n), a - k
+
+    def host_after_far_key_frame(self):
+        """Hands a file whose key frames lie further apart than KEY_SCAN_FRAMES back to the host decoder, with one stderr line."""
+        import sys
+        if self.device_decode:
+            self.device_decode = self.stream_decode = False
+            print(f"video_decoder device_all: {self.decoder_name} {self.path} is decoded on the host (intra: a key-frame distance of more "
+                  f"than {KEY_SCAN_FRAMES} frames; the device decodes a call's frames from the key frame before them)", file=sys.stderr)
 
     def read_packets(self, a: int, n: int):
         """The stored FFV1 packets of frames a ... a + n - 1 (a reader of its own: packets are not decoded, so nothing is shared
@@ -119,7 +152,7 @@ class VideoFrames:
         r = self._packet_reader
         with r[2]:
             if r[1] != a:
-                r[0].seek(a)
+                r[0].seek_packet(a) if self.stream_decode else r[0].seek(a)
             out = []
             for i in range(n):
                 pkt = r[0].next_packet()
@@ -188,7 +221,14 @@ class VideoFrames:
 VIDEO_ENCODERS = ("host", "device")
 
 
-VIDEO_DECODERS = ("host", "device")
+# "device": the class this project's writer makes goes to the device (mdvt_decode_video_frames).  "device_all": that, and the
+# stream decoder's class as well (mdvt_decode_video_stream: Golomb-Rice or range coder with inter frames).  Anything else: the host.
+VIDEO_DECODERS = ("host", "device", "device_all")
+
+# How far back fetch() looks for the key frame in front of a batch of a "device_all" file: FFmpeg's default distance is 12, twice
+# that must work; 64 keeps the frames decoded for their state alone below the size of a usual batch of 64.  State is not carried
+# from one fetch to the next, so every batch pays for the frames between its key frame and its first frame.
+KEY_SCAN_FRAMES = 64
 
 
 class VideoSink:
@@ -424,11 +464,11 @@ def check_video_encoder(video_encoder: str, video: bool):
 
 
 def check_video_decoder(video_decoder: str, video: bool) -> str:
-    """ValueError unless video_decoder is "host" or "device", and "device" only where the inputs are .mkv files."""
+    """ValueError unless video_decoder is one of VIDEO_DECODERS, and a device decoder only where the inputs are .mkv files."""
     if video_decoder not in VIDEO_DECODERS:
         raise ValueError(f"video_decoder must be one of {VIDEO_DECODERS}, got {video_decoder!r}")
-    if video_decoder == "device" and not video:
-        raise ValueError("--video_decoder device decodes .mkv inputs: a .npy input is a raw frame dump, which is not decoded "
+    if video_decoder != "host" and not video:
+        raise ValueError(f"--video_decoder {video_decoder} decodes .mkv inputs: a .npy input is a raw frame dump, which is not decoded "
                          "(use the default --video_decoder host)")
     return video_decoder
 
@@ -468,8 +508,16 @@ def fetch(frames, a: int, b: int, dev, dec_ctx):
     out = torch.empty((b - a, H, W, 3), dtype=torch.uint8, device=dev)
     for p, b0 in parts:
         lo, hi = max(a, b0), min(b, b0 + len(p))
-        if lo < hi:
+        if lo >= hi:
+            continue
+        if not p.stream_decode:
             ffv1_device.enqueue_decode(dec_ctx, p.read_packets(lo - b0, hi - lo), p.config, W, H, out=out[lo - a:hi - a]).collect()
+            continue
+        got = p.read_stream_packets(lo - b0, hi - lo)
+        if got is None:                                      # key frames too far apart: this file is the host's from here on
+            p.host_after_far_key_frame()
+            return torch.from_numpy(np.array(frames[a:b])).to(dev)
+        ffv1_device.enqueue_decode_stream(dec_ctx, got[0], p.config, W, H, first_out=got[1], out=out[lo - a:hi - a]).collect()
     return out
 
 
@@ -491,15 +539,16 @@ class ClipInputs:
 
     def on_device(self, dev, video_decoder: str = "host", video_encoder: str = "host"):
         """Reads go to `dev` from here on.  With a "device" codec this makes the context the decoder and the encoder run in (its
-        own workspace; the render size does not matter to them); video_decoder "device" switches every video part over."""
+        own workspace; the render size does not matter to them); video_decoder "device" / "device_all" switches every video part
+        over whose stream is in that decoder's class."""
         self.dev = dev
-        if video_decoder == "device" or video_encoder == "device":
+        if video_decoder in ("device", "device_all") or video_encoder == "device":
             self.ctx = _lib.Context(dev.index, 16, 16)
-        if video_decoder == "device":
+        if video_decoder in ("device", "device_all"):
             self.dec_ctx = self.ctx
             for name, frames in self.opened:
                 for p, _ in video_parts(frames):
-                    p.use_device_decoder(name)
+                    p.use_device_decoder(name, video_decoder)
 
     def fetch(self, frames, a: int, b: int):
         return fetch(frames, a, b, self.dev, self.dec_ctx)

@@ -4,6 +4,7 @@
 #include "mdvt_context.h"
 #include "mdvt_ffv1_core.h"
 #include "mdvt_ffv1_decode.h"
+#include "mdvt_ffv1_stream_decode.h"
 #include "mdvt_convergence.h"
 #include "mdvt_metric_align.h"
 #include "mdvt_infill_adapter.h"
@@ -513,6 +514,68 @@ int mdvt_decode_video_frames(mdvt_ctx* c, int width, int height, const uint8_t* 
         MDVT_HIP(c, hipMemsetAsync(a.claims, 0, (size_t)nf * spf * sizeof(uint32_t), s));
         MDVT_HIP(c, mdvt::launch_ffv1_decode(a, tab, s));
     }
+    return MDVT_OK;
+}
+
+const char* mdvt_ffv1_stream_decode_supported(const uint8_t* h_config, size_t config_size)
+{
+    mdvt_ffv1::StreamClass2 sc{};
+    return mdvt_ffv1::parse_stream_class2(h_config, config_size, &sc);
+}
+
+int mdvt_ffv1_packet_is_key(const uint8_t* h_packet, size_t size)
+{
+    if (!h_packet || size < 3) return -1;
+    return mdvt_ffv1::key_frame_bit(h_packet[0], h_packet[1]);
+}
+
+// Consecutive FFV1 packets in device memory -> frames, the context state carried along each key-frame run
+// (mdvt_ffv1_stream_decode.hip).  One pass: a run cannot be cut where the workspace budget would cut it.
+int mdvt_decode_video_stream(mdvt_ctx* c, int width, int height, const uint8_t* h_config, size_t config_size, const uint8_t* d_packets,
+                             uint64_t packets_bytes, const uint64_t* d_offsets, const uint32_t* d_sizes, int n_packets, int first_out,
+                             uint8_t* d_dst, size_t pitch, size_t frame_stride, int order, uint32_t* d_status, void* stream)
+{
+    if (!c) return MDVT_ERR_INVALID_ARG;
+    if (!h_config || !d_packets || !d_offsets || !d_sizes || !d_dst || !d_status) return fail(c, MDVT_ERR_INVALID_ARG, "NULL buffer");
+    if (width < 1 || height < 1) return fail(c, MDVT_ERR_INVALID_ARG, "bad frame size %d x %d", width, height);
+    if (order != 0 && order != 1) return fail(c, MDVT_ERR_INVALID_ARG, "order must be 0 (RGB) or 1 (BGR), got %d", order);
+    if (n_packets < 1) return fail(c, MDVT_ERR_INVALID_ARG, "n_packets must be >= 1");
+    if (first_out < 0 || first_out >= n_packets) return fail(c, MDVT_ERR_INVALID_ARG, "first_out %d outside [0, n_packets = %d)", first_out, n_packets);
+    if (pitch < (size_t)width * 3u) return fail(c, MDVT_ERR_INVALID_ARG, "pitch smaller than one row");
+    if (n_packets - first_out > 1 && frame_stride < pitch * (size_t)height) return fail(c, MDVT_ERR_INVALID_ARG, "frame_stride smaller than one frame");
+    mdvt_ffv1::StreamClass2 sc{};
+    if (const char* why = mdvt_ffv1::parse_stream_class2(h_config, config_size, &sc))
+        return fail(c, MDVT_ERR_UNSUPPORTED, "FFV1 stream outside the device stream decoder's class: %s", why);
+    if (sc.nh > width || sc.nv > height)
+        return fail(c, MDVT_ERR_UNSUPPORTED, "FFV1 stream outside the device stream decoder's class: num_h_slices / num_v_slices %d x %d for a frame of %d x %d",
+                    sc.nh, sc.nv, width, height);
+    if ((uint64_t)width * (uint64_t)height > ((uint64_t)1 << 28))
+        return fail(c, MDVT_ERR_UNSUPPORTED, "frame too large for the device FFV1 decoder (%d x %d)", width, height);
+    const int line_stride = (width + sc.nh - 1) / sc.nh + 2;           // the widest slice, its left and right neighbours
+    if (mdvt::ffv1_stream_static_lds_bytes() + mdvt::ffv1_stream_lds_bytes(sc.coder, line_stride) > (size_t)160 * 1024)
+        return fail(c, MDVT_ERR_UNSUPPORTED, "a slice of %d pixels' width does not fit the device FFV1 decoder's row buffers (num_h_slices %d)",
+                    line_stride - 2, sc.nh);
+    const int spf = sc.nh * sc.nv;
+    const size_t per_frame = (size_t)spf * 3 * sizeof(uint32_t) + sizeof(uint32_t);
+    if (slots_afforded(c, per_frame, n_packets) < n_packets)
+        return fail(c, MDVT_ERR_UNSUPPORTED, "%d packets of %d slices pass the workspace budget: split the call at a key frame", n_packets, spf);
+    DeviceGuard g(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    MDVT_HIP(c, scratch_reserve(c, c->scratch[SCR_FFV1_STREAM], (size_t)n_packets * per_frame, s));
+    static const mdvt::Ffv1StateTables tab = mdvt::ffv1_default_states();
+    mdvt::Ffv1StreamArgs a{};
+    a.packets = d_packets; a.packets_bytes = packets_bytes;
+    a.offsets = reinterpret_cast<const unsigned long long*>(d_offsets); a.sizes = d_sizes;
+    a.n_frames = n_packets; a.first_out = first_out;
+    a.W = width; a.H = height; a.nh = sc.nh; a.nv = sc.nv; a.ec = sc.ec; a.coder = sc.coder; a.micro = sc.micro;
+    a.dst = d_dst; a.pitch = pitch; a.frame_stride = frame_stride; a.ri = order == 1 ? 2 : 0; a.bi = order == 1 ? 0 : 2;
+    a.status = d_status;
+    a.table = c->scratch[SCR_FFV1_STREAM].as<uint32_t>();
+    a.claims = a.table + (size_t)2 * n_packets * spf;
+    a.kind = a.claims + (size_t)n_packets * spf;
+    a.line_stride = line_stride;
+    MDVT_HIP(c, hipMemsetAsync(a.claims, 0, (size_t)n_packets * spf * sizeof(uint32_t), s));
+    MDVT_HIP(c, mdvt::launch_ffv1_stream_decode(a, tab, s));
     return MDVT_OK;
 }
 

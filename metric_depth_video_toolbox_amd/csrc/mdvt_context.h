@@ -53,6 +53,7 @@ enum ScratchId {
     SCR_CONV,                         // mdvt_convergence_depths: per frame of a launch set its chunk sums; with a mask also the ballot words, codes and unit counts
     SCR_FIT,                          // mdvt_scale_shift_fit: the running totals (32 B), then per chunk of a launch set its five sums
     SCR_ADAPTER,                      // mdvt_adapter_composite_eye: the listed-pixel workspace of one eye-sized image, its marks image, grown plane and row-blurred plane
+    SCR_FFV1_STREAM,                  // mdvt_decode_video_stream: per slice of the call its offset, payload bytes and cell claim, per frame its kind
     SCR_COUNT
 };
 

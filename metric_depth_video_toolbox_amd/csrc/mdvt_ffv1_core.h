@@ -8,6 +8,11 @@
 // 8 bits, no alpha, the default 666-context quantisation tables.  Nothing read from a packet steers a loop or an address: every
 // loop runs to a count fixed by the frame's geometry, bytes past a slice's end read as zero and are counted (the host's overread),
 // a symbol's exponent loop has the RFC's bound, and a context index is bounded by the quantisation arithmetic (|ctx| <= 665).
+//
+// The second half (BitReader, the Golomb-Rice pieces, ChainDec, parse_stream_class2) serves the stream decoder
+// (mdvt_ffv1_stream_decode.hip): version 3 with coder_type 0 or 1 and inter frames, whose context state carries from frame to
+// frame of a key-frame run.  The same rule holds there: a run length is consumed sample by sample inside the row's loop,
+// run_index is held inside kLog2Run whatever the bits say, and bits past a slice's end read as zero (the host reader's BitReader).
 #pragma once
 
 #include <stddef.h>
@@ -306,5 +311,317 @@ inline const char* parse_stream_class(const uint8_t* data, size_t size, StreamCl
     out->version = version; out->micro = micro; out->nh = nh; out->nv = nv; out->ec = ec;
     return nullptr;
 }
+
+// ---- the stream decoder's class (mdvt_decode_video_stream): the same record with coder_type 0 or 1 and intra 0 or 1.  The walk is
+// parse_stream_class's, restated so that the function above stays as it is. ----
+struct StreamClass2 { int version, micro, nh, nv, ec, coder, intra; };
+
+// -> nullptr and *out when the stream decoder decodes the stream; else the reason (a static string naming the field)
+inline const char* parse_stream_class2(const uint8_t* data, size_t size, StreamClass2* out)
+{
+    if (!data || size < 6 || size > (1u << 20)) return "configuration record: missing or of an impossible size";
+    uint32_t crc = 0;
+    for (size_t i = 0; i < size; ++i) crc = (crc << 8) ^ crc_table_entry((crc >> 24) ^ data[i]);
+    uint8_t zero[256], one[256], state[32];
+    uint16_t next[256];
+    default_states(zero, one);
+    for (int k = 0; k < 256; ++k) next[k] = (uint16_t)(zero[k] | (one[k] << 8));
+    for (int k = 0; k < 32; ++k) state[k] = 128;
+    RacDec<PtrSrc> c;
+    c.src = PtrSrc{data}; c.next = next; c.range = 0xFF00; c.overread = 0; c.pos = 2; c.end = (uint32_t)size;
+    c.low = (data[0] << 8) | data[1];
+    if (c.low >= 0xFF00) { c.low = 0xFF00; c.end = 2; }
+    bool bad = false;
+    const int version = c.symbol(state, false, &bad);
+    if (bad || version != 3) return "version: only FFV1 version 3 is decoded on the device";
+    c.end = c.end >= 4u ? c.end - 4u : 0u;                   // the record's CRC parity is not range-coded
+    const int micro = c.symbol(state, false, &bad);
+    const int coder = c.symbol(state, false, &bad);
+    if (!bad && coder == 2) return "coder_type 2: a custom state-transition table is not decoded on the device";
+    if (bad || (coder != 0 && coder != 1))
+        return "coder_type: only Golomb-Rice (coder_type 0) and the range coder with the default state table (coder_type 1) are decoded on the device";
+    const int colorspace = c.symbol(state, false, &bad);
+    if (bad || colorspace != 1) return "colorspace_type: only RGB (JPEG 2000 RCT) is decoded on the device";
+    const int bits = c.symbol(state, false, &bad);
+    if (bad || (bits != 0 && bits != 8)) return "bits_per_raw_sample: only 8 bits are decoded on the device";
+    (void)c.get(state);                                      // chroma_planes
+    (void)c.symbol(state, false, &bad);                      // log2_h_chroma_subsample, log2_v_chroma_subsample
+    (void)c.symbol(state, false, &bad);
+    if (c.get(state)) return "extra_plane: alpha planes are not decoded on the device";
+    const int nh = 1 + c.symbol(state, false, &bad), nv = 1 + c.symbol(state, false, &bad);
+    if (bad || nh < 1 || nv < 1 || nh > kMaxSlices || nv > kMaxSlices || nh * nv > kMaxSlices)
+        return "num_h_slices / num_v_slices: 1 to 1024 slices per frame are decoded on the device";
+    const int qcount = c.symbol(state, false, &bad);
+    if (bad || qcount != 1) return "quant_table_set_count: only one quantisation table set is decoded on the device";
+    int scale = 1;
+    for (int t = 0; t < 5; ++t) {                            // the host's read_quant_tables, compared with the default set
+        uint8_t qs[32];
+        for (int k = 0; k < 32; ++k) qs[k] = 128;
+        int i = 0, v = 0;
+        for (; i < 128; ++v) {
+            const unsigned len = (unsigned)c.symbol(qs, false, &bad) + 1u;
+            if (bad || len > (unsigned)(128 - i)) return "quantisation tables: malformed";
+            for (unsigned k = 0; k < len; ++k, ++i)
+                if (scale * v != (t < 3 ? scale * quant11(i) : 0))
+                    return "quantisation tables: only the default 666-context set (quant11, three inputs) is decoded on the device";
+        }
+        scale *= 2 * v - 1;
+        if (scale > 32768 || scale <= 0) return "quantisation tables: malformed";
+    }
+    if (scale != 11 * 11 * 11) return "quantisation tables: only the default 666-context set (quant11, three inputs) is decoded on the device";
+    if (c.get(state)) return "states_coded: initial states other than 128 are not decoded on the device";
+    const int ec = c.symbol(state, false, &bad);
+    if (bad || (ec != 0 && ec != 1)) return "ec: unknown error-correction mode";
+    const int intra = micro > 2 ? c.symbol(state, false, &bad) : 0;
+    if (bad) return "configuration record: malformed symbol";
+    if (crc != 0) return "configuration record: CRC mismatch";
+    out->version = version; out->micro = micro; out->nh = nh; out->nv = nv; out->ec = ec; out->coder = coder; out->intra = intra ? 1 : 0;
+    return nullptr;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The stream decoder's half: Golomb-Rice (RFC 9043 section 3.8.2) and context state that carries across the frames of a run
+// ---------------------------------------------------------------------------------------------------------------------
+// further status words, of mdvt_decode_video_stream alone (include/mdvt_ffv1_stream_decode.h)
+enum : uint32_t { kNoKeyFrame = 5, kBrokenRun = 6 };
+
+// the walk's word per frame: the packet's slice table holds and its key-frame bit is clear / set, or the packet is refused
+enum : uint32_t { kFrameInter = 0, kFrameKey = 1, kFrameBad = 2 };
+
+// the key-frame bit as RacDec decides it: the first decision of the packet's range coder, state 128 (b0, b1: the first two bytes)
+MDVT_HD int key_frame_bit(uint8_t b0, uint8_t b1)
+{
+    int low = ((int)b0 << 8) | (int)b1;
+    if (low >= 0xFF00) low = 0xFF00;
+    return low >= 0xFF00 - ((0xFF00 * 128) >> 8);
+}
+
+MDVT_HD int clz32(uint32_t v) { return v ? __builtin_clz(v) : 32; }
+
+// The host's BitReader over a byte source: bits [0, 8 * nbytes) of the bytes from `base` on, most significant bit first; every bit
+// past them is zero.  A 64-bit accumulator holds the next `n` bits at its top, refilled a byte at a time through Src::byte (which
+// keeps its own window of aligned words on the device).
+template <class Src>
+struct BitReader {
+    Src src;
+    uint32_t base, nbytes, next;   // next: the first byte (from base) not yet in the accumulator; it stops at nbytes
+    uint64_t acc;
+    int n;
+
+    MDVT_HD void init(Src s, uint32_t base_, uint32_t nbytes_) { src = s; base = base_; nbytes = nbytes_; next = 0; acc = 0; n = 0; }
+    MDVT_HD void refill()                                  // -> n > 56
+    {
+        while (n <= 56) {
+            uint64_t b = 0;
+            if (next < nbytes) { b = src.byte(base + next); ++next; }
+            acc |= b << (56 - n);
+            n += 8;
+        }
+    }
+    MDVT_HD unsigned get(int k)                            // 0 <= k <= 32
+    {
+        if (k == 0) return 0u;
+        if (n < k) refill();
+        const unsigned v = (unsigned)(acc >> (64 - k));
+        acc <<= k; n -= k;
+        return v;
+    }
+    // zeros up to the next one bit, at most `limit` (<= 32) of them: consumes the zeros, and the one when there are fewer than `limit`
+    MDVT_HD int zeros(int limit)
+    {
+        if (n < limit + 1) refill();
+        int q = clz32((uint32_t)(acc >> 32));
+        if (q >= limit) { acc <<= limit; n -= limit; return limit; }
+        acc <<= q + 1; n -= q + 1;
+        return q;
+    }
+};
+
+// one context of the Golomb-Rice coder (the host's VlcState)
+struct VlcState { int16_t drift; uint16_t error_sum; int8_t bias; uint8_t count; };
+constexpr int kVlcBytes = kContexts * (int)sizeof(VlcState);       // one set: 666 x 6 bytes
+MDVT_HD void vlc_reset(VlcState* v) { v->drift = 0; v->error_sum = 4; v->bias = 0; v->count = 1; }
+
+constexpr int kRunIndexMax = 40;
+// (a function, not a table at namespace scope: one definition for host and device)
+MDVT_HD int log2_run(int run_index)
+{
+    return run_index < 16 ? run_index >> 2 : run_index < 24 ? 4 + ((run_index - 16) >> 1) : run_index - 16;
+}
+
+struct NoStats {
+    MDVT_HD void escape() {}
+    MDVT_HD void halving() {}
+    MDVT_HD void run_index(int) {}
+    MDVT_HD void short_tail_run() {}
+};
+
+// get_ur_golomb(k, limit 12, esc_len 9) folded to a signed value: q zeros + a one + k bits -> (q << k) | bits; 12 zeros -> 9 bits + 11
+template <class Src, class Stats>
+MDVT_HD int get_sr_golomb(BitReader<Src>& gb, int k, Stats& stats)
+{
+    const int q = gb.zeros(12);
+    unsigned v;
+    if (q < 12) v = ((unsigned)q << k) | gb.get(k);
+    else { v = gb.get(9) + 11u; stats.escape(); }
+    return (int)(v >> 1) ^ -(int)(v & 1u);
+}
+
+// the host's get_vlc_symbol with update_vlc_state, for 9-bit samples
+template <class Src, class Stats>
+MDVT_HD int get_vlc_symbol(BitReader<Src>& gb, VlcState* st, Stats& stats)
+{
+    int i = st->count, k = 0;
+    while (i < st->error_sum) { ++k; i += i; }             // (count >= 1 and error_sum < 2^16: at most 16 rounds)
+    int v = get_sr_golomb(gb, k, stats);
+    v ^= ((2 * st->drift + st->count) >> 31);
+    const int ret = (((v + st->bias) + 256) & 511) - 256;  // fold(., 9)
+    int drift = st->drift, count = st->count;
+    int es = st->error_sum + (v < 0 ? -v : v);
+    drift += v;
+    if (count == 128) { count >>= 1; drift >>= 1; es >>= 1; stats.halving(); }
+    ++count;
+    if (drift <= -count) {
+        st->bias = (int8_t)(st->bias - 1 > -128 ? st->bias - 1 : -128);
+        drift = drift + count > -count + 1 ? drift + count : -count + 1;
+    } else if (drift > 0) {
+        st->bias = (int8_t)(st->bias + 1 < 127 ? st->bias + 1 : 127);
+        drift = drift - count < 0 ? drift - count : 0;
+    }
+    st->drift = (int16_t)drift; st->count = (uint8_t)count; st->error_sum = (uint16_t)es;
+    return ret;
+}
+
+// One slice through the frames of a key-frame run (the host's Decoder::slices[index] with decode_slice).  The caller owns the
+// memory: `st` the context state, which it resets at a key frame and leaves alone otherwise -- coder_type 1: two range state sets
+// (2 * kStateBytes, all 128); coder_type 0: VlcState[2][kContexts] (vlc_reset) --, `lines` as for SliceDec and zeroed before every
+// frame, `misc` 64 bytes, q11[256].  Per frame: begin() reads the key-frame bit (first slice; its value is the caller's business),
+// the slice header and, for coder_type 0, the sentinel bit, and starts the bit reader where the host starts it; row(y) and
+// finish() as for SliceDec.
+template <class Src, class Stats = NoStats>
+struct ChainDec {
+    RacDec<Src> c;
+    BitReader<Src> gb;
+    uint8_t* st; int16_t* lines; uint8_t* misc; const int8_t* q11;
+    int stride, sw, sh, x0, y0, cell, coder, run_index;
+    bool error;
+    Stats stats;
+
+    MDVT_HD size_t state_bytes() const { return 2u * (size_t)(coder ? kStateBytes : kVlcBytes); }
+    MDVT_HD void reset_state()                             // (the kernel does this with the whole workgroup instead)
+    {
+        if (coder) for (int k = 0; k < 2 * kStateBytes; ++k) st[k] = 128;
+        else for (int k = 0; k < 2 * kContexts; ++k) vlc_reset(reinterpret_cast<VlcState*>(st) + k);
+    }
+
+    MDVT_HD uint32_t begin(Src src, uint32_t avail, uint32_t size, bool first, int coder_type, int micro, int W, int H, int nh, int nv,
+                           const uint16_t* next)
+    {
+        c.src = src; c.next = next;
+        c.range = 0xFF00; c.overread = 0; c.pos = 2; c.end = size;
+        coder = coder_type; run_index = 0;
+        error = false; sw = sh = 0; x0 = y0 = 0; cell = 0;
+        if (first ? avail < 2u : size < 2u) return kDamaged;
+        c.low = ((int)src.byte(0) << 8) | (int)src.byte(1);
+        if (c.low >= 0xFF00) { c.low = 0xFF00; if (!first) c.end = 2; }
+        for (int k = 0; k < 64; ++k) misc[k] = 128;
+        if (first) (void)c.get(misc + 32);
+        bool bad = false;
+        const unsigned sx = (unsigned)c.symbol(misc, false, &bad), sy = (unsigned)c.symbol(misc, false, &bad);
+        const unsigned cw = (unsigned)c.symbol(misc, false, &bad) + 1u, ch = (unsigned)c.symbol(misc, false, &bad) + 1u;
+        if (bad || sx >= (unsigned)nh || sy >= (unsigned)nv || cw > (unsigned)nh - sx || ch > (unsigned)nv - sy) return kBadSliceHeader;
+        if (cw != 1u || ch != 1u) return kBadSliceHeader;                          // (as SliceDec: the slices tile the frame)
+        for (int p = 0; p < 2; ++p)
+            if (c.symbol(misc, false, &bad) != 0 || bad) return kBadSliceHeader;     // quant_table_set_index: one set
+        (void)c.symbol(misc, false, &bad);                                         // picture_structure, sar_num, sar_den
+        (void)c.symbol(misc, false, &bad);
+        (void)c.symbol(misc, false, &bad);
+        if (bad) return kBadSliceHeader;
+        cell = (int)(sy * (unsigned)nh + sx);
+        x0 = (int)((long long)sx * W / nh); y0 = (int)((long long)sy * H / nv);
+        sw = (int)((long long)(sx + 1u) * W / nh) - x0; sh = (int)((long long)(sy + 1u) * H / nv) - y0;
+        if (sw < 1 || sh < 1 || sw + 2 > stride) return kBadSliceHeader;
+        if (!coder) {
+            if (micro > 1) { misc[33] = 129; (void)c.get(misc + 33); }             // the sentinel of ff_rac_terminate
+            const uint32_t consumed = c.pos - 1u;                                  // the host's `p - start - 1`
+            if (consumed > size) return kBadSliceHeader;                           // "header overruns the slice"
+            gb.init(src, consumed, size - consumed);
+        }
+        return kOk;
+    }
+
+    MDVT_HD void row(int y)
+    {
+        const int cs = y % 3, ls = (y + 2) % 3;
+        for (int p = 0; p < 3; ++p) {
+            int16_t* cur = lines + (size_t)(p * 3 + cs) * (size_t)stride + 1;
+            int16_t* last = lines + (size_t)(p * 3 + ls) * (size_t)stride + 1;
+            cur[-1] = last[0];
+            last[sw] = last[sw - 1];
+            int L = cur[-1], LT = last[-1], T = last[0];
+            int q_lt_t = q11[(LT - T) & 0xFF];
+            if (coder) {
+                uint8_t* states = st + (p ? kStateBytes : 0);
+                for (int x = 0; x < sw; ++x) {
+                    const int RT = last[x + 1];
+                    const int q_t_rt = q11[(T - RT) & 0xFF];
+                    int context = q11[(L - LT) & 0xFF] + 11 * q_lt_t + 121 * q_t_rt;
+                    q_lt_t = q_t_rt;
+                    const bool sign = context < 0;
+                    if (sign) context = -context;
+                    bool bad = false;
+                    int diff = c.symbol(states + (size_t)context * 32u, true, &bad);
+                    error |= bad;
+                    if (sign) diff = -diff;
+                    const int v = (median3(L, T, L + T - LT) + diff) & 511;
+                    cur[x] = (int16_t)v;
+                    L = v; LT = T; T = RT;
+                }
+                continue;
+            }
+            // Golomb-Rice with run mode (the host's decode_line): run_index runs on across rows and planes
+            VlcState* vs = reinterpret_cast<VlcState*>(st) + (p ? kContexts : 0);
+            int run_count = 0, run_mode = 0;
+            for (int x = 0; x < sw; ++x) {
+                const int RT = last[x + 1];
+                const int q_t_rt = q11[(T - RT) & 0xFF];
+                int context = q11[(L - LT) & 0xFF] + 11 * q_lt_t + 121 * q_t_rt;
+                q_lt_t = q_t_rt;
+                const bool sign = context < 0;
+                if (sign) context = -context;
+                int diff;
+                if (context == 0 && run_mode == 0) run_mode = 1;
+                if (run_mode) {
+                    if (run_count == 0 && run_mode == 1) {
+                        const int lr = log2_run(run_index);
+                        if (gb.get(1)) {
+                            run_count = 1 << lr;
+                            if (x + run_count <= sw) { if (run_index < kRunIndexMax) ++run_index; }
+                            else stats.short_tail_run();
+                            stats.run_index(run_index);
+                        } else {
+                            run_count = (int)gb.get(lr);
+                            if (run_index) --run_index;
+                            run_mode = 2;
+                        }
+                    }
+                    --run_count;
+                    if (run_count < 0) {
+                        run_mode = 0; run_count = 0;
+                        diff = get_vlc_symbol(gb, vs + context, stats);
+                        if (diff >= 0) ++diff;
+                    } else diff = 0;
+                } else diff = get_vlc_symbol(gb, vs + context, stats);
+                if (sign) diff = -diff;
+                const int v = (median3(L, T, L + T - LT) + diff) & 511;
+                cur[x] = (int16_t)v;
+                L = v; LT = T; T = RT;
+            }
+        }
+    }
+
+    // (the host reader has no overread check on the Golomb side: c.overread counts the header's reads alone there)
+    MDVT_HD uint32_t finish() const { return (error || c.overread > 4) ? kDamaged : kOk; }
+};
 
 }  // namespace mdvt_ffv1

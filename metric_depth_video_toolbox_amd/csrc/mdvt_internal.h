@@ -263,6 +263,22 @@ struct Ffv1DecodeArgs {
 size_t ffv1_decode_lds_bytes(int line_stride);                     // dynamic LDS of the slice kernel
 size_t ffv1_decode_static_lds_bytes();
 hipError_t launch_ffv1_decode(const Ffv1DecodeArgs& a, const Ffv1StateTables& tab, hipStream_t s);
+// mdvt_ffv1_stream_decode.hip: FFV1 streams with inter frames and Golomb-Rice coding (mdvt_decode_video_stream,
+// include/mdvt_ffv1_stream_decode.h)
+struct Ffv1StreamArgs {
+    const uint8_t* packets; unsigned long long packets_bytes;
+    const unsigned long long* offsets; const uint32_t* sizes;      // the caller's arrays: n_frames consecutive packets
+    int n_frames, first_out, W, H, nh, nv, ec, coder, micro;
+    uint8_t* dst; size_t pitch, frame_stride; int ri, bi;          // frame first_out lies at dst
+    uint32_t* status;                                              // the caller's n_frames status words
+    uint32_t* table;                                               // workspace [2][n_frames * slices]: slice offsets, payload bytes
+    uint32_t* claims;                                              // workspace [n_frames * slices], zeroed: a cell's claim
+    uint32_t* kind;                                                // workspace [n_frames]: mdvt_ffv1::kFrameInter / Key / Bad
+    int line_stride;
+};
+size_t ffv1_stream_lds_bytes(int coder, int line_stride);          // dynamic LDS of the chain kernel: context state, then the row slots
+size_t ffv1_stream_static_lds_bytes();
+hipError_t launch_ffv1_stream_decode(const Ffv1StreamArgs& a, const Ffv1StateTables& tab, hipStream_t s);
 // mdvt_convergence.hip: per-frame masked depth means (mdvt_convergence_depths, include/mdvt_convergence.h)
 struct ConvergenceArgs {
     const uint8_t* depth; size_t depth_pitch, depth_stride; int depth_bgr, depth_vec;     // the set's first frame; _vec: 12-byte loads are aligned

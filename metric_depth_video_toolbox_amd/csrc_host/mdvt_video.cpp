@@ -18,6 +18,7 @@
 //
 // Slices are decoded / encoded on std::threads (one per slice up to the host's cores).
 #include "mdvt_video.h"
+#include "mdvt_video_stream.h"
 
 #include <stdarg.h>
 #include <stdio.h>
@@ -683,7 +684,7 @@ struct EncoderTables {
 };
 const EncoderTables g_enc_tables;
 
-std::vector<uint8_t> make_config_record(int nh, int nv)
+std::vector<uint8_t> make_config_record(int nh, int nv, int coder = 1, int intra = 1)
 {
     RacEnc c;
     c.init();
@@ -692,7 +693,7 @@ std::vector<uint8_t> make_config_record(int nh, int nv)
     memset(state, 128, sizeof state);
     put_symbol(c, state, 3, false);          // version
     put_symbol(c, state, 4, false);          // micro_version
-    put_symbol(c, state, 1, false);          // coder_type: range coder, default state transition table
+    put_symbol(c, state, coder, false);      // coder_type: 1 range coder, default state transition table; 0 Golomb-Rice (the stream class)
     put_symbol(c, state, 1, false);          // colorspace_type: RGB
     put_symbol(c, state, 8, false);          // bits_per_raw_sample
     c.put(state, 1);                         // chroma_planes
@@ -705,7 +706,7 @@ std::vector<uint8_t> make_config_record(int nh, int nv)
     for (int i = 0; i < kMaxContextInputs; ++i) write_quant_table(c, g_enc_tables.q[i]);
     c.put(state, 0);                         // states_coded
     put_symbol(c, state, 1, false);          // ec
-    put_symbol(c, state, 1, false);          // intra
+    put_symbol(c, state, intra, false);      // intra
     c.terminate(false);
     std::vector<uint8_t> out = c.out;
     const uint32_t crc = crc32_msb(0, out.data(), out.size());
@@ -799,6 +800,151 @@ int encode_frame(int W, int H, int nh, int nv, const uint8_t* src, size_t pitch,
     for (auto& p : parts) total += p.size();
     packet.clear();
     packet.reserve(total);
+    for (auto& p : parts) {
+        if (p.size() - 8 >= (1u << 24)) return fail(ERR_UNSUPPORTED, "an FFV1 slice of %zu bytes does not fit the 24-bit slice size: use more slices", p.size());
+        packet.insert(packet.end(), p.begin(), p.end());
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// encoder of the opt-in stream class (include/mdvt_video_stream.h): version 3.4, Golomb-Rice with run mode, intra = 0, a key frame
+// every `gop` frames, CRC-32 parities -- what FFmpeg writes by default for 8-bit RGB.  A slice's VLC states carry from frame to
+// frame and are reset at a key frame.  Byte for byte the independent restatement ffv1_ref.py's StreamEncoder(Params(coder=0, intra=0, nh, nv), W, H, gop).
+// ---------------------------------------------------------------------------------------------------------------------
+struct BitWriter {
+    std::vector<uint8_t> out;
+    uint64_t acc = 0;
+    int n = 0;
+    inline void put(int bits, uint32_t v)        // bits <= 32
+    {
+        acc = (acc << bits) | v; n += bits;
+        while (n >= 8) { out.push_back((uint8_t)(acc >> (n - 8))); n -= 8; }
+    }
+    void flush() { if (n) { out.push_back((uint8_t)(acc << (8 - n))); n = 0; } }
+};
+
+struct GolombSliceState { std::vector<VlcState> vlc[2]; };
+
+inline void put_vlc_symbol(BitWriter& bw, VlcState& st, int diff)
+{
+    const int v = fold(diff - st.bias, 9);
+    int i = st.count, k = 0;
+    while (i < st.error_sum) { ++k; i += i; }
+    const int code = v ^ ((2 * st.drift + st.count) >> 31);
+    const unsigned u = code >= 0 ? 2u * (unsigned)code : 2u * (unsigned)(-code) - 1u;
+    if ((u >> k) < 12u) bw.put((int)(u >> k) + k + 1, (1u << k) + (u & ((1u << k) - 1u)));
+    else bw.put(12 + 9, u - 11u);
+    // update_vlc_state, as get_vlc_symbol does it
+    int drift = st.drift + v, count = st.count;
+    int es = st.error_sum + (v < 0 ? -v : v);
+    if (count == 128) { count >>= 1; drift >>= 1; es >>= 1; }
+    ++count;
+    if (drift <= -count) { st.bias = (int8_t)std::max(st.bias - 1, -128); drift = std::max(drift + count, -count + 1); }
+    else if (drift > 0) { st.bias = (int8_t)std::min(st.bias + 1, 127); drift = std::min(drift - count, 0); }
+    st.drift = (int16_t)drift; st.count = (uint8_t)count; st.error_sum = (uint16_t)es;
+}
+
+void encode_slice_golomb(int W, int H, int nh, int nv, int sx, int sy, const uint8_t* src, size_t pitch, int order, bool first, bool key,
+                         GolombSliceState& ss, std::vector<uint8_t>& out)
+{
+    const int x0 = (int)((int64_t)sx * W / nh), y0 = (int)((int64_t)sy * H / nv);
+    const int sw = (int)((int64_t)(sx + 1) * W / nh) - x0, sh = (int)((int64_t)(sy + 1) * H / nv) - y0;
+    RacEnc c;
+    c.init();
+    c.ensure(1024);
+    if (first) { uint8_t keystate = 128; c.put(&keystate, key ? 1 : 0); }
+    uint8_t hstate[kContextSize];
+    memset(hstate, 128, sizeof hstate);
+    const int header[9] = {sx, sy, 0, 0, 0, 0, 3, 0, 0};        // position, size - 1 in slice units, two table indices, progressive, unknown aspect
+    for (int v : header) put_symbol(c, hstate, v, false);
+    c.terminate(true);                                          // the sentinel bit: the bit stream starts behind the range coder's bytes
+    if (key || ss.vlc[0].empty())
+        for (auto& v : ss.vlc) v.assign((size_t)g_enc_tables.context_count, VlcState());
+    BitWriter bw;
+    bw.out.reserve((size_t)sw * sh * 3);
+    std::vector<int16_t> buf((size_t)3 * 2 * (size_t)(sw + 6), 0);
+    int16_t* sample[3][2];
+    for (int p = 0; p < 3; ++p)
+        for (int k = 0; k < 2; ++k) sample[p][k] = buf.data() + ((size_t)p * 2 + (size_t)k) * (size_t)(sw + 6) + 3;
+    const int ri = order == MDVT_VIDEO_BGR ? 2 : 0, bi = order == MDVT_VIDEO_BGR ? 0 : 2;
+    LineCtx lc{g_enc_tables.q, false};
+    int run_index = 0;
+    auto flush_run = [&](int& run_count) {                      // whole runs of the current length: a one bit each
+        while (run_count >= (1 << kLog2Run[run_index])) { run_count -= 1 << kLog2Run[run_index]; if (run_index < 40) ++run_index; bw.put(1, 1); }
+    };
+    for (int y = 0; y < sh; ++y) {
+        const uint8_t* s = src + (size_t)(y0 + y) * pitch + (size_t)x0 * 3;
+        for (int p = 0; p < 3; ++p) std::swap(sample[p][0], sample[p][1]);
+        for (int x = 0; x < sw; ++x) {
+            int r = s[3 * x + ri], g = s[3 * x + 1], b = s[3 * x + bi];
+            b -= g; r -= g;
+            g += (b + r) >> 2;
+            sample[0][1][x] = (int16_t)g; sample[1][1][x] = (int16_t)(b + 256); sample[2][1][x] = (int16_t)(r + 256);
+        }
+        for (int p = 0; p < 3; ++p) {
+            int16_t* cur = sample[p][1];
+            int16_t* last = sample[p][0];
+            cur[-1] = last[0];
+            last[sw] = last[sw - 1];
+            VlcState* vlc = ss.vlc[(p + 1) / 2].data();
+            int run_count = 0, run_mode = 0;
+            for (int x = 0; x < sw; ++x) {
+                int context = get_context(lc, cur + x, last + x, cur + x);
+                int diff = cur[x] - median3(cur[x - 1], last[x], cur[x - 1] + last[x] - last[x - 1]);
+                if (context < 0) { context = -context; diff = -diff; }
+                diff = fold(diff, 9);
+                if (context == 0) run_mode = 1;
+                if (run_mode) {
+                    if (diff) {
+                        flush_run(run_count);
+                        bw.put(1 + kLog2Run[run_index], (uint32_t)run_count);
+                        if (run_index) --run_index;
+                        run_count = 0; run_mode = 0;
+                        if (diff > 0) --diff;
+                    } else ++run_count;
+                }
+                if (run_mode == 0) put_vlc_symbol(bw, vlc[(size_t)context], diff);
+            }
+            if (run_mode) {
+                flush_run(run_count);
+                if (run_count) bw.put(1, 1);
+            }
+        }
+    }
+    bw.flush();
+    out = c.out;
+    out.insert(out.end(), bw.out.begin(), bw.out.end());
+    const size_t payload = out.size();
+    out.push_back((uint8_t)(payload >> 16)); out.push_back((uint8_t)(payload >> 8)); out.push_back((uint8_t)payload);
+    out.push_back(0);                                                                 // error_status
+    const uint32_t crc = crc32_msb(0, out.data(), out.size());
+    out.push_back((uint8_t)(crc >> 24)); out.push_back((uint8_t)(crc >> 16)); out.push_back((uint8_t)(crc >> 8)); out.push_back((uint8_t)crc);
+}
+
+int encode_frame_golomb(int W, int H, int nh, int nv, const uint8_t* src, size_t pitch, int order, int threads, bool key,
+                        std::vector<GolombSliceState>& states, std::vector<uint8_t>& packet)
+{
+    const int n = nh * nv;
+    states.resize((size_t)n);
+    std::vector<std::vector<uint8_t>> parts((size_t)n);
+    std::atomic<int> next(0);
+    auto work = [&]() {
+        for (;;) {
+            const int i = next.fetch_add(1);
+            if (i >= n) break;
+            encode_slice_golomb(W, H, nh, nv, i % nh, i / nh, src, pitch, order, i == 0, key, states[(size_t)i], parts[(size_t)i]);
+        }
+    };
+    int nt = threads > 0 ? threads : (int)std::thread::hardware_concurrency();
+    nt = std::max(1, std::min(nt, n));
+    if (nt == 1) work();
+    else {
+        std::vector<std::thread> th;
+        for (int t = 0; t < nt; ++t) th.emplace_back(work);
+        for (auto& t : th) t.join();
+    }
+    packet.clear();
     for (auto& p : parts) {
         if (p.size() - 8 >= (1u << 24)) return fail(ERR_UNSUPPORTED, "an FFV1 slice of %zu bytes does not fit the 24-bit slice size: use more slices", p.size());
         packet.insert(packet.end(), p.begin(), p.end());
@@ -1047,8 +1193,12 @@ struct mdvt_video_writer {
     uint64_t segment_size_pos = 0;   // file offset of the Segment's 8-byte size field
     std::vector<std::pair<uint64_t, uint64_t>> cues;     // timecode (ms), cluster position relative to segment_data
     std::vector<uint8_t> packet;
+    int coder = 1, gop = 1;          // the stream class of mdvt_video_create_stream: coder 0, a key frame every gop frames
+    std::vector<GolombSliceState> golomb;
     uint64_t frame_ms(int64_t k) const { return (uint64_t)((k * 1000 * (int64_t)fps_den + fps_num / 2) / fps_num); }
 };
+
+struct mdvt_ffv1_stream_decoder { Decoder dec; };
 
 extern "C" {
 
@@ -1193,7 +1343,8 @@ int mdvt_ffv1_decode_frame(int width, int height, const uint8_t* config, size_t 
     return dec.decode_frame(packet, packet_size, dst, pitch, order, threads);
 }
 
-int mdvt_video_create(const char* path, int width, int height, int fps_num, int fps_den, int slices_h, int slices_v, mdvt_video_writer** out)
+static int create_writer(const char* path, int width, int height, int fps_num, int fps_den, int slices_h, int slices_v, int coder, int gop,
+                         mdvt_video_writer** out)
 {
     if (!path || !out || width < 1 || height < 1 || fps_num < 1 || fps_den < 1) return fail(ERR_ARG, "bad argument");
     if (slices_h == 0 && slices_v == 0) { slices_h = std::min(4, width); slices_v = std::min(4, height); }
@@ -1203,6 +1354,7 @@ int mdvt_video_create(const char* path, int width, int height, int fps_num, int 
     w->fp = fopen(path, "wb");
     if (!w->fp) { delete w; return fail(ERR_IO, "cannot create %s", path); }
     w->W = width; w->H = height; w->nh = slices_h; w->nv = slices_v; w->fps_num = fps_num; w->fps_den = fps_den;
+    w->coder = coder; w->gop = gop;
     EbmlBuf head, eb;
     eb.uint_el(ID_EBMLVERSION, 1); eb.uint_el(ID_EBMLREADVERSION, 1); eb.uint_el(ID_EBMLMAXIDLENGTH, 4); eb.uint_el(ID_EBMLMAXSIZELENGTH, 8);
     eb.str_el(ID_DOCTYPE, "matroska"); eb.uint_el(ID_DOCTYPEVERSION, 4); eb.uint_el(ID_DOCTYPEREADVERSION, 2);
@@ -1226,7 +1378,7 @@ int mdvt_video_create(const char* path, int width, int height, int fps_num, int 
     entry.uint_el(ID_TRACKNUMBER, 1); entry.uint_el(ID_TRACKUID, 1); entry.uint_el(ID_TRACKTYPE, 1); entry.uint_el(ID_FLAGLACING, 0);
     entry.uint_el(ID_DEFAULTDURATION, (uint64_t)((1000000000.0 * fps_den) / fps_num + 0.5));
     entry.str_el(ID_CODECID, "V_FFV1");
-    const std::vector<uint8_t> rec = make_config_record(slices_h, slices_v);
+    const std::vector<uint8_t> rec = make_config_record(slices_h, slices_v, coder, coder ? 1 : 0);
     entry.bin_el(ID_CODECPRIVATE, rec.data(), rec.size());
     entry.master(ID_VIDEO, video);
     tracks.master(ID_TRACKENTRY, entry);
@@ -1236,12 +1388,26 @@ int mdvt_video_create(const char* path, int width, int height, int fps_num, int 
     return 0;
 }
 
+int mdvt_video_create(const char* path, int width, int height, int fps_num, int fps_den, int slices_h, int slices_v, mdvt_video_writer** out)
+{
+    return create_writer(path, width, height, fps_num, fps_den, slices_h, slices_v, 1, 1, out);
+}
+
+int mdvt_video_create_stream(const char* path, int width, int height, int fps_num, int fps_den, int slices_h, int slices_v, int coder_type,
+                             int gop, mdvt_video_writer** out)
+{
+    if (coder_type != 0) return fail(ERR_ARG, "coder_type %d: the stream class is Golomb-Rice (0); mdvt_video_create writes the range coder's", coder_type);
+    if (gop < 1) return fail(ERR_ARG, "gop must be >= 1");
+    return create_writer(path, width, height, fps_num, fps_den, slices_h, slices_v, 0, gop, out);
+}
+
 int mdvt_video_write(mdvt_video_writer* w, const uint8_t* src, size_t pitch, int order, int threads)
 {
     if (!w || !src) return fail(ERR_ARG, "NULL argument");
     if (pitch < (size_t)w->W * 3) return fail(ERR_ARG, "pitch smaller than one row");
     if (order != MDVT_VIDEO_RGB && order != MDVT_VIDEO_BGR) return fail(ERR_ARG, "order must be MDVT_VIDEO_RGB or MDVT_VIDEO_BGR");
-    int rc = encode_frame(w->W, w->H, w->nh, w->nv, src, pitch, order, threads, w->packet);
+    int rc = w->coder ? encode_frame(w->W, w->H, w->nh, w->nv, src, pitch, order, threads, w->packet)
+                      : encode_frame_golomb(w->W, w->H, w->nh, w->nv, src, pitch, order, threads, w->frames % w->gop == 0, w->golomb, w->packet);
     if (rc) return rc;
     return mdvt_video_write_packet(w, w->packet.data(), w->packet.size());
 }
@@ -1249,21 +1415,65 @@ int mdvt_video_write(mdvt_video_writer* w, const uint8_t* src, size_t pitch, int
 int mdvt_video_write_packet(mdvt_video_writer* w, const uint8_t* packet, size_t packet_size)
 {
     if (!w || !packet || packet_size < 8) return fail(ERR_ARG, "bad argument");
-    // one Cluster per frame: intra-only video, every frame a seek point (what FFmpeg's muxer does for such streams at this size)
+    // one Cluster per frame; a key frame (every frame of the default, intra-only class) is flagged in its block and gets a cue: a seek
+    // point.  An inter frame of the stream class is neither.
     const uint64_t tc = w->frame_ms(w->frames);
     EbmlBuf cl, body;
     body.uint_el(ID_TIMECODE, tc);
     body.id(ID_SIMPLEBLOCK); body.size(packet_size + 4);
-    body.b.push_back(0x81); body.b.push_back(0); body.b.push_back(0); body.b.push_back(0x80);       // track 1, relative time 0, key frame
+    RacDec kc;
+    uint8_t kst = 128;
+    const bool key = kc.init(packet, 2) && kc.get(&kst);                                            // the packet's first range-coded bit
+    body.b.push_back(0x81); body.b.push_back(0); body.b.push_back(0); body.b.push_back(key ? 0x80 : 0x00);   // track 1, relative time 0, key frame
     cl.id(ID_CLUSTER); cl.size(body.b.size() + packet_size);
     const uint64_t pos = (uint64_t)ftello(w->fp);
     if (fwrite(cl.b.data(), 1, cl.b.size(), w->fp) != cl.b.size() || fwrite(body.b.data(), 1, body.b.size(), w->fp) != body.b.size() ||
         fwrite(packet, 1, packet_size, w->fp) != packet_size)
         return fail(ERR_IO, "write failed (disk full?)");
-    w->cues.push_back({tc, pos - w->segment_data});
+    if (key) w->cues.push_back({tc, pos - w->segment_data});
     ++w->frames;
     return 0;
 }
+
+int mdvt_video_seek_packet(mdvt_video_reader* r, int64_t frame)
+{
+    if (!r) return fail(ERR_ARG, "NULL argument");
+    if (frame < 0 || frame > (int64_t)r->frames.size()) return fail(ERR_ARG, "frame %lld outside 0..%zu", (long long)frame, r->frames.size());
+    r->next = (size_t)frame;
+    r->dec.key_frame_ok = false;          // nothing is decoded on the way: the next decode must start at a key frame
+    return 0;
+}
+
+int mdvt_video_packet_is_key(mdvt_video_reader* r, int64_t frame)
+{
+    if (!r) return fail(ERR_ARG, "NULL argument");
+    if (frame < 0 || frame >= (int64_t)r->frames.size()) return fail(ERR_ARG, "frame %lld outside 0..%zu", (long long)frame, r->frames.size());
+    const int key = packet_is_key(r, (size_t)frame);
+    return key < 0 ? fail(ERR_IO, "short read of frame %lld", (long long)frame) : key;
+}
+
+int mdvt_ffv1_stream_decoder_create(int width, int height, const uint8_t* config, size_t config_size, mdvt_ffv1_stream_decoder** out)
+{
+    if (!config || !out || width < 1 || height < 1) return fail(ERR_ARG, "bad argument");
+    *out = nullptr;
+    mdvt_ffv1_stream_decoder* d = new mdvt_ffv1_stream_decoder();
+    d->dec.W = width; d->dec.H = height;
+    int rc = parse_config_record(config, config_size, d->dec.f);
+    if (!rc) { d->dec.have_config = true; rc = d->dec.check_supported(); }
+    if (rc) { delete d; return rc; }
+    *out = d;
+    return 0;
+}
+
+int mdvt_ffv1_stream_decoder_decode(mdvt_ffv1_stream_decoder* d, const uint8_t* packet, size_t packet_size, uint8_t* dst, size_t pitch, int order,
+                                    int threads)
+{
+    if (!d || !packet || !dst || pitch < (size_t)d->dec.W * 3) return fail(ERR_ARG, "bad argument");
+    if (order != MDVT_VIDEO_RGB && order != MDVT_VIDEO_BGR) return fail(ERR_ARG, "order must be MDVT_VIDEO_RGB or MDVT_VIDEO_BGR");
+    return d->dec.decode_frame(packet, packet_size, dst, pitch, order, threads);
+}
+
+void mdvt_ffv1_stream_decoder_destroy(mdvt_ffv1_stream_decoder* d) { delete d; }
 
 int mdvt_video_finish(mdvt_video_writer* w, int64_t* frames)
 {

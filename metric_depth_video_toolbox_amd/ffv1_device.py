@@ -4,7 +4,10 @@ re-encoded on the host, which gives the same bytes, or refuses the frame as the 
 
 The other direction (mdvt_decode_video_frames, include/mdvt_ffv1_decode.h): packets of the stream class the project's writer makes
 are copied to the device as stored and decoded there into the bytes video_io.VideoReader gives; a frame the device flags is
-decoded on the host, which gives the same bytes or the host's own VideoError."""
+decoded on the host, which gives the same bytes or the host's own VideoError.
+
+A third part (mdvt_decode_video_stream, include/mdvt_ffv1_stream_decode.h) does the same for streams whose context state carries
+from frame to frame: Golomb-Rice or range coder, with inter frames -- the files FFmpeg and OpenCV write by default."""
 from __future__ import annotations
 
 import ctypes as C
@@ -291,3 +294,130 @@ def decode_frames_on_device(packets, config: bytes, width: int, height: int, *, 
     p = enqueue_decode(_context(device if out is None else out.device), packets, config, width, height, bgr, out, stream)
     frames = p.collect()
     return frames, p.flags
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# decoding streams whose context state carries from frame to frame (mdvt_decode_video_stream, include/mdvt_ffv1_stream_decode.h)
+# ---------------------------------------------------------------------------------------------------------------------
+NO_KEY_FRAME, BROKEN_RUN = 5, 6
+STREAM_STATUS = {**DECODE_STATUS, NO_KEY_FRAME: "no key frame at or before this frame inside the call",
+                 BROKEN_RUN: "an earlier frame of this key-frame run was flagged"}
+
+
+def stream_supported(info, config: Optional[bytes] = None) -> Optional[str]:
+    """supported() for the stream decoder's class: version 3, coder_type 0 or 1, intra 0 or 1 (the files FFmpeg and OpenCV write
+    by default are in it).  None, or the reason, naming the field."""
+    if info.ffv1_version != 3:
+        return f"version: FFV1 version {info.ffv1_version} (only version 3 is decoded on the device)"
+    if info.coder_type not in (0, 1):
+        return f"coder_type {info.coder_type}: a custom state-transition table is not decoded on the device"
+    if info.alpha:
+        return "extra_plane: alpha planes are not decoded on the device"
+    if not 1 <= info.slices <= 1024:
+        return f"num_h_slices / num_v_slices: {info.slices} slices per frame (1 to 1024 are decoded on the device)"
+    if config is not None:
+        why = _lib.load().mdvt_ffv1_stream_decode_supported(config, len(config))
+        if why:
+            return why.decode()
+    return None
+
+
+def packet_is_key(packet: bytes) -> bool:
+    """The packet's key-frame bit (mdvt_ffv1_packet_is_key: its first range-coded bit); a packet too short to have one is none."""
+    return _lib.load().mdvt_ffv1_packet_is_key(packet, len(packet)) == 1
+
+
+class PendingStreamFrames:
+    """The device side of one stream decode: `out` holds frames first_out ... of the packets, `status` one word per packet."""
+
+    def __init__(self, packets, config, W, H, bgr, first_out, out, status, done, staged):
+        self.packets, self.config, self.W, self.H, self.bgr, self.first_out = packets, config, W, H, bgr, first_out
+        self.out, self.status, self.done, self._staged = out, status, done, staged
+        self.host_frames = 0                  # stored frames collect() had to decode on the host
+        self.flags = None                     # numpy uint32 [packets] after collect(): the device's status words
+
+    def collect(self, threads: int = 1):
+        """Waits for the decode and reads the status words.  A flagged frame cannot be decoded alone: the host decodes its whole
+        key-frame run from the run's key frame (video_io.StreamDecoder: the same bytes, or the host's VideoError), and every stored
+        frame of the run from the first flagged one on is copied into its place and counted in host_frames.  -> out"""
+        import torch
+        from . import video_io
+        self.done.synchronize()
+        self.flags = self.status.cpu().numpy().view(np.uint32)
+        self._staged = None
+        bad = np.nonzero(self.flags[self.first_out:])[0] + self.first_out
+        done_to = -1
+        for k in bad:
+            k = int(k)
+            if k <= done_to:
+                continue
+            start = k
+            while start > 0 and not packet_is_key(self.packets[start]):
+                start -= 1
+            if not packet_is_key(self.packets[start]):
+                raise video_io.VideoError(f"FFV1: frame {k} of the call has no key frame at or before it")
+            end = k + 1
+            while end < len(self.packets) and not packet_is_key(self.packets[end]):
+                end += 1
+            with video_io.StreamDecoder(self.config, self.W, self.H, bgr=self.bgr, threads=threads) as dec:
+                for j in range(start, end):
+                    frame = dec.decode(self.packets[j])
+                    if j >= k and j >= self.first_out:
+                        self.host_frames += 1
+                        self.out[j - self.first_out].copy_(torch.from_numpy(frame))
+            done_to = end - 1
+        return self.out
+
+
+def enqueue_decode_stream(ctx: "_lib.Context", packets, config: bytes, width: int, height: int, first_out: int = 0, bgr: bool = False,
+                          out=None, stream=None) -> PendingStreamFrames:
+    """enqueue_decode for consecutive packets of one stream of the stream decoder's class.  Frames first_out ... are stored in `out`
+    (default: a new (N - first_out) x H x W x 3 tensor); the packets before first_out are decoded for their context state alone
+    (the caller prepends them from the last key frame on).  State is not carried from one call to the next."""
+    import torch
+    W, H = int(width), int(height)
+    if W < 1 or H < 1:
+        raise ValueError(f"frames of {W} x {H}")
+    why = _lib.load().mdvt_ffv1_stream_decode_supported(config, len(config))
+    if why:
+        raise _lib.MdvtError(-3, f"FFV1 stream outside the device stream decoder's class: {why.decode()}")
+    staged = packets if isinstance(packets, StagedPackets) else StagedPackets(packets)
+    N, total = len(staged), staged.total
+    first_out = int(first_out)
+    if not 0 <= first_out < N:
+        raise ValueError(f"first_out {first_out} outside [0, {N})")
+    dev = torch.device("cuda", ctx.device)
+    n_out = N - first_out
+    if out is None:
+        out = torch.empty((n_out, H, W, 3), dtype=torch.uint8, device=dev)
+    check_out(out, n_out, H, W)
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    side = torch.cuda.Stream(dev)
+    with torch.cuda.stream(side):
+        d_blob = torch.empty(max(1, total), dtype=torch.uint8, device=dev)
+        d_meta = torch.empty(2 * N, dtype=torch.int64, device=dev)
+        d_blob.copy_(staged.h_blob, non_blocking=True)
+        d_meta.copy_(staged.h_meta, non_blocking=True)
+        d_sizes = d_meta[N:].to(torch.int32)
+        status = torch.empty(N, dtype=torch.int32, device=dev)
+        copied = torch.cuda.Event()
+        copied.record(side)
+    s.wait_event(copied)
+    for t in (d_blob, d_meta, d_sizes, status):
+        t.record_stream(s)
+    ctx.call("mdvt_decode_video_stream", W, H, config, len(config), C.c_void_p(d_blob.data_ptr()), total,
+             C.c_void_p(d_meta.data_ptr()), C.c_void_p(d_sizes.data_ptr()), N, first_out,
+             C.c_void_p(out.data_ptr()), out.stride(1), out.stride(0) if n_out > 1 else out.stride(1) * H,
+             1 if bgr else 0, C.c_void_p(status.data_ptr()), _lib.stream_arg(dev, s))
+    done = torch.cuda.Event()
+    done.record(s)
+    return PendingStreamFrames(staged.packets, config, W, H, bgr, first_out, out, status, done, (staged, d_blob, d_meta, d_sizes))
+
+
+def decode_stream_on_device(packets, config: bytes, width: int, height: int, *, first_out: int = 0, bgr: bool = False, out=None,
+                            stream=None, device: int = 0):
+    """-> (frames, status, host_frames): frames first_out ... of consecutive packets as video_io.VideoReader gives them, the
+    device's status words (numpy uint32, one per packet) and the count of stored frames the host had to decode instead."""
+    p = enqueue_decode_stream(_context(device if out is None else out.device), packets, config, width, height, first_out, bgr, out, stream)
+    frames = p.collect()
+    return frames, p.flags, p.host_frames

@@ -16,7 +16,7 @@ import os
 import numpy as np
 
 from . import _lib
-from .clip_io import ClipInputs, check_video_decoder, video_parts
+from .clip_io import VIDEO_DECODERS, ClipInputs, check_video_decoder, video_parts
 
 SIDECAR_SUFFIX = "_convergence_depths.json"             # fcd:41
 
@@ -127,9 +127,10 @@ def build_parser():
                    help="black and white mask video for the main focus area. White where area of interest is.")
     p.add_argument("--max_depth", default=100, type=int, help="the max depth that the video uses")
     p.add_argument("--batch", default=64, type=int, help="not a reference flag: frames per device call")
-    p.add_argument("--video_decoder", choices=("host", "device"), default="host",
+    p.add_argument("--video_decoder", choices=VIDEO_DECODERS, default="host",
                    help="not a reference flag: where the .mkv inputs are FFV1-decoded -- 'host' (default) or 'device' (on the GPU, the "
-                        "same bytes; a stream the device does not decode is read on the host). Not with .npy inputs")
+                        "same bytes; a stream the device does not decode is read on the host) or 'device_all' (as 'device', and Golomb-Rice "
+                        "or inter-coded FFV1, FFmpeg's default, is decoded on the GPU as well). Not with .npy inputs")
     return p
 
 

@@ -37,7 +37,7 @@ import numpy as np
 
 from . import _lib
 from .basic_nomal_infill import pairs_from_arguments
-from .clip_io import ClipInputs, ClipOutput, check_video_decoder, check_video_encoder, video_parts
+from .clip_io import VIDEO_DECODERS, ClipInputs, ClipOutput, check_video_decoder, check_video_encoder, video_parts
 
 MODEL_W, MODEL_H = 1024, 768              # scr:95-96
 FRAMES_CHUNK, OVERLAP = 25, 6             # scr:222, 250-257
@@ -327,8 +327,9 @@ def build_parser():
                    help="not a reference flag: the in-painting model, 'stereocrafter' (default) or pkg.module:callable with "
                         "generate(frames, masks, fps) -> frames on uint8 CUDA tensors [T,768,1024,3] and [T,768,1024]")
     p.add_argument("--batch", default=8, type=int, help="not a reference flag: frames per read from the input")
-    p.add_argument("--video_decoder", choices=("host", "device"), default="host",
-                   help="not a reference flag: where the .mkv inputs are FFV1-decoded -- 'host' (default) or 'device' (on the GPU, the same bytes). Not with .npy inputs")
+    p.add_argument("--video_decoder", choices=VIDEO_DECODERS, default="host",
+                   help="not a reference flag: where the .mkv inputs are FFV1-decoded -- 'host' (default), 'device' (on the GPU, the same bytes) "
+                        "or 'device_all' (as 'device', and Golomb-Rice or inter-coded FFV1, FFmpeg's default, as well). Not with .npy inputs")
     p.add_argument("--video_encoder", choices=("host", "device"), default="host",
                    help="not a reference flag: where the .mkv output is FFV1-encoded -- 'host' (default) or 'device' (on the GPU, the same bytes). Not with .npy inputs")
     return p

@@ -669,6 +669,7 @@ class StereoRerenderer:
 # ------------------------------------------------------------------------------------------------
 def build_arg_parser():
     import argparse
+    from . import clip_io
     ap = argparse.ArgumentParser(description="Convert an RGB-encoded depth frame dump and optional colour frame dump "
                                              "into a stereoscopic side-by-side output on MI355X GPUs.")
     ap.add_argument("--master_xfov", type=float, default=45.0)
@@ -717,10 +718,11 @@ def build_arg_parser():
     ap.add_argument("--video_encoder", choices=("host", "device"), default="host",
                     help="not a reference flag: where the .mkv outputs are FFV1-encoded -- 'host' (default) or 'device' (on the GPU, "
                          "the same bytes; only the compressed packets are copied to the host). Not with .npy input and outputs")
-    ap.add_argument("--video_decoder", choices=("host", "device"), default="host",
+    ap.add_argument("--video_decoder", choices=clip_io.VIDEO_DECODERS, default="host",
                     help="not a reference flag: where the .mkv inputs are FFV1-decoded -- 'host' (default) or 'device' (on the GPU, "
                          "the same bytes; only the compressed packets are copied to the device; an input the device does not decode, "
-                         "such as a file FFmpeg made, is read on the host). Not with .npy inputs")
+                         "such as a file FFmpeg made, is read on the host) or 'device_all' (as 'device', and Golomb-Rice or inter-coded "
+                         "FFV1, what FFmpeg and OpenCV write by default, is decoded on the GPU as well). Not with .npy inputs")
     ap.add_argument("--near_clip", action="store_true",
                     help="not a reference flag: clip a mesh triangle that crosses the near plane (z = 1e-4 m) as a GL does, instead of "
                          "dropping it whole (the default) -- matters where depth code 0 or a pose puts the camera inside the scene "
@@ -777,7 +779,7 @@ def main(argv=None):
                             do_basic_infill=args.do_basic_infill, normal_infill=args.normal_infill, inpaint_order=args.inpaint_order,
                             multisample=multisample_kwargs(args), near_clip=bool(args.near_clip),
                             video_encoder=args.video_encoder,
-                            **({"video_decoder": "device"} if args.video_decoder == "device" else {}),
+                            **({"video_decoder": args.video_decoder} if args.video_decoder != "host" else {}),
                             **({"find_convergence": True, "convergence_mask_video": args.convergence_mask_video}
                                if args.find_convergence else {}),
                             touchly_max_depth=args.touchly_max_depth, touchly_min_depth=args.touchly_min_depth)

@@ -24,6 +24,10 @@ SYMBOLS = ("mdvt_video_last_error", "mdvt_video_abi", "mdvt_video_open", "mdvt_v
            "mdvt_video_next_packet", "mdvt_video_config_record", "mdvt_video_close", "mdvt_video_create", "mdvt_video_write",
            "mdvt_video_write_packet", "mdvt_video_finish", "mdvt_ffv1_encode_frame", "mdvt_ffv1_decode_frame")
 
+# the entry points include/mdvt_video_stream.h declares (the inter-coded stream class), listed apart from mdvt_video.h's
+STREAM_SYMBOLS = ("mdvt_video_create_stream", "mdvt_video_seek_packet", "mdvt_video_packet_is_key", "mdvt_ffv1_stream_decoder_create", "mdvt_ffv1_stream_decoder_decode",
+                  "mdvt_ffv1_stream_decoder_destroy")
+
 RGB, BGR = 0, 1
 
 
@@ -64,6 +68,14 @@ def load():
                                              C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
         L.mdvt_ffv1_decode_frame.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                              C.c_int, C.c_int]
+        L.mdvt_video_create_stream.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                               C.POINTER(C.c_void_p)]
+        L.mdvt_video_seek_packet.argtypes = [C.c_void_p, C.c_int64]
+        L.mdvt_video_packet_is_key.argtypes = [C.c_void_p, C.c_int64]
+        L.mdvt_ffv1_stream_decoder_create.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
+        L.mdvt_ffv1_stream_decoder_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int]
+        L.mdvt_ffv1_stream_decoder_destroy.argtypes = [C.c_void_p]
+        L.mdvt_ffv1_stream_decoder_destroy.restype = None
         _lib = L
     return _lib
 
@@ -108,6 +120,14 @@ class VideoReader:
         """The next read returns `frame` (an inter-coded stream is decoded forward from its last key frame)."""
         _check(load().mdvt_video_seek(self._h, int(frame), self.threads))
 
+    def seek_packet(self, frame: int):
+        """The next next_packet() returns `frame`'s; nothing is decoded on the way (seek() decodes an inter-coded stream forward)."""
+        _check(load().mdvt_video_seek_packet(self._h, int(frame)))
+
+    def packet_is_key(self, frame: int) -> bool:
+        """Whether `frame`'s packet is a key frame (two bytes read from the file; the reader's position stays)."""
+        return _check(load().mdvt_video_packet_is_key(self._h, int(frame))) == 1
+
     def next_packet(self):
         """The next frame's FFV1 packet as stored (bytes), or None at the end."""
         cap = self.width * self.height * 8 + (1 << 16)
@@ -137,15 +157,25 @@ class VideoReader:
 
 
 class VideoWriter:
-    """cv2.VideoWriter(path, fourcc('F','F','V','1'), fps, (W, H)): FFV1 version 3, intra-only, in Matroska."""
+    """cv2.VideoWriter(path, fourcc('F','F','V','1'), fps, (W, H)): FFV1 version 3, intra-only, in Matroska.  coder=0 opts into
+    the stream class FFmpeg writes by default instead (include/mdvt_video_stream.h): Golomb-Rice, intra = 0, a key frame every
+    `gop` frames; frames must then be written in order with write()."""
 
-    def __init__(self, path: str, width: int, height: int, fps: float, slices=(0, 0), bgr: bool = False, threads: int = 0):
+    def __init__(self, path: str, width: int, height: int, fps: float, slices=(0, 0), bgr: bool = False, threads: int = 0,
+                 coder: int = 1, gop: int = 12):
         fr = Fraction(float(fps)).limit_denominator(1001)
         self._h = C.c_void_p()
         self.path, self.width, self.height, self.order, self.threads = path, int(width), int(height), BGR if bgr else RGB, int(threads)
         self.slices = (int(slices[0]) or min(4, self.width), int(slices[1]) or min(4, self.height))
-        _check(load().mdvt_video_create(os.fsencode(path), self.width, self.height, fr.numerator, fr.denominator, int(slices[0]), int(slices[1]),
-                                        C.byref(self._h)))
+        if coder not in (0, 1):
+            raise ValueError(f"coder must be 1 (range coder, intra-only: the default) or 0 (Golomb-Rice, a key frame every gop frames), got {coder!r}")
+        self.coder, self.gop = int(coder), int(gop) if coder == 0 else 1
+        if coder == 0:
+            _check(load().mdvt_video_create_stream(os.fsencode(path), self.width, self.height, fr.numerator, fr.denominator, int(slices[0]),
+                                                   int(slices[1]), 0, self.gop, C.byref(self._h)))
+        else:
+            _check(load().mdvt_video_create(os.fsencode(path), self.width, self.height, fr.numerator, fr.denominator, int(slices[0]),
+                                            int(slices[1]), C.byref(self._h)))
         self.frames = 0
 
     def write(self, frame: np.ndarray):
@@ -171,6 +201,32 @@ class VideoWriter:
 
     def __exit__(self, *a):
         self.close()
+
+
+class StreamDecoder:
+    """The host decoder for consecutive packets of one stream (context state carries from packet to packet): what VideoReader does
+    with a file's packets, without the file.  The first packet must be a key frame."""
+
+    def __init__(self, config: bytes, width: int, height: int, bgr: bool = False, threads: int = 1):
+        self._h = C.c_void_p()
+        self.width, self.height, self.order, self.threads = int(width), int(height), BGR if bgr else RGB, int(threads)
+        _check(load().mdvt_ffv1_stream_decoder_create(self.width, self.height, config, len(config), C.byref(self._h)))
+
+    def decode(self, packet: bytes, out=None) -> np.ndarray:
+        if out is None:
+            out = np.empty((self.height, self.width, 3), np.uint8)
+        assert out.dtype == np.uint8 and out.shape == (self.height, self.width, 3) and out.strides[2] == 1 and out.strides[1] == 3
+        _check(load().mdvt_ffv1_stream_decoder_decode(self._h, packet, len(packet), out.ctypes.data, out.strides[0], self.order, self.threads))
+        return out
+
+    def close(self):
+        if self._h:
+            load().mdvt_ffv1_stream_decoder_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __enter__ = lambda self: self
+    __exit__ = lambda self, *a: self.close()
+    __del__ = close
 
 
 def encode_frame(frame: np.ndarray, slices=(2, 2), bgr: bool = False, threads: int = 1):

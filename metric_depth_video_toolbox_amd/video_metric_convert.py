@@ -18,7 +18,7 @@ import os
 import numpy as np
 
 from . import _lib, video_io
-from .clip_io import ClipInputs, ClipOutput, check_video_decoder, check_video_encoder
+from .clip_io import VIDEO_DECODERS, ClipInputs, ClipOutput, check_video_decoder, check_video_encoder
 
 ENGINES = {"vda": 0, "depthcrafter": 1}                  # engine -> reconstruction style (include/mdvt_metric_align.h)
 FIT_FRAMES = 32                                          # vmc:107
@@ -267,8 +267,9 @@ def build_parser():
     p.add_argument("--batch", default=16, type=int, help="not a reference flag: frames per device call")
     p.add_argument("--video_encoder", choices=("host", "device"), default="host",
                    help="not a reference flag: where the .mkv output is FFV1-encoded -- 'host' (default) or 'device' (the same bytes)")
-    p.add_argument("--video_decoder", choices=("host", "device"), default="host",
-                   help="not a reference flag: where an .mkv --depth_video is FFV1-decoded -- 'host' (default) or 'device' (the same bytes)")
+    p.add_argument("--video_decoder", choices=VIDEO_DECODERS, default="host",
+                   help="not a reference flag: where an .mkv --depth_video is FFV1-decoded -- 'host' (default), 'device' or 'device_all' "
+                        "(the same bytes; 'device_all' also takes Golomb-Rice and inter-coded FFV1, FFmpeg's default, to the GPU)")
     return p
 
 

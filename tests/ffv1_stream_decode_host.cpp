@@ -1,0 +1,165 @@
+// The device FFV1 stream decoder's core (csrc/mdvt_ffv1_core.h: BitReader, the Golomb-Rice pieces, ChainDec, parse_stream_class2)
+// compiled for the host: tests/test_video_stream_decoder_cpu.py builds this program at test time (plain, and with
+// -fsanitize=address,undefined where the compiler has the runtime) and feeds it streams.
+//
+//   ffv1_stream_decode_host <jobs file> <results file>
+// jobs:    u32 count, then per job u32 width, height, order, first_out, config bytes, packets, then the record, then per packet u32
+//          bytes and the packet
+// results: per job u32 verdict (0; 100 = the record is outside the class, and nothing else follows), u32 escapes, halvings, largest
+//          run_index, short tail runs, then per packet u32 status, and per packet from first_out on width * height * 3 bytes (zero
+//          where nothing was stored)
+// The stream is decoded the way the kernels do it: every packet's slice table and key-frame bit first (the walk), then for every key
+// frame and slice one chain through the run's frames, with the CRCs, the cell claims and the flags of k_ffv1_stream_chain.  Every
+// buffer is allocated at its exact size and every byte of a packet is read through a checked accessor.
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <vector>
+
+#include "mdvt_ffv1_core.h"
+
+using namespace mdvt_ffv1;
+
+#define CHECK(c) do { if (!(c)) { fprintf(stderr, "bound violated: %s (line %d)\n", #c, __LINE__); abort(); } } while (0)
+
+struct CheckedSrc {
+    const uint8_t* p; uint32_t avail;
+    uint8_t byte(uint32_t k) const { CHECK(k < avail); return p[k]; }
+};
+
+struct CheckedPacket {
+    const uint8_t* p; uint32_t size;
+    uint8_t operator()(uint32_t k) const { CHECK(k < size); return p[k]; }
+};
+
+struct Counters {
+    uint32_t escapes = 0, halvings = 0, max_run_index = 0, short_tail_runs = 0;
+    void escape() { ++escapes; }
+    void halving() { ++halvings; }
+    void run_index(int r) { CHECK(r >= 0 && r <= kRunIndexMax); if ((uint32_t)r > max_run_index) max_run_index = (uint32_t)r; }
+    void short_tail_run() { ++short_tail_runs; }
+};
+
+struct Packet { uint8_t* p; uint32_t size; };           // on the heap at its exact size: a read past it is the sanitizer's
+
+static void raise_status(std::vector<uint32_t>& status, size_t k, uint32_t v) { if (v > status[k]) status[k] = v; }
+
+static uint32_t decode(int W, int H, int order, int first_out, const std::vector<uint8_t>& cfg, const std::vector<Packet>& pk,
+                       std::vector<uint32_t>& status, uint8_t* dst, Counters& total)
+{
+    StreamClass2 sc{};
+    if (parse_stream_class2(cfg.data(), cfg.size(), &sc) || sc.nh > W || sc.nv > H) return 100;
+    const int n = (int)pk.size(), spf = sc.nh * sc.nv;
+    const uint32_t trailer = sc.ec ? 8u : 3u;
+    std::vector<uint32_t> off((size_t)n * spf), len((size_t)n * spf), claims((size_t)n * spf, 0), kind((size_t)n);
+    for (int f = 0; f < n; ++f) {                            // k_ffv1_stream_walk
+        status[(size_t)f] = walk_slices(CheckedPacket{pk[f].p, pk[f].size}, pk[f].size, spf, sc.ec, &off[(size_t)f * spf], &len[(size_t)f * spf]);
+        kind[(size_t)f] = status[(size_t)f] != kOk ? kFrameBad : key_frame_bit(CheckedPacket{pk[f].p, pk[f].size}(0), CheckedPacket{pk[f].p, pk[f].size}(1)) ? kFrameKey : kFrameInter;
+    }
+    for (int j = 0; j < n && kind[(size_t)j] != kFrameKey; ++j) raise_status(status, (size_t)j, kNoKeyFrame);
+    uint8_t zero[256], one[256];
+    int8_t q11[256];
+    uint16_t next[256];
+    default_states(zero, one);
+    for (int k = 0; k < 256; ++k) { q11[k] = (int8_t)quant11(k); next[k] = (uint16_t)(zero[k] | (one[k] << 8)); }
+    const int stride = (W + sc.nh - 1) / sc.nh + 2;
+    const int ri = order == 1 ? 2 : 0, bi = order == 1 ? 0 : 2;
+    for (int f0 = 0; f0 < n; ++f0) {
+        if (kind[(size_t)f0] != kFrameKey) continue;
+        for (int si = 0; si < spf; ++si) {                   // one chain: k_ffv1_stream_chain
+            ChainDec<CheckedSrc, Counters> d;
+            d.coder = sc.coder;
+            uint8_t* st = (uint8_t*)malloc(d.state_bytes());
+            int16_t* lines = (int16_t*)malloc((size_t)9 * stride * sizeof(int16_t));
+            uint8_t* misc = (uint8_t*)malloc(64);
+            d.st = st; d.lines = lines; d.misc = misc; d.q11 = q11; d.stride = stride;
+            d.reset_state();
+            int f = f0;
+            uint32_t flag = kOk;
+            for (; f < n; ++f) {
+                if (f > f0 && kind[(size_t)f] == kFrameKey) break;
+                if (kind[(size_t)f] == kFrameBad) { flag = kBadPacket; break; }
+                const size_t i = (size_t)f * spf + (size_t)si;
+                CHECK((size_t)off[i] + len[i] + trailer <= pk[f].size);
+                const uint8_t* data = pk[f].p + off[i];
+                if (sc.ec) {
+                    uint32_t crc = 0;
+                    for (uint32_t k = 0; k < len[i] + trailer; ++k) crc = (crc << 8) ^ crc_table_entry((crc >> 24) ^ CheckedPacket{pk[f].p, pk[f].size}(off[i] + k));
+                    if (crc) { flag = kCrcMismatch; break; }
+                }
+                memset(lines, 0, (size_t)9 * stride * sizeof(int16_t));
+                uint32_t s = d.begin(CheckedSrc{data, len[i] + trailer}, len[i] + trailer, len[i], si == 0, sc.coder, sc.micro, W, H, sc.nh, sc.nv, next);
+                if (s == kOk) {
+                    CHECK(d.cell >= 0 && d.cell < spf);
+                    if (claims[(size_t)f * spf + (size_t)d.cell]++) s = kBadSliceHeader;
+                }
+                if (s != kOk) { flag = s; break; }
+                CHECK(d.x0 >= 0 && d.y0 >= 0 && d.x0 + d.sw <= W && d.y0 + d.sh <= H);
+                for (int y = 0; y < d.sh; ++y) {
+                    d.row(y);
+                    CHECK(d.run_index >= 0 && d.run_index <= kRunIndexMax);
+                    if (f < first_out) continue;
+                    uint8_t* o = dst + (size_t)(f - first_out) * W * H * 3 + ((size_t)(d.y0 + y) * W + d.x0) * 3;
+                    for (int x = 0; x < d.sw; ++x) {
+                        int g = lines[(size_t)(0 * 3 + y % 3) * stride + 1 + x], b = lines[(size_t)(1 * 3 + y % 3) * stride + 1 + x] - 256,
+                            r = lines[(size_t)(2 * 3 + y % 3) * stride + 1 + x] - 256;
+                        g -= (b + r) >> 2;
+                        b += g; r += g;
+                        o[3 * x + ri] = (uint8_t)r; o[3 * x + 1] = (uint8_t)g; o[3 * x + bi] = (uint8_t)b;
+                    }
+                }
+                s = d.finish();
+                if (s != kOk) { flag = s; break; }
+            }
+            if (flag != kOk) {
+                raise_status(status, (size_t)f, flag);
+                for (int j = f + 1; j < n && kind[(size_t)j] != kFrameKey; ++j) raise_status(status, (size_t)j, kBrokenRun);
+            }
+            total.escapes += d.stats.escapes; total.halvings += d.stats.halvings; total.short_tail_runs += d.stats.short_tail_runs;
+            if (d.stats.max_run_index > total.max_run_index) total.max_run_index = d.stats.max_run_index;
+            free(st); free(lines); free(misc);
+        }
+    }
+    return 0;
+}
+
+static bool rd(FILE* f, void* p, size_t n) { return fread(p, 1, n, f) == n; }
+
+int main(int argc, char** argv)
+{
+    if (argc != 3) return 2;
+    FILE* in = fopen(argv[1], "rb");
+    FILE* out = fopen(argv[2], "wb");
+    if (!in || !out) return 2;
+    uint32_t count = 0;
+    if (!rd(in, &count, 4)) return 2;
+    for (uint32_t j = 0; j < count; ++j) {
+        uint32_t h[6];
+        if (!rd(in, h, sizeof h) || h[0] < 1 || h[1] < 1 || h[0] > 8192 || h[1] > 8192 || h[4] > (1u << 20) || h[5] < 1 || h[5] > 4096 || h[3] >= h[5]) return 2;
+        std::vector<uint8_t> cfg(h[4]);
+        if (!rd(in, cfg.data(), cfg.size())) return 2;
+        std::vector<Packet> pk;
+        for (uint32_t k = 0; k < h[5]; ++k) {
+            uint32_t size = 0;
+            if (!rd(in, &size, 4) || size > (1u << 28)) return 2;
+            Packet p{(uint8_t*)malloc(size ? size : 1), size};
+            if (!rd(in, p.p, size)) return 2;
+            pk.push_back(p);
+        }
+        const size_t frame = (size_t)h[0] * h[1] * 3;
+        std::vector<uint8_t> dst(frame * (h[5] - h[3]), 0);
+        std::vector<uint32_t> status(h[5], 0);
+        Counters total;
+        uint32_t res[5] = {decode((int)h[0], (int)h[1], (int)h[2], (int)h[3], cfg, pk, status, dst.data(), total), 0, 0, 0, 0};
+        res[1] = total.escapes; res[2] = total.halvings; res[3] = total.max_run_index; res[4] = total.short_tail_runs;
+        fwrite(res, 4, 5, out);
+        if (res[0] == 0) {
+            fwrite(status.data(), 4, status.size(), out);
+            fwrite(dst.data(), 1, dst.size(), out);
+        }
+        for (auto& p : pk) free(p.p);
+    }
+    fclose(in);
+    return fclose(out) ? 2 : 0;
+}

@@ -9,6 +9,10 @@ memory, frames left on the device) against the host decoder as the clip driver u
 two readers sharing the host threads, + the copy of the raw frames to the device); every timed batch is compared with the host's
 bytes first, and the run stops if the device flagged a frame.
 
+--decode --stream-class golomb-gop12 measures mdvt_decode_video_stream on the class FFmpeg writes by default (Golomb-Rice, a key
+frame every 12 frames; written here by video_io.VideoWriter(coder=0, gop=12)) against what such a file gets today: one host reader
+with --host-threads slice threads + the copy of the raw frames.  The rows carry the class in a `class` field.
+
 Every device packet is compared with the host's bytes before it is timed, and the run stops if the device flagged any frame
 (a flagged frame is re-encoded on the host: its time would not be the device's).  Prints one line per case and, with --json,
 writes the table."""
@@ -46,6 +50,9 @@ def main(argv=None):
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--json", default=None)
     ap.add_argument("--decode", action="store_true", help="measure the decoders instead of the encoders")
+    ap.add_argument("--stream-class", default="intra", choices=("intra", "golomb-gop12"),
+                    help="with --decode: the stream class of the files -- 'intra' (default: this project's writer, mdvt_decode_video_frames) "
+                         "or 'golomb-gop12' (Golomb-Rice, a key frame every 12 frames: mdvt_decode_video_stream)")
     a = ap.parse_args(argv)
     if a.decode:
         return decode_main(a)
@@ -101,6 +108,7 @@ def decode_main(a):
     rng = np.random.default_rng(1)
     pool = ThreadPoolExecutor(a.host_threads)
     ctx = _lib.shared_context(0)
+    stream = a.stream_class != "intra"
     rows = []
     nmax = max(int(v) for v in a.frames.split(","))
     tmp = tempfile.mkdtemp(prefix="ffv1_bench_")
@@ -114,16 +122,25 @@ def decode_main(a):
             for sl in a.slices.split(","):
                 slices = tuple(int(v) for v in sl.split("x"))
                 path = os.path.join(tmp, f"{size}_{kind}_{sl}.mkv")
-                enc = list(pool.map(lambda f: video_io.encode_frame(f, slices=slices, threads=1), frames))
-                with video_io.VideoWriter(path, W, H, 30.0, slices=slices) as w:
-                    for pkt, _ in enc:
-                        w.write_packet(pkt)
-                packets, cfg = [e[0] for e in enc], enc[0][1]
-                vf = clip.VideoFrames(path)
+                if stream:
+                    with video_io.VideoWriter(path, W, H, 30.0, slices=slices, coder=0, gop=12, threads=a.host_threads) as w:
+                        for f in frames:
+                            w.write(f)
+                    with video_io.VideoReader(path) as r:
+                        cfg = r.config_record()
+                        packets = [r.next_packet() for _ in range(len(frames))]
+                else:
+                    enc = list(pool.map(lambda f: video_io.encode_frame(f, slices=slices, threads=1), frames))
+                    with video_io.VideoWriter(path, W, H, 30.0, slices=slices) as w:
+                        for pkt, _ in enc:
+                            w.write_packet(pkt)
+                    packets, cfg = [e[0] for e in enc], enc[0][1]
+                # an inter-coded file gets one reader (contexts carry over) with all the slice threads; an intra file the driver's two
+                vf = clip.VideoFrames(path, threads=a.host_threads) if stream else clip.VideoFrames(path)
 
                 def host(n):                      # render_clip's load() + its H2D copy
                     h = pinned[:n].numpy()
-                    half = n // 2
+                    half = 0 if stream else n // 2
                     jobs = [pool.submit(vf.read_into, h[:half], 0, half)] if half else []
                     jobs.append(pool.submit(vf.read_into, h[half:], half, n - half))
                     for j in jobs:
@@ -132,7 +149,8 @@ def decode_main(a):
                     torch.cuda.synchronize()
 
                 def device(staged):
-                    p = ffv1_device.enqueue_decode(ctx, staged, cfg, W, H, out=d_dev[:len(staged)])
+                    enqueue = ffv1_device.enqueue_decode_stream if stream else ffv1_device.enqueue_decode
+                    p = enqueue(ctx, staged, cfg, W, H, out=d_dev[:len(staged)])
                     p.done.synchronize()
                     flags = p.status.cpu()
                     if bool(flags.any()):
@@ -155,8 +173,10 @@ def decode_main(a):
                     r = dict(size=size, content=kind, slices=sl, frames=n, device_fps=n / min(dt_dev), host_fps=n / min(dt_host),
                              bytes_per_frame=staged.total / n)
                     r["speedup"] = r["device_fps"] / r["host_fps"]
+                    if stream:
+                        r["class"] = a.stream_class
                     rows.append(r)
-                    print(f"decode {size:>9} {kind:>9} {sl:>3} n={n:<3} device {r['device_fps']:8.1f} fps  host({a.host_threads}t) "
+                    print(f"decode {'' if not stream else a.stream_class + ' '}{size:>9} {kind:>9} {sl:>3} n={n:<3} device {r['device_fps']:8.1f} fps  host({a.host_threads}t) "
                           f"{r['host_fps']:8.1f} fps  x{r['speedup']:.2f}  {r['bytes_per_frame'] / 1e6:.2f} MB/frame", flush=True)
                 vf.close()
                 os.remove(path)
