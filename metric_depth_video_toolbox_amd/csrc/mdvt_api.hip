@@ -465,7 +465,55 @@ int mdvt_encode_video_frames(mdvt_ctx* c, int width, int height, int slices_h, i
 const char* mdvt_ffv1_decode_supported(const uint8_t* h_config, size_t config_size)
 {
     mdvt_ffv1::StreamClass sc{};
-    return mdvt_ffv1::parse_stream_class(h_config, config_size, &sc);
+    return mdvt_ffv1::parse_stream_class(h_config, config_size, false, &sc);
+}
+
+const char* mdvt_ffv1_stream_decode_supported(const uint8_t* h_config, size_t config_size)
+{
+    mdvt_ffv1::StreamClass sc{};
+    return mdvt_ffv1::parse_stream_class(h_config, config_size, true, &sc);
+}
+
+int mdvt_ffv1_packet_is_key(const uint8_t* h_packet, size_t size)
+{
+    if (!h_packet || size < 3) return -1;
+    return mdvt_ffv1::key_frame_bit(h_packet[0], h_packet[1]);
+}
+
+// What both FFV1 decode entry points do before they differ: the argument checks, the record's class (`stream`: the stream
+// decoder's, with first_out), the refusals of what the kernels cannot hold, and the fields of `a` that do not depend on the pass.
+// n packets, of which those from first_out on are stored.
+static int ffv1_decode_prologue(mdvt_ctx* c, bool stream, int width, int height, const uint8_t* h_config, size_t config_size,
+                                const uint8_t* d_packets, uint64_t packets_bytes, const uint64_t* d_offsets, const uint32_t* d_sizes, int n,
+                                int first_out, uint8_t* d_dst, size_t pitch, size_t frame_stride, int order, uint32_t* d_status,
+                                mdvt::Ffv1DecodeArgs* a)
+{
+    if (!c) return MDVT_ERR_INVALID_ARG;
+    if (!h_config || !d_packets || !d_offsets || !d_sizes || !d_dst || !d_status) return fail(c, MDVT_ERR_INVALID_ARG, "NULL buffer");
+    if (width < 1 || height < 1) return fail(c, MDVT_ERR_INVALID_ARG, "bad frame size %d x %d", width, height);
+    if (order != 0 && order != 1) return fail(c, MDVT_ERR_INVALID_ARG, "order must be 0 (RGB) or 1 (BGR), got %d", order);
+    if (n < 1) return fail(c, MDVT_ERR_INVALID_ARG, "%s must be >= 1", stream ? "n_packets" : "n_frames");
+    if (first_out < 0 || first_out >= n) return fail(c, MDVT_ERR_INVALID_ARG, "first_out %d outside [0, n_packets = %d)", first_out, n);
+    if (pitch < (size_t)width * 3u) return fail(c, MDVT_ERR_INVALID_ARG, "pitch smaller than one row");
+    if (n - first_out > 1 && frame_stride < pitch * (size_t)height) return fail(c, MDVT_ERR_INVALID_ARG, "frame_stride smaller than one frame");
+    const char* decoder = stream ? "stream decoder" : "decoder";
+    mdvt_ffv1::StreamClass sc{};
+    if (const char* why = mdvt_ffv1::parse_stream_class(h_config, config_size, stream, &sc))
+        return fail(c, MDVT_ERR_UNSUPPORTED, "FFV1 stream outside the device %s's class: %s", decoder, why);
+    if (sc.nh > width || sc.nv > height)
+        return fail(c, MDVT_ERR_UNSUPPORTED, "FFV1 stream outside the device %s's class: num_h_slices / num_v_slices %d x %d for a frame of %d x %d",
+                    decoder, sc.nh, sc.nv, width, height);
+    if ((uint64_t)width * (uint64_t)height > ((uint64_t)1 << 28))
+        return fail(c, MDVT_ERR_UNSUPPORTED, "frame too large for the device FFV1 decoder (%d x %d)", width, height);
+    const int line_stride = (width + sc.nh - 1) / sc.nh + 2;           // the widest slice, its left and right neighbours
+    if (mdvt::ffv1_decode_static_lds_bytes() + mdvt::ffv1_stream_lds_bytes(sc.coder, line_stride) > (size_t)160 * 1024)
+        return fail(c, MDVT_ERR_UNSUPPORTED, "a slice of %d pixels' width does not fit the device FFV1 decoder's row buffers (num_h_slices %d)",
+                    line_stride - 2, sc.nh);
+    a->packets = d_packets; a->packets_bytes = packets_bytes;
+    a->W = width; a->H = height; a->nh = sc.nh; a->nv = sc.nv; a->ec = sc.ec; a->coder = sc.coder; a->micro = sc.micro;
+    a->pitch = pitch; a->frame_stride = frame_stride; a->ri = order == 1 ? 2 : 0; a->bi = order == 1 ? 0 : 2;
+    a->line_stride = line_stride;
+    return MDVT_OK;
 }
 
 // FFV1 packets in device memory -> frames (mdvt_ffv1_decode.hip).  Passes: as many frames as the ctx's workspace budget affords.
@@ -473,37 +521,17 @@ int mdvt_decode_video_frames(mdvt_ctx* c, int width, int height, const uint8_t* 
                              uint64_t packets_bytes, const uint64_t* d_offsets, const uint32_t* d_sizes, int n_frames, uint8_t* d_dst,
                              size_t pitch, size_t frame_stride, int order, uint32_t* d_status, void* stream)
 {
-    if (!c) return MDVT_ERR_INVALID_ARG;
-    if (!h_config || !d_packets || !d_offsets || !d_sizes || !d_dst || !d_status) return fail(c, MDVT_ERR_INVALID_ARG, "NULL buffer");
-    if (width < 1 || height < 1) return fail(c, MDVT_ERR_INVALID_ARG, "bad frame size %d x %d", width, height);
-    if (order != 0 && order != 1) return fail(c, MDVT_ERR_INVALID_ARG, "order must be 0 (RGB) or 1 (BGR), got %d", order);
-    if (n_frames < 1) return fail(c, MDVT_ERR_INVALID_ARG, "n_frames must be >= 1");
-    if (pitch < (size_t)width * 3u) return fail(c, MDVT_ERR_INVALID_ARG, "pitch smaller than one row");
-    if (n_frames > 1 && frame_stride < pitch * (size_t)height) return fail(c, MDVT_ERR_INVALID_ARG, "frame_stride smaller than one frame");
-    mdvt_ffv1::StreamClass sc{};
-    if (const char* why = mdvt_ffv1::parse_stream_class(h_config, config_size, &sc))
-        return fail(c, MDVT_ERR_UNSUPPORTED, "FFV1 stream outside the device decoder's class: %s", why);
-    if (sc.nh > width || sc.nv > height)
-        return fail(c, MDVT_ERR_UNSUPPORTED, "FFV1 stream outside the device decoder's class: num_h_slices / num_v_slices %d x %d for a frame of %d x %d",
-                    sc.nh, sc.nv, width, height);
-    if ((uint64_t)width * (uint64_t)height > ((uint64_t)1 << 28))
-        return fail(c, MDVT_ERR_UNSUPPORTED, "frame too large for the device FFV1 decoder (%d x %d)", width, height);
-    const int line_stride = (width + sc.nh - 1) / sc.nh + 2;           // the widest slice, its left and right neighbours
-    if (mdvt::ffv1_decode_static_lds_bytes() + mdvt::ffv1_decode_lds_bytes(line_stride) > (size_t)160 * 1024)
-        return fail(c, MDVT_ERR_UNSUPPORTED, "a slice of %d pixels' width does not fit the device FFV1 decoder's row buffers (num_h_slices %d)",
-                    line_stride - 2, sc.nh);
+    mdvt::Ffv1DecodeArgs a{};                                          // (first_out, kind: none; coder 1)
+    if (int e = ffv1_decode_prologue(c, false, width, height, h_config, config_size, d_packets, packets_bytes, d_offsets, d_sizes, n_frames, 0,
+                                     d_dst, pitch, frame_stride, order, d_status, &a))
+        return e;
     DeviceGuard g(c->device);
     hipStream_t s = (hipStream_t)stream;
-    const int spf = sc.nh * sc.nv;
+    const int spf = a.nh * a.nv;
     const size_t per_frame = (size_t)spf * 3 * sizeof(uint32_t);
     const int fchunk = slots_afforded(c, per_frame, n_frames);
     MDVT_HIP(c, scratch_reserve(c, c->scratch[SCR_FFV1_DEC], (size_t)fchunk * per_frame, s));
     static const mdvt::Ffv1StateTables tab = mdvt::ffv1_default_states();
-    mdvt::Ffv1DecodeArgs a{};
-    a.packets = d_packets; a.packets_bytes = packets_bytes;
-    a.W = width; a.H = height; a.nh = sc.nh; a.nv = sc.nv; a.ec = sc.ec;
-    a.pitch = pitch; a.frame_stride = frame_stride; a.ri = order == 1 ? 2 : 0; a.bi = order == 1 ? 0 : 2;
-    a.line_stride = line_stride;
     for (int f0 = 0; f0 < n_frames; f0 += fchunk) {
         const int nf = n_frames - f0 < fchunk ? n_frames - f0 : fchunk;
         a.n_frames = nf;
@@ -517,45 +545,17 @@ int mdvt_decode_video_frames(mdvt_ctx* c, int width, int height, const uint8_t* 
     return MDVT_OK;
 }
 
-const char* mdvt_ffv1_stream_decode_supported(const uint8_t* h_config, size_t config_size)
-{
-    mdvt_ffv1::StreamClass2 sc{};
-    return mdvt_ffv1::parse_stream_class2(h_config, config_size, &sc);
-}
-
-int mdvt_ffv1_packet_is_key(const uint8_t* h_packet, size_t size)
-{
-    if (!h_packet || size < 3) return -1;
-    return mdvt_ffv1::key_frame_bit(h_packet[0], h_packet[1]);
-}
-
 // Consecutive FFV1 packets in device memory -> frames, the context state carried along each key-frame run
 // (mdvt_ffv1_stream_decode.hip).  One pass: a run cannot be cut where the workspace budget would cut it.
 int mdvt_decode_video_stream(mdvt_ctx* c, int width, int height, const uint8_t* h_config, size_t config_size, const uint8_t* d_packets,
                              uint64_t packets_bytes, const uint64_t* d_offsets, const uint32_t* d_sizes, int n_packets, int first_out,
                              uint8_t* d_dst, size_t pitch, size_t frame_stride, int order, uint32_t* d_status, void* stream)
 {
-    if (!c) return MDVT_ERR_INVALID_ARG;
-    if (!h_config || !d_packets || !d_offsets || !d_sizes || !d_dst || !d_status) return fail(c, MDVT_ERR_INVALID_ARG, "NULL buffer");
-    if (width < 1 || height < 1) return fail(c, MDVT_ERR_INVALID_ARG, "bad frame size %d x %d", width, height);
-    if (order != 0 && order != 1) return fail(c, MDVT_ERR_INVALID_ARG, "order must be 0 (RGB) or 1 (BGR), got %d", order);
-    if (n_packets < 1) return fail(c, MDVT_ERR_INVALID_ARG, "n_packets must be >= 1");
-    if (first_out < 0 || first_out >= n_packets) return fail(c, MDVT_ERR_INVALID_ARG, "first_out %d outside [0, n_packets = %d)", first_out, n_packets);
-    if (pitch < (size_t)width * 3u) return fail(c, MDVT_ERR_INVALID_ARG, "pitch smaller than one row");
-    if (n_packets - first_out > 1 && frame_stride < pitch * (size_t)height) return fail(c, MDVT_ERR_INVALID_ARG, "frame_stride smaller than one frame");
-    mdvt_ffv1::StreamClass2 sc{};
-    if (const char* why = mdvt_ffv1::parse_stream_class2(h_config, config_size, &sc))
-        return fail(c, MDVT_ERR_UNSUPPORTED, "FFV1 stream outside the device stream decoder's class: %s", why);
-    if (sc.nh > width || sc.nv > height)
-        return fail(c, MDVT_ERR_UNSUPPORTED, "FFV1 stream outside the device stream decoder's class: num_h_slices / num_v_slices %d x %d for a frame of %d x %d",
-                    sc.nh, sc.nv, width, height);
-    if ((uint64_t)width * (uint64_t)height > ((uint64_t)1 << 28))
-        return fail(c, MDVT_ERR_UNSUPPORTED, "frame too large for the device FFV1 decoder (%d x %d)", width, height);
-    const int line_stride = (width + sc.nh - 1) / sc.nh + 2;           // the widest slice, its left and right neighbours
-    if (mdvt::ffv1_stream_static_lds_bytes() + mdvt::ffv1_stream_lds_bytes(sc.coder, line_stride) > (size_t)160 * 1024)
-        return fail(c, MDVT_ERR_UNSUPPORTED, "a slice of %d pixels' width does not fit the device FFV1 decoder's row buffers (num_h_slices %d)",
-                    line_stride - 2, sc.nh);
-    const int spf = sc.nh * sc.nv;
+    mdvt::Ffv1DecodeArgs a{};
+    if (int e = ffv1_decode_prologue(c, true, width, height, h_config, config_size, d_packets, packets_bytes, d_offsets, d_sizes, n_packets,
+                                     first_out, d_dst, pitch, frame_stride, order, d_status, &a))
+        return e;
+    const int spf = a.nh * a.nv;
     const size_t per_frame = (size_t)spf * 3 * sizeof(uint32_t) + sizeof(uint32_t);
     if (slots_afforded(c, per_frame, n_packets) < n_packets)
         return fail(c, MDVT_ERR_UNSUPPORTED, "%d packets of %d slices pass the workspace budget: split the call at a key frame", n_packets, spf);
@@ -563,17 +563,12 @@ int mdvt_decode_video_stream(mdvt_ctx* c, int width, int height, const uint8_t* 
     hipStream_t s = (hipStream_t)stream;
     MDVT_HIP(c, scratch_reserve(c, c->scratch[SCR_FFV1_STREAM], (size_t)n_packets * per_frame, s));
     static const mdvt::Ffv1StateTables tab = mdvt::ffv1_default_states();
-    mdvt::Ffv1StreamArgs a{};
-    a.packets = d_packets; a.packets_bytes = packets_bytes;
     a.offsets = reinterpret_cast<const unsigned long long*>(d_offsets); a.sizes = d_sizes;
     a.n_frames = n_packets; a.first_out = first_out;
-    a.W = width; a.H = height; a.nh = sc.nh; a.nv = sc.nv; a.ec = sc.ec; a.coder = sc.coder; a.micro = sc.micro;
-    a.dst = d_dst; a.pitch = pitch; a.frame_stride = frame_stride; a.ri = order == 1 ? 2 : 0; a.bi = order == 1 ? 0 : 2;
-    a.status = d_status;
+    a.dst = d_dst; a.status = d_status;
     a.table = c->scratch[SCR_FFV1_STREAM].as<uint32_t>();
     a.claims = a.table + (size_t)2 * n_packets * spf;
     a.kind = a.claims + (size_t)n_packets * spf;
-    a.line_stride = line_stride;
     MDVT_HIP(c, hipMemsetAsync(a.claims, 0, (size_t)n_packets * spf * sizeof(uint32_t), s));
     MDVT_HIP(c, mdvt::launch_ffv1_stream_decode(a, tab, s));
     return MDVT_OK;

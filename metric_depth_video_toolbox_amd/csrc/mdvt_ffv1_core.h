@@ -1,18 +1,20 @@
-// mdvt_ffv1_core.h -- the parts of FFV1 (RFC 9043) that the device encoder (mdvt_ffv1.hip), the device decoder
-// (mdvt_ffv1_decode.hip), the C ABI (mdvt_api.hip) and a host test program share: the tables, the CRC algebra, the slice-table
-// walk, the configuration record's parser and the range decoder of one slice.  Plain C++: it compiles for the host alone (g++,
-// where the tests run it under the sanitizers) and for host + device under hipcc; no HIP intrinsic, no allocation, no recursion.
+// mdvt_ffv1_core.h -- the parts of FFV1 (RFC 9043) that the device encoder (mdvt_ffv1.hip), the two device decode kernels
+// (mdvt_ffv1_decode.hip, mdvt_ffv1_stream_decode.hip), the C ABI (mdvt_api.hip) and the host test programs share: the tables, the
+// CRC algebra, the slice-table walk, the configuration record's parser and the decoder of one slice.  Plain C++: it compiles for
+// the host alone (g++, where the tests run it under the sanitizers) and for host + device under hipcc; no HIP intrinsic, no
+// allocation, no recursion.
 //
-// The decoder side restates csrc_host/mdvt_video.cpp (RacDec, get_symbol, Decoder::decode_frame / decode_slice) for the one
-// stream class the device reads: version 3, range coder with the default state table, key frames only, RGB (JPEG 2000 RCT),
-// 8 bits, no alpha, the default 666-context quantisation tables.  Nothing read from a packet steers a loop or an address: every
-// loop runs to a count fixed by the frame's geometry, bytes past a slice's end read as zero and are counted (the host's overread),
-// a symbol's exponent loop has the RFC's bound, and a context index is bounded by the quantisation arithmetic (|ctx| <= 665).
-//
-// The second half (BitReader, the Golomb-Rice pieces, ChainDec, parse_stream_class2) serves the stream decoder
-// (mdvt_ffv1_stream_decode.hip): version 3 with coder_type 0 or 1 and inter frames, whose context state carries from frame to
-// frame of a key-frame run.  The same rule holds there: a run length is consumed sample by sample inside the row's loop,
-// run_index is held inside kLog2Run whatever the bits say, and bits past a slice's end read as zero (the host reader's BitReader).
+// The decoder side restates csrc_host/mdvt_video.cpp (RacDec, BitReader, get_symbol, get_vlc_symbol, Decoder::decode_frame /
+// decode_slice) for version 3, RGB (JPEG 2000 RCT), 8 bits, no alpha, the default 666-context quantisation tables.  There is one
+// record parser and one slice decoder, SliceDec; the two entry points ask them for different classes of that format:
+//   intra    (mdvt_decode_video_frames)   the range coder with the default state table, key frames only: every slice of every
+//                                         frame starts from fresh context state
+//   stream   (mdvt_decode_video_stream)   Golomb-Rice or the range coder, key and inter frames: the context state carries from
+//                                         frame to frame of a key-frame run, and the caller resets it at a key frame
+// Nothing read from a packet steers a loop or an address: every loop runs to a count fixed by the frame's geometry, bytes and bits
+// past a slice's end read as zero (the host's overread, which the range coder counts), a symbol's exponent loop has the RFC's
+// bound, a context index is bounded by the quantisation arithmetic (|ctx| <= 665), a run length is consumed sample by sample
+// inside the row's loop, and run_index is held inside log2_run's domain whatever the bits say.
 #pragma once
 
 #include <stddef.h>
@@ -30,8 +32,9 @@ constexpr int kContexts = (11 * 11 * 11 + 1) / 2;         // 666
 constexpr int kStateBytes = kContexts * 32;                // one state set
 constexpr int kMaxSlices = 1024;                           // slices per frame the device codes / decodes
 
-// per-frame status words of mdvt_decode_video_frames (include/mdvt_ffv1_decode.h); the largest of a frame's slices wins
-enum : uint32_t { kOk = 0, kCrcMismatch = 1, kBadSliceHeader = 2, kDamaged = 3, kBadPacket = 4 };
+// per-frame status words (include/mdvt_ffv1_decode.h); the largest of a frame's slices wins.  The last two are
+// mdvt_decode_video_stream's alone (include/mdvt_ffv1_stream_decode.h)
+enum : uint32_t { kOk = 0, kCrcMismatch = 1, kBadSliceHeader = 2, kDamaged = 3, kBadPacket = 4, kNoKeyFrame = 5, kBrokenRun = 6 };
 
 // FFmpeg's quant11 (the host's quant11_of): the 11-level quantisation of (difference & 0xFF), with the i == 128 entry at -5
 MDVT_HD int quant11(int i)
@@ -166,225 +169,7 @@ struct RacDec {
         return (int)((a ^ (unsigned)neg) - (unsigned)neg);
     }
 };
-
-// One slice of an in-class frame.  The caller owns the memory: `st` two state sets (2 * kStateBytes, all 128), `lines` three
-// planes x three row slots x `stride` samples (stride >= slice width + 2, all zero), `misc` 64 bytes, q11[256] = quant11.
-// begin() reads the key-frame bit (first slice) and the slice header; row(y) decodes the three planes of slice row y into slot
-// y % 3 (sample k of plane p at lines[(p * 3 + y % 3) * stride + 1 + k]: Y, Cb + 256, Cr + 256 of the RCT); finish() gives the status.
-template <class Src>
-struct SliceDec {
-    RacDec<Src> c;
-    uint8_t* st; int16_t* lines; uint8_t* misc; const int8_t* q11;
-    int stride, sw, sh, x0, y0, cell;        // cell: the slice's index in the frame's nh x nv grid
-    bool error;
-
-    // `avail` bytes can be read through src (the payload and what follows it in the packet), `size` of them are the payload
-    MDVT_HD uint32_t begin(Src src, uint32_t avail, uint32_t size, bool first, int W, int H, int nh, int nv, const uint16_t* next)
-    {
-        c.src = src; c.next = next;
-        c.range = 0xFF00; c.overread = 0; c.pos = 2; c.end = size;
-        error = false; sw = sh = 0; x0 = y0 = 0; cell = 0;
-        // the host starts the first slice's coder on the whole packet (>= 3 bytes), the others on their payload (>= 2 bytes, or refused)
-        if (first ? avail < 2u : size < 2u) return kDamaged;
-        c.low = ((int)src.byte(0) << 8) | (int)src.byte(1);
-        if (c.low >= 0xFF00) { c.low = 0xFF00; if (!first) c.end = 2; }
-        for (int k = 0; k < 64; ++k) misc[k] = 128;
-        if (first && !c.get(misc + 32)) return kBadSliceHeader;                   // not a key frame: outside the device's class
-        bool bad = false;
-        const unsigned sx = (unsigned)c.symbol(misc, false, &bad), sy = (unsigned)c.symbol(misc, false, &bad);
-        const unsigned cw = (unsigned)c.symbol(misc, false, &bad) + 1u, ch = (unsigned)c.symbol(misc, false, &bad) + 1u;
-        if (bad || sx >= (unsigned)nh || sy >= (unsigned)nv || cw > (unsigned)nh - sx || ch > (unsigned)nv - sy) return kBadSliceHeader;
-        // nh * nv slices share nh * nv cells: a slice of more than one cell overlaps another or leaves a hole (the caller checks
-        // that no two slices claim the same cell, so the frame's slices tile it)
-        if (cw != 1u || ch != 1u) return kBadSliceHeader;
-        for (int p = 0; p < 2; ++p)
-            if (c.symbol(misc, false, &bad) != 0 || bad) return kBadSliceHeader;     // quant_table_set_index: one set
-        (void)c.symbol(misc, false, &bad);                                         // picture_structure, sar_num, sar_den
-        (void)c.symbol(misc, false, &bad);
-        (void)c.symbol(misc, false, &bad);
-        if (bad) return kBadSliceHeader;
-        cell = (int)(sy * (unsigned)nh + sx);
-        x0 = (int)((long long)sx * W / nh); y0 = (int)((long long)sy * H / nv);
-        sw = (int)((long long)(sx + 1u) * W / nh) - x0; sh = (int)((long long)(sy + 1u) * H / nv) - y0;
-        if (sw < 1 || sh < 1 || sw + 2 > stride) return kBadSliceHeader;
-        return kOk;
-    }
-
-    MDVT_HD void row(int y)
-    {
-        const int cs = y % 3, ls = (y + 2) % 3;
-        for (int p = 0; p < 3; ++p) {
-            int16_t* cur = lines + (size_t)(p * 3 + cs) * (size_t)stride + 1;
-            int16_t* last = lines + (size_t)(p * 3 + ls) * (size_t)stride + 1;
-            cur[-1] = last[0];
-            last[sw] = last[sw - 1];
-            uint8_t* states = st + (p ? kStateBytes : 0);
-            int L = cur[-1], LT = last[-1], T = last[0];
-            int q_lt_t = q11[(LT - T) & 0xFF];                 // (this sample's T - RT is the next one's LT - T)
-            for (int x = 0; x < sw; ++x) {
-                const int RT = last[x + 1];
-                const int q_t_rt = q11[(T - RT) & 0xFF];
-                int context = q11[(L - LT) & 0xFF] + 11 * q_lt_t + 121 * q_t_rt;
-                q_lt_t = q_t_rt;
-                const bool sign = context < 0;
-                if (sign) context = -context;
-                bool bad = false;
-                int diff = c.symbol(states + (size_t)context * 32u, true, &bad);
-                error |= bad;
-                if (sign) diff = -diff;
-                const int v = (median3(L, T, L + T - LT) + diff) & 511;
-                cur[x] = (int16_t)v;
-                L = v; LT = T; T = RT;
-            }
-        }
-    }
-
-    MDVT_HD uint32_t finish() const { return (error || c.overread > 4) ? kDamaged : kOk; }
-};
-
-// ---- the configuration record (RFC 9043 section 4.2), host side: is the stream in the device's class? ----
-struct PtrSrc {
-    const uint8_t* p;
-    MDVT_HD uint8_t byte(uint32_t k) const { return p[k]; }
-};
-
-struct StreamClass { int version, micro, nh, nv, ec; };
-
-// -> nullptr and *out when the device decodes the stream; else the reason (a static string naming the field)
-inline const char* parse_stream_class(const uint8_t* data, size_t size, StreamClass* out)
-{
-    if (!data || size < 6 || size > (1u << 20)) return "configuration record: missing or of an impossible size";
-    uint32_t crc = 0;
-    for (size_t i = 0; i < size; ++i) crc = (crc << 8) ^ crc_table_entry((crc >> 24) ^ data[i]);
-    uint8_t zero[256], one[256], state[32];
-    uint16_t next[256];
-    default_states(zero, one);
-    for (int k = 0; k < 256; ++k) next[k] = (uint16_t)(zero[k] | (one[k] << 8));
-    for (int k = 0; k < 32; ++k) state[k] = 128;
-    RacDec<PtrSrc> c;
-    c.src = PtrSrc{data}; c.next = next; c.range = 0xFF00; c.overread = 0; c.pos = 2; c.end = (uint32_t)size;
-    c.low = (data[0] << 8) | data[1];
-    if (c.low >= 0xFF00) { c.low = 0xFF00; c.end = 2; }
-    bool bad = false;
-    const int version = c.symbol(state, false, &bad);
-    if (bad || version != 3) return "version: only FFV1 version 3 is decoded on the device";
-    c.end = c.end >= 4u ? c.end - 4u : 0u;                   // the record's CRC parity is not range-coded
-    const int micro = c.symbol(state, false, &bad);
-    const int coder = c.symbol(state, false, &bad);
-    if (bad || coder != 1) return "coder_type: only the range coder with the default state table (coder_type 1) is decoded on the device";
-    const int colorspace = c.symbol(state, false, &bad);
-    if (bad || colorspace != 1) return "colorspace_type: only RGB (JPEG 2000 RCT) is decoded on the device";
-    const int bits = c.symbol(state, false, &bad);
-    if (bad || (bits != 0 && bits != 8)) return "bits_per_raw_sample: only 8 bits are decoded on the device";
-    (void)c.get(state);                                      // chroma_planes
-    (void)c.symbol(state, false, &bad);                      // log2_h_chroma_subsample, log2_v_chroma_subsample
-    (void)c.symbol(state, false, &bad);
-    if (c.get(state)) return "extra_plane: alpha planes are not decoded on the device";
-    const int nh = 1 + c.symbol(state, false, &bad), nv = 1 + c.symbol(state, false, &bad);
-    if (bad || nh < 1 || nv < 1 || nh > kMaxSlices || nv > kMaxSlices || nh * nv > kMaxSlices)
-        return "num_h_slices / num_v_slices: 1 to 1024 slices per frame are decoded on the device";
-    const int qcount = c.symbol(state, false, &bad);
-    if (bad || qcount != 1) return "quant_table_set_count: only one quantisation table set is decoded on the device";
-    int scale = 1;
-    for (int t = 0; t < 5; ++t) {                            // the host's read_quant_tables, compared with the default set
-        uint8_t qs[32];
-        for (int k = 0; k < 32; ++k) qs[k] = 128;
-        int i = 0, v = 0;
-        for (; i < 128; ++v) {
-            const unsigned len = (unsigned)c.symbol(qs, false, &bad) + 1u;
-            if (bad || len > (unsigned)(128 - i)) return "quantisation tables: malformed";
-            for (unsigned k = 0; k < len; ++k, ++i)
-                if (scale * v != (t < 3 ? scale * quant11(i) : 0))
-                    return "quantisation tables: only the default 666-context set (quant11, three inputs) is decoded on the device";
-        }
-        scale *= 2 * v - 1;
-        if (scale > 32768 || scale <= 0) return "quantisation tables: malformed";
-    }
-    if (scale != 11 * 11 * 11) return "quantisation tables: only the default 666-context set (quant11, three inputs) is decoded on the device";
-    if (c.get(state)) return "states_coded: initial states other than 128 are not decoded on the device";
-    const int ec = c.symbol(state, false, &bad);
-    if (bad || (ec != 0 && ec != 1)) return "ec: unknown error-correction mode";
-    const int intra = micro > 2 ? c.symbol(state, false, &bad) : 0;
-    if (bad) return "configuration record: malformed symbol";
-    if (!intra) return "intra: only streams whose every frame is a key frame are decoded on the device";
-    if (crc != 0) return "configuration record: CRC mismatch";
-    out->version = version; out->micro = micro; out->nh = nh; out->nv = nv; out->ec = ec;
-    return nullptr;
-}
-
-// ---- the stream decoder's class (mdvt_decode_video_stream): the same record with coder_type 0 or 1 and intra 0 or 1.  The walk is
-// parse_stream_class's, restated so that the function above stays as it is. ----
-struct StreamClass2 { int version, micro, nh, nv, ec, coder, intra; };
-
-// -> nullptr and *out when the stream decoder decodes the stream; else the reason (a static string naming the field)
-inline const char* parse_stream_class2(const uint8_t* data, size_t size, StreamClass2* out)
-{
-    if (!data || size < 6 || size > (1u << 20)) return "configuration record: missing or of an impossible size";
-    uint32_t crc = 0;
-    for (size_t i = 0; i < size; ++i) crc = (crc << 8) ^ crc_table_entry((crc >> 24) ^ data[i]);
-    uint8_t zero[256], one[256], state[32];
-    uint16_t next[256];
-    default_states(zero, one);
-    for (int k = 0; k < 256; ++k) next[k] = (uint16_t)(zero[k] | (one[k] << 8));
-    for (int k = 0; k < 32; ++k) state[k] = 128;
-    RacDec<PtrSrc> c;
-    c.src = PtrSrc{data}; c.next = next; c.range = 0xFF00; c.overread = 0; c.pos = 2; c.end = (uint32_t)size;
-    c.low = (data[0] << 8) | data[1];
-    if (c.low >= 0xFF00) { c.low = 0xFF00; c.end = 2; }
-    bool bad = false;
-    const int version = c.symbol(state, false, &bad);
-    if (bad || version != 3) return "version: only FFV1 version 3 is decoded on the device";
-    c.end = c.end >= 4u ? c.end - 4u : 0u;                   // the record's CRC parity is not range-coded
-    const int micro = c.symbol(state, false, &bad);
-    const int coder = c.symbol(state, false, &bad);
-    if (!bad && coder == 2) return "coder_type 2: a custom state-transition table is not decoded on the device";
-    if (bad || (coder != 0 && coder != 1))
-        return "coder_type: only Golomb-Rice (coder_type 0) and the range coder with the default state table (coder_type 1) are decoded on the device";
-    const int colorspace = c.symbol(state, false, &bad);
-    if (bad || colorspace != 1) return "colorspace_type: only RGB (JPEG 2000 RCT) is decoded on the device";
-    const int bits = c.symbol(state, false, &bad);
-    if (bad || (bits != 0 && bits != 8)) return "bits_per_raw_sample: only 8 bits are decoded on the device";
-    (void)c.get(state);                                      // chroma_planes
-    (void)c.symbol(state, false, &bad);                      // log2_h_chroma_subsample, log2_v_chroma_subsample
-    (void)c.symbol(state, false, &bad);
-    if (c.get(state)) return "extra_plane: alpha planes are not decoded on the device";
-    const int nh = 1 + c.symbol(state, false, &bad), nv = 1 + c.symbol(state, false, &bad);
-    if (bad || nh < 1 || nv < 1 || nh > kMaxSlices || nv > kMaxSlices || nh * nv > kMaxSlices)
-        return "num_h_slices / num_v_slices: 1 to 1024 slices per frame are decoded on the device";
-    const int qcount = c.symbol(state, false, &bad);
-    if (bad || qcount != 1) return "quant_table_set_count: only one quantisation table set is decoded on the device";
-    int scale = 1;
-    for (int t = 0; t < 5; ++t) {                            // the host's read_quant_tables, compared with the default set
-        uint8_t qs[32];
-        for (int k = 0; k < 32; ++k) qs[k] = 128;
-        int i = 0, v = 0;
-        for (; i < 128; ++v) {
-            const unsigned len = (unsigned)c.symbol(qs, false, &bad) + 1u;
-            if (bad || len > (unsigned)(128 - i)) return "quantisation tables: malformed";
-            for (unsigned k = 0; k < len; ++k, ++i)
-                if (scale * v != (t < 3 ? scale * quant11(i) : 0))
-                    return "quantisation tables: only the default 666-context set (quant11, three inputs) is decoded on the device";
-        }
-        scale *= 2 * v - 1;
-        if (scale > 32768 || scale <= 0) return "quantisation tables: malformed";
-    }
-    if (scale != 11 * 11 * 11) return "quantisation tables: only the default 666-context set (quant11, three inputs) is decoded on the device";
-    if (c.get(state)) return "states_coded: initial states other than 128 are not decoded on the device";
-    const int ec = c.symbol(state, false, &bad);
-    if (bad || (ec != 0 && ec != 1)) return "ec: unknown error-correction mode";
-    const int intra = micro > 2 ? c.symbol(state, false, &bad) : 0;
-    if (bad) return "configuration record: malformed symbol";
-    if (crc != 0) return "configuration record: CRC mismatch";
-    out->version = version; out->micro = micro; out->nh = nh; out->nv = nv; out->ec = ec; out->coder = coder; out->intra = intra ? 1 : 0;
-    return nullptr;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// The stream decoder's half: Golomb-Rice (RFC 9043 section 3.8.2) and context state that carries across the frames of a run
-// ---------------------------------------------------------------------------------------------------------------------
-// further status words, of mdvt_decode_video_stream alone (include/mdvt_ffv1_stream_decode.h)
-enum : uint32_t { kNoKeyFrame = 5, kBrokenRun = 6 };
-
+// ---- Golomb-Rice (RFC 9043 section 3.8.2), and what the stream class needs besides ----
 // the walk's word per frame: the packet's slice table holds and its key-frame bit is clear / set, or the packet is refused
 enum : uint32_t { kFrameInter = 0, kFrameKey = 1, kFrameBad = 2 };
 
@@ -492,45 +277,65 @@ MDVT_HD int get_vlc_symbol(BitReader<Src>& gb, VlcState* st, Stats& stats)
     return ret;
 }
 
-// One slice through the frames of a key-frame run (the host's Decoder::slices[index] with decode_slice).  The caller owns the
-// memory: `st` the context state, which it resets at a key frame and leaves alone otherwise -- coder_type 1: two range state sets
-// (2 * kStateBytes, all 128); coder_type 0: VlcState[2][kContexts] (vlc_reset) --, `lines` as for SliceDec and zeroed before every
-// frame, `misc` 64 bytes, q11[256].  Per frame: begin() reads the key-frame bit (first slice; its value is the caller's business),
-// the slice header and, for coder_type 0, the sentinel bit, and starts the bit reader where the host starts it; row(y) and
-// finish() as for SliceDec.
-template <class Src, class Stats = NoStats>
-struct ChainDec {
+// ---- one slice ----
+// the bytes of two context-state sets (luma, chroma): range coder 2 x 666 x 32, Golomb-Rice VlcState[2][666]; both multiples of 4
+MDVT_HD size_t state_bytes(int coder) { return 2u * (size_t)(coder ? kStateBytes : kVlcBytes); }
+
+// The JPEG 2000 RCT undone for one pixel: the samples of SliceDec's three planes (Y, Cb + 256, Cr + 256) -> the bytes o[ri], o[gi], o[bi]
+MDVT_HD void store_rct_pixel(int y, int cb, int cr, uint8_t* o, int ri, int gi, int bi)
+{
+    int g = y, b = cb - 256, r = cr - 256;
+    g -= (b + r) >> 2;
+    b += g; r += g;
+    o[ri] = (uint8_t)r; o[gi] = (uint8_t)g; o[bi] = (uint8_t)b;
+}
+
+// One slice of one frame (the host's Decoder::slices[index] with decode_slice).  kGolomb = false leaves the Golomb-Rice side out
+// of the compiled code: the intra class, whose coder_type is 1 whatever begin() is told.  The caller owns the memory: `st` the
+// context state (state_bytes(coder)), which it resets (reset_state(), or its own fill) where a run begins and leaves alone
+// otherwise; `lines` three planes x three row slots x `stride` samples (stride >= slice width + 2), all zero before every frame;
+// `misc` 64 bytes; q11[256] = quant11.  Per frame: begin() reads the key-frame bit (first slice: left in `key` for the caller to
+// judge), the slice header and, for coder_type 0, the sentinel bit, and starts the bit reader where the host starts it; row(y)
+// decodes the three planes of slice row y into slot y % 3 (sample k of plane p at lines[(p * 3 + y % 3) * stride + 1 + k]);
+// finish() gives the status.
+template <class Src, bool kGolomb = false, class Stats = NoStats>
+struct SliceDec {
     RacDec<Src> c;
     BitReader<Src> gb;
     uint8_t* st; int16_t* lines; uint8_t* misc; const int8_t* q11;
-    int stride, sw, sh, x0, y0, cell, coder, run_index;
+    int stride, sw, sh, x0, y0, cell;        // cell: the slice's index in the frame's nh x nv grid
+    int coder, run_index, key;               // key: the packet's key-frame bit, read by the frame's first slice (else 0)
     bool error;
     Stats stats;
 
-    MDVT_HD size_t state_bytes() const { return 2u * (size_t)(coder ? kStateBytes : kVlcBytes); }
-    MDVT_HD void reset_state()                             // (the kernel does this with the whole workgroup instead)
+    MDVT_HD bool golomb() const { return kGolomb && !coder; }
+    MDVT_HD void reset_state()                             // (the kernels do this with the whole workgroup instead)
     {
-        if (coder) for (int k = 0; k < 2 * kStateBytes; ++k) st[k] = 128;
+        if (!golomb()) for (int k = 0; k < 2 * kStateBytes; ++k) st[k] = 128;
         else for (int k = 0; k < 2 * kContexts; ++k) vlc_reset(reinterpret_cast<VlcState*>(st) + k);
     }
 
+    // `avail` bytes can be read through src (the payload and what follows it in the packet), `size` of them are the payload
     MDVT_HD uint32_t begin(Src src, uint32_t avail, uint32_t size, bool first, int coder_type, int micro, int W, int H, int nh, int nv,
                            const uint16_t* next)
     {
         c.src = src; c.next = next;
         c.range = 0xFF00; c.overread = 0; c.pos = 2; c.end = size;
-        coder = coder_type; run_index = 0;
+        coder = kGolomb ? coder_type : 1; run_index = 0; key = 0;
         error = false; sw = sh = 0; x0 = y0 = 0; cell = 0;
+        // the host starts the first slice's coder on the whole packet (>= 3 bytes), the others on their payload (>= 2 bytes, or refused)
         if (first ? avail < 2u : size < 2u) return kDamaged;
         c.low = ((int)src.byte(0) << 8) | (int)src.byte(1);
         if (c.low >= 0xFF00) { c.low = 0xFF00; if (!first) c.end = 2; }
         for (int k = 0; k < 64; ++k) misc[k] = 128;
-        if (first) (void)c.get(misc + 32);
+        if (first) key = c.get(misc + 32);
         bool bad = false;
         const unsigned sx = (unsigned)c.symbol(misc, false, &bad), sy = (unsigned)c.symbol(misc, false, &bad);
         const unsigned cw = (unsigned)c.symbol(misc, false, &bad) + 1u, ch = (unsigned)c.symbol(misc, false, &bad) + 1u;
         if (bad || sx >= (unsigned)nh || sy >= (unsigned)nv || cw > (unsigned)nh - sx || ch > (unsigned)nv - sy) return kBadSliceHeader;
-        if (cw != 1u || ch != 1u) return kBadSliceHeader;                          // (as SliceDec: the slices tile the frame)
+        // nh * nv slices share nh * nv cells: a slice of more than one cell overlaps another or leaves a hole (the caller checks
+        // that no two slices claim the same cell, so the frame's slices tile it)
+        if (cw != 1u || ch != 1u) return kBadSliceHeader;
         for (int p = 0; p < 2; ++p)
             if (c.symbol(misc, false, &bad) != 0 || bad) return kBadSliceHeader;     // quant_table_set_index: one set
         (void)c.symbol(misc, false, &bad);                                         // picture_structure, sar_num, sar_den
@@ -541,7 +346,7 @@ struct ChainDec {
         x0 = (int)((long long)sx * W / nh); y0 = (int)((long long)sy * H / nv);
         sw = (int)((long long)(sx + 1u) * W / nh) - x0; sh = (int)((long long)(sy + 1u) * H / nv) - y0;
         if (sw < 1 || sh < 1 || sw + 2 > stride) return kBadSliceHeader;
-        if (!coder) {
+        if (golomb()) {
             if (micro > 1) { misc[33] = 129; (void)c.get(misc + 33); }             // the sentinel of ff_rac_terminate
             const uint32_t consumed = c.pos - 1u;                                  // the host's `p - start - 1`
             if (consumed > size) return kBadSliceHeader;                           // "header overruns the slice"
@@ -559,8 +364,8 @@ struct ChainDec {
             cur[-1] = last[0];
             last[sw] = last[sw - 1];
             int L = cur[-1], LT = last[-1], T = last[0];
-            int q_lt_t = q11[(LT - T) & 0xFF];
-            if (coder) {
+            int q_lt_t = q11[(LT - T) & 0xFF];                 // (this sample's T - RT is the next one's LT - T)
+            if (!golomb()) {
                 uint8_t* states = st + (p ? kStateBytes : 0);
                 for (int x = 0; x < sw; ++x) {
                     const int RT = last[x + 1];
@@ -623,5 +428,82 @@ struct ChainDec {
     // (the host reader has no overread check on the Golomb side: c.overread counts the header's reads alone there)
     MDVT_HD uint32_t finish() const { return (error || c.overread > 4) ? kDamaged : kOk; }
 };
+
+// ---- the configuration record (RFC 9043 section 4.2), host side: is the stream in the class the entry point decodes? ----
+struct PtrSrc {
+    const uint8_t* p;
+    MDVT_HD uint8_t byte(uint32_t k) const { return p[k]; }
+};
+
+struct StreamClass { int version, micro, nh, nv, ec, coder, intra; };
+
+// -> nullptr and *out when the stream is in the class asked for -- intra: coder_type 1 and intra 1; stream: coder_type 0 or 1,
+// intra 0 or 1 --, else the reason (a static string naming the field)
+inline const char* parse_stream_class(const uint8_t* data, size_t size, bool stream, StreamClass* out)
+{
+    if (!data || size < 6 || size > (1u << 20)) return "configuration record: missing or of an impossible size";
+    uint32_t crc = 0;
+    for (size_t i = 0; i < size; ++i) crc = (crc << 8) ^ crc_table_entry((crc >> 24) ^ data[i]);
+    uint8_t zero[256], one[256], state[32];
+    uint16_t next[256];
+    default_states(zero, one);
+    for (int k = 0; k < 256; ++k) next[k] = (uint16_t)(zero[k] | (one[k] << 8));
+    for (int k = 0; k < 32; ++k) state[k] = 128;
+    RacDec<PtrSrc> c;
+    c.src = PtrSrc{data}; c.next = next; c.range = 0xFF00; c.overread = 0; c.pos = 2; c.end = (uint32_t)size;
+    c.low = (data[0] << 8) | data[1];
+    if (c.low >= 0xFF00) { c.low = 0xFF00; c.end = 2; }
+    bool bad = false;
+    const int version = c.symbol(state, false, &bad);
+    if (bad || version != 3) return "version: only FFV1 version 3 is decoded on the device";
+    c.end = c.end >= 4u ? c.end - 4u : 0u;                   // the record's CRC parity is not range-coded
+    const int micro = c.symbol(state, false, &bad);
+    const int coder = c.symbol(state, false, &bad);
+    if (!stream) {
+        if (bad || coder != 1) return "coder_type: only the range coder with the default state table (coder_type 1) is decoded on the device";
+    } else {
+        if (!bad && coder == 2) return "coder_type 2: a custom state-transition table is not decoded on the device";
+        if (bad || (coder != 0 && coder != 1))
+            return "coder_type: only Golomb-Rice (coder_type 0) and the range coder with the default state table (coder_type 1) are decoded on the device";
+    }
+    const int colorspace = c.symbol(state, false, &bad);
+    if (bad || colorspace != 1) return "colorspace_type: only RGB (JPEG 2000 RCT) is decoded on the device";
+    const int bits = c.symbol(state, false, &bad);
+    if (bad || (bits != 0 && bits != 8)) return "bits_per_raw_sample: only 8 bits are decoded on the device";
+    (void)c.get(state);                                      // chroma_planes
+    (void)c.symbol(state, false, &bad);                      // log2_h_chroma_subsample, log2_v_chroma_subsample
+    (void)c.symbol(state, false, &bad);
+    if (c.get(state)) return "extra_plane: alpha planes are not decoded on the device";
+    const int nh = 1 + c.symbol(state, false, &bad), nv = 1 + c.symbol(state, false, &bad);
+    if (bad || nh < 1 || nv < 1 || nh > kMaxSlices || nv > kMaxSlices || nh * nv > kMaxSlices)
+        return "num_h_slices / num_v_slices: 1 to 1024 slices per frame are decoded on the device";
+    const int qcount = c.symbol(state, false, &bad);
+    if (bad || qcount != 1) return "quant_table_set_count: only one quantisation table set is decoded on the device";
+    int scale = 1;
+    for (int t = 0; t < 5; ++t) {                            // the host's read_quant_tables, compared with the default set
+        uint8_t qs[32];
+        for (int k = 0; k < 32; ++k) qs[k] = 128;
+        int i = 0, v = 0;
+        for (; i < 128; ++v) {
+            const unsigned len = (unsigned)c.symbol(qs, false, &bad) + 1u;
+            if (bad || len > (unsigned)(128 - i)) return "quantisation tables: malformed";
+            for (unsigned k = 0; k < len; ++k, ++i)
+                if (scale * v != (t < 3 ? scale * quant11(i) : 0))
+                    return "quantisation tables: only the default 666-context set (quant11, three inputs) is decoded on the device";
+        }
+        scale *= 2 * v - 1;
+        if (scale > 32768 || scale <= 0) return "quantisation tables: malformed";
+    }
+    if (scale != 11 * 11 * 11) return "quantisation tables: only the default 666-context set (quant11, three inputs) is decoded on the device";
+    if (c.get(state)) return "states_coded: initial states other than 128 are not decoded on the device";
+    const int ec = c.symbol(state, false, &bad);
+    if (bad || (ec != 0 && ec != 1)) return "ec: unknown error-correction mode";
+    const int intra = micro > 2 ? c.symbol(state, false, &bad) : 0;
+    if (bad) return "configuration record: malformed symbol";
+    if (!stream && !intra) return "intra: only streams whose every frame is a key frame are decoded on the device";
+    if (crc != 0) return "configuration record: CRC mismatch";
+    out->version = version; out->micro = micro; out->nh = nh; out->nv = nv; out->ec = ec; out->coder = coder; out->intra = intra ? 1 : 0;
+    return nullptr;
+}
 
 }  // namespace mdvt_ffv1

@@ -249,36 +249,29 @@ Ffv1StateTables ffv1_default_states();
 hipError_t launch_ffv1_code(const Ffv1CodeArgs& a, const Ffv1StateTables& tab, int n_slices, hipStream_t s);
 hipError_t launch_ffv1_layout(const Ffv1LayoutArgs& a, hipStream_t s);
 hipError_t launch_ffv1_emit(const Ffv1EmitArgs& a, int n_slices, hipStream_t s);
-// mdvt_ffv1_decode.hip: FFV1 decoding of packets in device memory (mdvt_decode_video_frames, include/mdvt_ffv1_decode.h)
+// mdvt_ffv1_decode.hip, mdvt_ffv1_stream_decode.hip: FFV1 decoding of packets in device memory (mdvt_decode_video_frames,
+// include/mdvt_ffv1_decode.h: key frames only, a pass of frames at a time; mdvt_decode_video_stream,
+// include/mdvt_ffv1_stream_decode.h: inter frames and Golomb-Rice coding, consecutive packets).  The first call leaves the last
+// four fields zero.
 struct Ffv1DecodeArgs {
     const uint8_t* packets; unsigned long long packets_bytes;      // the packet buffer and its size: no packet may pass it
     const unsigned long long* offsets; const uint32_t* sizes;      // the caller's arrays, at the pass's first frame
     int n_frames, W, H, nh, nv, ec;
-    uint8_t* dst; size_t pitch, frame_stride; int ri, bi;          // the pass's first frame; the byte of R and of B in a pixel
+    uint8_t* dst; size_t pitch, frame_stride; int ri, bi;          // the pass's first stored frame; the byte of R and of B in a pixel
     uint32_t* status;                                              // the caller's status words, at the pass's first frame
     uint32_t* table;                                               // workspace [2][frames of the pass * slices]: slice offsets, payload bytes
     uint32_t* claims;                                              // workspace [frames of the pass * slices], zeroed: a cell's claim
     int line_stride;                                               // samples per row slot in LDS: the widest slice + 2
+    int first_out, coder, micro;                                   // the first frame that is stored; the record's coder_type and micro_version
+    uint32_t* kind;                                                // workspace [n_frames]: mdvt_ffv1::kFrameInter / Key / Bad
 };
-size_t ffv1_decode_lds_bytes(int line_stride);                     // dynamic LDS of the slice kernel
+size_t ffv1_decode_lds_bytes(int line_stride);                     // dynamic LDS of k_ffv1_dec_slice: the row slots
+size_t ffv1_stream_lds_bytes(int coder, int line_stride);          // dynamic LDS of k_ffv1_stream_chain: the context state, then the row slots
+// static LDS of k_ffv1_stream_chain, rounded up.  k_ffv1_dec_slice keeps its context state (coder_type 1) there as well, so this +
+// ffv1_stream_lds_bytes(coder, line_stride) is the whole LDS of either kernel: what is left of a CU's 160 KiB bounds the widest slice
 size_t ffv1_decode_static_lds_bytes();
 hipError_t launch_ffv1_decode(const Ffv1DecodeArgs& a, const Ffv1StateTables& tab, hipStream_t s);
-// mdvt_ffv1_stream_decode.hip: FFV1 streams with inter frames and Golomb-Rice coding (mdvt_decode_video_stream,
-// include/mdvt_ffv1_stream_decode.h)
-struct Ffv1StreamArgs {
-    const uint8_t* packets; unsigned long long packets_bytes;
-    const unsigned long long* offsets; const uint32_t* sizes;      // the caller's arrays: n_frames consecutive packets
-    int n_frames, first_out, W, H, nh, nv, ec, coder, micro;
-    uint8_t* dst; size_t pitch, frame_stride; int ri, bi;          // frame first_out lies at dst
-    uint32_t* status;                                              // the caller's n_frames status words
-    uint32_t* table;                                               // workspace [2][n_frames * slices]: slice offsets, payload bytes
-    uint32_t* claims;                                              // workspace [n_frames * slices], zeroed: a cell's claim
-    uint32_t* kind;                                                // workspace [n_frames]: mdvt_ffv1::kFrameInter / Key / Bad
-    int line_stride;
-};
-size_t ffv1_stream_lds_bytes(int coder, int line_stride);          // dynamic LDS of the chain kernel: context state, then the row slots
-size_t ffv1_stream_static_lds_bytes();
-hipError_t launch_ffv1_stream_decode(const Ffv1StreamArgs& a, const Ffv1StateTables& tab, hipStream_t s);
+hipError_t launch_ffv1_stream_decode(const Ffv1DecodeArgs& a, const Ffv1StateTables& tab, hipStream_t s);
 // mdvt_convergence.hip: per-frame masked depth means (mdvt_convergence_depths, include/mdvt_convergence.h)
 struct ConvergenceArgs {
     const uint8_t* depth; size_t depth_pitch, depth_stride; int depth_bgr, depth_vec;     // the set's first frame; _vec: 12-byte loads are aligned

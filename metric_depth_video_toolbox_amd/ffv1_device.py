@@ -162,24 +162,37 @@ DECODE_STATUS = {0: "decoded", 1: "CRC mismatch in a slice", 2: "malformed slice
                  4: "slice sizes do not add up to the packet"}
 
 
-def supported(info, config: Optional[bytes] = None) -> Optional[str]:
-    """None when the device decodes the stream of a video_io.VideoInfo (and, when given, its configuration record), else the
-    reason, naming the field.  Touches no GPU: the record is parsed by the library's host code."""
+def _class_reason(info, config: Optional[bytes], stream: bool) -> Optional[str]:
+    """None when the stream of a video_io.VideoInfo (and, when given, its configuration record) is in the intra decoder's class or
+    (`stream`) the stream decoder's, else the reason, naming the field."""
     if info.ffv1_version != 3:
         return f"version: FFV1 version {info.ffv1_version} (only version 3 is decoded on the device)"
-    if info.coder_type != 1:
+    if stream and info.coder_type not in (0, 1):
+        return f"coder_type {info.coder_type}: a custom state-transition table is not decoded on the device"
+    if not stream and info.coder_type != 1:
         return f"coder_type: {info.coder_type} (only the range coder with the default state table, 1, is decoded on the device)"
     if info.alpha:
         return "extra_plane: alpha planes are not decoded on the device"
-    if not info.intra:
+    if not stream and not info.intra:
         return "intra: only streams whose every frame is a key frame are decoded on the device"
     if not 1 <= info.slices <= 1024:
         return f"num_h_slices / num_v_slices: {info.slices} slices per frame (1 to 1024 are decoded on the device)"
     if config is not None:
-        why = _lib.load().mdvt_ffv1_decode_supported(config, len(config))
+        why = _record_reason(config, stream)
         if why:
             return why.decode()
     return None
+
+
+def _record_reason(config: bytes, stream: bool):
+    L = _lib.load()
+    return (L.mdvt_ffv1_stream_decode_supported if stream else L.mdvt_ffv1_decode_supported)(config, len(config))
+
+
+def supported(info, config: Optional[bytes] = None) -> Optional[str]:
+    """None when the device decodes the stream of a video_io.VideoInfo (and, when given, its configuration record), else the
+    reason, naming the field.  Touches no GPU: the record is parsed by the library's host code."""
+    return _class_reason(info, config, False)
 
 
 def check_out(out, N: int, H: int, W: int) -> None:
@@ -194,14 +207,19 @@ def check_out(out, N: int, H: int, W: int) -> None:
 
 
 class PendingFrames:
-    """The device side of one decode: `out` and the status words, filled on the stream the decode was enqueued on (`done` is
-    recorded there behind it).  The pinned staging buffers live as long as this object."""
+    """The device side of one decode: `out` (the frames from first_out on) and the status words (one per packet), filled on the
+    stream the decode was enqueued on (`done` is recorded there behind it).  The pinned staging buffers live as long as this object."""
 
-    def __init__(self, packets, config, W, H, bgr, out, status, done, staged):
-        self.packets, self.config, self.W, self.H, self.bgr = packets, config, W, H, bgr
+    def __init__(self, packets, config, W, H, bgr, out, status, done, staged, first_out=0):
+        self.packets, self.config, self.W, self.H, self.bgr, self.first_out = packets, config, W, H, bgr, first_out
         self.out, self.status, self.done, self._staged = out, status, done, staged
-        self.host_frames = 0                  # frames collect() had to decode on the host (flagged by the device)
-        self.flags = None                     # numpy uint32 [N] after collect(): the device's status words
+        self.host_frames = 0                  # stored frames collect() had to decode on the host (flagged by the device)
+        self.flags = None                     # numpy uint32 [packets] after collect(): the device's status words
+
+    def _wait(self) -> None:
+        self.done.synchronize()
+        self.flags = self.status.cpu().numpy().view(np.uint32)
+        self._staged = None
 
     def collect(self, threads: int = 1):
         """Waits for the decode and reads the status words.  A flagged frame is decoded on the host (video_io.decode_frame: the
@@ -209,9 +227,7 @@ class PendingFrames:
         host_frames.  -> out"""
         import torch
         from . import video_io
-        self.done.synchronize()
-        self.flags = self.status.cpu().numpy().view(np.uint32)
-        self._staged = None
+        self._wait()
         for k in np.nonzero(self.flags)[0]:
             self.host_frames += 1
             frame = video_io.decode_frame(self.packets[k], self.config, self.W, self.H, bgr=self.bgr, threads=threads)
@@ -245,24 +261,28 @@ class StagedPackets:
         return len(self.packets)
 
 
-def enqueue_decode(ctx: "_lib.Context", packets, config: bytes, width: int, height: int, bgr: bool = False, out=None,
-                   stream=None) -> PendingFrames:
-    """Packs the packets into one pinned blob (or takes a StagedPackets), copies it on a side stream and enqueues the decode into
-    `out` (default: a new N x H x W x 3 tensor on the ctx's device) on `stream` (default: the current stream).  MdvtError
-    (MDVT_ERR_UNSUPPORTED) for a configuration record outside the device's class, before anything is copied."""
+def _enqueue_decode(pending, ctx, packets, config, width, height, first_out, bgr, out, stream):
+    """Both decoders' staging: the class check, the pinned blob (or a StagedPackets), its copy on a side stream, the call on
+    `stream` and the event behind it.  first_out None: mdvt_decode_video_frames, every frame stored; else mdvt_decode_video_stream.
+    -> pending(...)"""
     import torch
     W, H = int(width), int(height)
     if W < 1 or H < 1:
         raise ValueError(f"frames of {W} x {H}")
-    why = _lib.load().mdvt_ffv1_decode_supported(config, len(config))
+    streamed = first_out is not None
+    why = _record_reason(config, streamed)
     if why:
-        raise _lib.MdvtError(-3, f"FFV1 stream outside the device decoder's class: {why.decode()}")
+        raise _lib.MdvtError(-3, f"FFV1 stream outside the device {'stream ' if streamed else ''}decoder's class: {why.decode()}")
     staged = packets if isinstance(packets, StagedPackets) else StagedPackets(packets)
     N, total = len(staged), staged.total
+    first = int(first_out) if streamed else 0
+    if not 0 <= first < N:
+        raise ValueError(f"first_out {first} outside [0, {N})")
     dev = torch.device("cuda", ctx.device)
+    n_out = N - first
     if out is None:
-        out = torch.empty((N, H, W, 3), dtype=torch.uint8, device=dev)
-    check_out(out, N, H, W)
+        out = torch.empty((n_out, H, W, 3), dtype=torch.uint8, device=dev)
+    check_out(out, n_out, H, W)
     s = stream if stream is not None else torch.cuda.current_stream(dev)
     side = torch.cuda.Stream(dev)
     with torch.cuda.stream(side):
@@ -277,13 +297,22 @@ def enqueue_decode(ctx: "_lib.Context", packets, config: bytes, width: int, heig
     s.wait_event(copied)
     for t in (d_blob, d_meta, d_sizes, status):
         t.record_stream(s)
-    ctx.call("mdvt_decode_video_frames", W, H, config, len(config), C.c_void_p(d_blob.data_ptr()), total,
-             C.c_void_p(d_meta.data_ptr()), C.c_void_p(d_sizes.data_ptr()), N,
-             C.c_void_p(out.data_ptr()), out.stride(1), out.stride(0) if N > 1 else out.stride(1) * H,
+    ctx.call("mdvt_decode_video_stream" if streamed else "mdvt_decode_video_frames", W, H, config, len(config),
+             C.c_void_p(d_blob.data_ptr()), total, C.c_void_p(d_meta.data_ptr()), C.c_void_p(d_sizes.data_ptr()), N,
+             *((first,) if streamed else ()),
+             C.c_void_p(out.data_ptr()), out.stride(1), out.stride(0) if n_out > 1 else out.stride(1) * H,
              1 if bgr else 0, C.c_void_p(status.data_ptr()), _lib.stream_arg(dev, s))
     done = torch.cuda.Event()
     done.record(s)
-    return PendingFrames(staged.packets, config, W, H, bgr, out, status, done, (staged, d_blob, d_meta, d_sizes))
+    return pending(staged.packets, config, W, H, bgr, out, status, done, (staged, d_blob, d_meta, d_sizes), first)
+
+
+def enqueue_decode(ctx: "_lib.Context", packets, config: bytes, width: int, height: int, bgr: bool = False, out=None,
+                   stream=None) -> PendingFrames:
+    """Packs the packets into one pinned blob (or takes a StagedPackets), copies it on a side stream and enqueues the decode into
+    `out` (default: a new N x H x W x 3 tensor on the ctx's device) on `stream` (default: the current stream).  MdvtError
+    (MDVT_ERR_UNSUPPORTED) for a configuration record outside the device's class, before anything is copied."""
+    return _enqueue_decode(PendingFrames, ctx, packets, config, width, height, None, bgr, out, stream)
 
 
 def decode_frames_on_device(packets, config: bytes, width: int, height: int, *, bgr: bool = False, out=None, stream=None,
@@ -307,19 +336,7 @@ STREAM_STATUS = {**DECODE_STATUS, NO_KEY_FRAME: "no key frame at or before this 
 def stream_supported(info, config: Optional[bytes] = None) -> Optional[str]:
     """supported() for the stream decoder's class: version 3, coder_type 0 or 1, intra 0 or 1 (the files FFmpeg and OpenCV write
     by default are in it).  None, or the reason, naming the field."""
-    if info.ffv1_version != 3:
-        return f"version: FFV1 version {info.ffv1_version} (only version 3 is decoded on the device)"
-    if info.coder_type not in (0, 1):
-        return f"coder_type {info.coder_type}: a custom state-transition table is not decoded on the device"
-    if info.alpha:
-        return "extra_plane: alpha planes are not decoded on the device"
-    if not 1 <= info.slices <= 1024:
-        return f"num_h_slices / num_v_slices: {info.slices} slices per frame (1 to 1024 are decoded on the device)"
-    if config is not None:
-        why = _lib.load().mdvt_ffv1_stream_decode_supported(config, len(config))
-        if why:
-            return why.decode()
-    return None
+    return _class_reason(info, config, True)
 
 
 def packet_is_key(packet: bytes) -> bool:
@@ -327,14 +344,8 @@ def packet_is_key(packet: bytes) -> bool:
     return _lib.load().mdvt_ffv1_packet_is_key(packet, len(packet)) == 1
 
 
-class PendingStreamFrames:
+class PendingStreamFrames(PendingFrames):
     """The device side of one stream decode: `out` holds frames first_out ... of the packets, `status` one word per packet."""
-
-    def __init__(self, packets, config, W, H, bgr, first_out, out, status, done, staged):
-        self.packets, self.config, self.W, self.H, self.bgr, self.first_out = packets, config, W, H, bgr, first_out
-        self.out, self.status, self.done, self._staged = out, status, done, staged
-        self.host_frames = 0                  # stored frames collect() had to decode on the host
-        self.flags = None                     # numpy uint32 [packets] after collect(): the device's status words
 
     def collect(self, threads: int = 1):
         """Waits for the decode and reads the status words.  A flagged frame cannot be decoded alone: the host decodes its whole
@@ -342,9 +353,7 @@ class PendingStreamFrames:
         frame of the run from the first flagged one on is copied into its place and counted in host_frames.  -> out"""
         import torch
         from . import video_io
-        self.done.synchronize()
-        self.flags = self.status.cpu().numpy().view(np.uint32)
-        self._staged = None
+        self._wait()
         bad = np.nonzero(self.flags[self.first_out:])[0] + self.first_out
         done_to = -1
         for k in bad:
@@ -374,44 +383,7 @@ def enqueue_decode_stream(ctx: "_lib.Context", packets, config: bytes, width: in
     """enqueue_decode for consecutive packets of one stream of the stream decoder's class.  Frames first_out ... are stored in `out`
     (default: a new (N - first_out) x H x W x 3 tensor); the packets before first_out are decoded for their context state alone
     (the caller prepends them from the last key frame on).  State is not carried from one call to the next."""
-    import torch
-    W, H = int(width), int(height)
-    if W < 1 or H < 1:
-        raise ValueError(f"frames of {W} x {H}")
-    why = _lib.load().mdvt_ffv1_stream_decode_supported(config, len(config))
-    if why:
-        raise _lib.MdvtError(-3, f"FFV1 stream outside the device stream decoder's class: {why.decode()}")
-    staged = packets if isinstance(packets, StagedPackets) else StagedPackets(packets)
-    N, total = len(staged), staged.total
-    first_out = int(first_out)
-    if not 0 <= first_out < N:
-        raise ValueError(f"first_out {first_out} outside [0, {N})")
-    dev = torch.device("cuda", ctx.device)
-    n_out = N - first_out
-    if out is None:
-        out = torch.empty((n_out, H, W, 3), dtype=torch.uint8, device=dev)
-    check_out(out, n_out, H, W)
-    s = stream if stream is not None else torch.cuda.current_stream(dev)
-    side = torch.cuda.Stream(dev)
-    with torch.cuda.stream(side):
-        d_blob = torch.empty(max(1, total), dtype=torch.uint8, device=dev)
-        d_meta = torch.empty(2 * N, dtype=torch.int64, device=dev)
-        d_blob.copy_(staged.h_blob, non_blocking=True)
-        d_meta.copy_(staged.h_meta, non_blocking=True)
-        d_sizes = d_meta[N:].to(torch.int32)
-        status = torch.empty(N, dtype=torch.int32, device=dev)
-        copied = torch.cuda.Event()
-        copied.record(side)
-    s.wait_event(copied)
-    for t in (d_blob, d_meta, d_sizes, status):
-        t.record_stream(s)
-    ctx.call("mdvt_decode_video_stream", W, H, config, len(config), C.c_void_p(d_blob.data_ptr()), total,
-             C.c_void_p(d_meta.data_ptr()), C.c_void_p(d_sizes.data_ptr()), N, first_out,
-             C.c_void_p(out.data_ptr()), out.stride(1), out.stride(0) if n_out > 1 else out.stride(1) * H,
-             1 if bgr else 0, C.c_void_p(status.data_ptr()), _lib.stream_arg(dev, s))
-    done = torch.cuda.Event()
-    done.record(s)
-    return PendingStreamFrames(staged.packets, config, W, H, bgr, first_out, out, status, done, (staged, d_blob, d_meta, d_sizes))
+    return _enqueue_decode(PendingStreamFrames, ctx, packets, config, width, height, int(first_out), bgr, out, stream)
 
 
 def decode_stream_on_device(packets, config: bytes, width: int, height: int, *, first_out: int = 0, bgr: bool = False, out=None,

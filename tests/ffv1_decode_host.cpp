@@ -7,32 +7,12 @@
 //          then width * height * 3 bytes (zero where nothing was stored)
 // The frame is decoded the way the kernels do it: slice table first, CRCs next, then slice by slice with the cell claims.  Every
 // buffer is allocated at its exact size and every byte of a packet is read through a checked accessor.
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <vector>
-
-#include "mdvt_ffv1_core.h"
-
-using namespace mdvt_ffv1;
-
-#define CHECK(c) do { if (!(c)) { fprintf(stderr, "bound violated: %s (line %d)\n", #c, __LINE__); abort(); } } while (0)
-
-struct CheckedSrc {
-    const uint8_t* p; uint32_t avail;
-    uint8_t byte(uint32_t k) const { CHECK(k < avail); return p[k]; }
-};
-
-struct CheckedPacket {
-    const uint8_t* p; uint32_t size;
-    uint8_t operator()(uint32_t k) const { CHECK(k < size); return p[k]; }
-};
+#include "ffv1_host_common.h"
 
 static uint32_t decode(int W, int H, int order, const std::vector<uint8_t>& cfg, const std::vector<uint8_t>& pkt_in, uint8_t* dst, uint32_t* samples)
 {
     StreamClass sc{};
-    if (parse_stream_class(cfg.data(), cfg.size(), &sc) || sc.nh > W || sc.nv > H) return 100;
+    if (parse_stream_class(cfg.data(), cfg.size(), false, &sc) || sc.nh > W || sc.nv > H) return 100;
     // the packet at its exact size on the heap: a read past it is the sanitizer's
     uint8_t* pkt = (uint8_t*)malloc(pkt_in.size() ? pkt_in.size() : 1);
     memcpy(pkt, pkt_in.data(), pkt_in.size());
@@ -42,26 +22,21 @@ static uint32_t decode(int W, int H, int order, const std::vector<uint8_t>& cfg,
     uint32_t status = walk_slices(CheckedPacket{pkt, size}, size, n, sc.ec, off.data(), len.data());
     const uint32_t trailer = sc.ec ? 8u : 3u;
     if (status == kOk && sc.ec)
-        for (int i = 0; i < n; ++i) {
-            uint32_t crc = 0;
-            for (uint32_t k = 0; k < len[i] + trailer; ++k) crc = (crc << 8) ^ crc_table_entry((crc >> 24) ^ CheckedPacket{pkt, size}(off[i] + k));
-            if (crc) status = kCrcMismatch;                      // (the kernel skips the slice; here the whole frame)
-        }
-    uint8_t zero[256], one[256];
-    int8_t q11[256];
-    uint16_t next[256];
-    default_states(zero, one);
-    for (int k = 0; k < 256; ++k) { q11[k] = (int8_t)quant11(k); next[k] = (uint16_t)(zero[k] | (one[k] << 8)); }
+        for (int i = 0; i < n; ++i)
+            if (slice_crc(CheckedPacket{pkt, size}, off[i], len[i] + trailer)) status = kCrcMismatch;      // (the kernel skips the slice; here the whole frame)
+    const Tables tab;
     const int stride = (W + sc.nh - 1) / sc.nh + 2;
     const int ri = order == 1 ? 2 : 0, bi = order == 1 ? 0 : 2;
     for (int i = 0; i < n && status == kOk; ++i) {
-        uint8_t* st = (uint8_t*)malloc(2 * kStateBytes);
+        SliceDec<CheckedSrc> d;
+        d.coder = sc.coder;
+        uint8_t* st = (uint8_t*)malloc(state_bytes(d.coder));
         int16_t* lines = (int16_t*)calloc((size_t)9 * stride, sizeof(int16_t));
         uint8_t* misc = (uint8_t*)malloc(64);
-        memset(st, 128, 2 * kStateBytes);
-        SliceDec<CheckedSrc> d;
-        d.st = st; d.lines = lines; d.misc = misc; d.q11 = q11; d.stride = stride;
-        uint32_t s = d.begin(CheckedSrc{pkt + off[i], len[i] + trailer}, len[i] + trailer, len[i], i == 0, W, H, sc.nh, sc.nv, next);
+        d.st = st; d.lines = lines; d.misc = misc; d.q11 = tab.q11; d.stride = stride;
+        d.reset_state();
+        uint32_t s = d.begin(CheckedSrc{pkt + off[i], len[i] + trailer}, len[i] + trailer, len[i], i == 0, sc.coder, sc.micro, W, H, sc.nh, sc.nv, tab.next);
+        if (s == kOk && i == 0 && !d.key) s = kBadSliceHeader;   // not a key frame: k_ffv1_dec_slice's verdict
         if (s == kOk) {
             CHECK(d.cell >= 0 && d.cell < n);
             if (claims[(size_t)d.cell]++) s = kBadSliceHeader;
@@ -71,14 +46,7 @@ static uint32_t decode(int W, int H, int order, const std::vector<uint8_t>& cfg,
             for (int y = 0; y < d.sh; ++y) {
                 d.row(y);
                 *samples += 3u * (uint32_t)d.sw;
-                uint8_t* o = dst + ((size_t)(d.y0 + y) * W + d.x0) * 3;
-                for (int x = 0; x < d.sw; ++x) {
-                    int g = lines[(size_t)(0 * 3 + y % 3) * stride + 1 + x], b = lines[(size_t)(1 * 3 + y % 3) * stride + 1 + x] - 256,
-                        r = lines[(size_t)(2 * 3 + y % 3) * stride + 1 + x] - 256;
-                    g -= (b + r) >> 2;
-                    b += g; r += g;
-                    o[3 * x + ri] = (uint8_t)r; o[3 * x + 1] = (uint8_t)g; o[3 * x + bi] = (uint8_t)b;
-                }
+                store_row(d, y, dst, W, ri, bi);
             }
             s = d.finish();
         }
@@ -88,8 +56,6 @@ static uint32_t decode(int W, int H, int order, const std::vector<uint8_t>& cfg,
     free(pkt);
     return status;
 }
-
-static bool rd(FILE* f, void* p, size_t n) { return fread(p, 1, n, f) == n; }
 
 int main(int argc, char** argv)
 {

@@ -1,4 +1,4 @@
-// The device FFV1 stream decoder's core (csrc/mdvt_ffv1_core.h: BitReader, the Golomb-Rice pieces, ChainDec, parse_stream_class2)
+// The device FFV1 stream decoder's core (csrc/mdvt_ffv1_core.h: SliceDec with its Golomb-Rice side, the stream class of the parser)
 // compiled for the host: tests/test_video_stream_decoder_cpu.py builds this program at test time (plain, and with
 // -fsanitize=address,undefined where the compiler has the runtime) and feeds it streams.
 //
@@ -11,27 +11,7 @@
 // The stream is decoded the way the kernels do it: every packet's slice table and key-frame bit first (the walk), then for every key
 // frame and slice one chain through the run's frames, with the CRCs, the cell claims and the flags of k_ffv1_stream_chain.  Every
 // buffer is allocated at its exact size and every byte of a packet is read through a checked accessor.
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <vector>
-
-#include "mdvt_ffv1_core.h"
-
-using namespace mdvt_ffv1;
-
-#define CHECK(c) do { if (!(c)) { fprintf(stderr, "bound violated: %s (line %d)\n", #c, __LINE__); abort(); } } while (0)
-
-struct CheckedSrc {
-    const uint8_t* p; uint32_t avail;
-    uint8_t byte(uint32_t k) const { CHECK(k < avail); return p[k]; }
-};
-
-struct CheckedPacket {
-    const uint8_t* p; uint32_t size;
-    uint8_t operator()(uint32_t k) const { CHECK(k < size); return p[k]; }
-};
+#include "ffv1_host_common.h"
 
 struct Counters {
     uint32_t escapes = 0, halvings = 0, max_run_index = 0, short_tail_runs = 0;
@@ -48,8 +28,8 @@ static void raise_status(std::vector<uint32_t>& status, size_t k, uint32_t v) { 
 static uint32_t decode(int W, int H, int order, int first_out, const std::vector<uint8_t>& cfg, const std::vector<Packet>& pk,
                        std::vector<uint32_t>& status, uint8_t* dst, Counters& total)
 {
-    StreamClass2 sc{};
-    if (parse_stream_class2(cfg.data(), cfg.size(), &sc) || sc.nh > W || sc.nv > H) return 100;
+    StreamClass sc{};
+    if (parse_stream_class(cfg.data(), cfg.size(), true, &sc) || sc.nh > W || sc.nv > H) return 100;
     const int n = (int)pk.size(), spf = sc.nh * sc.nv;
     const uint32_t trailer = sc.ec ? 8u : 3u;
     std::vector<uint32_t> off((size_t)n * spf), len((size_t)n * spf), claims((size_t)n * spf, 0), kind((size_t)n);
@@ -58,22 +38,18 @@ static uint32_t decode(int W, int H, int order, int first_out, const std::vector
         kind[(size_t)f] = status[(size_t)f] != kOk ? kFrameBad : key_frame_bit(CheckedPacket{pk[f].p, pk[f].size}(0), CheckedPacket{pk[f].p, pk[f].size}(1)) ? kFrameKey : kFrameInter;
     }
     for (int j = 0; j < n && kind[(size_t)j] != kFrameKey; ++j) raise_status(status, (size_t)j, kNoKeyFrame);
-    uint8_t zero[256], one[256];
-    int8_t q11[256];
-    uint16_t next[256];
-    default_states(zero, one);
-    for (int k = 0; k < 256; ++k) { q11[k] = (int8_t)quant11(k); next[k] = (uint16_t)(zero[k] | (one[k] << 8)); }
+    const Tables tab;
     const int stride = (W + sc.nh - 1) / sc.nh + 2;
     const int ri = order == 1 ? 2 : 0, bi = order == 1 ? 0 : 2;
     for (int f0 = 0; f0 < n; ++f0) {
         if (kind[(size_t)f0] != kFrameKey) continue;
         for (int si = 0; si < spf; ++si) {                   // one chain: k_ffv1_stream_chain
-            ChainDec<CheckedSrc, Counters> d;
+            SliceDec<CheckedSrc, true, Counters> d;
             d.coder = sc.coder;
-            uint8_t* st = (uint8_t*)malloc(d.state_bytes());
+            uint8_t* st = (uint8_t*)malloc(state_bytes(d.coder));
             int16_t* lines = (int16_t*)malloc((size_t)9 * stride * sizeof(int16_t));
             uint8_t* misc = (uint8_t*)malloc(64);
-            d.st = st; d.lines = lines; d.misc = misc; d.q11 = q11; d.stride = stride;
+            d.st = st; d.lines = lines; d.misc = misc; d.q11 = tab.q11; d.stride = stride;
             d.reset_state();
             int f = f0;
             uint32_t flag = kOk;
@@ -83,13 +59,9 @@ static uint32_t decode(int W, int H, int order, int first_out, const std::vector
                 const size_t i = (size_t)f * spf + (size_t)si;
                 CHECK((size_t)off[i] + len[i] + trailer <= pk[f].size);
                 const uint8_t* data = pk[f].p + off[i];
-                if (sc.ec) {
-                    uint32_t crc = 0;
-                    for (uint32_t k = 0; k < len[i] + trailer; ++k) crc = (crc << 8) ^ crc_table_entry((crc >> 24) ^ CheckedPacket{pk[f].p, pk[f].size}(off[i] + k));
-                    if (crc) { flag = kCrcMismatch; break; }
-                }
+                if (sc.ec && slice_crc(CheckedPacket{pk[f].p, pk[f].size}, off[i], len[i] + trailer)) { flag = kCrcMismatch; break; }
                 memset(lines, 0, (size_t)9 * stride * sizeof(int16_t));
-                uint32_t s = d.begin(CheckedSrc{data, len[i] + trailer}, len[i] + trailer, len[i], si == 0, sc.coder, sc.micro, W, H, sc.nh, sc.nv, next);
+                uint32_t s = d.begin(CheckedSrc{data, len[i] + trailer}, len[i] + trailer, len[i], si == 0, sc.coder, sc.micro, W, H, sc.nh, sc.nv, tab.next);
                 if (s == kOk) {
                     CHECK(d.cell >= 0 && d.cell < spf);
                     if (claims[(size_t)f * spf + (size_t)d.cell]++) s = kBadSliceHeader;
@@ -99,15 +71,7 @@ static uint32_t decode(int W, int H, int order, int first_out, const std::vector
                 for (int y = 0; y < d.sh; ++y) {
                     d.row(y);
                     CHECK(d.run_index >= 0 && d.run_index <= kRunIndexMax);
-                    if (f < first_out) continue;
-                    uint8_t* o = dst + (size_t)(f - first_out) * W * H * 3 + ((size_t)(d.y0 + y) * W + d.x0) * 3;
-                    for (int x = 0; x < d.sw; ++x) {
-                        int g = lines[(size_t)(0 * 3 + y % 3) * stride + 1 + x], b = lines[(size_t)(1 * 3 + y % 3) * stride + 1 + x] - 256,
-                            r = lines[(size_t)(2 * 3 + y % 3) * stride + 1 + x] - 256;
-                        g -= (b + r) >> 2;
-                        b += g; r += g;
-                        o[3 * x + ri] = (uint8_t)r; o[3 * x + 1] = (uint8_t)g; o[3 * x + bi] = (uint8_t)b;
-                    }
+                    if (f >= first_out) store_row(d, y, dst + (size_t)(f - first_out) * W * H * 3, W, ri, bi);
                 }
                 s = d.finish();
                 if (s != kOk) { flag = s; break; }
@@ -123,8 +87,6 @@ static uint32_t decode(int W, int H, int order, int first_out, const std::vector
     }
     return 0;
 }
-
-static bool rd(FILE* f, void* p, size_t n) { return fread(p, 1, n, f) == n; }
 
 int main(int argc, char** argv)
 {

@@ -40,6 +40,27 @@ def test_the_matrix(mods, case):
             assert np.array_equal(got, frames[first_out:, ..., ::-1] if bgr else frames[first_out:]), (first_out, bgr)
 
 
+def test_both_entry_points_decode_an_intra_stream_alike(mods):
+    """The coder 1, intra = 1 stream of the matrix (67x37, 2 frames, 3x2 slices) is in both classes: mdvt_decode_video_frames and
+    mdvt_decode_video_stream (first_out 0 and 1) give the source frames, with all-zero status words and nothing left to the host."""
+    torch, fd, video_io, _lib = mods
+    case = (67, 37, 2, 1, 1, 1, 1, (3, 2))
+    assert case in fs.MATRIX
+    W, H, N = case[:3]
+    frames, packets, cfg = fs.make_stream(case)
+    p = fd.enqueue_decode(_lib.shared_context(0), list(packets), cfg, W, H)
+    intra = p.collect().cpu().numpy()
+    assert p.host_frames == 0 and p.flags.tolist() == [0] * N
+    assert np.array_equal(intra, frames)
+    for first_out in (0, 1):
+        got, flags, host_frames = fd.decode_stream_on_device(list(packets), cfg, W, H, first_out=first_out)
+        assert host_frames == 0 and flags.tolist() == [0] * N
+        got = got.cpu().numpy()
+        assert np.array_equal(got, frames[first_out:]) and got.tobytes() == intra[first_out:].tobytes()
+    got, flags = fd.decode_frames_on_device(list(packets), cfg, W, H)
+    assert flags.tolist() == [0] * N and np.array_equal(got.cpu().numpy(), frames)
+
+
 def test_the_host_reader_agrees_on_the_gpu_machine(mods):
     case = fs.COUNTERS_CASE
     frames, packets, cfg = fs.make_stream(case)

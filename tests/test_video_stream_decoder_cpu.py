@@ -1,4 +1,4 @@
-"""The device FFV1 stream decoder's host side -- no GPU: the decoder core (csrc/mdvt_ffv1_core.h: BitReader, Golomb-Rice, ChainDec)
+"""The device FFV1 stream decoder's host side -- no GPU: the decoder core (csrc/mdvt_ffv1_core.h: BitReader, Golomb-Rice, SliceDec)
 compiled for the host, plain and with the sanitizers (tests/ffv1_stream_decode_host.cpp), on the stream matrix of
 tests/ffv1_streams.py and on damaged packets; the class parser; the host entry points through ctypes; the device_all plumbing;
 the opt-in writer class against oracle/ffv1_ref.py."""
@@ -129,6 +129,30 @@ def test_a_call_that_starts_inside_a_run_and_a_flagged_frame(programs):
         assert np.array_equal(crc["frames"][:3], frames[:3]) and np.array_equal(crc["frames"][6], frames[6])
         assert bad["status"] == [0, 0, 0, 0, fs.BAD_PACKET, fs.BROKEN_RUN, 0]
         assert np.array_equal(bad["frames"][:2], frames[2:4]) and np.array_equal(bad["frames"][4], frames[6])
+
+
+def test_the_intra_program_runs_the_same_decoder(tmp_path):
+    """The two intra = 1 streams of the matrix (67x37, 2 frames, 3x2 slices, ec 1) through the intra decoder's host program
+    (tests/ffv1_decode_host.cpp): the coder 1 stream packet by packet gives status 0 and the source frames, the coder 0 record is
+    refused (verdict 100).  With test_core_decodes_the_matrix_on_the_host: both programs decode that stream with one SliceDec."""
+    import test_video_decoder_cpu as intra
+    range_case, golomb_case = (67, 37, 2, 1, 1, 1, 1, (3, 2)), (67, 37, 2, 0, 1, 1, 1, (3, 2))
+    assert range_case in fs.MATRIX and golomb_case in fs.MATRIX
+    W, H = range_case[:2]
+    tmp = str(tmp_path)
+    for sanitize in (False, True):
+        exe, why = intra._build(tmp, sanitize)                         # (the plain build must succeed; the instrumented one may be missing,
+        if exe is None or intra._run(exe, tmp, [])[0].returncode:      # or unable to start, as in test_video_decoder_cpu.py's fixture)
+            assert sanitize, why
+            continue
+        frames, packets, cfg = fs.make_stream(range_case)
+        r, out = intra._run(exe, tmp, [(W, H, 0, cfg, p) for p in packets])
+        assert r.returncode == 0, r.stderr[-2000:]
+        for (st, n, frame), want in zip(out, frames):
+            assert st == 0 and n == 3 * W * H and np.array_equal(frame, want)
+        _, packets, cfg = fs.make_stream(golomb_case)
+        r, out = intra._run(exe, tmp, [(W, H, 0, cfg, packets[0])])
+        assert r.returncode == 0 and out[0][0] == 100 and not out[0][2].any()
 
 
 # ---------------------------------------------------------------------------------------------------------------------
