@@ -44,6 +44,9 @@ METRIC_ALIGN_SYMBOLS = ("mdvt_scale_shift_fit", "mdvt_metric_depth_codes")
 # the entry points include/mdvt_infill_adapter.h declares (the frames around an in-painting model), listed apart in the same way
 INFILL_ADAPTER_SYMBOLS = ("mdvt_adapter_prepare_eye", "mdvt_lhm_moments", "mdvt_lhm_apply", "mdvt_adapter_composite_eye")
 
+# the entry points include/mdvt_infill_engines.h declares (the m2svid and stereo_dissoclusion_net steps around their models), likewise
+INFILL_ENGINE_SYMBOLS = ("mdvt_m2svid_prepare_eye", "mdvt_model_infill_finish")
+
 
 class MdvtError(RuntimeError):
     def __init__(self, code: int, text: str):
@@ -196,6 +199,11 @@ def load():
     L.mdvt_adapter_composite_eye.restype = C.c_int
     L.mdvt_adapter_composite_eye.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, st, st, vp, st, st, vp, st, st,
                                              vp, st, st, vp, st, st, vp]
+    L.mdvt_m2svid_prepare_eye.restype = C.c_int
+    L.mdvt_m2svid_prepare_eye.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, st, st, vp, st, st, vp, C.c_int, C.c_int, st, st,
+                                          C.c_int, C.c_int, C.c_int, C.c_int, vp, st, st, vp, st, st, vp, st, st, vp, vp]
+    L.mdvt_model_infill_finish.restype = C.c_int
+    L.mdvt_model_infill_finish.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, st, st, vp, st, st, vp, st, st, vp, st, st, vp]
     _libs[variant] = L
     return L
 

@@ -1,5 +1,5 @@
 // mdvt_api.hip -- the entry points of the C ABI of include/mdvt.h beside the render (mdvt_api_render.hip) and the context
-// (mdvt_context.hip): formats, equirect, blur, the infills, both infill-mask completions, FFV1 in both directions, convergence depths, the metric alignment, the infill adapter.
+// (mdvt_context.hip): formats, equirect, blur, the infills, both infill-mask completions, FFV1 in both directions, convergence depths, the metric alignment, the infill adapter, the two further infill engines.
 // Host code only; the kernels are in the other *.hip units.
 #include "mdvt_context.h"
 #include "mdvt_ffv1_core.h"
@@ -8,6 +8,7 @@
 #include "mdvt_convergence.h"
 #include "mdvt_metric_align.h"
 #include "mdvt_infill_adapter.h"
+#include "mdvt_infill_engines.h"
 
 #include <math.h>
 
@@ -901,6 +902,90 @@ int mdvt_adapter_composite_eye(mdvt_ctx* c, int eye_w, int eye_h, int n_frames, 
         a.mask = {mask, mask_pitch, 0};
         a.pasted = d_pasted + k * pasted_stride + at; a.blended = d_blended + k * blended_stride + at;
         MDVT_HIP(c, mdvt::launch_adapter_composite(a, s));
+    }
+    return MDVT_OK;
+}
+
+}  // extern "C"
+
+// ---- the m2svid and stereo_dissoclusion_net infill steps around their models (include/mdvt_infill_engines.h) ----
+
+extern "C" {
+
+int mdvt_m2svid_prepare_eye(mdvt_ctx* c, int eye_w, int eye_h, int n_frames, int eye,
+                            const uint8_t* d_color, size_t color_pitch, size_t color_stride,
+                            const uint8_t* d_mask, size_t mask_pitch, size_t mask_stride,
+                            const uint8_t* d_org, int org_w, int org_h, size_t org_pitch, size_t org_stride,
+                            int image_w, int image_h, int mask_w, int mask_h,
+                            uint8_t* d_image, size_t image_pitch, size_t image_stride,
+                            uint8_t* d_org_image, size_t org_image_pitch, size_t org_image_stride,
+                            uint8_t* d_model_mask, size_t model_mask_pitch, size_t model_mask_stride, uint32_t* d_hole_counts, void* stream)
+{
+    if (!c) return MDVT_ERR_INVALID_ARG;
+    if (!d_org || !d_image || !d_org_image || !d_model_mask || !d_hole_counts) return fail(c, MDVT_ERR_INVALID_ARG, "NULL buffer");
+    if (const int rc = check_adapter_sbs(c, eye_w, eye_h, n_frames, eye, d_color, color_pitch, color_stride, d_mask, mask_pitch, mask_stride, image_w, image_h)) return rc;
+    if (org_w < 1 || org_h < 1 || mask_w < 1 || mask_h < 1) return fail(c, MDVT_ERR_INVALID_ARG, "bad size: original %d x %d, mask %d x %d", org_w, org_h, mask_w, mask_h);
+    if (org_pitch < (size_t)3 * org_w) return fail(c, MDVT_ERR_INVALID_ARG, "pitch smaller than one row of the original frame");
+    if (image_pitch < (size_t)3 * image_w || org_image_pitch < (size_t)3 * image_w || model_mask_pitch < (size_t)mask_w)
+        return fail(c, MDVT_ERR_INVALID_ARG, "pitch smaller than one model row");
+    if (n_frames > 1 && (org_stride < org_pitch * (size_t)org_h || image_stride < image_pitch * (size_t)image_h ||
+                         org_image_stride < org_image_pitch * (size_t)image_h || model_mask_stride < model_mask_pitch * (size_t)mask_h))
+        return fail(c, MDVT_ERR_INVALID_ARG, "stride smaller than one frame");
+    if ((uintptr_t)d_hole_counts % 4) return fail(c, MDVT_ERR_INVALID_ARG, "d_hole_counts must be 4-byte aligned");
+    if (image_h > 65535 || mask_h > 65535) return fail(c, MDVT_ERR_UNSUPPORTED, "model frame too tall (%d and %d rows)", image_h, mask_h);
+    DeviceGuard g(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (n_frames == 1) color_stride = mask_stride = org_stride = image_stride = org_image_stride = model_mask_stride = 0;
+    MDVT_HIP(c, hipMemsetAsync(d_hole_counts, 0, (size_t)n_frames * sizeof(uint32_t), s));
+    mdvt::M2sPrepareArgs a{};
+    a.mirror = eye == 0;
+    a.rs_image = mdvt::adapter_resize(eye_w, eye_h, image_w, image_h);
+    a.rs_org = mdvt::adapter_resize(org_w, org_h, image_w, image_h);
+    a.rs_mask = mdvt::adapter_resize(eye_w, eye_h, mask_w, mask_h);
+    a.image_pitch = image_pitch; a.image_stride = image_stride; a.org_image_pitch = org_image_pitch; a.org_image_stride = org_image_stride;
+    a.mmask_pitch = model_mask_pitch; a.mmask_stride = model_mask_stride;
+    const size_t at = (size_t)eye * 3 * eye_w;
+    for (int f0 = 0; f0 < n_frames; f0 += mdvt::kM2sPrepareFrames) {
+        a.color = {d_color + at + (size_t)f0 * color_stride, color_pitch, color_stride};
+        a.mask = {d_mask + at + (size_t)f0 * mask_stride, mask_pitch, mask_stride};
+        a.org = {d_org + (size_t)f0 * org_stride, org_pitch, org_stride};
+        a.image = d_image + (size_t)f0 * image_stride; a.org_image = d_org_image + (size_t)f0 * org_image_stride;
+        a.mmask = d_model_mask + (size_t)f0 * model_mask_stride; a.holes = d_hole_counts + f0;
+        MDVT_HIP(c, mdvt::launch_m2s_prepare(a, n_frames - f0 < mdvt::kM2sPrepareFrames ? n_frames - f0 : mdvt::kM2sPrepareFrames, s));
+    }
+    return MDVT_OK;
+}
+
+int mdvt_model_infill_finish(mdvt_ctx* c, int width, int height, int n_images,
+                             const uint8_t* d_img, size_t img_pitch, size_t img_stride,
+                             const uint8_t* d_model, size_t model_pitch, size_t model_stride,
+                             const uint8_t* d_infill_mask, size_t mask_pitch, size_t mask_stride,
+                             uint8_t* d_out, size_t out_pitch, size_t out_stride, void* stream)
+{
+    if (!c) return MDVT_ERR_INVALID_ARG;
+    if (!d_img || !d_model || !d_infill_mask || !d_out) return fail(c, MDVT_ERR_INVALID_ARG, "NULL buffer");
+    if (width < 1 || height < 1) return fail(c, MDVT_ERR_INVALID_ARG, "bad image size %d x %d", width, height);
+    if (n_images < 1) return fail(c, MDVT_ERR_INVALID_ARG, "n_images must be >= 1");
+    const size_t row = (size_t)3 * width;
+    if (img_pitch < row || model_pitch < row || mask_pitch < row || out_pitch < row) return fail(c, MDVT_ERR_INVALID_ARG, "pitch smaller than one row");
+    if (n_images > 1 && (img_stride < img_pitch * (size_t)height || model_stride < model_pitch * (size_t)height ||
+                         mask_stride < mask_pitch * (size_t)height || out_stride < out_pitch * (size_t)height))
+        return fail(c, MDVT_ERR_INVALID_ARG, "stride smaller than one image");
+    if (d_out == d_img || d_out == d_model || d_out == d_infill_mask) return fail(c, MDVT_ERR_INVALID_ARG, "d_out may not alias an input");
+    if (mask_pitch >= (1u << 24) || (unsigned long long)mask_pitch * height > 0xFFFFFFFFull)
+        return fail(c, MDVT_ERR_UNSUPPORTED, "image too large for the march's 32-bit offsets (pitch %zu, %d x %d)", mask_pitch, width, height);
+    if (height > 65535) return fail(c, MDVT_ERR_UNSUPPORTED, "image too tall (%d rows)", height);
+    DeviceGuard g(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (n_images == 1) img_stride = model_stride = mask_stride = out_stride = 0;
+    const int chunk = n_images < kNormalInfillChunk ? n_images : kNormalInfillChunk;
+    MDVT_HIP(c, scratch_reserve(c, c->scratch[SCR_NI], mdvt::normal_infill_workspace_bytes(chunk, width, height), s));
+    const mdvt::BlurKernel K = masked_blur_kernel();
+    for (int i0 = 0; i0 < n_images; i0 += chunk) {
+        const int n = n_images - i0 < chunk ? n_images - i0 : chunk;
+        MDVT_HIP(c, launch_model_infill_finish(slice(d_img, img_pitch, img_stride, i0, n), slice(d_model, model_pitch, model_stride, i0, n),
+                                               slice(d_infill_mask, mask_pitch, mask_stride, i0, n), slice(d_out, out_pitch, out_stride, i0, n),
+                                               c->scratch[SCR_NI].p, n, width, height, K, s));
     }
     return MDVT_OK;
 }

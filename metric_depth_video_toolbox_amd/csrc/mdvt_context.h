@@ -47,7 +47,7 @@ enum ScratchId {
     SCR_TELEA_STAMP, SCR_TELEA_T, SCR_TELEA_IMG, SCR_TELEA_NEED, SCR_TELEA_NLIST, SCR_TELEA_COUNTS, SCR_TELEA_REMAINING, SCR_TELEA_LAST_ROUND,
     // infill-mask completion in the heap order: one block of mdvt::telea_heap_image_bytes per image of a pass, + remaining
     SCR_HEAP_WS, SCR_HEAP_REMAINING,
-    SCR_NI,                           // normal_infill / infill_using_mask_normals: about 16 B/px per image in flight
+    SCR_NI,                           // normal_infill / infill_using_mask_normals / model_infill_finish (at its own size): about 16 B/px per image in flight
     SCR_FFV1,                         // mdvt_encode_video_frames: the running packet offset, then per slice of a pass its size word and scratch
     SCR_FFV1_DEC,                     // mdvt_decode_video_frames: per slice of a pass its offset, payload bytes and cell claim
     SCR_CONV,                         // mdvt_convergence_depths: per frame of a launch set its chunk sums; with a mask also the ballot words, codes and unit counts

@@ -222,6 +222,9 @@ hipError_t launch_normal_infill(const ImageSet& img, const ImageSet& mask, const
                                 const BlurKernel& K, hipStream_t s);
 hipError_t launch_infill_mask_normals(const ImageSet& img, const ImageSet& hole, const ImageSet& mask, uint8_t* workspace, int n, int W, int H,
                                       int max_steps, hipStream_t s);
+// the tail of normal_infill behind a model's dense image (mdvt_model_infill_finish, include/mdvt_infill_engines.h); workspace as above
+hipError_t launch_model_infill_finish(const ImageSet& img, const ImageSet& model, const ImageSet& mask, const ImageSet& out, uint8_t* workspace,
+                                      int n, int W, int H, const BlurKernel& K, hipStream_t s);
 // mdvt_ffv1.hip: FFV1 encoding of device frames (mdvt_encode_video_frames).  A slice's size word holds its payload bytes or one of
 // the flags below; a frame's size word the packet bytes or the flag of its first flagged slice.
 constexpr uint32_t kSliceTooLarge = 0xFFFFFFFEu;     // the payload does not fit the 24-bit slice size
@@ -354,6 +357,19 @@ struct AdapterCompositeArgs {
     AdapterGauss g;
 };
 hipError_t launch_adapter_composite(const AdapterCompositeArgs& a, hipStream_t s);
+// mdvt_infill_engines.hip: the three model inputs of the m2svid infill step (include/mdvt_infill_engines.h)
+constexpr int kM2sPrepareFrames = 21845;                           // frames per launch: 3 * frames in the grid's third dimension
+struct M2sPrepareArgs {
+    AdapterImage color, mask;                                      // the eye's half of the side-by-side frames (p at the eye's first column)
+    AdapterImage org;                                              // the original colour frames, whole
+    int mirror;                                                    // the eye and the original frame are read right to left
+    AdapterResize rs_image, rs_org, rs_mask;                       // eye -> image, original -> image, eye -> mask
+    uint8_t* image; size_t image_pitch, image_stride;
+    uint8_t* org_image; size_t org_image_pitch, org_image_stride;
+    uint8_t* mmask; size_t mmask_pitch, mmask_stride;              // the model's mask, one byte per pixel
+    uint32_t* holes;                                               // [n], zeroed before the launch
+};
+hipError_t launch_m2s_prepare(const M2sPrepareArgs& a, int n, hipStream_t s);
 hipError_t launch_selftest(int which, unsigned long long seed, unsigned long long* d_mism, hipStream_t s);
 hipError_t launch_coherence_test(uint32_t* blk, size_t dwords, uint32_t tag, uint32_t* d_xcc, uint32_t* d_out, hipStream_t s);     // (mdvt_selftest.hip; r05 diagnosis)
 

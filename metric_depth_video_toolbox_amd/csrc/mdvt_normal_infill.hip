@@ -33,6 +33,14 @@
 //   k_ni_run<3>      list C: blur_under_mask into the side buffer (the image is still read by the neighbours' taps)
 //   k_ni_run<4>      list C: side buffer -> image
 // The output image itself is the work image (the caller's input is never written).
+//
+// mdvt_model_infill_finish (include/mdvt_infill_engines.h; stereo_dissoclusion_net_infill.py:100-123, "sdn") is the same tail behind
+// a dense image that a model made: no masked blur, no hole march, no requests.  Its launches:
+//   k_ni_prep<., true>   as above, but the bg pixels keep the image's colour (sdn:108-111 write only the box mean over them)
+//   k_ni_run<6>          list A: the lower-side march alone -> marks plane
+//   k_ni_collect<2>, k_ni_run<5>   as above
+//   k_ni_run<7>          list A: the box mean for the bg pixels, its 16 taps read from the model's image
+//   k_ni_collect<1>, k_ni_run<3>, k_ni_run<4>   as above
 #include "mdvt_device.h"
 
 #include <stdio.h>
@@ -52,6 +60,7 @@ constexpr int kMarchBatch = 8;                // samples of a march fetched toge
 
 struct NiArgs {
     ImageSet img, mask, out;          // caller's images (u8 RGB rows); out doubles as the work image
+    ImageSet model;                   // mdvt_model_infill_finish only: the model's image, read by the box window
     uint8_t* filled;                  // [n][H*W*3] valid where need != 0; later the side buffer of the last stage
     uint8_t* bg;                      // [n][H*W]
     uint8_t* need;                    // [n][H*W]
@@ -122,7 +131,7 @@ __device__ __forceinline__ void ni_emit(uint32_t* sublist, uint32_t* counter, co
 }
 
 // bni:88-91; list A
-template <int PX>
+template <int PX, bool FINISH = false>
 __global__ void __launch_bounds__(128) k_ni_prep(NiArgs a)
 {
     __shared__ uint32_t lds_list[128 * PX];
@@ -155,7 +164,7 @@ __global__ void __launch_bounds__(128) k_ni_prep(NiArgs a)
 #pragma unroll
         for (int q = 0; q < PX; ++q) {
             const bool bg = (m[q] & 0xFFu) != 0u && (m[q] & 0xFF00u) != 0u && (m[q] & 0xFF0000u) != 0u;     // bni:88
-            if (bg) { c[q] = 0u; bgw |= 1u << (8 * q); }                                                    // bni:91
+            if (bg) { if (!FINISH) c[q] = 0u; bgw |= 1u << (8 * q); }                                       // bni:91 (sdn: the colour stays)
         }
         uint8_t* orow = a.out.image(im) + (size_t)y * a.out.pitch;
         if (PX == 4) {
@@ -269,13 +278,14 @@ __device__ __forceinline__ uint32_t ni_masked_blur_px(const uint8_t* work, size_
 }
 
 // STAGE 0, a pixel of list A: its requests (bni:104-107 read the 16 taps of a bg pixel's box window) and its lower-side
-// march (bni:111).
+// march (bni:111).  STAGE 6 (REQUESTS false): the march alone (sdn:115).
+template <bool REQUESTS>
 __device__ __forceinline__ void ni_stage_requests_and_marks(const NiArgs& a, int im, int x, int y)
 {
     const int W = a.W, H = a.H;
     const size_t ib = (size_t)im * H * W;
     const uint8_t* mimg = a.mask.image(im);
-    if (a.bg[ib + (size_t)y * W + x] && !(MDVT_DEBUG_SKIP(a) & 2)) {
+    if (REQUESTS && a.bg[ib + (size_t)y * W + x] && !(MDVT_DEBUG_SKIP(a) & 2)) {
         uint8_t* need = a.need + ib;
         if (x >= 2 && x + 1 < W && y >= 2 && y + 1 < H) {                 // (no reflection: 4 bytes per row)
 #pragma unroll
@@ -373,7 +383,8 @@ __device__ __forceinline__ void ni_stage_filled(const NiArgs& a, int im, int x, 
     store_px_bytes(a.filled + 3 * (ib + (size_t)y * W), x, v);
 }
 
-// STAGE 2, a bg pixel of list A: the 4 x 4 mean of the filled image (bni:104-107)
+// STAGE 2, a bg pixel of list A: the 4 x 4 mean of the filled image (bni:104-107).  STAGE 7 (MODEL): of the model's image (sdn:108-111)
+template <bool MODEL>
 __device__ __forceinline__ void ni_stage_box(const NiArgs& a, int im, int x, int y)
 {
     const int W = a.W, H = a.H;
@@ -382,10 +393,12 @@ __device__ __forceinline__ void ni_stage_box(const NiArgs& a, int im, int x, int
     uint32_t sum[3] = {0u, 0u, 0u};
 #pragma unroll
     for (int dy = -2; dy <= 1; ++dy) {
-        const uint8_t* row = a.filled + 3 * (ib + (size_t)reflect101(y + dy, H) * W);
+        const int ry = reflect101(y + dy, H);
+        const uint8_t* row = MODEL ? a.model.image(im) + (size_t)ry * a.model.pitch : a.filled + 3 * (ib + (size_t)ry * W);
 #pragma unroll
         for (int dx = -2; dx <= 1; ++dx) {
-            const uint32_t px = ni_load_px(row, reflect101(x + dx, W), true);      // (the buffer is padded)
+            const int rx = reflect101(x + dx, W);
+            const uint32_t px = ni_load_px(row, rx, !MODEL || ry < H - 1 || rx < W - 1);      // (the filled buffer is padded; the caller's image is not)
             sum[0] += px & 0xFFu; sum[1] += (px >> 8) & 0xFFu; sum[2] += (px >> 16) & 0xFFu;
         }
     }
@@ -446,15 +459,17 @@ __global__ void __launch_bounds__(256) k_ni_run(NiArgs a)
 {
     const int im = blockIdx.z, sub = blockIdx.y, W = a.W;
     const size_t ib = (size_t)im * a.H * W;
-    constexpr int L = (STAGE == 0 || STAGE == 2) ? 0 : STAGE == 1 ? 1 : STAGE == 5 ? 3 : 2;
+    constexpr int L = (STAGE == 0 || STAGE == 2 || STAGE == 6 || STAGE == 7) ? 0 : STAGE == 1 ? 1 : STAGE == 5 ? 3 : 2;
     const uint32_t* list = L == 0 ? a.list_a + ((size_t)im * kNSub + sub) * a.cap_a : a.list_b + ((size_t)im * kNSub + sub) * a.cap_b;
     const uint32_t n = a.count[(size_t)(4 * im + L) * kNSub + sub];
     for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
         const uint32_t idx = list[i];
         const int y = (int)(idx / (uint32_t)W), x = (int)(idx - (uint32_t)y * (uint32_t)W);
-        if (STAGE == 0) ni_stage_requests_and_marks(a, im, x, y);
+        if (STAGE == 0) ni_stage_requests_and_marks<true>(a, im, x, y);
+        else if (STAGE == 6) ni_stage_requests_and_marks<false>(a, im, x, y);
         else if (STAGE == 1) ni_stage_filled(a, im, x, y);
-        else if (STAGE == 2) ni_stage_box(a, im, x, y);
+        else if (STAGE == 2) ni_stage_box<false>(a, im, x, y);
+        else if (STAGE == 7) ni_stage_box<true>(a, im, x, y);
         else if (STAGE == 3) ni_stage_blur_under(a, im, x, y);
         else if (STAGE == 5) ni_stage_grow(a, im, x, y);
         else store_px_bytes(a.out.image(im) + (size_t)y * a.out.pitch, x, load_px_bytes(a.filled + 3 * ib, (int)idx));
@@ -763,12 +778,12 @@ hipError_t launch_grow_marks(const uint8_t* marks, size_t marks_pitch, uint8_t* 
     return hipGetLastError();
 }
 
-hipError_t launch_normal_infill(const ImageSet& img, const ImageSet& mask, const ImageSet& out, uint8_t* workspace, int n, int W, int H,
-                                const BlurKernel& K, hipStream_t s)
+// What both launch sets share: the workspace laid out, its zero block cleared, the dense pass run.  -> the lanes per sub-list
+static hipError_t ni_begin(NiArgs& a, bool finish, const ImageSet& img, const ImageSet& mask, const ImageSet& out, uint8_t* workspace, int n, int W, int H,
+                           const BlurKernel& K, hipStream_t s, unsigned* lanes_per_sub)
 {
     const size_t npx = (size_t)W * H;
     const NiLayout l = ni_layout(n, W, H);
-    NiArgs a;
     a.img = img; a.mask = mask; a.out = out;
     a.W = W; a.H = H; a.K = K;
     a.tiles_x = l.tiles_x; a.tiles_y = l.tiles_y;
@@ -790,11 +805,48 @@ hipError_t launch_normal_infill(const ImageSet& img, const ImageSet& mask, const
     if (e != hipSuccess) return e;
     auto dwords = [](const ImageSet& i) { return (((uintptr_t)i.base | i.pitch | i.stride) & 3) == 0; };
     const bool vec = W % 4 == 0 && dwords(img) && dwords(mask) && dwords(out);
-    if (vec) hipLaunchKernelGGL(k_ni_prep<4>, dim3((W / 4 + 127) / 128, H, n), dim3(128), 0, s, a);
-    else hipLaunchKernelGGL(k_ni_prep<1>, dim3((W + 127) / 128, H, n), dim3(128), 0, s, a);
+    const dim3 g4((W / 4 + 127) / 128, H, n), g1((W + 127) / 128, H, n);
+    if (finish) {
+        if (vec) hipLaunchKernelGGL((k_ni_prep<4, true>), g4, dim3(128), 0, s, a);
+        else hipLaunchKernelGGL((k_ni_prep<1, true>), g1, dim3(128), 0, s, a);
+    } else {
+        if (vec) hipLaunchKernelGGL((k_ni_prep<4, false>), g4, dim3(128), 0, s, a);
+        else hipLaunchKernelGGL((k_ni_prep<1, false>), g1, dim3(128), 0, s, a);
+    }
     // lanes per sub-list: a sixteenth of what it could hold at most (holes are a few per cent of a frame; the rest loops)
     unsigned per_sub = (unsigned)((npx / kNSub / 16 + 255) / 256);
-    per_sub = per_sub < 1 ? 1 : (per_sub > 16 ? 16 : per_sub);
+    *lanes_per_sub = per_sub < 1 ? 1 : (per_sub > 16 ? 16 : per_sub);
+    return hipSuccess;
+}
+
+// sdn:100-123 behind the model: the image pasted with the box mean of the model's image under bg, blurred under the grown lower side
+hipError_t launch_model_infill_finish(const ImageSet& img, const ImageSet& model, const ImageSet& mask, const ImageSet& out, uint8_t* workspace,
+                                      int n, int W, int H, const BlurKernel& K, hipStream_t s)
+{
+    NiArgs a;
+    a.model = model;
+    unsigned per_sub = 1;
+    const hipError_t e = ni_begin(a, true, img, mask, out, workspace, n, W, H, K, s, &per_sub);
+    if (e != hipSuccess) return e;
+    const dim3 tiles(a.tiles_x, a.tiles_y, n), lanes(per_sub, kNSub, n);
+    hipLaunchKernelGGL(k_ni_run<6>, lanes, dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_ni_collect<2>, tiles, dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_ni_run<5>, lanes, dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_ni_run<7>, lanes, dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_ni_collect<1>, tiles, dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_ni_run<3>, lanes, dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_ni_run<4>, lanes, dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_normal_infill(const ImageSet& img, const ImageSet& mask, const ImageSet& out, uint8_t* workspace, int n, int W, int H,
+                                const BlurKernel& K, hipStream_t s)
+{
+    NiArgs a;
+    a.model = ImageSet{nullptr, 0, 0, 0, 1};
+    unsigned per_sub = 1;
+    hipError_t e = ni_begin(a, false, img, mask, out, workspace, n, W, H, K, s, &per_sub);
+    if (e != hipSuccess) return e;
     const dim3 tiles(a.tiles_x, a.tiles_y, n), lanes(per_sub, kNSub, n);
     hipLaunchKernelGGL(k_ni_run<0>, lanes, dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_ni_collect<2>, tiles, dim3(256), 0, s, a);

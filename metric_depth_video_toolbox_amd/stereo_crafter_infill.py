@@ -304,17 +304,20 @@ class StereoCrafterGenerator:
         return torch.from_numpy((video * 255).astype(np.uint8)).to(frames.device)
 
 
-def load_generator(spec: str, num_inference_steps: int = 5):
-    """`stereocrafter` (the default model) or `pkg.module:callable`."""
-    if spec == "stereocrafter":
-        return StereoCrafterGenerator(num_inference_steps)
+def callable_from_spec(spec: str, default_name: str):
+    """The callable a `--generator pkg.module:callable` names (default_name: the engine's own model, for the message)."""
     mod, sep, name = spec.partition(":")
     if not sep or not mod or not name:
-        raise ValueError(f"--generator must be 'stereocrafter' or 'pkg.module:callable', got {spec!r}")
+        raise ValueError(f"--generator must be '{default_name}' or 'pkg.module:callable', got {spec!r}")
     fn = getattr(importlib.import_module(mod), name, None)
     if not callable(fn):
         raise ValueError(f"{spec}: {mod} has no callable {name!r}")
     return fn
+
+
+def load_generator(spec: str, num_inference_steps: int = 5):
+    """`stereocrafter` (the default model) or `pkg.module:callable`."""
+    return StereoCrafterGenerator(num_inference_steps) if spec == "stereocrafter" else callable_from_spec(spec, "stereocrafter")
 
 
 def build_parser():
