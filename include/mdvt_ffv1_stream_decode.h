@@ -37,9 +37,12 @@ extern "C" {
  * is read back.
  *
  * h_config / config_size: the configuration record in host memory.  Decoded: version 3 (any micro version), coder_type 0
- * (Golomb-Rice) or 1 (range coder, default state-transition table), intra 0 or 1, RGB, 8 bits, no alpha plane, one
- * quantisation-table set equal to the default 666-context set without initial states, ec 0 or 1, 1 to 1024 slices per frame.  Any
- * other record returns MDVT_ERR_UNSUPPORTED with the reason (it names the field) before anything is launched or written.  The old
+ * (Golomb-Rice) or 1 (range coder, default state-transition table), intra 0 or 1, 8 bits, no alpha plane, one
+ * quantisation-table set equal to the default 666-context set without initial states, ec 0 or 1, 1 to 1024 slices per frame;
+ * colorspace_type 1 (RGB, the JPEG 2000 RCT) or 0 (YCbCr) with chroma_planes 1 and log2 chroma subsampling (0, 0), (1, 0) or
+ * (1, 1): yuv444p, yuv422p, yuv420p.  Any other record returns MDVT_ERR_UNSUPPORTED with the reason (it names the field) before
+ * anything is launched or written; so does a YCbCr record whose slice grid puts a slice origin off the chroma grid on this frame
+ * size (x0 not a multiple of 2^hs, or y0 of 2^vs: the reason names the grid), which the host reader refuses as well.  The old
  * cases of mdvt_decode_video_frames and a first_out outside [0, n_packets) return MDVT_ERR_INVALID_ARG (frame_stride matters when
  * more than one frame is stored).
  *
@@ -51,6 +54,12 @@ extern "C" {
  * mdvt_decode_video_frames, a frame whose slice headers do not place exactly one slice on every cell is flagged.  The host reader
  * has no overread check on the Golomb-Rice side (bits past a slice's end read as zero): such a slice decodes to the host's bytes
  * with status 0 here too.  Nothing read from a packet steers a loop or an address.
+ *
+ * A YCbCr stream's planes are decoded exactly (RFC 9043: Y, then Cb, then Cr, 8-bit samples, the run index restarting at each
+ * plane) and converted to R, G, B as include/mdvt_video.h decrees it -- BT.601 limited range, chroma replicated; this project's
+ * formula, not an observation of swscale or cv2.  The planes of a slice arrive one after another, so its luma and Cb rows wait
+ * inside the slice's own pixels of the stored frame until their Cr row converts them: nothing outside the footprint below is
+ * touched, every byte inside it is finally the frame's, and frames before first_out still store nothing.
  *
  * Footprint: the first 3 * width bytes of each row of each stored frame, and n_packets status words; nothing else of the caller's.
  * The result does not depend on bytes outside the packets.  Workspace (12 bytes per slice and 4 per frame of the call) comes from

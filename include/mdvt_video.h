@@ -4,7 +4,22 @@
  * for the reference.  Host code only (C++17, no GPU, no third-party library): FFmpeg / OpenCV are absent from the image,
  * so both directions are written from the published specifications -- FFV1: RFC 9043 (versions 0, 1 and 3; range coder with
  * the default or a custom state-transition table and Golomb-Rice; the JPEG 2000 RCT "RGB" colour space at 8 bits with or
- * without alpha; slices with CRC-32 parities); Matroska: RFC 9559 / EBML RFC 8794 (the subset one video track needs).
+ * without alpha, and YCbCr at 8 bits in 4:4:4, 4:2:2 and 4:2:0; slices with CRC-32 parities); Matroska: RFC 9559 / EBML
+ * RFC 8794 (the subset one video track needs).
+ *
+ * YCbCr streams (colorspace_type 0, chroma_planes 1, log2 chroma subsampling (0, 0), (1, 0) or (1, 1): yuv444p, yuv422p,
+ * yuv420p, FFmpeg's default for a movie).  The planes are decoded exactly, by the RFC: Y, then Cb, then Cr, 8-bit samples, the
+ * run index restarting at each plane, the chroma rectangle of a slice at (x0 >> hs, y0 >> vs) with ceil(sw / 2^hs) x
+ * ceil(sh / 2^vs) samples.  Only slice grids whose every origin is a multiple of the subsampling are read (then the chroma
+ * rectangles tile the chroma plane); others are refused when the stream is opened.  The frames handed out are RGB / BGR as for
+ * any other file, converted BY DECREE, not by observation of swscale or cv2 (neither exists here): for pixel (x, y),
+ *     Y = Yp[y][x], U = Cb[y >> vs][x >> hs], V = Cr[y >> vs][x >> hs]      (chroma replicated, not interpolated)
+ *     c = Y - 16, d = U - 128, e = V - 128                                  (32-bit signed, arithmetic right shift)
+ *     R = clip8((298 c + 409 e + 128) >> 8)
+ *     G = clip8((298 c - 100 d - 208 e + 128) >> 8)
+ *     B = clip8((298 c + 516 d + 128) >> 8)
+ * which is BT.601 limited range, swscale's default for a file that signals nothing.  A Matroska Colour element is ignored.
+ * Refused with a message: YCbCr with alpha, more than 8 bits, chroma_planes 0 (grey), other subsampling shifts, misaligned grids.
  *
  * What it replaces in the reference:
  *   reader  cv2.VideoCapture(depth_video / color_video) + .read()             stereo_rerender.py:326-341, 489-509
@@ -44,8 +59,12 @@ typedef struct mdvt_video_info {
     int32_t alpha;               /* the stream carries a fourth plane (ignored on output)              */
     int32_t intra;               /* every frame is a key frame                                         */
     int32_t ec;                  /* slices end in a CRC-32 parity                                      */
-    int32_t reserved;
+    int32_t pix_fmt;             /* MDVT_VIDEO_PIX_*: what the stream codes (the frames read are RGB / BGR whatever it is) */
 } mdvt_video_info;
+
+/* mdvt_video_info.pix_fmt: colorspace_type 1 (the JPEG 2000 RCT over R, G, B), or colorspace_type 0 (YCbCr) with the chroma
+ * planes subsampled by log2 (0, 0), (1, 0), (1, 1). */
+enum { MDVT_VIDEO_PIX_RGB = 0, MDVT_VIDEO_PIX_YUV444P = 1, MDVT_VIDEO_PIX_YUV422P = 2, MDVT_VIDEO_PIX_YUV420P = 3 };
 
 /* Pixel order of the caller's interleaved 8-bit buffers. */
 enum { MDVT_VIDEO_RGB = 0, MDVT_VIDEO_BGR = 1 };   /* BGR = what cv2 hands the reference (sr:489-509 convert it) */

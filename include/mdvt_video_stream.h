@@ -38,7 +38,9 @@ int mdvt_video_seek_packet(mdvt_video_reader* r, int64_t frame);
 int mdvt_video_packet_is_key(mdvt_video_reader* r, int64_t frame);
 
 /* A decoder for consecutive packets of one stream with this configuration record (version 3): what mdvt_video_read does with the
- * packets of a file.  The first packet must be a key frame. */
+ * packets of a file, YCbCr streams included (converted to RGB / BGR as include/mdvt_video.h states; a slice grid off the chroma
+ * grid of this frame size is refused here).  The first packet must be a key frame.  It is the arbiter of the device's
+ * mdvt_decode_video_stream. */
 int mdvt_ffv1_stream_decoder_create(int width, int height, const uint8_t* config, size_t config_size, mdvt_ffv1_stream_decoder** out);
 /* Decodes the next packet into width x 3 bytes of each of height rows of dst (threads as for mdvt_video_read). */
 int mdvt_ffv1_stream_decoder_decode(mdvt_ffv1_stream_decoder* d, const uint8_t* packet, size_t packet_size, uint8_t* dst, size_t pitch,

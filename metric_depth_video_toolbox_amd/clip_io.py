@@ -82,6 +82,7 @@ class VideoFrames:
         from . import video_io
         first = video_io.VideoReader(path)
         self.path, self.fps, self.info = path, first.fps, first.info
+        self.pix_fmt = first.pix_fmt                         # what the stream codes; the frames are RGB either way
         self.shape = (first.frames, first.height, first.width, 3)
         self.dtype, self.ndim = np.dtype(np.uint8), 4
         n = max(1, int(readers)) if first.info.intra else 1
@@ -222,7 +223,8 @@ VIDEO_ENCODERS = ("host", "device")
 
 
 # "device": the class this project's writer makes goes to the device (mdvt_decode_video_frames).  "device_all": that, and the
-# stream decoder's class as well (mdvt_decode_video_stream: Golomb-Rice or range coder with inter frames).  Anything else: the host.
+# stream decoder's class as well (mdvt_decode_video_stream: Golomb-Rice or range coder with inter frames, RGB or YCbCr -- a colour
+# video FFmpeg coded as yuv420p is in it, and outside "device"'s class like any other file of FFmpeg's).  Anything else: the host.
 VIDEO_DECODERS = ("host", "device", "device_all")
 
 # How far back fetch() looks for the key frame in front of a batch of a "device_all" file: FFmpeg's default distance is 12, twice

@@ -506,6 +506,20 @@ static int ffv1_decode_prologue(mdvt_ctx* c, bool stream, int width, int height,
                     decoder, sc.nh, sc.nv, width, height);
     if ((uint64_t)width * (uint64_t)height > ((uint64_t)1 << 28))
         return fail(c, MDVT_ERR_UNSUPPORTED, "frame too large for the device FFV1 decoder (%d x %d)", width, height);
+    // YCbCr: a slice's chroma rectangle starts at (x0 >> hs, y0 >> vs), so the chroma rectangles tile the chroma plane only when
+    // every slice origin is a multiple of the subsampling (the host reader's refusal, csrc_host/mdvt_video.cpp check_supported)
+    if (sc.planar) {
+        for (int sx = 0; sx < sc.nh; ++sx)
+            if (((long long)sx * width / sc.nh) & ((1 << sc.hs) - 1))
+                return fail(c, MDVT_ERR_UNSUPPORTED, "FFV1 stream outside the device %s's class: num_h_slices / num_v_slices: the %d x %d slice "
+                            "grid puts a slice at x = %d of the %d x %d frame, off the chroma grid of shifts (%d, %d)", decoder, sc.nh, sc.nv,
+                            (int)((long long)sx * width / sc.nh), width, height, sc.hs, sc.vs);
+        for (int sy = 0; sy < sc.nv; ++sy)
+            if (((long long)sy * height / sc.nv) & ((1 << sc.vs) - 1))
+                return fail(c, MDVT_ERR_UNSUPPORTED, "FFV1 stream outside the device %s's class: num_h_slices / num_v_slices: the %d x %d slice "
+                            "grid puts a slice at y = %d of the %d x %d frame, off the chroma grid of shifts (%d, %d)", decoder, sc.nh, sc.nv,
+                            (int)((long long)sy * height / sc.nv), width, height, sc.hs, sc.vs);
+    }
     const int line_stride = (width + sc.nh - 1) / sc.nh + 2;           // the widest slice, its left and right neighbours
     if (mdvt::ffv1_decode_static_lds_bytes() + mdvt::ffv1_stream_lds_bytes(sc.coder, line_stride) > (size_t)160 * 1024)
         return fail(c, MDVT_ERR_UNSUPPORTED, "a slice of %d pixels' width does not fit the device FFV1 decoder's row buffers (num_h_slices %d)",
@@ -514,6 +528,7 @@ static int ffv1_decode_prologue(mdvt_ctx* c, bool stream, int width, int height,
     a->W = width; a->H = height; a->nh = sc.nh; a->nv = sc.nv; a->ec = sc.ec; a->coder = sc.coder; a->micro = sc.micro;
     a->pitch = pitch; a->frame_stride = frame_stride; a->ri = order == 1 ? 2 : 0; a->bi = order == 1 ? 0 : 2;
     a->line_stride = line_stride;
+    a->planar = sc.planar; a->hs = sc.hs; a->vs = sc.vs;
     return MDVT_OK;
 }
 

@@ -10,7 +10,10 @@
 //   intra    (mdvt_decode_video_frames)   the range coder with the default state table, key frames only: every slice of every
 //                                         frame starts from fresh context state
 //   stream   (mdvt_decode_video_stream)   Golomb-Rice or the range coder, key and inter frames: the context state carries from
-//                                         frame to frame of a key-frame run, and the caller resets it at a key frame
+//                                         frame to frame of a key-frame run, and the caller resets it at a key frame.  This class
+//                                         also holds YCbCr (colorspace_type 0; 4:4:4, 4:2:2, 4:2:0): SliceDec's planar mode, in
+//                                         which a slice is plane Y row by row, then Cb, then Cr, 8-bit samples, and the store side
+//                                         converts to RGB (store_ycbcr_pixel) once a row of Cr is there
 // Nothing read from a packet steers a loop or an address: every loop runs to a count fixed by the frame's geometry, bytes and bits
 // past a slice's end read as zero (the host's overread, which the range coder counts), a symbol's exponent loop has the RFC's
 // bound, a context index is bounded by the quantisation arithmetic (|ctx| <= 665), a run length is consumed sample by sample
@@ -241,26 +244,27 @@ struct NoStats {
     MDVT_HD void short_tail_run() {}
 };
 
-// get_ur_golomb(k, limit 12, esc_len 9) folded to a signed value: q zeros + a one + k bits -> (q << k) | bits; 12 zeros -> 9 bits + 11
-template <class Src, class Stats>
+// get_ur_golomb(k, limit 12, esc_len kBits) folded to a signed value: q zeros + a one + k bits -> (q << k) | bits; 12 zeros ->
+// kBits bits + 11.  kBits: the bits of a sample, 9 for the RCT's planes, 8 for YCbCr's
+template <int kBits, class Src, class Stats>
 MDVT_HD int get_sr_golomb(BitReader<Src>& gb, int k, Stats& stats)
 {
     const int q = gb.zeros(12);
     unsigned v;
     if (q < 12) v = ((unsigned)q << k) | gb.get(k);
-    else { v = gb.get(9) + 11u; stats.escape(); }
+    else { v = gb.get(kBits) + 11u; stats.escape(); }
     return (int)(v >> 1) ^ -(int)(v & 1u);
 }
 
-// the host's get_vlc_symbol with update_vlc_state, for 9-bit samples
-template <class Src, class Stats>
+// the host's get_vlc_symbol with update_vlc_state, for samples of kBits bits
+template <int kBits, class Src, class Stats>
 MDVT_HD int get_vlc_symbol(BitReader<Src>& gb, VlcState* st, Stats& stats)
 {
     int i = st->count, k = 0;
     while (i < st->error_sum) { ++k; i += i; }             // (count >= 1 and error_sum < 2^16: at most 16 rounds)
-    int v = get_sr_golomb(gb, k, stats);
+    int v = get_sr_golomb<kBits>(gb, k, stats);
     v ^= ((2 * st->drift + st->count) >> 31);
-    const int ret = (((v + st->bias) + 256) & 511) - 256;  // fold(., 9)
+    const int ret = (((v + st->bias) + (1 << (kBits - 1))) & ((1 << kBits) - 1)) - (1 << (kBits - 1));      // fold(., kBits)
     int drift = st->drift, count = st->count;
     int es = st->error_sum + (v < 0 ? -v : v);
     drift += v;
@@ -290,6 +294,50 @@ MDVT_HD void store_rct_pixel(int y, int cb, int cr, uint8_t* o, int ri, int gi, 
     o[ri] = (uint8_t)r; o[gi] = (uint8_t)g; o[bi] = (uint8_t)b;
 }
 
+// YCbCr -> the bytes o[ri], o[gi], o[bi] as include/mdvt_video.h decrees it (BT.601 limited range, the host's store_ycbcr_pixel)
+MDVT_HD uint8_t clip8(int v) { return (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v); }
+MDVT_HD void store_ycbcr_pixel(int y, int u, int v, uint8_t* o, int ri, int gi, int bi)
+{
+    const int c = y - 16, d = u - 128, e = v - 128;
+    o[ri] = clip8((298 * c + 409 * e + 128) >> 8);
+    o[gi] = clip8((298 * c - 100 * d - 208 * e + 128) >> 8);
+    o[bi] = clip8((298 * c + 516 * d + 128) >> 8);
+}
+
+// The store side of SliceDec's planar mode, for `lanes` workers of which this is `lane`.  `l`: row y of plane p as plane_row() left
+// it; `rect`: the slice's first pixel in the frame, rows `pitch` bytes apart; hs, vs: the log2 chroma subsampling; csw: the chroma
+// rectangle's width.  The planes of a slice arrive one after another, so luma and Cb wait inside the slice's own pixels, which
+// are all overwritten in the end: a row of Y goes to byte 0 of its pixels, a row of Cb to byte 1 of the top left pixel of each
+// sample's 2^hs x 2^vs block, and a row of Cr converts the blocks of its samples -- one worker per block, which reads the block's Y
+// and Cb before it writes the block's pixels.  Every address depends on the geometry alone.
+MDVT_HD void planar_store_row(const int16_t* l, int p, int y, uint8_t* rect, size_t pitch, int sw, int sh, int csw, int hs, int vs, int ri,
+                              int bi, int lane, int lanes)
+{
+    if (p == 0) {
+        uint8_t* o = rect + (size_t)y * pitch;
+        for (int x = lane; x < sw; x += lanes) o[3 * x] = (uint8_t)l[x];
+        return;
+    }
+    const int ya = y << vs;
+    uint8_t* top = rect + (size_t)ya * pitch;
+    if (p == 1) {
+        for (int cx = lane; cx < csw; cx += lanes) top[3 * (cx << hs) + 1] = (uint8_t)l[cx];
+        return;
+    }
+    const int rows = sh - ya < (1 << vs) ? sh - ya : (1 << vs);
+    for (int cx = lane; cx < csw; cx += lanes) {
+        const int xa = cx << hs;
+        const int cols = sw - xa < (1 << hs) ? sw - xa : (1 << hs);
+        uint8_t* o = top + 3 * xa;
+        const int u = o[1], v = l[cx];
+        int yy[4] = {0, 0, 0, 0};
+        for (int dy = 0; dy < rows; ++dy)
+            for (int dx = 0; dx < cols; ++dx) yy[2 * dy + dx] = o[(size_t)dy * pitch + 3 * dx];
+        for (int dy = 0; dy < rows; ++dy)
+            for (int dx = 0; dx < cols; ++dx) store_ycbcr_pixel(yy[2 * dy + dx], u, v, o + (size_t)dy * pitch + 3 * dx, ri, 1, bi);
+    }
+}
+
 // One slice of one frame (the host's Decoder::slices[index] with decode_slice).  kGolomb = false leaves the Golomb-Rice side out
 // of the compiled code: the intra class, whose coder_type is 1 whatever begin() is told.  The caller owns the memory: `st` the
 // context state (state_bytes(coder)), which it resets (reset_state(), or its own fill) where a run begins and leaves alone
@@ -297,13 +345,16 @@ MDVT_HD void store_rct_pixel(int y, int cb, int cr, uint8_t* o, int ri, int gi, 
 // `misc` 64 bytes; q11[256] = quant11.  Per frame: begin() reads the key-frame bit (first slice: left in `key` for the caller to
 // judge), the slice header and, for coder_type 0, the sentinel bit, and starts the bit reader where the host starts it; row(y)
 // decodes the three planes of slice row y into slot y % 3 (sample k of plane p at lines[(p * 3 + y % 3) * stride + 1 + k]);
-// finish() gives the status.
+// finish() gives the status.  Planar mode (begin's `planar`: a YCbCr stream with log2 chroma subsampling hs, vs): the caller asks
+// for plane_row(p, y) instead, in coding order -- plane 0 rows 0 .. sh - 1, then plane 1 and plane 2 rows 0 .. csh - 1 --, which
+// decodes row y of plane p (8-bit samples, sw or csw of them) into plane p's slot y % 3.
 template <class Src, bool kGolomb = false, class Stats = NoStats>
 struct SliceDec {
     RacDec<Src> c;
     BitReader<Src> gb;
     uint8_t* st; int16_t* lines; uint8_t* misc; const int8_t* q11;
     int stride, sw, sh, x0, y0, cell;        // cell: the slice's index in the frame's nh x nv grid
+    int csw, csh;                            // planar mode: the chroma rectangle, ceil(sw / 2^hs) x ceil(sh / 2^vs)
     int coder, run_index, key;               // key: the packet's key-frame bit, read by the frame's first slice (else 0)
     bool error;
     Stats stats;
@@ -317,12 +368,12 @@ struct SliceDec {
 
     // `avail` bytes can be read through src (the payload and what follows it in the packet), `size` of them are the payload
     MDVT_HD uint32_t begin(Src src, uint32_t avail, uint32_t size, bool first, int coder_type, int micro, int W, int H, int nh, int nv,
-                           const uint16_t* next)
+                           const uint16_t* next, int planar = 0, int hs = 0, int vs = 0)
     {
         c.src = src; c.next = next;
         c.range = 0xFF00; c.overread = 0; c.pos = 2; c.end = size;
         coder = kGolomb ? coder_type : 1; run_index = 0; key = 0;
-        error = false; sw = sh = 0; x0 = y0 = 0; cell = 0;
+        error = false; sw = sh = 0; x0 = y0 = 0; cell = 0; csw = csh = 0;
         // the host starts the first slice's coder on the whole packet (>= 3 bytes), the others on their payload (>= 2 bytes, or refused)
         if (first ? avail < 2u : size < 2u) return kDamaged;
         c.low = ((int)src.byte(0) << 8) | (int)src.byte(1);
@@ -346,6 +397,7 @@ struct SliceDec {
         x0 = (int)((long long)sx * W / nh); y0 = (int)((long long)sy * H / nv);
         sw = (int)((long long)(sx + 1u) * W / nh) - x0; sh = (int)((long long)(sy + 1u) * H / nv) - y0;
         if (sw < 1 || sh < 1 || sw + 2 > stride) return kBadSliceHeader;
+        if (planar) { csw = (sw + (1 << hs) - 1) >> hs; csh = (sh + (1 << vs) - 1) >> vs; }
         if (golomb()) {
             if (micro > 1) { misc[33] = 129; (void)c.get(misc + 33); }             // the sentinel of ff_rac_terminate
             const uint32_t consumed = c.pos - 1u;                                  // the host's `p - start - 1`
@@ -355,74 +407,87 @@ struct SliceDec {
         return kOk;
     }
 
-    MDVT_HD void row(int y)
+    // one row of `w` samples of kBits bits: `cur` the row's slot, `last` the slot of the row above; set: the context set (0 luma, 1 chroma)
+    template <int kBits>
+    MDVT_HD void line(int16_t* cur, int16_t* last, int w, int set)
     {
-        const int cs = y % 3, ls = (y + 2) % 3;
-        for (int p = 0; p < 3; ++p) {
-            int16_t* cur = lines + (size_t)(p * 3 + cs) * (size_t)stride + 1;
-            int16_t* last = lines + (size_t)(p * 3 + ls) * (size_t)stride + 1;
-            cur[-1] = last[0];
-            last[sw] = last[sw - 1];
-            int L = cur[-1], LT = last[-1], T = last[0];
-            int q_lt_t = q11[(LT - T) & 0xFF];                 // (this sample's T - RT is the next one's LT - T)
-            if (!golomb()) {
-                uint8_t* states = st + (p ? kStateBytes : 0);
-                for (int x = 0; x < sw; ++x) {
-                    const int RT = last[x + 1];
-                    const int q_t_rt = q11[(T - RT) & 0xFF];
-                    int context = q11[(L - LT) & 0xFF] + 11 * q_lt_t + 121 * q_t_rt;
-                    q_lt_t = q_t_rt;
-                    const bool sign = context < 0;
-                    if (sign) context = -context;
-                    bool bad = false;
-                    int diff = c.symbol(states + (size_t)context * 32u, true, &bad);
-                    error |= bad;
-                    if (sign) diff = -diff;
-                    const int v = (median3(L, T, L + T - LT) + diff) & 511;
-                    cur[x] = (int16_t)v;
-                    L = v; LT = T; T = RT;
-                }
-                continue;
-            }
-            // Golomb-Rice with run mode (the host's decode_line): run_index runs on across rows and planes
-            VlcState* vs = reinterpret_cast<VlcState*>(st) + (p ? kContexts : 0);
-            int run_count = 0, run_mode = 0;
-            for (int x = 0; x < sw; ++x) {
+        constexpr int kMask = (1 << kBits) - 1;
+        cur[-1] = last[0];
+        last[w] = last[w - 1];
+        int L = cur[-1], LT = last[-1], T = last[0];
+        int q_lt_t = q11[(LT - T) & 0xFF];                 // (this sample's T - RT is the next one's LT - T)
+        if (!golomb()) {
+            uint8_t* states = st + (set ? kStateBytes : 0);
+            for (int x = 0; x < w; ++x) {
                 const int RT = last[x + 1];
                 const int q_t_rt = q11[(T - RT) & 0xFF];
                 int context = q11[(L - LT) & 0xFF] + 11 * q_lt_t + 121 * q_t_rt;
                 q_lt_t = q_t_rt;
                 const bool sign = context < 0;
                 if (sign) context = -context;
-                int diff;
-                if (context == 0 && run_mode == 0) run_mode = 1;
-                if (run_mode) {
-                    if (run_count == 0 && run_mode == 1) {
-                        const int lr = log2_run(run_index);
-                        if (gb.get(1)) {
-                            run_count = 1 << lr;
-                            if (x + run_count <= sw) { if (run_index < kRunIndexMax) ++run_index; }
-                            else stats.short_tail_run();
-                            stats.run_index(run_index);
-                        } else {
-                            run_count = (int)gb.get(lr);
-                            if (run_index) --run_index;
-                            run_mode = 2;
-                        }
-                    }
-                    --run_count;
-                    if (run_count < 0) {
-                        run_mode = 0; run_count = 0;
-                        diff = get_vlc_symbol(gb, vs + context, stats);
-                        if (diff >= 0) ++diff;
-                    } else diff = 0;
-                } else diff = get_vlc_symbol(gb, vs + context, stats);
+                bool bad = false;
+                int diff = c.symbol(states + (size_t)context * 32u, true, &bad);
+                error |= bad;
                 if (sign) diff = -diff;
-                const int v = (median3(L, T, L + T - LT) + diff) & 511;
+                const int v = (median3(L, T, L + T - LT) + diff) & kMask;
                 cur[x] = (int16_t)v;
                 L = v; LT = T; T = RT;
             }
+            return;
         }
+        // Golomb-Rice with run mode (the host's decode_line): run_index runs on across rows (and, in the RCT's slices, planes)
+        VlcState* vs = reinterpret_cast<VlcState*>(st) + (set ? kContexts : 0);
+        int run_count = 0, run_mode = 0;
+        for (int x = 0; x < w; ++x) {
+            const int RT = last[x + 1];
+            const int q_t_rt = q11[(T - RT) & 0xFF];
+            int context = q11[(L - LT) & 0xFF] + 11 * q_lt_t + 121 * q_t_rt;
+            q_lt_t = q_t_rt;
+            const bool sign = context < 0;
+            if (sign) context = -context;
+            int diff;
+            if (context == 0 && run_mode == 0) run_mode = 1;
+            if (run_mode) {
+                if (run_count == 0 && run_mode == 1) {
+                    const int lr = log2_run(run_index);
+                    if (gb.get(1)) {
+                        run_count = 1 << lr;
+                        if (x + run_count <= w) { if (run_index < kRunIndexMax) ++run_index; }
+                        else stats.short_tail_run();
+                        stats.run_index(run_index);
+                    } else {
+                        run_count = (int)gb.get(lr);
+                        if (run_index) --run_index;
+                        run_mode = 2;
+                    }
+                }
+                --run_count;
+                if (run_count < 0) {
+                    run_mode = 0; run_count = 0;
+                    diff = get_vlc_symbol<kBits>(gb, vs + context, stats);
+                    if (diff >= 0) ++diff;
+                } else diff = 0;
+            } else diff = get_vlc_symbol<kBits>(gb, vs + context, stats);
+            if (sign) diff = -diff;
+            const int v = (median3(L, T, L + T - LT) + diff) & kMask;
+            cur[x] = (int16_t)v;
+            L = v; LT = T; T = RT;
+        }
+    }
+
+    MDVT_HD void row(int y)
+    {
+        const int cs = y % 3, ls = (y + 2) % 3;
+        for (int p = 0; p < 3; ++p)
+            line<9>(lines + (size_t)(p * 3 + cs) * (size_t)stride + 1, lines + (size_t)(p * 3 + ls) * (size_t)stride + 1, sw, p ? 1 : 0);
+    }
+
+    // planar mode: row y of plane p; the run index restarts at each plane
+    MDVT_HD void plane_row(int p, int y)
+    {
+        const int cs = y % 3, ls = (y + 2) % 3;
+        if (y == 0) run_index = 0;
+        line<8>(lines + (size_t)(p * 3 + cs) * (size_t)stride + 1, lines + (size_t)(p * 3 + ls) * (size_t)stride + 1, p ? csw : sw, p ? 1 : 0);
     }
 
     // (the host reader has no overread check on the Golomb side: c.overread counts the header's reads alone there)
@@ -435,10 +500,10 @@ struct PtrSrc {
     MDVT_HD uint8_t byte(uint32_t k) const { return p[k]; }
 };
 
-struct StreamClass { int version, micro, nh, nv, ec, coder, intra; };
+struct StreamClass { int version, micro, nh, nv, ec, coder, intra, planar, hs, vs; };      // planar: YCbCr with log2 chroma subsampling hs, vs
 
-// -> nullptr and *out when the stream is in the class asked for -- intra: coder_type 1 and intra 1; stream: coder_type 0 or 1,
-// intra 0 or 1 --, else the reason (a static string naming the field)
+// -> nullptr and *out when the stream is in the class asked for -- intra: coder_type 1, intra 1, RGB; stream: coder_type 0 or 1,
+// intra 0 or 1, RGB or 8-bit YCbCr in 4:4:4, 4:2:2 or 4:2:0 --, else the reason (a static string naming the field)
 inline const char* parse_stream_class(const uint8_t* data, size_t size, bool stream, StreamClass* out)
 {
     if (!data || size < 6 || size > (1u << 20)) return "configuration record: missing or of an impossible size";
@@ -467,12 +532,19 @@ inline const char* parse_stream_class(const uint8_t* data, size_t size, bool str
             return "coder_type: only Golomb-Rice (coder_type 0) and the range coder with the default state table (coder_type 1) are decoded on the device";
     }
     const int colorspace = c.symbol(state, false, &bad);
-    if (bad || colorspace != 1) return "colorspace_type: only RGB (JPEG 2000 RCT) is decoded on the device";
+    if (!stream) {
+        if (bad || colorspace != 1) return "colorspace_type: only RGB (JPEG 2000 RCT) is decoded on the device";
+    } else if (bad || (colorspace != 0 && colorspace != 1))
+        return "colorspace_type: only YCbCr (0) and RGB (1, the JPEG 2000 RCT) are decoded on the device";
     const int bits = c.symbol(state, false, &bad);
     if (bad || (bits != 0 && bits != 8)) return "bits_per_raw_sample: only 8 bits are decoded on the device";
-    (void)c.get(state);                                      // chroma_planes
-    (void)c.symbol(state, false, &bad);                      // log2_h_chroma_subsample, log2_v_chroma_subsample
-    (void)c.symbol(state, false, &bad);
+    const int chroma_planes = c.get(state);
+    const int hs = c.symbol(state, false, &bad), vs = c.symbol(state, false, &bad);      // (an RGB stream's are not looked at)
+    if (colorspace == 0) {
+        if (!chroma_planes) return "chroma_planes: a YCbCr stream without chroma planes (grey) is not decoded on the device";
+        if (bad || !((hs == 0 && vs == 0) || (hs == 1 && vs == 0) || (hs == 1 && vs == 1)))
+            return "log2_h_chroma_subsample / log2_v_chroma_subsample: only (0, 0), (1, 0) and (1, 1) -- yuv444p, yuv422p, yuv420p -- are decoded on the device";
+    }
     if (c.get(state)) return "extra_plane: alpha planes are not decoded on the device";
     const int nh = 1 + c.symbol(state, false, &bad), nv = 1 + c.symbol(state, false, &bad);
     if (bad || nh < 1 || nv < 1 || nh > kMaxSlices || nv > kMaxSlices || nh * nv > kMaxSlices)
@@ -503,6 +575,7 @@ inline const char* parse_stream_class(const uint8_t* data, size_t size, bool str
     if (!stream && !intra) return "intra: only streams whose every frame is a key frame are decoded on the device";
     if (crc != 0) return "configuration record: CRC mismatch";
     out->version = version; out->micro = micro; out->nh = nh; out->nv = nv; out->ec = ec; out->coder = coder; out->intra = intra ? 1 : 0;
+    out->planar = colorspace == 0; out->hs = out->planar ? hs : 0; out->vs = out->planar ? vs : 0;
     return nullptr;
 }
 

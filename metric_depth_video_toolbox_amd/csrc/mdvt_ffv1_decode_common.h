@@ -117,7 +117,7 @@ __device__ __forceinline__ uint32_t ffv1_begin_slice(Dec& d, const Ffv1DecodeArg
     const uint32_t avail = len + (a.ec ? 8u : 3u);         // [data, data + avail) lies inside the packet (the walk)
     GlobalSrc src;
     src.p = data; src.avail = avail; src.wbase = 0xFFFFFF00u; src.w = 0;
-    return d.begin(src, avail, len, si == 0, a.coder, a.micro, a.W, a.H, a.nh, a.nv, s.next);
+    return d.begin(src, avail, len, si == 0, a.coder, a.micro, a.W, a.H, a.nh, a.nv, s.next, a.planar, a.hs, a.vs);
 }
 
 // Lane 0, with begin's status: every slice of frame f claims its cell before it stores, so two slices never write the same pixels,
@@ -148,6 +148,32 @@ __device__ __forceinline__ void ffv1_decode_rows(Dec& d, const Ffv1DecodeArgs& a
             const int16_t* l2 = s_lines + (size_t)(2 * 3 + slot) * a.line_stride + 1;
             uint8_t* o = out + (size_t)(y0 + y - 1) * a.pitch;
             for (int x = tid - 64; x < sw; x += 64) store_rct_pixel(l0[x], l1[x], l2[x], o, 3 * x + a.ri, 3 * x + 1, 3 * x + a.bi);
+        }
+        __syncthreads();
+    }
+}
+
+// The workgroup, for a slice of a YCbCr stream (a.planar): the slice's plane rows in coding order -- Y's, then Cb's, then Cr's.  Lane 0
+// decodes plane row r while the second wave takes plane row r - 1 from its slot to the frame (planar_store_row): Y and Cb wait in
+// the slice's own pixels, a row of Cr converts its blocks to RGB.  The barrier between two steps orders the second wave's stores of
+// one step before its loads of a later one.  Nothing is stored for a frame decoded for its context state alone.
+template <class Dec>
+__device__ __forceinline__ void ffv1_decode_rows_planar(Dec& d, const Ffv1DecodeArgs& a, const Ffv1DecLds& s, const int16_t* s_lines, uint8_t* frame,
+                                                        bool stored)
+{
+    const int tid = (int)threadIdx.x;
+    const int x0 = s.geom[1], y0 = s.geom[2], sw = s.geom[3], sh = s.geom[4];
+    const int csw = (sw + (1 << a.hs) - 1) >> a.hs, csh = (sh + (1 << a.vs) - 1) >> a.vs;
+    const int total = sh + 2 * csh;
+    uint8_t* rect = frame + (size_t)y0 * a.pitch + (size_t)x0 * 3u;
+    for (int r = 0; r <= total; ++r) {
+        if (tid == 0) {
+            if (r < total) d.plane_row(r < sh ? 0 : r < sh + csh ? 1 : 2, r < sh ? r : r < sh + csh ? r - sh : r - sh - csh);
+        } else if (tid >= 64 && r > 0 && stored) {
+            const int q = r - 1;
+            const int p = q < sh ? 0 : q < sh + csh ? 1 : 2, y = q < sh ? q : q < sh + csh ? q - sh : q - sh - csh;
+            planar_store_row(s_lines + (size_t)(p * 3 + y % 3) * a.line_stride + 1, p, y, rect, a.pitch, sw, sh, csw, a.hs, a.vs, a.ri, a.bi,
+                             tid - 64, 64);
         }
         __syncthreads();
     }

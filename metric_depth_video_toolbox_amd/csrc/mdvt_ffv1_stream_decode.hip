@@ -1,5 +1,6 @@
 // mdvt_ffv1_stream_decode.hip -- FFV1 streams whose context state carries from frame to frame (mdvt_decode_video_stream,
-// include/mdvt_ffv1_stream_decode.h): version 3, coder_type 0 (Golomb-Rice with run mode) or 1 (range coder), intra 0 or 1.  The
+// include/mdvt_ffv1_stream_decode.h): version 3, coder_type 0 (Golomb-Rice with run mode) or 1 (range coder), intra 0 or 1, RGB
+// (the JPEG 2000 RCT) or 8-bit YCbCr in 4:4:4, 4:2:2 or 4:2:0.  The
 // bytes mdvt_video_read writes when it reads the same packets in order from a run's key frame.
 //
 // Where a frame of the intra class is nh x nv independent decoders (mdvt_ffv1_decode.hip), here a slice's decoder of frame k needs
@@ -14,7 +15,9 @@
 //                         state sets (42 KiB) --, reset by the workgroup at the run's start.  Per frame: the slice's CRC (ec), then
 //                         lane 0 reads the slice header, claims the slice's cell and decodes row y while the second wave undoes the
 //                         RCT of row y - 1 and stores it (not for frames before first_out): the steps of k_ffv1_dec_slice, from
-//                         mdvt_ffv1_decode_common.h.
+//                         mdvt_ffv1_decode_common.h.  A YCbCr stream's slice is plane after plane instead: lane 0 decodes a plane
+//                         row while the second wave parks the row before it (Y, Cb) in the slice's own pixels of the stored frame,
+//                         or, for a row of Cr, converts its blocks to RGB there (ffv1_decode_rows_planar).
 //                         A frame it has to flag ends the chain: every later frame of the run gets kBrokenRun.
 //                         The workgroup of (frame 0, slice 0) also flags the frames in front of the call's first key frame.
 // Every loop here is bounded by the frame's geometry, the packet's byte count or the number of frames, never by a decoded value.
@@ -71,7 +74,9 @@ __global__ void __launch_bounds__(kFfv1DecThreads) k_ffv1_stream_chain(Ffv1Decod
         __syncthreads();
         if (s.geom[0] != 0) { flag = (uint32_t)s.geom[0]; break; }
         const bool stored = f >= a.first_out;
-        ffv1_decode_rows(d, a, s, s_lines, a.dst + (size_t)(stored ? f - a.first_out : 0) * a.frame_stride, stored);
+        uint8_t* frame = a.dst + (size_t)(stored ? f - a.first_out : 0) * a.frame_stride;
+        if (a.planar) ffv1_decode_rows_planar(d, a, s, s_lines, frame, stored);
+        else ffv1_decode_rows(d, a, s, s_lines, frame, stored);
         if (tid == 0) s.geom[0] = (int)d.finish();
         __syncthreads();
         if (s.geom[0] != 0) { flag = (uint32_t)s.geom[0]; break; }

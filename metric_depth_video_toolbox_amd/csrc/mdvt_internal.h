@@ -255,7 +255,7 @@ hipError_t launch_ffv1_emit(const Ffv1EmitArgs& a, int n_slices, hipStream_t s);
 // mdvt_ffv1_decode.hip, mdvt_ffv1_stream_decode.hip: FFV1 decoding of packets in device memory (mdvt_decode_video_frames,
 // include/mdvt_ffv1_decode.h: key frames only, a pass of frames at a time; mdvt_decode_video_stream,
 // include/mdvt_ffv1_stream_decode.h: inter frames and Golomb-Rice coding, consecutive packets).  The first call leaves the last
-// four fields zero.
+// seven fields zero.
 struct Ffv1DecodeArgs {
     const uint8_t* packets; unsigned long long packets_bytes;      // the packet buffer and its size: no packet may pass it
     const unsigned long long* offsets; const uint32_t* sizes;      // the caller's arrays, at the pass's first frame
@@ -267,6 +267,7 @@ struct Ffv1DecodeArgs {
     int line_stride;                                               // samples per row slot in LDS: the widest slice + 2
     int first_out, coder, micro;                                   // the first frame that is stored; the record's coder_type and micro_version
     uint32_t* kind;                                                // workspace [n_frames]: mdvt_ffv1::kFrameInter / Key / Bad
+    int planar, hs, vs;                                            // a YCbCr stream (SliceDec's planar mode) and its log2 chroma subsampling
 };
 size_t ffv1_decode_lds_bytes(int line_stride);                     // dynamic LDS of k_ffv1_dec_slice: the row slots
 size_t ffv1_stream_lds_bytes(int coder, int line_stride);          // dynamic LDS of k_ffv1_stream_chain: the context state, then the row slots

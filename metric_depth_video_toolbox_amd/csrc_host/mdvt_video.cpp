@@ -8,8 +8,10 @@
 //             container's CodecPrivate, N slices per frame, each followed by its 24-bit size, an error-status byte and a CRC-32
 //             parity when ec = 1); coder_type 0 (Golomb-Rice with run mode), 1 (range coder, default state-transition table) and
 //             2 (custom table sent as deltas); colorspace_type 1 (JPEG 2000 RCT over 8-bit R, G, B, +- alpha: what FFmpeg codes
-//             for bgr0 / bgra, the pixel format OpenCV feeds FFV1); key frames AND inter frames (inter frames keep the context
-//             states of the previous frame, so the stream is read in order).  YUV streams are refused with a message.
+//             for bgr0 / bgra, the pixel format OpenCV feeds FFV1) and colorspace_type 0 (YCbCr, 8 bits, chroma subsampled by
+//             (0, 0), (1, 0) or (1, 1): yuv444p, yuv422p, yuv420p -- FFmpeg's default for a movie -- converted to RGB as
+//             include/mdvt_video.h states it); key frames AND inter frames (inter frames keep the context states of the previous
+//             frame, so the stream is read in order).  Grey, alpha beside YCbCr and more than 8 bits are refused with a message.
 //   encoder   version 3.4, coder_type 1, intra-only, RGB colour space, 8 bits, slices_h x slices_v slices, ec = 1; the
 //             quantisation tables FFmpeg's encoder uses for 8-bit input (quant11, context model 0: 666 contexts).
 //   container one video track, CodecID V_FFV1 with the configuration record as CodecPrivate (reader also: V_MS/VFW/FOURCC with a
@@ -290,7 +292,9 @@ struct Ffv1Config {
     std::vector<uint8_t> initial_states[kMaxQuantTables];      // context_count * 32, empty = all 128
     StateTables states;                                        // of the slices' range coders
     bool custom_states = false;
-    int plane_count() const { return 2 + alpha; }              // RGB: Y, the two chroma planes share one context set, alpha
+    int plane_count() const { return 2 + alpha; }              // Y, the two chroma planes share one context set, alpha
+    bool ycbcr() const { return colorspace == 0; }
+    int pix_fmt() const { return !ycbcr() ? MDVT_VIDEO_PIX_RGB : vshift ? MDVT_VIDEO_PIX_YUV420P : hshift ? MDVT_VIDEO_PIX_YUV422P : MDVT_VIDEO_PIX_YUV444P; }
 };
 
 // one set of five tables, run-length coded (RFC 9043 section 4.9.? QuantizationTable)
@@ -405,6 +409,17 @@ void reset_plane(const Ffv1Config& f, PlaneState& p)
 
 inline int median3(int a, int b, int c) { return a > b ? (b > c ? b : (a > c ? c : a)) : (a > c ? a : (b > c ? c : b)); }
 
+// Y, Cb, Cr -> the bytes o[ri], o[1], o[bi]: BT.601 limited range in the integers include/mdvt_video.h states (a decree of this
+// project's, not a claim about swscale's bits)
+inline uint8_t clip8(int v) { return (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v); }
+inline void store_ycbcr_pixel(int y, int u, int v, uint8_t* o, int ri, int bi)
+{
+    const int c = y - 16, d = u - 128, e = v - 128;
+    o[ri] = clip8((298 * c + 409 * e + 128) >> 8);
+    o[1] = clip8((298 * c - 100 * d - 208 * e + 128) >> 8);
+    o[bi] = clip8((298 * c + 516 * d + 128) >> 8);
+}
+
 struct LineCtx {
     const int16_t (*q)[256];
     bool five;
@@ -509,11 +524,31 @@ struct Decoder {
     {
         if (f.version != 0 && f.version != 1 && f.version != 3)
             return fail(ERR_UNSUPPORTED, "FFV1 version %d (0, 1 and 3 are implemented; 2 was experimental, 4 is not final)", f.version);
-        if (f.colorspace != 1)
-            return fail(ERR_UNSUPPORTED, "FFV1 colorspace_type %d: only the RGB (JPEG 2000 RCT) colour space is implemented -- what FFmpeg codes for "
-                                         "the bgr0 / bgra frames OpenCV hands it; a YCbCr stream is not one of the toolbox's", f.colorspace);
+        if (f.colorspace != 0 && f.colorspace != 1)
+            return fail(ERR_UNSUPPORTED, "FFV1 colorspace_type %d: YCbCr (0) and RGB (1, the JPEG 2000 RCT) are implemented", f.colorspace);
         if (f.bits != 0 && f.bits != 8) return fail(ERR_UNSUPPORTED, "FFV1 with %d bits per sample (8 implemented)", f.bits);
         if (f.coder < 0 || f.coder > 2) return fail(ERR_FORMAT, "FFV1 coder_type %d", f.coder);
+        if (!f.ycbcr()) return 0;
+        if (f.alpha) return fail(ERR_UNSUPPORTED, "FFV1 YCbCr with an alpha plane (extra_plane 1) is not implemented");
+        if (!f.chroma_planes) return fail(ERR_UNSUPPORTED, "FFV1 YCbCr with chroma_planes 0 (grey) is not implemented");
+        const int hs = f.hshift, vs = f.vshift;
+        if (!((hs == 0 && vs == 0) || (hs == 1 && vs == 0) || (hs == 1 && vs == 1)))
+            return fail(ERR_UNSUPPORTED, "FFV1 YCbCr with chroma subsampling shifts (%d, %d): (0, 0), (1, 0) and (1, 1) -- yuv444p, yuv422p, "
+                                         "yuv420p -- are implemented", hs, vs);
+        // a slice's chroma rectangle starts at (x0 >> hs, y0 >> vs): the chroma rectangles tile the chroma plane only when every
+        // slice origin is a multiple of the subsampling
+        if (f.version >= 3) {
+            for (int sx = 0; sx < f.nh; ++sx)
+                if (((int64_t)sx * W / f.nh) & ((1 << hs) - 1))
+                    return fail(ERR_UNSUPPORTED, "FFV1 YCbCr: the %d x %d slice grid puts a slice at x = %d of the %d x %d frame, off the chroma "
+                                                 "grid of shifts (%d, %d); only aligned slice grids are decoded", f.nh, f.nv,
+                                (int)((int64_t)sx * W / f.nh), W, H, hs, vs);
+            for (int sy = 0; sy < f.nv; ++sy)
+                if (((int64_t)sy * H / f.nv) & ((1 << vs) - 1))
+                    return fail(ERR_UNSUPPORTED, "FFV1 YCbCr: the %d x %d slice grid puts a slice at y = %d of the %d x %d frame, off the chroma "
+                                                 "grid of shifts (%d, %d); only aligned slice grids are decoded", f.nh, f.nv,
+                                (int)((int64_t)sy * H / f.nv), W, H, hs, vs);
+        }
         return 0;
     }
 
@@ -564,14 +599,44 @@ struct Decoder {
             if (consumed > total) return fail(ERR_DATA, "FFV1 slice %d: header overruns the slice", index);
             sd.gb.init(base + consumed, total - consumed);
         }
-        // ---- the samples: lines of Y, Cb, Cr (, A) interleaved (RFC 9043 section 3.7.2 / 4.7) ----
+        const int ri = order == MDVT_VIDEO_BGR ? 2 : 0, bi = order == MDVT_VIDEO_BGR ? 0 : 2;
+        if (f.ycbcr()) {
+            // ---- YCbCr: plane after plane, 8-bit samples, the run index restarting at each plane (RFC 9043 section 4.6) ----
+            const int hs = f.hshift, vs = f.vshift;
+            const int cw = (sw + (1 << hs) - 1) >> hs, chh = (sh + (1 << vs) - 1) >> vs;
+            std::vector<uint8_t> pl[3];
+            std::vector<int16_t> buf((size_t)2 * (size_t)(sw + 6));
+            for (int p = 0; p < 3; ++p) {
+                const int w = p ? cw : sw, h = p ? chh : sh;
+                pl[p].resize((size_t)w * (size_t)h);
+                std::fill(buf.begin(), buf.end(), (int16_t)0);
+                int16_t* sample[2] = {buf.data() + 3, buf.data() + (size_t)(sw + 6) + 3};
+                sd.run_index = 0;
+                for (int y = 0; y < h; ++y) {
+                    std::swap(sample[0], sample[1]);
+                    sample[1][-1] = sample[0][0];
+                    sample[0][w] = sample[0][w - 1];
+                    sd.decode_line(ss.plane[p ? 1 : 0], w, sample, 8);
+                    for (int x = 0; x < w; ++x) pl[p][(size_t)y * (size_t)w + (size_t)x] = (uint8_t)sample[1][x];
+                }
+            }
+            for (int y = 0; y < sh; ++y) {
+                uint8_t* o = dst + (size_t)(y0 + y) * pitch + (size_t)x0 * 3;
+                const uint8_t* ly = pl[0].data() + (size_t)y * (size_t)sw;
+                const uint8_t* lu = pl[1].data() + (size_t)(y >> vs) * (size_t)cw;
+                const uint8_t* lv = pl[2].data() + (size_t)(y >> vs) * (size_t)cw;
+                for (int x = 0; x < sw; ++x) store_ycbcr_pixel(ly[x], lu[x >> hs], lv[x >> hs], o + 3 * x, ri, bi);
+            }
+            if (sd.error || sd.c.overread > 4) return fail(ERR_DATA, "FFV1 slice %d: bitstream damaged (overread %d)", index, sd.c.overread);
+            return 0;
+        }
+        // ---- RGB: lines of Y, Cb, Cr (, A) interleaved (RFC 9043 section 3.7.2 / 4.7) ----
         const int np = 3 + f.alpha;
         std::vector<int16_t> buf((size_t)np * 2 * (size_t)(sw + 6), 0);
         int16_t* sample[4][2];
         for (int p = 0; p < np; ++p)
             for (int k = 0; k < 2; ++k) sample[p][k] = buf.data() + ((size_t)p * 2 + (size_t)k) * (size_t)(sw + 6) + 3;
         sd.run_index = 0;
-        const int ri = order == MDVT_VIDEO_BGR ? 2 : 0, bi = order == MDVT_VIDEO_BGR ? 0 : 2;
         for (int y = 0; y < sh; ++y) {
             for (int p = 0; p < np; ++p) {
                 std::swap(sample[p][0], sample[p][1]);
@@ -684,7 +749,8 @@ struct EncoderTables {
 };
 const EncoderTables g_enc_tables;
 
-std::vector<uint8_t> make_config_record(int nh, int nv, int coder = 1, int intra = 1)
+// (colorspace 0 with its chroma shifts: tools/ffv1_ycbcr_writer.cpp, which makes YCbCr streams for measurements; no writer of this library's does)
+std::vector<uint8_t> make_config_record(int nh, int nv, int coder = 1, int intra = 1, int colorspace = 1, int hshift = 0, int vshift = 0)
 {
     RacEnc c;
     c.init();
@@ -694,11 +760,11 @@ std::vector<uint8_t> make_config_record(int nh, int nv, int coder = 1, int intra
     put_symbol(c, state, 3, false);          // version
     put_symbol(c, state, 4, false);          // micro_version
     put_symbol(c, state, coder, false);      // coder_type: 1 range coder, default state transition table; 0 Golomb-Rice (the stream class)
-    put_symbol(c, state, 1, false);          // colorspace_type: RGB
+    put_symbol(c, state, colorspace, false); // colorspace_type: RGB
     put_symbol(c, state, 8, false);          // bits_per_raw_sample
     c.put(state, 1);                         // chroma_planes
-    put_symbol(c, state, 0, false);          // log2_h_chroma_subsample
-    put_symbol(c, state, 0, false);          // log2_v_chroma_subsample
+    put_symbol(c, state, hshift, false);     // log2_h_chroma_subsample
+    put_symbol(c, state, vshift, false);     // log2_v_chroma_subsample
     c.put(state, 0);                         // extra_plane
     put_symbol(c, state, nh - 1, false);
     put_symbol(c, state, nv - 1, false);
@@ -826,15 +892,15 @@ struct BitWriter {
 
 struct GolombSliceState { std::vector<VlcState> vlc[2]; };
 
-inline void put_vlc_symbol(BitWriter& bw, VlcState& st, int diff)
+inline void put_vlc_symbol(BitWriter& bw, VlcState& st, int diff, int bits = 9)
 {
-    const int v = fold(diff - st.bias, 9);
+    const int v = fold(diff - st.bias, bits);
     int i = st.count, k = 0;
     while (i < st.error_sum) { ++k; i += i; }
     const int code = v ^ ((2 * st.drift + st.count) >> 31);
     const unsigned u = code >= 0 ? 2u * (unsigned)code : 2u * (unsigned)(-code) - 1u;
     if ((u >> k) < 12u) bw.put((int)(u >> k) + k + 1, (1u << k) + (u & ((1u << k) - 1u)));
-    else bw.put(12 + 9, u - 11u);
+    else bw.put(12 + bits, u - 11u);
     // update_vlc_state, as get_vlc_symbol does it
     int drift = st.drift + v, count = st.count;
     int es = st.error_sum + (v < 0 ? -v : v);
@@ -1161,6 +1227,7 @@ void fill_codec_info(mdvt_video_reader& r)
     const Ffv1Config& f = r.dec.f;
     r.info.ffv1_version = f.version; r.info.ffv1_micro_version = f.micro; r.info.coder_type = f.coder;
     r.info.slices = f.version >= 3 ? f.nh * f.nv : 1; r.info.alpha = f.alpha; r.info.intra = f.intra; r.info.ec = f.ec;
+    r.info.pix_fmt = f.pix_fmt();
 }
 
 // ---- writer ----

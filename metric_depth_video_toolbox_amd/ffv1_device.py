@@ -7,7 +7,8 @@ are copied to the device as stored and decoded there into the bytes video_io.Vid
 decoded on the host, which gives the same bytes or the host's own VideoError.
 
 A third part (mdvt_decode_video_stream, include/mdvt_ffv1_stream_decode.h) does the same for streams whose context state carries
-from frame to frame: Golomb-Rice or range coder, with inter frames -- the files FFmpeg and OpenCV write by default."""
+from frame to frame: Golomb-Rice or range coder, with inter frames -- the files FFmpeg and OpenCV write by default, RGB or
+8-bit YCbCr (yuv444p, yuv422p, yuv420p: converted on the device as include/mdvt_video.h states, the host reader's bytes)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -334,8 +335,8 @@ STREAM_STATUS = {**DECODE_STATUS, NO_KEY_FRAME: "no key frame at or before this 
 
 
 def stream_supported(info, config: Optional[bytes] = None) -> Optional[str]:
-    """supported() for the stream decoder's class: version 3, coder_type 0 or 1, intra 0 or 1 (the files FFmpeg and OpenCV write
-    by default are in it).  None, or the reason, naming the field."""
+    """supported() for the stream decoder's class: version 3, coder_type 0 or 1, intra 0 or 1, RGB or YCbCr in 4:4:4, 4:2:2, 4:2:0
+    (the files FFmpeg and OpenCV write by default are in it).  None, or the reason, naming the field."""
     return _class_reason(info, config, True)
 
 

@@ -30,11 +30,15 @@ STREAM_SYMBOLS = ("mdvt_video_create_stream", "mdvt_video_seek_packet", "mdvt_vi
 
 RGB, BGR = 0, 1
 
+# VideoInfo.pix_fmt (MDVT_VIDEO_PIX_*): what the stream codes.  The frames read are RGB / BGR whatever it is: a YCbCr stream is
+# converted as include/mdvt_video.h states it (BT.601 limited range, chroma replicated; this project's decree, not cv2's bits)
+PIX_FMTS = ("rgb", "yuv444p", "yuv422p", "yuv420p")
+
 
 class VideoInfo(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("frames", C.c_int64), ("fps", C.c_double),
                 ("ffv1_version", C.c_int32), ("ffv1_micro_version", C.c_int32), ("coder_type", C.c_int32), ("slices", C.c_int32),
-                ("alpha", C.c_int32), ("intra", C.c_int32), ("ec", C.c_int32), ("reserved", C.c_int32)]
+                ("alpha", C.c_int32), ("intra", C.c_int32), ("ec", C.c_int32), ("pix_fmt", C.c_int32)]
 
 
 class VideoError(RuntimeError):
@@ -103,6 +107,11 @@ class VideoReader:
         self.path, self.order, self.threads = path, BGR if bgr else RGB, int(threads)
         _check(load().mdvt_video_open(os.fsencode(path), C.byref(self._h), C.byref(self.info)))
         self.width, self.height, self.frames, self.fps = self.info.width, self.info.height, int(self.info.frames), float(self.info.fps)
+
+    @property
+    def pix_fmt(self) -> str:
+        """What the stream codes: "rgb", "yuv444p", "yuv422p" or "yuv420p" (frames come out as RGB / BGR either way)."""
+        return PIX_FMTS[self.info.pix_fmt]
 
     def read_into(self, out: np.ndarray) -> bool:
         """Decodes the next frame into `out` (H x W x 3 uint8, rows contiguous; e.g. a pinned staging buffer).  False at the end."""
