@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import threading
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libmdvt_hip.so")
@@ -204,6 +205,20 @@ def load():
                                           C.c_int, C.c_int, C.c_int, C.c_int, vp, st, st, vp, st, st, vp, st, st, vp, vp]
     L.mdvt_model_infill_finish.restype = C.c_int
     L.mdvt_model_infill_finish.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, st, st, vp, st, st, vp, st, st, vp, st, st, vp]
+    # the HIP calls SharedContext orders its streams with, reached through the library's own link to the HIP runtime (dlsym
+    # searches a library's dependencies), so the events belong to the runtime the kernels are launched by
+    L.hipEventCreateWithFlags.restype = C.c_int
+    L.hipEventCreateWithFlags.argtypes = [C.POINTER(vp), C.c_uint]
+    L.hipEventRecord.restype = C.c_int
+    L.hipEventRecord.argtypes = [vp, vp]
+    L.hipStreamWaitEvent.restype = C.c_int
+    L.hipStreamWaitEvent.argtypes = [vp, vp, C.c_uint]
+    L.hipEventDestroy.restype = C.c_int
+    L.hipEventDestroy.argtypes = [vp]
+    L.hipGetDevice.restype = C.c_int
+    L.hipGetDevice.argtypes = [C.POINTER(C.c_int)]
+    L.hipSetDevice.restype = C.c_int
+    L.hipSetDevice.argtypes = [C.c_int]
     _libs[variant] = L
     return L
 
@@ -252,17 +267,35 @@ def stream_arg(dev, stream=None):
     return C.c_void_p((torch.cuda.current_stream(dev) if stream is None else stream).cuda_stream)
 
 
-_shared = {}
+class _ThreadContexts:
+    """The shared contexts of one host thread, by key.  They are closed when the store goes away, which is when its thread ends."""
+
+    def __init__(self):
+        self.by_key = {}
+
+    def __del__(self):
+        for ctx in self.by_key.values():
+            try:
+                ctx.close()
+            except Exception:
+                pass
 
 
-def shared_context(device, W: int = 16, H: int = 16) -> "Context":
-    """The process-wide context of a GPU (a torch.device or an index) and render size, for the entry points that keep no state in
-    it (for most of them the size is irrelevant: 16 x 16).  A context belongs to the library that made it, so MDVT_LIB_VARIANT
-    is part of the key."""
+_shared = threading.local()
+
+
+def shared_context(device, W: int = 16, H: int = 16) -> "SharedContext":
+    """The calling thread's context of a GPU (a torch.device or an index) and render size, for the entry points that keep no state
+    in it (for most of them the size is irrelevant: 16 x 16).  A context belongs to the library that made it, so MDVT_LIB_VARIANT
+    is part of the key.  A ctx is not thread-safe (include/mdvt.h) and ctypes releases the GIL, so every host thread gets contexts
+    of its own; they are closed when the thread ends.  Within a thread the context orders its calls across streams (SharedContext)."""
     key = (device_index(device), int(W), int(H), os.environ.get("MDVT_LIB_VARIANT", ""))
-    ctx = _shared.get(key)
+    store = getattr(_shared, "store", None)
+    if store is None:
+        store = _shared.store = _ThreadContexts()
+    ctx = store.by_key.get(key)
     if ctx is None:
-        ctx = _shared[key] = Context(*key[:3])
+        ctx = store.by_key[key] = SharedContext(*key[:3])
     return ctx
 
 
@@ -337,3 +370,66 @@ class Context:
             self.close()
         except Exception:
             pass
+
+
+# the entry points that take a ctx and no stream (every other one takes `void* stream` as its last argument;
+# tests/test_shared_context_cpu.py holds the list to the headers)
+NO_STREAM = ("mdvt_set_config", "mdvt_set_near_clip", "mdvt_selftest", "mdvt_workspace_bytes", "mdvt_debug_read")
+
+HIP_EVENT_DISABLE_TIMING = 2
+
+
+class SharedContext(Context):
+    """The context shared_context hands out.  Its callers do not see it and still choose a stream, so include/mdvt.h's "ONE stream
+    per ctx at a time" is kept here: the context remembers the stream of its latest call and records an event behind that call; a
+    call that arrives on another stream first makes that stream wait for the event.  Calls on one stream add the event record
+    and nothing else.  Context itself (the renderer's, the benchmark's) records and waits on nothing."""
+
+    def __init__(self, device: int, width: int, height: int):
+        super().__init__(device, width, height)
+        self._event = None                    # the hipEvent_t, made at the first call
+        self._last_stream = None              # the stream (an integer) of the latest call ...
+        self._last_event = None               # ... and the event recorded behind it
+
+    def _hip(self, rc: int, what: str):
+        if rc != 0:
+            raise MdvtError(-2, f"{what} failed with HIP error {rc} while ordering a shared context's streams")
+
+    def _record_event(self, stream: int):
+        """Records the context's event on `stream` and returns it (one event serves: a wait takes the record that precedes it)."""
+        if self._event is None:
+            ev, cur = C.c_void_p(), C.c_int(-1)
+            self._hip(self._L.hipGetDevice(C.byref(cur)), "hipGetDevice")
+            self._hip(self._L.hipSetDevice(self.device), "hipSetDevice")
+            try:
+                self._hip(self._L.hipEventCreateWithFlags(C.byref(ev), HIP_EVENT_DISABLE_TIMING), "hipEventCreateWithFlags")
+            finally:
+                self._L.hipSetDevice(cur.value)
+            self._event = ev
+        self._hip(self._L.hipEventRecord(self._event, C.c_void_p(stream)), "hipEventRecord")
+        return self._event
+
+    def _wait_event(self, stream: int, event):
+        """Makes `stream` wait for `event`."""
+        self._hip(self._L.hipStreamWaitEvent(C.c_void_p(stream), event, 0), "hipStreamWaitEvent")
+
+    def call(self, name: str, *args):
+        if name in NO_STREAM:
+            return super().call(name, *args)
+        argtypes = getattr(getattr(self._L, name), "argtypes", None)
+        if argtypes is not None and argtypes[-1] is not C.c_void_p:
+            raise TypeError(f"{name} does not end in `void* stream`: list it in _lib.NO_STREAM, or say here where its stream is")
+        stream = args[-1]
+        stream = int(getattr(stream, "value", stream) or 0)
+        if self._last_event is not None and stream != self._last_stream:
+            self._wait_event(stream, self._last_event)
+        try:
+            super().call(name, *args)
+        finally:                              # a call that failed may have enqueued part of its work
+            self._last_stream, self._last_event = stream, self._record_event(stream)
+
+    def close(self):
+        if getattr(self, "_event", None) is not None:
+            self._L.hipEventDestroy(self._event)
+            self._event = self._last_event = None
+        super().close()
