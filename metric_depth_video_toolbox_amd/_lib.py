@@ -48,6 +48,9 @@ INFILL_ADAPTER_SYMBOLS = ("mdvt_adapter_prepare_eye", "mdvt_lhm_moments", "mdvt_
 # the entry points include/mdvt_infill_engines.h declares (the m2svid and stereo_dissoclusion_net steps around their models), likewise
 INFILL_ENGINE_SYMBOLS = ("mdvt_m2svid_prepare_eye", "mdvt_model_infill_finish")
 
+# the entry point include/mdvt_view.h declares (the free-camera viewer's vertex centres), likewise
+VIEW_SYMBOLS = ("mdvt_view_centers", "mdvt_render_view_batch")
+
 
 class MdvtError(RuntimeError):
     def __init__(self, code: int, text: str):
@@ -66,6 +69,15 @@ class MdvtConfig(C.Structure):
 class MdvtFrameParams(C.Structure):
     _fields_ = [("K", C.c_double * 9), ("Krender", C.c_double * 9), ("depth_scale", C.c_double),
                 ("convergence_angle", C.c_double), ("T", C.c_double * 16), ("has_T", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MdvtViewIO(C.Structure):
+    _fields_ = [("depth_rgb", C.c_void_p), ("depth_pitch", C.c_size_t), ("depth_stride", C.c_size_t),
+                ("color_rgb", C.c_void_p), ("color_pitch", C.c_size_t), ("color_stride", C.c_size_t),
+                ("rgb", C.c_void_p), ("rgb_pitch", C.c_size_t), ("rgb_stride", C.c_size_t),
+                ("mask", C.c_void_p), ("mask_pitch", C.c_size_t), ("mask_stride", C.c_size_t),
+                ("depth", C.c_void_p), ("zout_pitch", C.c_size_t), ("zout_stride", C.c_size_t),
+                ("hole_counts", C.c_void_p)]
 
 
 class MdvtIO(C.Structure):
@@ -205,6 +217,10 @@ def load():
                                           C.c_int, C.c_int, C.c_int, C.c_int, vp, st, st, vp, st, st, vp, st, st, vp, vp]
     L.mdvt_model_infill_finish.restype = C.c_int
     L.mdvt_model_infill_finish.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, st, st, vp, st, st, vp, st, st, vp, st, st, vp]
+    L.mdvt_view_centers.restype = C.c_int
+    L.mdvt_view_centers.argtypes = [vp, C.c_int, C.POINTER(MdvtFrameParams), vp, st, st, vp, vp]
+    L.mdvt_render_view_batch.restype = C.c_int
+    L.mdvt_render_view_batch.argtypes = [vp, C.c_int, C.POINTER(MdvtFrameParams), C.POINTER(MdvtViewIO), vp]
     # the HIP calls SharedContext orders its streams with, reached through the library's own link to the HIP runtime (dlsym
     # searches a library's dependencies), so the events belong to the runtime the kernels are launched by
     L.hipEventCreateWithFlags.restype = C.c_int

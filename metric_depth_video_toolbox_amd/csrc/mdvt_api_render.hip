@@ -1,9 +1,11 @@
 // mdvt_api_render.hip -- the render half of the C ABI of include/mdvt.h: the preparation of frame parameters, the render workspace
 // (ensure_workspace; its layout is mdvt_workspace.h), the multisampled and near-clipping renders, mdvt_render_stereo_batch as a list of
 // steps, and the entry points beside it that stage frame parameters (mdvt_edge_point_pixels, mdvt_edge_filter) or read the workspace
-// (mdvt_debug_read).  Host code only; compiled with -ffp-contract=off (the f64 composition of the eye matrices below is part of the
+// (mdvt_debug_read), and the viewer's two calls (include/mdvt_view.h): mdvt_render_view_batch, the batch render with one eye's work,
+// and mdvt_view_centers, which stages the parameters and runs the edge filter.  Host code only; compiled with -ffp-contract=off (the f64 composition of the eye matrices below is part of the
 // arithmetic decree).
 #include "mdvt_context.h"
+#include "mdvt_view.h"
 
 #include <math.h>
 
@@ -172,9 +174,11 @@ int stage_params(mdvt_ctx* c, const std::vector<FrameDev>& v, hipStream_t s, con
 RenderWorkspaceLayout layout_of(const mdvt_ctx* c) { return RenderWorkspaceLayout(c->W, c->H, c->ws_frames, c->huge_lists); }
 // (the EMPTY fill of fresh key buffers goes on the caller's stream: PyTorch's pool streams do not synchronise with the
 //  legacy null stream, so a fill issued there could land after the first splat)
-int ensure_workspace(mdvt_ctx* c, int frames, bool need_keys, bool need_ekeys, bool need_edges, bool need_mesh_ws, hipStream_t s)
+// (eyes: 1 for a view render, which needs eye 0's planes only; a context that has rendered nothing but views holds no plane of a
+//  second eye, and its first stereo render replaces the workspace as a larger launch set would)
+int ensure_workspace(mdvt_ctx* c, int frames, bool need_keys, bool need_ekeys, bool need_edges, bool need_mesh_ws, hipStream_t s, int eyes = 2)
 {
-    const bool grow = frames > c->ws_frames;
+    const bool grow = frames > c->ws_frames || eyes > c->ws_eyes;
     // (blocks that are replaced go back to the pool, where another context may pick them up at once: whatever was submitted
     //  with them -- to any stream -- has to be through first; hipFree used to wait for that implicitly)
     if (grow && c->ws_bytes) MDVT_HIP(c, hipDeviceSynchronize());
@@ -188,13 +192,13 @@ int ensure_workspace(mdvt_ctx* c, int frames, bool need_keys, bool need_ekeys, b
     if (grow || (need_ekeys && !c->ws_ekeys)) { drop(c->ekeys[0]); drop(c->ekeys[1]); drop(c->elist); c->ws_ekeys = false; }
     if (grow || (need_edges && !c->ws_edges)) { drop(c->tri_invalid); drop(c->unused); c->ws_edges = false; }
     if (grow || (need_mesh_ws && !c->ws_mesh)) { drop(c->cbuf[0]); drop(c->cbuf[1]); c->ws_mesh = false; }
-    if (grow) c->ws_frames = frames;
+    if (grow) { c->ws_frames = std::max(frames, c->ws_frames); c->ws_eyes = std::max(eyes, c->ws_eyes); }
     // (tuning build, the r04 diagnosis: MDVT_WS_LAYOUT=joint puts the second bank's huge list back into the queue block, as at 47b4117 --
     //  2.2 MB for a 100 x 31 frame; it takes effect when that block is made, so it is read before the layout is)
     if (need_mesh_ws && !c->ws_mesh) { const char* e = tuning_env(TUNE_WS_LAYOUT); c->huge_lists = (e && strcmp(e, "joint") == 0) ? 2 : 1; }
     const RenderWorkspaceLayout L = layout_of(c);
     if (need_keys && !c->ws_keys) {
-        for (int e = 0; e < 2; ++e) {
+        for (int e = 0; e < c->ws_eyes; ++e) {
             MDVT_HIP(c, ws_malloc(c, (void**)&c->keys[e], L.plane_bytes(), s));
             MDVT_HIP(c, hipMemsetAsync(c->keys[e], 0xFF, L.plane_bytes(), s));     // parity 0's empty value
         }
@@ -202,7 +206,7 @@ int ensure_workspace(mdvt_ctx* c, int frames, bool need_keys, bool need_ekeys, b
         c->ws_keys = true;
     }
     if (need_ekeys && !c->ws_ekeys) {
-        for (int e = 0; e < 2; ++e) {
+        for (int e = 0; e < c->ws_eyes; ++e) {
             MDVT_HIP(c, ws_malloc(c, (void**)&c->ekeys[e], L.plane_bytes(), s));
             MDVT_HIP(c, hipMemsetAsync(c->ekeys[e], 0xFF, L.plane_bytes(), s));
         }
@@ -211,7 +215,7 @@ int ensure_workspace(mdvt_ctx* c, int frames, bool need_keys, bool need_ekeys, b
         c->ws_ekeys = true;
     }
     if (need_mesh_ws && !c->ws_mesh) {
-        for (int e = 0; e < 2; ++e) MDVT_HIP(c, ws_malloc(c, (void**)&c->cbuf[e], L.plane_bytes(), s));   // tie side words: a word is initialised by the fragment that marks its pixel, so the plane needs no clearing
+        for (int e = 0; e < c->ws_eyes; ++e) MDVT_HIP(c, ws_malloc(c, (void**)&c->cbuf[e], L.plane_bytes(), s));   // tie side words: a word is initialised by the fragment that marks its pixel, so the plane needs no clearing
         drop(c->bigq);
         // (entry indices are 32-bit: chunk_of() keeps a launch set's slots * npx * 4 below 2^32)
         if (queue_slots_max(c->W, c->H) < 1) return fail(c, MDVT_ERR_UNSUPPORTED, "general mesh path: a %d x %d frame exceeds the 32-bit triangle queue", c->W, c->H);
@@ -642,8 +646,8 @@ static int submit_run(mdvt_ctx* c, RenderPlan plan, const Run& r, int chunk, con
         if (r.general && e == hipSuccess) c->key_parity ^= (plan.n >= 32 ? 0xFFFFFFFFu : ((1u << plan.n) - 1u)) << slot0;   // these slots' next use has the other parity
         if (e == hipErrorNotSupported) return fail(c, MDVT_ERR_UNSUPPORTED, "render mode %d is not built yet", plan.mode);
         if (e != hipSuccess) return fail(c, MDVT_ERR_HIP, "render launch failed: %s", hipGetErrorString(e));
-        if ((bf.want_bits || a.hole_counts) && !plan.fused_bits) MDVT_HIP(c, launch_pack_mask(a, plan.n, s_set));
-        if (a.hole_counts && !plan.fused_bits) MDVT_HIP(c, launch_reduce_counts(a, plan.n, s_set));
+        if ((bf.want_bits || a.hole_counts) && !plan.fused_bits && plan.eyes != 1) MDVT_HIP(c, launch_pack_mask(a, plan.n, s_set));
+        if (a.hole_counts && !plan.fused_bits && plan.eyes != 1) MDVT_HIP(c, launch_reduce_counts(a, plan.n, s_set));
     }
     if (banks) {
         MDVT_HIP(c, hipEventRecord(c->ev_join, c->side));
@@ -652,6 +656,9 @@ static int submit_run(mdvt_ctx* c, RenderPlan plan, const Run& r, int chunk, con
     }
     return MDVT_OK;
 }
+
+static int render_frames(mdvt_ctx* c, int n_frames, std::vector<FrameDev>& fd, int any_general_frame, const mdvt_io* io, const BatchFlags& bf,
+                         hipStream_t s, int eyes);
 
 int mdvt_render_stereo_batch(mdvt_ctx* c, int n_frames, const mdvt_frame_params* params, const mdvt_io* io, void* stream)
 {
@@ -669,6 +676,15 @@ int mdvt_render_stereo_batch(mdvt_ctx* c, int n_frames, const mdvt_frame_params*
         fd[(size_t)k].div_slot = -1;
     }
     if (c->cfg.samples == 4) return render_msaa(c, n_frames, fd, io, s);
+    return render_frames(c, n_frames, fd, any_general_frame, io, bf, s, 2);
+}
+
+// The single-sample render of a validated batch.  eyes = 1: a view render (mdvt_render_view_batch) -- `io` carries eye 0's buffers in
+// its left_* fields and NULL right_* ones, every frame is posed (general), io->hole_counts is one word per frame.
+static int render_frames(mdvt_ctx* c, int n_frames, std::vector<FrameDev>& fd, int any_general_frame, const mdvt_io* io, const BatchFlags& bf,
+                         hipStream_t s, int eyes)
+{
+    int rc;
     if (c->cfg.mode == MDVT_MODE_POINTS && (rc = assign_div_slots(c, fd, s)) != MDVT_OK) return rc;
 
     const FrameDev* dfp = nullptr;
@@ -677,6 +693,7 @@ int mdvt_render_stereo_batch(mdvt_ctx* c, int n_frames, const mdvt_frame_params*
 
     RenderPlan plan{};
     plan.mode = c->cfg.mode;
+    plan.eyes = eyes;
     plan.remove_edges = c->cfg.remove_edges;
     plan.edge_points = c->cfg.remove_edges && c->cfg.edge_points;
     plan.general = any_general_frame;
@@ -703,22 +720,25 @@ int mdvt_render_stereo_batch(mdvt_ctx* c, int n_frames, const mdvt_frame_params*
         if (ch > count_frames) count_frames = ch;
     }
     if (ws_frames && (rc = ensure_workspace(c, ws_frames, any_global, uses_global_ws && plan.edge_points, plan.remove_edges,
-                                            any_global && plan.mode == MDVT_MODE_MESH, s)) != MDVT_OK) return rc;
+                                            any_global && plan.mode == MDVT_MODE_MESH, s, eyes)) != MDVT_OK) return rc;
     RenderArgs base{};
     bind_io(base, c, io, dfp);
     base.zout[0] = io->left_depth; base.zout[1] = io->right_depth; base.zout_pitch = io->zout_pitch; base.zout_stride = io->zout_stride;
     base.maskbits[0] = io->left_maskbits; base.maskbits[1] = io->right_maskbits;
     base.maskbits_pitch = io->maskbits_pitch; base.maskbits_stride = io->maskbits_stride;
     base.seed[0] = io->left_seed; base.seed[1] = io->right_seed; base.seed_pitch = io->seed_pitch; base.seed_stride = io->seed_stride;
-    if (io->hole_counts) {
+    if (io->hole_counts && eyes == 1) MDVT_HIP(c, hipMemsetAsync(io->hole_counts, 0, (size_t)n_frames * sizeof(uint32_t), s));      // (the view resolve adds to them)
+    if (io->hole_counts && eyes == 2) {
         if ((rc = ensure_count_buffers(c, count_frames, s)) != MDVT_OK) return rc;
         base.row_counts = c->scratch[SCR_ROW_COUNTS].as<uint32_t>(); base.wave_counts = c->scratch[SCR_WAVE_COUNTS].as<uint32_t>();
     }
     base.divcheck = c->divcheck; base.edge_paint = c->cfg.edge_points != 2; base.cull = c->cfg.cull;
     if (c->cfg.mode == MDVT_MODE_MESH) { if ((rc = ensure_rowcell(c, s)) != MDVT_OK) return rc; base.rowcell = c->rowcell; }
     const RenderWorkspaceLayout L = layout_of(c);
-    if (uses_global_ws && c->keys_dirty && (rc = reset_dirty_keys(c, L, s)) != MDVT_OK) return rc;
-    if (uses_global_ws) c->keys_dirty = true;
+    // (the z keys' parity is kept per slot for both eyes: after view renders eye 1's planes lag behind, and a stereo render starts from
+    //  planes reset to parity 0, as after an interrupted submission)
+    if (uses_global_ws && (c->keys_dirty || (eyes == 2 && c->eye1_stale)) && (rc = reset_dirty_keys(c, L, s)) != MDVT_OK) return rc;
+    if (uses_global_ws) { c->keys_dirty = true; c->eye1_stale = eyes == 1 && c->keys[1] != nullptr; }
     for (const Run& r : runs)
         if ((rc = submit_run(c, plan, r, chunk_of(c, plan, r, tuned_chunk), base, L, fd, bf, s)) != MDVT_OK) return rc;
     if (uses_global_ws) c->keys_dirty = false;
@@ -830,6 +850,108 @@ int mdvt_edge_filter(mdvt_ctx* c, const uint8_t* d_depth_rgb, size_t depth_pitch
                                    d_tri_invalid, 0, d_unused, 0, s));
     MDVT_HIP(c, hipEventRecord(slot->done, s));
     return MDVT_OK;
+}
+
+// The per-frame centre of the vertices (mdvt_view.hip).  Launch sets: as many frames as the ctx's workspace budget affords.
+int mdvt_view_centers(mdvt_ctx* c, int n_frames, const mdvt_frame_params* params, const uint8_t* d_depth_rgb, size_t depth_pitch,
+                      size_t depth_stride, double* d_centers, void* stream)
+{
+    if (!c) return MDVT_ERR_INVALID_ARG;
+    if (!c->cfg_set) return fail(c, MDVT_ERR_INVALID_ARG, "mdvt_set_config has not been called");
+    if (n_frames < 1 || !params) return fail(c, MDVT_ERR_INVALID_ARG, "n_frames/params invalid");
+    if (!d_depth_rgb || !d_centers) return fail(c, MDVT_ERR_INVALID_ARG, "NULL buffer");
+    if (!aligned(d_centers, 8)) return fail(c, MDVT_ERR_INVALID_ARG, "d_centers must be 8-byte aligned");
+    const int W = c->W, H = c->H;
+    if (depth_pitch < (size_t)3 * W) return fail(c, MDVT_ERR_INVALID_ARG, "depth_pitch smaller than one row");
+    if (n_frames > 1 && depth_stride < depth_pitch * (size_t)H) return fail(c, MDVT_ERR_INVALID_ARG, "depth_stride smaller than one frame");
+    const bool park = c->cfg.mode == MDVT_MODE_POINTS && c->cfg.remove_edges;
+    if (park && (W < 2 || H < 2)) return fail(c, MDVT_ERR_INVALID_ARG, "the edge filter needs at least a 2x2 frame");
+    if ((uint64_t)W * (uint64_t)H > ((uint64_t)1 << 28)) return fail(c, MDVT_ERR_UNSUPPORTED, "frame too large for the centres (%d x %d)", W, H);
+    std::vector<FrameDev> fd((size_t)n_frames);
+    for (int k = 0; k < n_frames; ++k) {
+        if (int rc = fill_frame_dev(c, params[k], fd[(size_t)k])) return rc;
+        fd[(size_t)k].div_slot = -1;
+    }
+    DeviceGuard g(c->device);
+    hipStream_t const s = (hipStream_t)stream;
+    const uint32_t npx = (uint32_t)W * (uint32_t)H, nchunks = (npx + 8191u) / 8192u;
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t sums_bytes = up16((size_t)nchunks * mdvt::kViewSumBytes), flag_bytes = park ? up16((size_t)npx) : 0;
+    const int fchunk = slots_afforded(c, sums_bytes + flag_bytes, n_frames < 4096 ? n_frames : 4096);
+    MDVT_HIP(c, scratch_reserve(c, c->scratch[SCR_VIEW], (size_t)fchunk * (sums_bytes + flag_bytes), s));
+    const FrameDev* dfp = nullptr;
+    ParamSlot* slot = nullptr;
+    if (int rc = stage_params(c, fd, s, &dfp, &slot)) return rc;
+    mdvt::ViewCentersArgs a{};
+    a.depth = d_depth_rgb; a.depth_pitch = depth_pitch; a.depth_stride = depth_stride;
+    a.fp = dfp; a.W = W; a.H = H; a.of_by_one = c->cfg.mode == MDVT_MODE_MESH ? 1 : 0;
+    a.npx = npx; a.nchunks = nchunks;
+    a.sums = c->scratch[SCR_VIEW].as<double>();
+    uint8_t* const flags = park ? c->scratch[SCR_VIEW].p + (size_t)fchunk * sums_bytes : nullptr;
+    a.unused = flags; a.unused_stride = flag_bytes;
+    a.centers = d_centers;
+    for (int f0 = 0; f0 < n_frames; f0 += fchunk) {
+        a.frame0 = f0;
+        a.n_frames = n_frames - f0 < fchunk ? n_frames - f0 : fchunk;
+        if (park) {
+            MDVT_HIP(c, launch_zero_bytes(flags, (size_t)a.n_frames * flag_bytes, s));
+            MDVT_HIP(c, launch_edge_filter(d_depth_rgb, depth_pitch, depth_stride, dfp, f0, a.n_frames, W, H, 0, nullptr, 0, flags, flag_bytes, s));
+        }
+        MDVT_HIP(c, mdvt::launch_view_centers(a, s));
+    }
+    MDVT_HIP(c, hipEventRecord(slot->done, s));
+    return MDVT_OK;
+}
+
+// One image per frame from the composed matrix in params[k].T (include/mdvt_view.h): the left eye of the stereo render with ipd_m = 0
+// and no convergence, by the one-eye instantiations of the general kernels.
+int mdvt_render_view_batch(mdvt_ctx* c, int n_frames, const mdvt_frame_params* params, const mdvt_view_io* vio, void* stream)
+{
+    if (!c) return MDVT_ERR_INVALID_ARG;
+    if (!c->cfg_set) return fail(c, MDVT_ERR_INVALID_ARG, "mdvt_set_config has not been called");
+    if (n_frames <= 0 || !params || !vio) return fail(c, MDVT_ERR_INVALID_ARG, "n_frames/params/io invalid");
+    if (!vio->depth_rgb || !vio->color_rgb || !vio->rgb) return fail(c, MDVT_ERR_INVALID_ARG, "depth_rgb, color_rgb and rgb are required");
+    const char* what = nullptr;
+    if (c->cfg.edge_points) what = "edge points (mdvt_config.edge_points != 0)";
+    else if (c->cfg.samples == 4) what = "multisampling (samples = 4)";
+    else if (c->near_clip) what = "near-plane clipping (mdvt_set_near_clip)";
+    if (what) return fail(c, MDVT_ERR_UNSUPPORTED, "the view render does not cover %s", what);
+    const int W = c->W, H = c->H;
+    if (W < 2 || H < 2) return fail(c, MDVT_ERR_INVALID_ARG, "rendering needs at least a 2x2 frame");
+    if (vio->depth_pitch < (size_t)3 * W || vio->color_pitch < (size_t)3 * W || vio->rgb_pitch < (size_t)3 * W ||
+        (vio->mask && vio->mask_pitch < (size_t)W) || (vio->depth && vio->zout_pitch < (size_t)4 * W))
+        return fail(c, MDVT_ERR_INVALID_ARG, "a pitch is smaller than one row");
+    if (n_frames > 1 && (vio->depth_stride < vio->depth_pitch * (size_t)H || vio->color_stride < vio->color_pitch * (size_t)H ||
+                         vio->rgb_stride < vio->rgb_pitch * (size_t)H || (vio->mask && vio->mask_stride < vio->mask_pitch * (size_t)H) ||
+                         (vio->depth && vio->zout_stride < vio->zout_pitch * (size_t)H)))
+        return fail(c, MDVT_ERR_INVALID_ARG, "a stride is smaller than one frame");
+    if ((vio->depth && !aligned(vio->depth, 4)) || (vio->depth && (vio->zout_pitch % 4 || vio->zout_stride % 4)) || (vio->hole_counts && !aligned(vio->hole_counts, 4)))
+        return fail(c, MDVT_ERR_INVALID_ARG, "the depth plane and the hole counts must be dword aligned");
+    for (int k = 0; k < n_frames; ++k)
+        if (!params[k].has_T) return fail(c, MDVT_ERR_INVALID_ARG, "frame %d: a view render takes the composed matrix V * T in T (has_T = 1)", k);
+    std::vector<FrameDev> fd((size_t)n_frames);
+    const double ipd = c->cfg.ipd_m;
+    c->cfg.ipd_m = 0.0;                       // (ignored here, as convergence_angle is: both eye matrices are T)
+    int rc = MDVT_OK;
+    for (int k = 0; k < n_frames && rc == MDVT_OK; ++k) {
+        mdvt_frame_params p = params[k];
+        p.convergence_angle = 0.0;
+        rc = fill_frame_dev(c, p, fd[(size_t)k]);
+        fd[(size_t)k].div_slot = -1;
+    }
+    c->cfg.ipd_m = ipd;
+    if (rc != MDVT_OK) return rc;
+    mdvt_io io{};
+    io.depth_rgb = vio->depth_rgb; io.depth_pitch = vio->depth_pitch; io.depth_stride = vio->depth_stride;
+    io.color_rgb = vio->color_rgb; io.color_pitch = vio->color_pitch; io.color_stride = vio->color_stride;
+    io.left_rgb = vio->rgb; io.rgb_pitch = vio->rgb_pitch; io.rgb_stride = vio->rgb_stride;
+    io.left_mask = vio->mask; io.mask_pitch = vio->mask ? vio->mask_pitch : 0; io.mask_stride = vio->mask ? vio->mask_stride : 0;
+    io.left_depth = vio->depth; io.zout_pitch = vio->zout_pitch; io.zout_stride = vio->zout_stride;
+    io.hole_counts = vio->hole_counts;
+    BatchFlags bf{};
+    bf.zout = vio->depth != nullptr;
+    DeviceGuard g(c->device);
+    return render_frames(c, n_frames, fd, 1, &io, bf, (hipStream_t)stream, 1);
 }
 
 }  // extern "C"

@@ -54,6 +54,7 @@ enum ScratchId {
     SCR_FIT,                          // mdvt_scale_shift_fit: the running totals (32 B), then per chunk of a launch set its five sums
     SCR_ADAPTER,                      // mdvt_adapter_composite_eye: the listed-pixel workspace of one eye-sized image, its marks image, grown plane and row-blurred plane
     SCR_FFV1_STREAM,                  // mdvt_decode_video_stream: per slice of the call its offset, payload bytes and cell claim, per frame its kind
+    SCR_VIEW,                         // mdvt_view_centers: per frame of a launch set its chunk sums (24 B per 8192 vertices); parking: also the edge filter's vertex flags (1 B/px)
     SCR_COUNT
 };
 
@@ -74,6 +75,7 @@ struct mdvt_ctx {
     hipStream_t last_stream = nullptr;
     // workspace for the general path / edge filter, sized for ws_frames frames (ensure_workspace, mdvt_api_render.hip)
     int ws_frames = 0;
+    int ws_eyes = 0;                  // eyes the per-eye planes (z keys, edge keys, tie side words) are allocated for: 1 after view renders only
     bool ws_keys = false, ws_ekeys = false, ws_edges = false;
     unsigned long long* keys[2] = {nullptr, nullptr};
     unsigned long long* ekeys[2] = {nullptr, nullptr};
@@ -81,6 +83,7 @@ struct mdvt_ctx {
     unsigned long long* cbuf[2] = {nullptr, nullptr};
     bool ws_mesh = false;
     bool keys_dirty = false;          // a general-path submission was interrupted between splat and resolve
+    bool eye1_stale = false;          // view renders have flipped the slots' parity without touching eye 1's z keys: the next stereo render resets the planes first
     uint32_t key_parity = 0;          // bit s: parity of the next use of z-key slot s (mdvt_device.h, parity scheme)
     uint8_t* tri_invalid = nullptr;
     uint8_t* unused = nullptr;

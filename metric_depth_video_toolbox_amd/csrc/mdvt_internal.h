@@ -153,6 +153,7 @@ struct RenderPlan {
     int n;               // frames in this launch
     int allow_conv;      // MDVT_MESH_CONV=1 when the context was created (mdvt_create): k_mesh_conv may take convergence-only frames
     int edge_rows_max;   // pure-shift launches with edge points: the most scanlines any frame leaves to k_edge_rows_exact (0: none)
+    int eyes;            // 1: a view render (mdvt_render_view_batch) -- eye 0 only, general path, holes keep the key colour, RenderArgs.hole_counts is [n_frames]; else both eyes
     hipEvent_t after_vertices;   // general paths: recorded on the launch's stream behind the first pass (the mesh's cell walk, the points' splat; nullptr: none)
 };
 // mdvt_msaa.hip: the opt-in 4x multisampled render (mdvt_config.samples = 4), one launch set of frames [frame0, frame0 + n).
@@ -291,6 +292,19 @@ struct ConvergenceArgs {
     float* means; uint32_t* counts;                                // the caller's, at the set's first frame; counts may be null
 };
 hipError_t launch_convergence(const ConvergenceArgs& a, hipStream_t s);
+// mdvt_view.hip: the per-frame centre of the vertices (mdvt_view_centers, include/mdvt_view.h), one launch set
+constexpr size_t kViewSumBytes = 3 * sizeof(double);               // a chunk's three coordinate sums
+struct ViewCentersArgs {
+    const uint8_t* depth; size_t depth_pitch, depth_stride;        // the batch's first frame
+    const FrameDev* fp;                                            // device array, one per frame of the batch
+    int frame0, n_frames;                                          // the set's first frame within the batch, its frames
+    int W, H, of_by_one;
+    uint32_t npx, nchunks;                                         // vertices and chunks of 8192 vertices of a frame
+    const uint8_t* unused; size_t unused_stride;                   // workspace [n_frames][npx]: the edge filter's flags of the set, or null (nothing is parked)
+    double* sums;                                                  // workspace [n_frames][nchunks][3]
+    double* centers;                                               // the caller's, at the batch's first frame
+};
+hipError_t launch_view_centers(const ViewCentersArgs& a, hipStream_t s);
 // mdvt_metric_align.hip: the scale-and-shift fit and the metric depth codes (include/mdvt_metric_align.h)
 constexpr uint32_t kFitSetChunks = 1024;                           // chunks of 8192 elements per launch set of the fit
 struct FitPlane {

@@ -560,7 +560,8 @@ __global__ void __launch_bounds__(64) k_edge_keys_reset(RenderArgs a)
     if (threadIdx.x == 0) a.elist_count[seg] = 0u;           // (every lane of the one wave has read n)
 }
 
-template <int FLAGS>
+// (EYES: 2, or 1 for a view render, which splats eye 0 only)
+template <int FLAGS, int EYES = 2>
 __global__ void __launch_bounds__(256) k_points_splat_general(RenderArgs a)
 {
     constexpr bool UNUSED = FLAGS & 2, EDGE = FLAGS & 4, EDGE_ONLY = FLAGS & 8;
@@ -584,7 +585,7 @@ __global__ void __launch_bounds__(256) k_points_splat_general(RenderArgs a)
     if (!un) {
         if (EDGE_ONLY) return;
 #pragma unroll
-        for (int eye = 0; eye < 2; ++eye) {
+        for (int eye = 0; eye < EYES; ++eye) {
             const Vert v = vertex_for_eye(fp, eye, gx, gy, z, xc, yc);
             if (!v.ok) continue;
             const int px = point_col(v.u), py = point_row(v.v);
@@ -764,14 +765,16 @@ hipError_t launch_edge_keys_reset(const RenderArgs& a, int n, hipStream_t s)
 // Resolve of both general paths: PX pixels per thread, coalesced key reads; the z keys need no clearing pass (parity
 // scheme, mdvt_device.h: only the uncovered words are rewritten; the edge keys: k_edge_keys_reset), colour from the key word (mesh: colour
 // keys) or gathered from the source frame by the winning source index (points).
-template <int PX, int FLAGS, bool MESH>
+// (EYES = 1, a view render: eye 0 only; a hole keeps the key colour (3dv:254 writes the render as it comes), the mask is optional and
+//  a.hole_counts, where given, is one zeroed word per frame of the batch that every wave adds its holes to)
+template <int PX, int FLAGS, bool MESH, int EYES = 2>
 __global__ void __launch_bounds__(256) k_resolve_general(RenderArgs a)
 {
     constexpr bool ZOUT = FLAGS & 1, EDGE = FLAGS & 4, SEED = FLAGS & 8;
     const int W = a.W;
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     const int y = blockIdx.y;
-    const int fr = blockIdx.z >> 1, eye = blockIdx.z & 1;
+    const int fr = EYES == 2 ? blockIdx.z >> 1 : blockIdx.z, eye = EYES == 2 ? blockIdx.z & 1 : 0;
     if (g >= W / PX) return;
     if (MDVT_DEBUG_SKIP(a) & 512) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");      // (r05 diagnosis, tuning build)
     const int f = a.frame0 + fr;
@@ -809,7 +812,7 @@ __global__ void __launch_bounds__(256) k_resolve_general(RenderArgs a)
             }
         }
         const bool hole = !covered || rgb == a.key_rgb;
-        uint32_t out = hole ? 0u : rgb;
+        uint32_t out = hole ? (EYES == 2 ? 0u : a.key_rgb) : rgb;
         uint32_t esrc = ~0u;
         if (EDGE && hole) {          // an edge point only matters where the render left a hole (sr:776): ~3 % of the pixels
             const u64 ek = erow[q];
@@ -825,7 +828,13 @@ __global__ void __launch_bounds__(256) k_resolve_general(RenderArgs a)
     }
     if (SEED && a.seed[eye]) RowIO<PX>::store_rgb(a.seed[eye] + (size_t)f * a.seed_stride + (size_t)y * a.seed_pitch, g, spx);
     RowIO<PX>::store_rgb(a.rgb[eye] + (size_t)f * a.rgb_stride + (size_t)y * a.rgb_pitch, g, opx);
-    RowIO<PX>::store_mask(a.mask[eye] + (size_t)f * a.mask_stride + (size_t)y * a.mask_pitch, g, om);
+    if (EYES == 2 || a.mask[eye]) RowIO<PX>::store_mask(a.mask[eye] + (size_t)f * a.mask_stride + (size_t)y * a.mask_pitch, g, om);
+    if (EYES == 1 && a.hole_counts) {
+        uint32_t cnt = 0;
+#pragma unroll
+        for (int q = 0; q < PX; ++q) cnt += (uint32_t)__popcll(__ballot(om[q] != 0u));
+        if ((threadIdx.x & 63u) == 0u && cnt) atomicAdd(&a.hole_counts[f], cnt);      // (lane 0 holds the wave's smallest g: active if any lane is)
+    }
     if (ZOUT && a.zout[eye])
         RowIO<PX>::store_z((float*)((uint8_t*)a.zout[eye] + (size_t)f * a.zout_stride + (size_t)y * a.zout_pitch), g, oz);
 }
@@ -837,6 +846,13 @@ static hipError_t launch_resolve_general(const RenderPlan& plan, const RenderArg
     const bool edge = plan.remove_edges && plan.edge_points;
     const int flags = (zout ? 1 : 0) | (edge ? 4 : 0) | (a.seed[0] ? 8 : 0);
     const int px = plan.vec4 ? 4 : 1;
+    if (plan.eyes == 1) {            // a view render: one image per frame, no edge points, no seed
+        const dim3 grid1((a.W / px + 255) / 256, a.H, plan.n);
+        if (edge || a.seed[0]) return hipErrorInvalidValue;
+        if (zout) { if (px == 4) hipLaunchKernelGGL((k_resolve_general<4, 1, MESH, 1>), grid1, dim3(256), 0, s, a); else hipLaunchKernelGGL((k_resolve_general<1, 1, MESH, 1>), grid1, dim3(256), 0, s, a); }
+        else { if (px == 4) hipLaunchKernelGGL((k_resolve_general<4, 0, MESH, 1>), grid1, dim3(256), 0, s, a); else hipLaunchKernelGGL((k_resolve_general<1, 0, MESH, 1>), grid1, dim3(256), 0, s, a); }
+        return hipGetLastError();
+    }
     const dim3 grid((a.W / px + 255) / 256, a.H, plan.n * 2), block(256);
 #define MDVT_CASE(F)                                                                                  \
     case F:                                                                                           \
@@ -1401,6 +1417,11 @@ static hipError_t launch_points_general(const RenderPlan& plan, const RenderArgs
     const dim3 block(256);
     const dim3 grid_s((a.W + 255) / 256, a.H, plan.n);
     const int sflags = (plan.remove_edges ? 2 : 0) | (edge ? 4 : 0);
+    if (plan.eyes == 1) {
+        if (edge) return hipErrorInvalidValue;
+        if (plan.remove_edges) hipLaunchKernelGGL((k_points_splat_general<2, 1>), grid_s, block, 0, s, a);
+        else hipLaunchKernelGGL((k_points_splat_general<0, 1>), grid_s, block, 0, s, a);
+    } else
     switch (sflags) {
         case 0: hipLaunchKernelGGL((k_points_splat_general<0>), grid_s, block, 0, s, a); break;
         case 2: hipLaunchKernelGGL((k_points_splat_general<2>), grid_s, block, 0, s, a); break;

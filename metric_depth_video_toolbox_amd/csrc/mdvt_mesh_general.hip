@@ -150,15 +150,20 @@ template <typename T> __device__ __forceinline__ uint4 readlane_u4(const uint4& 
 constexpr int kCellTPB = 64;          // threads per workgroup of the cell walks = vertex columns it stages
 constexpr int kCellsWG = kCellTPB - 1;   // cells per workgroup: between its 64 columns
 // Vertex row `row` of columns j0 .. j0 + 63, both eyes, into ring slot `slot`: sv[eye][slot][column].
-template <bool CONV>
-__device__ __forceinline__ void stage_vertex_row(const RenderArgs& a, int fr, int row, int j0, uint4 (&sv)[2][2][kCellTPB], int slot)
+// (EYES = 1, a view render: eye 0's records only, by the same device functions)
+template <bool CONV, int EYES = 2>
+__device__ __forceinline__ void stage_vertex_row(const RenderArgs& a, int fr, int row, int j0, uint4 (&sv)[EYES][2][kCellTPB], int slot)
 {
     const int t = threadIdx.x, f = a.frame0 + fr;
     const FrameDev& fp = a.fp[f];
     const int jc = min(j0 + t, a.W - 1);                                   // (clamped: columns past the row end are never used)
-    uint4 r0, r1;
-    vertex_records<CONV>(a, fp, f, row, jc, r0, r1);
-    sv[0][slot][t] = r0; sv[1][slot][t] = r1;
+    if constexpr (EYES == 2) {
+        uint4 r0, r1;
+        vertex_records<CONV>(a, fp, f, row, jc, r0, r1);
+        sv[0][slot][t] = r0; sv[1][slot][t] = r1;
+    } else {
+        sv[0][slot][t] = vertex_record_eye(a, fp, f, row, jc, 0);
+    }
 }
 // A workgroup of the cell walks takes kRowsWG rows of cells of its 63 columns, top to bottom, its vertex rows in a ring of two: the
 // row between two rows of cells is worked out once, not by the workgroup above it AND the one below (r05, second step: with the
@@ -283,8 +288,8 @@ __device__ __forceinline__ bool tie_tiles_hit(const FragOut& f, int bx0, int by0
 // One thread per cell, both triangles, both eyes.  MODE as mesh_global_fragment's; the second pass runs for the frames with a marked
 // pixel only, and only the triangles whose pixel box touches a marked tile get as far as their set-up.
 // (the caller has staged the row's two vertex rows: sv[eye][top] above, sv[eye][top ^ 1] below, and synchronised)
-template <int FLAGS, int MODE>
-__device__ __forceinline__ void mesh_raster_small_block(const RenderArgs& a, int fr, int bx, int i, uint4 (&sv)[2][2][kCellTPB], int top, Pending (&pds)[2])
+template <int FLAGS, int MODE, int EYES = 2>
+__device__ __forceinline__ void mesh_raster_small_block(const RenderArgs& a, int fr, int bx, int i, uint4 (&sv)[EYES][2][kCellTPB], int top, Pending (&pds)[EYES])
 {
     constexpr bool EDGES = FLAGS & 2;
     const int W = a.W, H = a.H;
@@ -298,10 +303,10 @@ __device__ __forceinline__ void mesh_raster_small_block(const RenderArgs& a, int
         const uint8_t* tinv = a.tri_invalid + (size_t)fr * a.ws_stride_tri + (size_t)i * (W - 1) + j;
         inv0 = tinv[0]; inv1 = tinv[ncell];
     }
-    bool tq[2][2] = {{false, false}, {false, false}};          // [eye][triangle of the cell]: goes to the queue
+    bool tq[EYES][2] = {};                                      // [eye][triangle of the cell]: goes to the queue
     // (unrolled: each eye has its own pending word, so the left eye's last post is in flight while the right eye is rasterised)
 #pragma unroll
-    for (int eye = 0; eye < 2; ++eye) {
+    for (int eye = 0; eye < EYES; ++eye) {
         Pending& pd = pds[eye];
         const FragOut fo = frag_out(a, fr, eye);
         uint4 A = make_uint4(0, 0, 0, 0), B = A, Cv = A, D = A;
@@ -358,7 +363,7 @@ __device__ __forceinline__ void mesh_raster_small_block(const RenderArgs& a, int
         u64 m[4];
         uint32_t total = 0;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) { m[k] = __ballot(tq[k >> 1][k & 1]); total += (uint32_t)__popcll(m[k]); }
+        for (int k = 0; k < 2 * EYES; ++k) { m[k] = __ballot(tq[k >> 1][k & 1]); total += (uint32_t)__popcll(m[k]); }
         if (total) {                                                      // (wave uniform)
             const size_t seg = (size_t)fr * H + i;                        // this row's segment: 4 (W - 1) entries at most
             uint32_t base = 0;
@@ -366,7 +371,7 @@ __device__ __forceinline__ void mesh_raster_small_block(const RenderArgs& a, int
             base = __shfl(base, 0);
             uint2* q = (uint2*)a.bigq + seg * (size_t)(4 * W);
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
+            for (int k = 0; k < 2 * EYES; ++k) {
                 if (tq[k >> 1][k & 1])
                     q[base + (uint32_t)__popcll(m[k] & ((1ull << lane) - 1ull))] = make_uint2(draw_id_global(k & 1, i, j), (uint32_t)fr * 2u + (uint32_t)(k >> 1));
                 base += (uint32_t)__popcll(m[k]);
@@ -376,29 +381,31 @@ __device__ __forceinline__ void mesh_raster_small_block(const RenderArgs& a, int
 }
 
 // First pass: a workgroup per block of 63 x kRowsWG cells (grid: cell_blocks x 1 x frames).
-template <int FLAGS>
+template <int FLAGS, int EYES = 2>
 __global__ void __launch_bounds__(kCellTPB, cell_waves(FLAGS, false)) k_mesh_raster_small(RenderArgs a)
 {
-    __shared__ uint4 sv[2][2][kCellTPB];
-    Pending pds[2] = {pending_none(), pending_none()};
+    __shared__ uint4 sv[EYES][2][kCellTPB];
+    Pending pds[EYES];
+#pragma unroll
+    for (int e = 0; e < EYES; ++e) pds[e] = pending_none();
     constexpr int kRowsWG = rows_wg(FLAGS, false);
     if (blockIdx.x >= cell_blocks(a.W, a.H, kRowsWG)) return;
     int bx, i0;
     cell_block_of(a.W, blockIdx.x, kRowsWG, bx, i0);
     const int fr = (int)blockIdx.z;
     if (MDVT_DEBUG_SKIP(a) & 512) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");      // (r05 diagnosis, tuning build)
-    stage_vertex_row<false>(a, fr, i0, bx * kCellsWG, sv, 0);
+    stage_vertex_row<false, EYES>(a, fr, i0, bx * kCellsWG, sv, 0);
 #pragma unroll 1
     for (int r = 0; r < kRowsWG && i0 + r < a.H - 1; ++r) {
         int bxr = bx, frr = fr;                            // (opaque per row: see k_mesh_raster_conv)
         asm volatile("" : "+s"(bxr), "+s"(frr));
-        stage_vertex_row<false>(a, frr, i0 + r + 1, bxr * kCellsWG, sv, (r + 1) & 1);
+        stage_vertex_row<false, EYES>(a, frr, i0 + r + 1, bxr * kCellsWG, sv, (r + 1) & 1);
         __syncthreads();
-        mesh_raster_small_block<FLAGS, 0>(a, frr, bxr, i0 + r, sv, r & 1, pds);
+        mesh_raster_small_block<FLAGS, 0, EYES>(a, frr, bxr, i0 + r, sv, r & 1, pds);
         __syncthreads();                                   // (the row above is replaced next: its last readers are through)
     }
     pending_settle(a, pds[0]);
-    pending_settle(a, pds[1]);
+    if constexpr (EYES == 2) pending_settle(a, pds[1]);
     if (MDVT_DEBUG_SKIP(a) & 512) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
 }
 
@@ -777,30 +784,33 @@ __global__ void __launch_bounds__(256) k_mesh_raster_huge(RenderArgs a) { mesh_h
 // the launch is over after `nframes` loads per workgroup) every triangle near a marked tile posts draw id | colour into the side
 // words of the marked pixels at the word's depth -- the cells again (k_mesh_raster_small's code), then the first pass's own lists
 // of queued and huge triangles.  No order between the three: all they do is atomic minima.
-template <int FLAGS, bool CONV>
+template <int FLAGS, bool CONV, int EYES = 2>
 __global__ void __launch_bounds__(kCellTPB) k_mesh_tie_pass(RenderArgs a, int nframes, int nseg)
 {
     static_assert(kCellTPB == kConvTPB, "one workgroup size for both cell walks");
-    __shared__ uint4 sv[2][2][kCellTPB];
+    static_assert(EYES == 2 || !CONV, "a view render is posed: never convergence-only");
+    __shared__ uint4 sv[EYES][2][kCellTPB];
     __shared__ uint32_t glist[2 * kConvTPB];
     __shared__ uint32_t gcount;
     extern __shared__ uint32_t cpre[];
     uint32_t any = 0;
     for (int fr = 0; fr < nframes; ++fr) any |= a.tie_flag[fr];
     if (!any) return;                                                          // (uniform)
-    Pending pds[2] = {pending_none(), pending_none()};                         // (unused in this mode)
+    Pending pds[EYES];                                                         // (unused in this mode)
+#pragma unroll
+    for (int e = 0; e < EYES; ++e) pds[e] = pending_none();
     const uint32_t nbx = (uint32_t)((a.W - 1 + kCellsWG - 1) / kCellsWG), nblk = nbx * (uint32_t)(a.H - 1);      // (here: a row of cells each)
     for (int fr = 0; fr < nframes; ++fr) {
         if (a.tie_flag[fr] == 0u) continue;                                    // (workgroup uniform)
         for (uint32_t v = blockIdx.x; v < nblk; v += gridDim.x) {
             const int bx = (int)(v % nbx), i = (int)(v / nbx);
-            stage_vertex_row<CONV>(a, fr, i, bx * kCellsWG, sv, 0);
-            stage_vertex_row<CONV>(a, fr, i + 1, bx * kCellsWG, sv, 1);
+            stage_vertex_row<CONV, EYES>(a, fr, i, bx * kCellsWG, sv, 0);
+            stage_vertex_row<CONV, EYES>(a, fr, i + 1, bx * kCellsWG, sv, 1);
             __syncthreads();
             // (the cells classified as the first pass classified them: k_mesh_raster_conv draws spans itself that k_mesh_raster_small
             //  would have queued)
-            if (CONV) mesh_raster_conv_block<FLAGS, 1>(a, fr, bx, i, sv, 0, glist, gcount, pds[0]);
-            else mesh_raster_small_block<FLAGS, 1>(a, fr, bx, i, sv, 0, pds);
+            if constexpr (CONV) mesh_raster_conv_block<FLAGS, 1>(a, fr, bx, i, sv, 0, glist, gcount, pds[0]);
+            else mesh_raster_small_block<FLAGS, 1, EYES>(a, fr, bx, i, sv, 0, pds);
             __syncthreads();
         }
     }
@@ -844,6 +854,9 @@ hipError_t launch_mesh_raster_general(const RenderPlan& plan, const RenderArgs& 
         const dim3 grid_v(cell_blocks(a.W, a.H, rows_wg(plan.remove_edges ? 2 : 0, true)), 1, plan.n);
         if (plan.remove_edges) hipLaunchKernelGGL((k_mesh_raster_conv<2>), grid_v, dim3(kConvTPB), 0, s, a);
         else hipLaunchKernelGGL((k_mesh_raster_conv<0>), grid_v, dim3(kConvTPB), 0, s, a);
+    } else if (plan.eyes == 1) {      // a view render: the cell walk of eye 0 only (its queue entries and huge row blocks carry eye 0)
+        if (plan.remove_edges) hipLaunchKernelGGL((k_mesh_raster_small<2, 1>), grid_c, dim3(kCellTPB), 0, s, a);
+        else hipLaunchKernelGGL((k_mesh_raster_small<0, 1>), grid_c, dim3(kCellTPB), 0, s, a);
     } else if (plan.remove_edges) hipLaunchKernelGGL((k_mesh_raster_small<2>), grid_c, dim3(kCellTPB), 0, s, a);
     else hipLaunchKernelGGL((k_mesh_raster_small<0>), grid_c, dim3(kCellTPB), 0, s, a);
     if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -866,6 +879,9 @@ hipError_t launch_mesh_raster_general(const RenderPlan& plan, const RenderArgs& 
     if (conv) {
         if (plan.remove_edges) hipLaunchKernelGGL((k_mesh_tie_pass<2, true>), dim3(2048), dim3(kCellTPB), tie_lds, s, a, plan.n, nseg);
         else hipLaunchKernelGGL((k_mesh_tie_pass<0, true>), dim3(2048), dim3(kCellTPB), tie_lds, s, a, plan.n, nseg);
+    } else if (plan.eyes == 1) {
+        if (plan.remove_edges) hipLaunchKernelGGL((k_mesh_tie_pass<2, false, 1>), dim3(2048), dim3(kCellTPB), tie_lds, s, a, plan.n, nseg);
+        else hipLaunchKernelGGL((k_mesh_tie_pass<0, false, 1>), dim3(2048), dim3(kCellTPB), tie_lds, s, a, plan.n, nseg);
     } else if (plan.remove_edges) hipLaunchKernelGGL((k_mesh_tie_pass<2, false>), dim3(2048), dim3(kCellTPB), tie_lds, s, a, plan.n, nseg);
     else hipLaunchKernelGGL((k_mesh_tie_pass<0, false>), dim3(2048), dim3(kCellTPB), tie_lds, s, a, plan.n, nseg);
     return hipGetLastError();

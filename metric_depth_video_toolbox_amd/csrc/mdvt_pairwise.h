@@ -1,5 +1,8 @@
 // mdvt_pairwise.h -- NumPy's float32 order of summation as device code over a value functor: what mdvt_convergence.hip (per-frame
 // means) and mdvt_metric_align.hip (the five sums of the scale-and-shift fit) share.  include/mdvt_convergence.h states the order.
+// The order is the same for every element type (the ufunc buffer counts elements): mdvt_view.hip instantiates the routines on a
+// triple of doubles (the three coordinate sums of a frame's vertices, which share one walk); T = float is what the names without
+// a template argument mean.
 //
 // A sum of n contiguous values runs in consecutive chunks of kChunk (the ufunc buffer), each summed by the pairwise routine
 // pw(a, n) -- n < 8: in order; n <= kLeaf: eight strided accumulators, ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then the last n % 8 in
@@ -19,15 +22,16 @@ constexpr int kChunk = 8192;          // NumPy's ufunc buffer, in elements
 constexpr int kLeaf = 128;            // the pairwise routine's block
 
 // pw for n <= kLeaf values v(i0) .. v(i0 + n - 1)
-template <class V>
-__device__ float leaf_sum(const V& v, int i0, int n)
+// (T: float, or a type with T(), operator+ and += that adds like its scalar, element by element; T() is zero)
+template <class T, class V>
+__device__ T leaf_sum_t(const V& v, int i0, int n)
 {
     if (n < 8) {
-        float r = 0.f;
+        T r = T();
         for (int i = 0; i < n; ++i) r += v(i0 + i);
         return r;
     }
-    float r[8];
+    T r[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) r[k] = v(i0 + k);
     int i = 8;
@@ -35,21 +39,26 @@ __device__ float leaf_sum(const V& v, int i0, int n)
 #pragma unroll
         for (int k = 0; k < 8; ++k) r[k] += v(i0 + i + k);
     }
-    float res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+    T res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
     for (; i < n; ++i) res += v(i0 + i);
     return res;
 }
+template <class V>
+__device__ float leaf_sum(const V& v, int i0, int n) { return leaf_sum_t<float>(v, i0, n); }
 
 // The general shape of a chunk of n <= kChunk values, in LDS: its leaves from left to right with their depths in the tree.
-struct Shape {
-    float leaf_sum[128], val[16];
+template <class T>
+struct ShapeT {
+    T leaf_sum[128], val[16];
     uint16_t leaf_at[128], leaf_n[128], at[16], n[16];
     uint8_t leaf_depth[128], depth[16];
     int leaves;
 };
+using Shape = ShapeT<float>;
 
 // One thread lists the leaves (a stack of at most 8 pending right halves); the workgroup synchronises before it reads them.
-__device__ inline void shape_list(Shape& s, int n)
+template <class T>
+__device__ inline void shape_list(ShapeT<T>& s, int n)
 {
     int sp = 0, nl = 0;
     s.at[0] = 0; s.n[0] = (uint16_t)n; s.depth[0] = 0; sp = 1;
@@ -71,16 +80,17 @@ __device__ inline void shape_list(Shape& s, int n)
 }
 
 // A thread each sums the listed leaves (tid < 128 suffices); the workgroup synchronises before shape_join.
-template <class V>
-__device__ inline void shape_leaves(Shape& s, const V& v, int tid)
+template <class T, class V>
+__device__ inline void shape_leaves(ShapeT<T>& s, const V& v, int tid)
 {
-    if (tid < s.leaves) s.leaf_sum[tid] = leaf_sum(v, s.leaf_at[tid], s.leaf_n[tid]);
+    if (tid < s.leaves) s.leaf_sum[tid] = leaf_sum_t<T>(v, s.leaf_at[tid], s.leaf_n[tid]);
 }
 
 // One thread joins neighbours of equal depth, which is the tree: every inner node has two children.  -> the chunk's sum.
 // leaf_sum: the sums of the listed leaves; val, depth: a stack of 16 entries.  With leaf sums and stacks of their own, several
 // sums over one shape are joined side by side, a thread each.
-__device__ inline float shape_join(const Shape& s, const float* leaf_sum, float* val, uint8_t* depth)
+template <class T>
+__device__ inline T shape_join(const ShapeT<T>& s, const T* leaf_sum, T* val, uint8_t* depth)
 {
     int sp = 0;
     for (int j = 0; j < s.leaves; ++j) {
@@ -95,7 +105,8 @@ __device__ inline float shape_join(const Shape& s, const float* leaf_sum, float*
     return val[0];
 }
 
-__device__ inline float shape_join(Shape& s) { return shape_join(s, s.leaf_sum, s.val, s.depth); }
+template <class T>
+__device__ inline T shape_join(ShapeT<T>& s) { return shape_join(s, s.leaf_sum, s.val, s.depth); }
 
 }  // namespace pairwise
 }  // namespace mdvt
