@@ -23,22 +23,17 @@ side (mdvt_adapter_composite_eye: m2s:290-327 is, word for word, the arithmetic 
 The reference has its colour match commented out here (m2s:275, 284), so there is none.  The file gets the blended frames with
 --apply_edge_blending, else the pasted ones (m2s:310-329); the pasted ones feed the overlap either way (m2s:308, 332).
 
-The chunk schedule is the reference's (m2s:398-453) and stereo_crafter_infill's: 25 frames per chunk, six kept -- three pasted
-frames, then three untouched ones; a chunk writes from its index 3 unless it is the first and stops 3 short unless it is the last.
-The same decision as there for the reference's off-by-three (its list of written frames is three short, so its [-6] is frame T-9,
-m2s:437-440): the pasted frames T-6 .. T-4 go with their own masks, and here with their own original frames too.
+The chunk schedule is the reference's (m2s:398-453) and stereo_crafter_infill's, with the same decision for the reference's
+off-by-three (m2s:437-440); infill_clip describes it and runs it.  The original frames are carried through the overlap with the others.
 """
 from __future__ import annotations
 
 import argparse
 import os
 
-import numpy as np
-
 from . import _lib
-from .basic_nomal_infill import _is_txt, _read_list_file
-from .clip_io import VIDEO_DECODERS, ClipInputs, ClipOutput, check_video_decoder, check_video_encoder, video_parts
-from .stereo_crafter_infill import FRAMES_CHUNK, OVERLAP, _frames4, callable_from_spec, chunk_schedule, composite_eye
+from .clip_io import ClipInputs
+from .infill_clip import add_common_flags, callable_from_spec, frames4, infill_chunk, open_clip, run_chunks, run_clips, tuples_from_arguments
 
 IMAGE_W, IMAGE_H = 512, 512               # m2s:215-216
 MASK_W, MASK_H = 64, 64                   # m2s:218
@@ -48,7 +43,7 @@ def prepare_eye(sbs_color, sbs_mask, org, eye: int, image_size=(IMAGE_W, IMAGE_H
     """m2s:224-261 for one eye (0 = left, read mirrored; 1 = right) of uint8 CUDA [N,H,2W,3] colour and infill-mask frames and the
     original frames [N,oh,ow,3] -> (image [N,ih,iw,3], org_image [N,ih,iw,3], mask [N,mh,mw], hole counts int32 [N]), on the device."""
     import torch
-    _frames4(sbs_color), _frames4(sbs_mask), _frames4(org)
+    frames4(sbs_color), frames4(sbs_mask), frames4(org)
     assert sbs_color.shape == sbs_mask.shape and sbs_color.shape[2] % 2 == 0 and org.shape[0] == sbs_color.shape[0]
     N, H, W2 = (int(v) for v in sbs_color.shape[:3])
     (iw, ih), (mw, mh) = image_size, mask_size
@@ -70,25 +65,8 @@ def deal_with_frame_chunk(keep_first_three: bool, color, mask, org, keep_last_th
     """m2s:211-332 on a chunk of uint8 CUDA [T,H,2W,3] colour and mask frames and [T,oh,ow,3] original frames.  Returns (first,
     pasted, blended): the chunk's index of the first frame it writes and the pasted (m2s:303-308) and blended (m2s:312-327) frames
     from there to the last one it writes."""
-    import torch
-    T = int(color.shape[0])
-    start = 0 if keep_first_three else 3
-    end = T if keep_last_three else T - 3
-    n = max(end - start, 0)
-    pasted = torch.empty((n,) + tuple(color.shape[1:]), dtype=torch.uint8, device=color.device)
-    blended = torch.empty_like(pasted)
-    for eye in (0, 1):                                             # m2s:270-284: the left eye first
-        image, org_image, mmask, counts = prepare_eye(color, mask, org, eye, image_size, mask_size)
-        if int(counts.sum().item()) == 0:                          # m2s:271, 280
-            frames = image
-        else:
-            frames = generate(image, mmask, org_image, fps)
-            if not (torch.is_tensor(frames) and frames.is_cuda and frames.dtype == torch.uint8 and frames.shape == image.shape):
-                raise TypeError(f"the generator must return a uint8 CUDA tensor of shape {tuple(image.shape)}")
-            frames = frames.contiguous()
-        if n:
-            composite_eye(frames[start:end], color[start:end], mask[start:end], eye, pasted, blended)
-    return start, pasted, blended
+    return infill_chunk(keep_first_three, keep_last_three, color, mask, lambda eye: prepare_eye(color, mask, org, eye, image_size, mask_size),
+                        lambda image, org_image, mmask: generate(image, mmask, org_image, fps))      # (no colour match: m2s:275, 284)
 
 
 def process_pair(sbs_color_video_path: str, sbs_mask_video_path: str, color_video_path: str, generate, max_frames: int = -1, batch: int = 8,
@@ -98,60 +76,13 @@ def process_pair(sbs_color_video_path: str, sbs_mask_video_path: str, color_vide
     uint8 [N,H,2W,3] and [N,oh,ow,3]) give `<sbs_color>_infilled.npy`; either is written under its `_tmp_infilled` name and renamed
     once every frame is in.  A mask clip shorter than the colour clip means black masks for the rest (m2s:415-417); an original clip
     shorter than the frames asked for is a ValueError (the reference raises when it gets there, m2s:421-423).  Returns the output path."""
-    import torch
     with ClipInputs() as inp:
-        color = inp.open(sbs_color_video_path, "sbs_color_video", Exception(f"input sbs_color_video does not exist: {sbs_color_video_path}"), True)
-        mask = inp.open(sbs_mask_video_path, "sbs_mask_video", Exception(f"input sbs_mask_video does not exist: {sbs_mask_video_path}"), True)
-        org = inp.open(color_video_path, "color_video", Exception(f"input color_video does not exist: {color_video_path}"))
-        video = bool(video_parts(color))
-        check_video_decoder(video_decoder, video)
-        check_video_encoder(video_encoder, video)
-        assert color.ndim == 4 and color.shape[-1] == 3 and color.dtype == np.uint8, "uint8 [N, H, 2W, 3] expected"
-        assert org.ndim == 4 and org.shape[-1] == 3 and org.dtype == np.uint8, "uint8 [N, H, W, 3] expected for the original video"
-        assert color.shape[1:] == mask.shape[1:], "mask and color video not same resolution"      # m2s:390
-        if color.shape[2] % 2:
-            raise ValueError(f"side-by-side frames need an even width, got {color.shape[2]}")
-        if max_frames == 0:
-            raise ValueError("max_frames = 0: ask for -1 (all) or a positive count")
-        n = color.shape[0] if max_frames == -1 else min(color.shape[0], max_frames)
-        if n < 1:
-            raise ValueError(f"{sbs_color_video_path} has no frames")
-        if org.shape[0] < n:
-            raise ValueError(f"org color ended early: {color_video_path} has {org.shape[0]} frames, {n} are needed")      # m2s:421-423
-        batch = max(1, int(batch))
-        ext = ".mkv" if video else ".npy"
-        tmp, final = sbs_color_video_path + "_tmp_infilled" + ext, sbs_color_video_path + "_infilled" + ext      # m2s:393-394
-        H, W2 = int(color.shape[1]), int(color.shape[2])
-        fps = (video_parts(color)[0][0].fps or 30.0) if video else 30.0
-        inp.on_device(torch.device("cuda", torch.cuda.current_device() if device is None else device), video_decoder, video_encoder)
-        dev = inp.dev
-        with ClipOutput(tmp, final, n, (H, W2, 3), fps if video else None, video_encoder, inp.ctx) as out, torch.cuda.device(dev):
-            buf_c = torch.empty((FRAMES_CHUNK, H, W2, 3), dtype=torch.uint8, device=dev)
-            buf_m = torch.zeros_like(buf_c)
-            buf_o = torch.empty((FRAMES_CHUNK,) + tuple(int(v) for v in org.shape[1:]), dtype=torch.uint8, device=dev)
-            read = 0
-            for first, last, base, held, (wa, wb) in chunk_schedule(n):
-                have = read - base                                 # the overlap is in the buffer already
-                while have < held:
-                    k = min(batch, held - have)
-                    buf_c[have:have + k] = inp.fetch(color, read, read + k)
-                    buf_o[have:have + k] = inp.fetch(org, read, read + k)
-                    got = max(0, min(read + k, mask.shape[0]) - read)
-                    if got:
-                        buf_m[have:have + got] = inp.fetch(mask, read, read + got)
-                    buf_m[have + got:have + k] = 0                 # m2s:415-417
-                    have += k
-                    read += k
-                start, pasted, blended = deal_with_frame_chunk(first, buf_c[:held], buf_m[:held], buf_o[:held], last, fps, generate,
-                                                               image_size, mask_size)
-                assert base + start == wa and len(blended) == wb - wa
-                if wb > wa:
-                    out.store(blended if apply_edge_blending else pasted, wa)      # m2s:310-329
-                if not last:                                       # m2s:437-444
-                    keep_c = torch.cat([pasted[held - OVERLAP - start:held - 3 - start], buf_c[held - 3:held]])
-                    keep_m, keep_o = buf_m[held - OVERLAP:held].clone(), buf_o[held - OVERLAP:held].clone()
-                    buf_c[:OVERLAP], buf_m[:OVERLAP], buf_o[:OVERLAP] = keep_c, keep_m, keep_o
-    return final
+        clip = open_clip(inp, sbs_color_video_path, sbs_mask_video_path, [("color_video", color_video_path, False, "org color ended early")],
+                         max_frames, video_decoder, video_encoder, device)
+        run_chunks(inp, clip, batch, lambda first, last, fps, color, mask, org: deal_with_frame_chunk(first, color, mask, org, last, fps, generate,
+                                                                                                   image_size, mask_size),
+                   store_blended=apply_edge_blending)              # m2s:310-329
+    return clip.final
 
 
 class M2SVidGenerator:
@@ -198,15 +129,7 @@ def load_generator(spec: str, num_inference_steps: int = 5):
 def triples_from_arguments(color_video: str, sbs_color_video: str, sbs_mask_video: str):
     """m2s:494-507: one (sbs_color, sbs_mask, color) triple, or -- if the side-by-side colour argument is a .txt list -- the triples of
     three lists of equal length.  The lists are read and compared before any clip is opened."""
-    if not _is_txt(sbs_color_video):
-        return [(sbs_color_video, sbs_mask_video, color_video)]
-    if not _is_txt(sbs_mask_video) or not _is_txt(color_video):
-        raise ValueError("If --sbs_color_video is a .txt file, then --sbs_mask_video and --color_video must also be .txt files.")
-    colors, masks, orgs = _read_list_file(sbs_color_video), _read_list_file(sbs_mask_video), _read_list_file(color_video)
-    if len(colors) != len(masks) or len(colors) != len(orgs):
-        raise ValueError(f"List length mismatch: {sbs_color_video} has {len(colors)} entries, {sbs_mask_video} has {len(masks)} entries, "
-                         f"{color_video} has {len(orgs)} entries.")
-    return list(zip(colors, masks, orgs))
+    return tuples_from_arguments([("sbs_color_video", sbs_color_video), ("sbs_mask_video", sbs_mask_video), ("color_video", color_video)])
 
 
 def build_parser():
@@ -214,47 +137,21 @@ def build_parser():
     p.add_argument("--color_video", type=str, required=True, help="Original input video (.mkv, or a .npy frame dump), or a .txt list of them")
     p.add_argument("--sbs_color_video", type=str, required=True, help="side by side stereo video rendered with point clouds in the masked area, or the matching .txt list")
     p.add_argument("--sbs_mask_video", type=str, required=True, help="side by side stereo video mask, or the matching .txt list")
-    p.add_argument("--max_frames", default=-1, type=int, help="quit after max_frames nr of frames", required=False)
     p.add_argument("--num_inference_steps", default=5, type=int, help="number of diffusion steps of the m2svid generator. More look better but is slower", required=False)
     p.add_argument("--apply_edge_blending", action="store_true", help="applies blending of the downward facing side of edges to reduce halo effect", required=False)
     p.add_argument("--generator", default="m2svid", type=str,
                    help="not a reference flag: the in-painting model, 'm2svid' (default) or pkg.module:callable with "
                         "generate(frames, masks, org_frames, fps) -> frames on uint8 CUDA tensors [T,512,512,3], [T,64,64] and [T,512,512,3]")
-    p.add_argument("--batch", default=8, type=int, help="not a reference flag: frames per read from the input")
-    p.add_argument("--video_decoder", choices=VIDEO_DECODERS, default="host",
-                   help="not a reference flag: where the .mkv inputs are FFV1-decoded -- 'host' (default), 'device' (on the GPU, the same bytes) "
-                        "or 'device_all' (as 'device', and Golomb-Rice or inter-coded FFV1, FFmpeg's default, as well). Not with .npy inputs")
-    p.add_argument("--video_encoder", choices=("host", "device"), default="host",
-                   help="not a reference flag: where the .mkv output is FFV1-encoded -- 'host' (default) or 'device' (on the GPU, the same bytes). Not with .npy inputs")
-    return p
+    return add_common_flags(p)
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    if args.max_frames == 0:
-        raise SystemExit("--max_frames 0: ask for -1 (all) or a positive count")
-    triples = triples_from_arguments(args.color_video, args.sbs_color_video, args.sbs_mask_video)
-    listed = _is_txt(args.sbs_color_video)
-    for c_path, m_path, o_path in triples:
-        for what, path, run_output in (("sbs_color_video", c_path, True), ("sbs_mask_video", m_path, True), ("color_video", o_path, False)):
-            if not listed and not (os.path.isfile(path) or (run_output and os.path.isfile(path + ".index.json"))):
-                raise SystemExit(f"input {what} does not exist: {path}")
-    try:
-        generate = load_generator(args.generator, args.num_inference_steps)
-    except (RuntimeError, ValueError, ImportError) as e:
-        raise SystemExit(str(e))
     kw = dict(batch=args.batch, apply_edge_blending=args.apply_edge_blending, video_decoder=args.video_decoder, video_encoder=args.video_encoder)
-    if listed:
-        # (the reference runs two clips at a time with the model serialised, m2s:509-520; here the clips follow each other)
-        print(f"Batch mode: {len(triples)} pairs")
-        for c_path, m_path, o_path in triples:
-            try:
-                print("Done. Wrote:", process_pair(c_path, m_path, o_path, generate, args.max_frames, **kw))
-            except Exception as e:                                # m2s:518-520: surface the error, keep the other clips going
-                print(f"[ERROR] A clip failed: {e}")
-        return 0
-    print("Done. Wrote:", process_pair(*triples[0], generate, args.max_frames, **kw))
-    return 0
+    # (the original video is no output of clip.run: it has no per-rank form)
+    return run_clips([("sbs_color_video", args.sbs_color_video), ("sbs_mask_video", args.sbs_mask_video), ("color_video", args.color_video)],
+                     args.max_frames, lambda paths, generate: process_pair(*paths, generate, args.max_frames, **kw), precheck=(True, True, False),
+                     load=lambda: load_generator(args.generator, args.num_inference_steps))
 
 
 if __name__ == "__main__":

@@ -21,43 +21,29 @@ the frames resized back, pasted under the mask and blended along the holes' lowe
 match follows the reference's single_precision=False; its default float32 path differs from that in a few per cent of the values by
 1 (include/mdvt_infill_adapter.h, DESIGN.md).
 
-The chunk schedule is the reference's (scr:218-266): 25 frames per chunk; after a chunk the buffer keeps six frames -- three pasted
-frames with their masks, then three untouched ones; a chunk writes from its index 3 unless it is the first and stops 3 short unless
-it is the last; the last call runs on whatever is buffered.  One difference, on purpose: the reference pairs the masks of the frames
-T-6 .. T-4 with the pasted frames T-9 .. T-7 (its list of written frames is three short, scr:148, 251-253); here the pasted frames
-T-6 .. T-4 go with their own masks.  Those three frames are context for the generator only and are never written again.
+The chunk schedule is the reference's (scr:218-266), with its one difference on purpose; infill_clip describes it and runs it
+(chunk_schedule, run_chunks), and owns composite_eye, which m2svid_infill uses too: both are re-exported here.
 """
 from __future__ import annotations
 
 import argparse
-import importlib
-import os
 
 import numpy as np
 
 from . import _lib
-from .basic_nomal_infill import pairs_from_arguments
-from .clip_io import VIDEO_DECODERS, ClipInputs, ClipOutput, check_video_decoder, check_video_encoder, video_parts
+from .clip_io import ClipInputs
+from .infill_clip import (FRAMES_CHUNK, OVERLAP, add_common_flags, callable_from_spec, chunk_schedule, composite_eye, frames4,      # noqa: F401
+                          infill_chunk, open_clip, run_chunks, run_clips)
 
 MODEL_W, MODEL_H = 1024, 768              # scr:95-96
-FRAMES_CHUNK, OVERLAP = 25, 6             # scr:222, 250-257
 EPS = 1e-5                                # ic:57
-
-
-def _frames4(t, channels=3):
-    import torch
-    ok = t.is_cuda and t.dtype == torch.uint8 and t.dim() == 3 + (channels == 3) and t.stride(-1) == 1
-    if channels == 3:
-        ok = ok and t.shape[-1] == 3 and t.stride(-2) == 3
-    assert ok, f"uint8 CUDA [N,H,W{',3' if channels == 3 else ''}] with packed pixels expected"
-    return t
 
 
 def prepare_eye(sbs_color, sbs_mask, eye: int, model_size=(MODEL_W, MODEL_H)):
     """scr:101-126 for one eye (0 = left, read mirrored; 1 = right) of uint8 CUDA [N,H,2W,3] colour and infill-mask frames ->
     (image [N,mh,mw,3], mask [N,mh,mw], hole counts int32 [N]), all on the device."""
     import torch
-    _frames4(sbs_color), _frames4(sbs_mask)
+    frames4(sbs_color), frames4(sbs_mask)
     assert sbs_color.shape == sbs_mask.shape and sbs_color.shape[2] % 2 == 0
     N, H, W2 = (int(v) for v in sbs_color.shape[:3])
     mw, mh = model_size
@@ -75,10 +61,10 @@ def lhm_moments(frames, mask=None, out=None):
     """mdvt_lhm_moments: per frame of uint8 CUDA [N,H,W,3] the ten exact integer moments (count, sums, second moments) over the
     pixels whose mask byte is 0 (all without a mask) -> int64 CUDA [N,10]."""
     import torch
-    _frames4(frames)
+    frames4(frames)
     N, H, W = (int(v) for v in frames.shape[:3])
     if mask is not None:
-        _frames4(mask, 1)
+        frames4(mask, 1)
         assert tuple(mask.shape) == (N, H, W)
     if out is None:
         out = torch.empty((N, 10), dtype=torch.int64, device=frames.device)
@@ -124,12 +110,12 @@ def lhm_params(mom_x, mom_r, mom_r_all):
 def lhm_apply(frames, params, out=None):
     """mdvt_lhm_apply: uint8 CUDA [N,H,W,3] and float64 CUDA [N,15] -> the matched frames."""
     import torch
-    _frames4(frames)
+    frames4(frames)
     N, H, W = (int(v) for v in frames.shape[:3])
     assert params.is_cuda and params.dtype == torch.float64 and tuple(params.shape) == (N, 15) and params.is_contiguous()
     if out is None:
         out = torch.empty((N, H, W, 3), dtype=torch.uint8, device=frames.device)
-    _frames4(out)
+    frames4(out)
     _lib.shared_context(frames.device).call("mdvt_lhm_apply", W, H, N, frames.data_ptr(), frames.stride(1), frames.stride(0), params.data_ptr(),
                                             out.data_ptr(), out.stride(1), out.stride(0), _lib.stream_arg(frames.device))
     return out
@@ -159,59 +145,11 @@ def transfer_lhm_video_refmask(video, reference, reference_mask=None):
     return lhm_apply(video, params)
 
 
-def composite_eye(model_frames, sbs_color, sbs_mask, eye: int, pasted, blended):
-    """scr:151-188 for one eye: the model's frames (uint8 CUDA [N,mh,mw,3]) resized back, pasted under the mask into that eye's half
-    of `pasted` and blended along the holes' lower side into that eye's half of `blended` (both uint8 CUDA [N,H,2W,3])."""
-    for t in (model_frames, sbs_color, sbs_mask, pasted, blended):
-        _frames4(t)
-    N, H, W2 = (int(v) for v in sbs_color.shape[:3])
-    assert sbs_mask.shape == sbs_color.shape == pasted.shape == blended.shape and int(model_frames.shape[0]) == N
-    _lib.shared_context(sbs_color.device).call(
-        "mdvt_adapter_composite_eye", W2 // 2, H, N, int(eye), model_frames.data_ptr(), int(model_frames.shape[2]), int(model_frames.shape[1]),
-        model_frames.stride(1), model_frames.stride(0), sbs_color.data_ptr(), sbs_color.stride(1), sbs_color.stride(0),
-        sbs_mask.data_ptr(), sbs_mask.stride(1), sbs_mask.stride(0), pasted.data_ptr(), pasted.stride(1), pasted.stride(0),
-        blended.data_ptr(), blended.stride(1), blended.stride(0), _lib.stream_arg(sbs_color.device))
-
-
 def deal_with_frame_chunk(keep_first_three: bool, color, mask, keep_last_three: bool, fps: float, generate, model_size=(MODEL_W, MODEL_H)):
     """scr:91-190 on a chunk of uint8 CUDA [T,H,2W,3] colour and mask frames.  Returns (first, pasted, blended): the chunk's index of
     the first frame it writes and the pasted and blended frames from there to the last one it writes (scr:147-148)."""
-    import torch
-    T = int(color.shape[0])
-    start = 0 if keep_first_three else 3
-    end = T if keep_last_three else T - 3
-    n = max(end - start, 0)
-    pasted = torch.empty((n,) + tuple(color.shape[1:]), dtype=torch.uint8, device=color.device)
-    blended = torch.empty_like(pasted)
-    for eye in (0, 1):                                             # scr:133-145: the left eye first
-        image, mmask, counts = prepare_eye(color, mask, eye, model_size)
-        if int(counts.sum().item()) == 0:                          # scr:134, 141
-            frames = image
-        else:
-            frames = generate(image, mmask, fps)
-            if not (torch.is_tensor(frames) and frames.is_cuda and frames.dtype == torch.uint8 and frames.shape == image.shape):
-                raise TypeError(f"the generator must return a uint8 CUDA tensor of shape {tuple(image.shape)}")
-            frames = transfer_lhm_video_refmask(frames.contiguous(), image, mmask)
-        if n:
-            composite_eye(frames[start:end], color[start:end], mask[start:end], eye, pasted, blended)
-    return start, pasted, blended
-
-
-def chunk_schedule(n_frames: int):
-    """The calls of scr:218-266 for a clip of n_frames: [(first, last, frame of the buffer's index 0, buffered frames, (a, b))], where
-    [a, b) are the clip's frames the call writes."""
-    if n_frames < 1:
-        raise ValueError("a clip needs at least one frame")
-    calls, first, base, held = [], True, 0, 0
-    for t in range(n_frames):
-        held += 1
-        if held >= FRAMES_CHUNK:
-            start = 0 if first else 3
-            calls.append((first, False, base, held, (base + start, base + held - 3)))
-            first, base, held = False, base + held - OVERLAP, OVERLAP
-    start = 0 if first else 3
-    calls.append((first, True, base, held, (base + start, base + held)))
-    return calls
+    return infill_chunk(keep_first_three, keep_last_three, color, mask, lambda eye: prepare_eye(color, mask, eye, model_size),
+                        lambda image, mmask: generate(image, mmask, fps), transfer_lhm_video_refmask)
 
 
 def process_pair(sbs_color_video_path: str, sbs_mask_video_path: str, generate, max_frames: int = -1, batch: int = 8, device=None, *,
@@ -219,53 +157,10 @@ def process_pair(sbs_color_video_path: str, sbs_mask_video_path: str, generate, 
     """scr:192-274.  `.mkv` inputs give `<sbs_color>_infilled.mkv` at the colour video's frame rate, frame dumps (`.npy`, uint8
     [N,H,2W,3]) give `<sbs_color>_infilled.npy`; either is written under its `_tmp_infilled` name and renamed once every frame is in.
     A mask clip shorter than the colour clip means black masks for the rest (scr:234-237).  Returns the output path."""
-    import torch
     with ClipInputs() as inp:
-        color = inp.open(sbs_color_video_path, "sbs_color_video", Exception(f"input sbs_color_video does not exist: {sbs_color_video_path}"), True)
-        mask = inp.open(sbs_mask_video_path, "sbs_mask_video", Exception(f"input sbs_mask_video does not exist: {sbs_mask_video_path}"), True)
-        video = bool(video_parts(color))
-        check_video_decoder(video_decoder, video)
-        check_video_encoder(video_encoder, video)
-        assert color.ndim == 4 and color.shape[-1] == 3 and color.dtype == np.uint8, "uint8 [N, H, 2W, 3] expected"
-        assert color.shape[1:] == mask.shape[1:], "mask and color video not same resolution"      # scr:210
-        if color.shape[2] % 2:
-            raise ValueError(f"side-by-side frames need an even width, got {color.shape[2]}")
-        if max_frames == 0:
-            raise ValueError("max_frames = 0: ask for -1 (all) or a positive count")
-        n = color.shape[0] if max_frames == -1 else min(color.shape[0], max_frames)
-        if n < 1:
-            raise ValueError(f"{sbs_color_video_path} has no frames")
-        batch = max(1, int(batch))
-        ext = ".mkv" if video else ".npy"
-        tmp, final = sbs_color_video_path + "_tmp_infilled" + ext, sbs_color_video_path + "_infilled" + ext      # scr:213-214
-        H, W2 = int(color.shape[1]), int(color.shape[2])
-        fps = (video_parts(color)[0][0].fps or 30.0) if video else 30.0
-        inp.on_device(torch.device("cuda", torch.cuda.current_device() if device is None else device), video_decoder, video_encoder)
-        dev = inp.dev
-        with ClipOutput(tmp, final, n, (H, W2, 3), fps if video else None, video_encoder, inp.ctx) as out, torch.cuda.device(dev):
-            buf_c = torch.empty((FRAMES_CHUNK, H, W2, 3), dtype=torch.uint8, device=dev)
-            buf_m = torch.zeros_like(buf_c)
-            read = 0
-            for first, last, base, held, (wa, wb) in chunk_schedule(n):
-                have = read - base                                 # the overlap is in the buffer already
-                while have < held:
-                    k = min(batch, held - have)
-                    buf_c[have:have + k] = inp.fetch(color, read, read + k)
-                    got = max(0, min(read + k, mask.shape[0]) - read)
-                    if got:
-                        buf_m[have:have + got] = inp.fetch(mask, read, read + got)
-                    buf_m[have + got:have + k] = 0                 # scr:234-237
-                    have += k
-                    read += k
-                start, pasted, blended = deal_with_frame_chunk(first, buf_c[:held], buf_m[:held], last, fps, generate, model_size)
-                assert base + start == wa and len(blended) == wb - wa
-                if wb > wa:
-                    out.store(blended, wa)
-                if not last:                                       # scr:250-257
-                    keep_c = torch.cat([pasted[held - OVERLAP - start:held - 3 - start], buf_c[held - 3:held]])
-                    keep_m = buf_m[held - OVERLAP:held].clone()
-                    buf_c[:OVERLAP], buf_m[:OVERLAP] = keep_c, keep_m
-    return final
+        clip = open_clip(inp, sbs_color_video_path, sbs_mask_video_path, [], max_frames, video_decoder, video_encoder, device)
+        run_chunks(inp, clip, batch, lambda first, last, fps, color, mask: deal_with_frame_chunk(first, color, mask, last, fps, generate, model_size))
+    return clip.final
 
 
 class StereoCrafterGenerator:
@@ -304,17 +199,6 @@ class StereoCrafterGenerator:
         return torch.from_numpy((video * 255).astype(np.uint8)).to(frames.device)
 
 
-def callable_from_spec(spec: str, default_name: str):
-    """The callable a `--generator pkg.module:callable` names (default_name: the engine's own model, for the message)."""
-    mod, sep, name = spec.partition(":")
-    if not sep or not mod or not name:
-        raise ValueError(f"--generator must be '{default_name}' or 'pkg.module:callable', got {spec!r}")
-    fn = getattr(importlib.import_module(mod), name, None)
-    if not callable(fn):
-        raise ValueError(f"{spec}: {mod} has no callable {name!r}")
-    return fn
-
-
 def load_generator(spec: str, num_inference_steps: int = 5):
     """`stereocrafter` (the default model) or `pkg.module:callable`."""
     return StereoCrafterGenerator(num_inference_steps) if spec == "stereocrafter" else callable_from_spec(spec, "stereocrafter")
@@ -324,46 +208,19 @@ def build_parser():
     p = argparse.ArgumentParser(description="StereoCrafter infill script (FFV1 .mkv videos, or frame dumps)")
     p.add_argument("--sbs_color_video", type=str, required=True, help="side by side stereo video rendered with point clouds in the masked area (.mkv, or a .npy frame dump), or a .txt list of them")
     p.add_argument("--sbs_mask_video", type=str, required=True, help="side by side stereo video mask, or the matching .txt list")
-    p.add_argument("--max_frames", default=-1, type=int, help="quit after max_frames nr of frames", required=False)
     p.add_argument("--num_inference_steps", default=5, type=int, help="number of diffusion steps of the stereocrafter generator. More look better but is slower", required=False)
     p.add_argument("--generator", default="stereocrafter", type=str,
                    help="not a reference flag: the in-painting model, 'stereocrafter' (default) or pkg.module:callable with "
                         "generate(frames, masks, fps) -> frames on uint8 CUDA tensors [T,768,1024,3] and [T,768,1024]")
-    p.add_argument("--batch", default=8, type=int, help="not a reference flag: frames per read from the input")
-    p.add_argument("--video_decoder", choices=VIDEO_DECODERS, default="host",
-                   help="not a reference flag: where the .mkv inputs are FFV1-decoded -- 'host' (default), 'device' (on the GPU, the same bytes) "
-                        "or 'device_all' (as 'device', and Golomb-Rice or inter-coded FFV1, FFmpeg's default, as well). Not with .npy inputs")
-    p.add_argument("--video_encoder", choices=("host", "device"), default="host",
-                   help="not a reference flag: where the .mkv output is FFV1-encoded -- 'host' (default) or 'device' (on the GPU, the same bytes). Not with .npy inputs")
-    return p
+    return add_common_flags(p)
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    if args.max_frames == 0:
-        raise SystemExit("--max_frames 0: ask for -1 (all) or a positive count")
-    pairs = pairs_from_arguments(args.sbs_color_video, args.sbs_mask_video)
-    listed = args.sbs_color_video.lower().endswith(".txt")        # (the rule of pairs_from_arguments, scr:343)
-    for c_path, m_path in pairs:
-        for what, path in (("sbs_color_video", c_path), ("sbs_mask_video", m_path)):
-            if not listed and not (os.path.isfile(path) or os.path.isfile(path + ".index.json")):
-                raise SystemExit(f"input {what} does not exist: {path}")
-    try:
-        generate = load_generator(args.generator, args.num_inference_steps)
-    except (RuntimeError, ValueError, ImportError) as e:
-        raise SystemExit(str(e))
     kw = dict(batch=args.batch, video_decoder=args.video_decoder, video_encoder=args.video_encoder)
-    if listed:
-        # (the reference runs two clips at a time with the model serialised, scr:343-354; here the clips follow each other)
-        print(f"Batch mode: {len(pairs)} pairs")
-        for c_path, m_path in pairs:
-            try:
-                print("Done. Wrote:", process_pair(c_path, m_path, generate, args.max_frames, **kw))
-            except Exception as e:                                # scr:352-354: surface the error, keep the other clips going
-                print(f"[ERROR] A clip failed: {e}")
-        return 0
-    print("Done. Wrote:", process_pair(*pairs[0], generate, args.max_frames, **kw))
-    return 0
+    return run_clips([("sbs_color_video", args.sbs_color_video), ("sbs_mask_video", args.sbs_mask_video)], args.max_frames,
+                     lambda paths, generate: process_pair(*paths, generate, args.max_frames, **kw), precheck=(True, True),
+                     load=lambda: load_generator(args.generator, args.num_inference_steps))
 
 
 if __name__ == "__main__":
