@@ -283,6 +283,57 @@ def stream_arg(dev, stream=None):
     return C.c_void_p((torch.cuda.current_stream(dev) if stream is None else stream).cuda_stream)
 
 
+def check_tensor(name: str, t, dtype, shape=None, *, ndim=None, device=None, packed: int = 0, contiguous: bool = False,
+                 output: bool = False, disjoint: bool = False):
+    """The refusal every wrapper makes before a tensor's address reaches the library; returns `t`.  TypeError unless `t` is a torch
+    tensor of `dtype` (one dtype or several), ValueError -- naming the argument -- unless it
+      is on a GPU, and on `device` (a torch.device, a tensor's, or an index) where one is given;
+      has one of `ndim` dimensions and the sizes of `shape` (None = any size; matched against the trailing dimensions);
+      packed = k: has its last k dimensions dense (stride 1, then the size of the last: packed pixels; rows and frames at any pitch);
+      contiguous: is contiguous (the wrapper passes no pitch of the tensor's own);
+      output: has no two elements at one address -- rows at least a row apart, frames at least a frame apart (the library writes
+      rows of whole pixels and owns every byte of them: an expanded or folded view would be written twice);
+      disjoint: the same for an input of an entry point that takes no pitch below a row and no stride below a frame.
+    These raise (an `assert` is stripped by python -O); nothing here runs per launch of a PreparedRender."""
+    import torch
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor, got {type(t).__name__}")
+    dtypes = dtype if isinstance(dtype, (tuple, list)) else (dtype,)
+    if t.dtype not in dtypes:
+        raise TypeError(f"{name} must be {' or '.join(str(d) for d in dtypes)}, got {t.dtype}")
+    if not t.is_cuda:
+        raise ValueError(f"{name} must be on a GPU, it is on {t.device}")
+    if device is not None:
+        want = device_index(device.device if isinstance(device, torch.Tensor) else device)
+        if t.device.index != want:
+            raise ValueError(f"{name} is on {t.device}, cuda:{want} is wanted")
+    if ndim is not None and t.dim() not in (ndim if isinstance(ndim, (tuple, list)) else (ndim,)):
+        raise ValueError(f"{name} must have {ndim} dimensions, got shape {tuple(t.shape)}")
+    if shape is not None:
+        shape = tuple(shape)
+        got = tuple(int(v) for v in t.shape)
+        if len(got) < len(shape) or (ndim is None and len(got) != len(shape)) \
+                or any(w is not None and int(w) != g for w, g in zip(shape, got[len(got) - len(shape):])):
+            raise ValueError(f"{name} must be {tuple('any' if w is None else int(w) for w in shape)}, got {got}")
+    dense = 1
+    for k in range(1, packed + 1):
+        if t.shape[-k] > 1 and t.stride(-k) != dense:
+            raise ValueError(f"{name} must have packed pixels (its last {packed} dimension(s) dense; rows and frames may be strided), "
+                             f"got strides {tuple(t.stride())}")
+        dense *= int(t.shape[-k])
+    if contiguous and not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous, got strides {tuple(t.stride())} for shape {tuple(t.shape)}")
+    if output or disjoint:
+        need = 1
+        for k in range(1, t.dim() + 1):
+            if t.shape[-k] > 1 and t.stride(-k) < need:
+                raise ValueError(f"{name}{' is written:' if output else ':'} its rows and frames must not overlap, got strides {tuple(t.stride())} "
+                                 f"for shape {tuple(t.shape)}")
+            if t.shape[-k] > 1:
+                need = t.stride(-k) * int(t.shape[-k])
+    return t
+
+
 class _ThreadContexts:
     """The shared contexts of one host thread, by key.  They are closed when the store goes away, which is when its thread ends."""
 

@@ -21,26 +21,20 @@ from .clip_io import ClipInputs
 from .infill_clip import add_common_flags, open_clip, run_batches, run_clips, tuples_from_arguments
 
 
-def _packed(t):
-    return t.stride(-1) == 1 and t.stride(-2) == 3
-
-
 def normal_infill(img, infill_mask, out=None):
     """basic_nomal_infill.normal_infill (basic_nomal_infill.py:87-119).  img, infill_mask: uint8 CUDA tensors [H,W,3] or
     [N,H,W,3] (RGB; rows and images may be strided, e.g. one half of a side-by-side frame).  Returns the image with its
     holes filled.  Unlike the reference, `img` itself is left untouched (the reference blackens and refills it in place
     and returns a new array; its caller only uses the returned one, basic_nomal_infill.py:186)."""
     import torch
-    for t in (img, infill_mask):
-        assert t.is_cuda and t.dtype == torch.uint8 and t.dim() in (3, 4) and t.shape[-1] == 3 and _packed(t), \
-            "uint8 CUDA [H,W,3] or [N,H,W,3] with packed RGB pixels"
-    assert img.shape == infill_mask.shape
+    _lib.check_tensor("img", img, torch.uint8, (None, None, 3), ndim=(3, 4), packed=2)
+    _lib.check_tensor("infill_mask", infill_mask, torch.uint8, tuple(img.shape), device=img, packed=2)
     batched = img.dim() == 4
     N = int(img.shape[0]) if batched else 1
     H, W = int(img.shape[-3]), int(img.shape[-2])
     if out is None:
         out = torch.empty(tuple(img.shape), dtype=torch.uint8, device=img.device)
-    assert out.shape == img.shape and out.is_cuda and out.dtype == torch.uint8 and _packed(out)
+    _lib.check_tensor("out", out, torch.uint8, tuple(img.shape), device=img, packed=2, output=True)
     stride = (lambda t: t.stride(0) if batched else 0)
     _lib.shared_context(img.device, W, H).call("mdvt_normal_infill", img.data_ptr(), img.stride(-3), stride(img),
                                                infill_mask.data_ptr(), infill_mask.stride(-3), stride(infill_mask),

@@ -116,11 +116,15 @@ def host_packet(frame, slices, bgr: bool, threads: int = 1) -> bytes:
 
 def enqueue(ctx: "_lib.Context", frames, slices=(4, 4), bgr: bool = False, slice_capacity: int = 0,
             packets_cap: Optional[int] = None, stream=None) -> PendingPackets:
-    """Enqueues the encode of frames on `stream` (default: the current stream of their device) and returns the buffers it fills."""
+    """Enqueues the encode of frames on `stream` (default: the current stream of their device) and returns the buffers it fills.
+    frames: uint8 [N,H,W,3] or [N,H,W] on the context's GPU; dense pixels with padded rows and frames are read where they lie, any
+    other layout (unpacked or transposed pixels, overlapping frames) is encoded from a contiguous copy."""
     import torch
     N, H, W, ch = check_frames(frames, slices)
     if int(slice_capacity) < 0:
         raise ValueError("slice_capacity must be >= 0 (0 = the default)")
+    if frames.device.index != ctx.device:
+        raise ValueError(f"frames are on {frames.device}, the context on cuda:{ctx.device}")
     # the kernel reads rows of W * ch bytes: pixels dense within a row, rows and frames at any pitch
     if frames.stride(2) != ch or (ch == 3 and frames.stride(3) != 1) or frames.stride(1) < W * ch or (N > 1 and frames.stride(0) < frames.stride(1) * H):
         frames = frames.contiguous()
@@ -284,6 +288,8 @@ def _enqueue_decode(pending, ctx, packets, config, width, height, first_out, bgr
     if out is None:
         out = torch.empty((n_out, H, W, 3), dtype=torch.uint8, device=dev)
     check_out(out, n_out, H, W)
+    if out.device.index != ctx.device:
+        raise ValueError(f"out is on {out.device}, the context on cuda:{ctx.device}")
     s = stream if stream is not None else torch.cuda.current_stream(dev)
     side = torch.cuda.Stream(dev)
     with torch.cuda.stream(side):

@@ -27,6 +27,8 @@ def _check_frames(t, name: str):
         raise ValueError(f"{name} must be a uint8 CUDA tensor [N, H, W, 3]")
     if t.shape[0] > 0 and not (t.stride(-1) == 1 and t.stride(-2) == 3):
         raise ValueError(f"{name} must have packed 3-byte pixels (rows and frames may be padded)")
+    if t.shape[0] > 0 and (t.stride(1) < 3 * t.shape[2] or (t.shape[0] > 1 and t.stride(0) < t.shape[1] * t.stride(1))):
+        raise ValueError(f"{name}: rows or frames overlap (they may be padded, not folded: strides {tuple(t.stride())})")
 
 
 def convergence_depths(depth_frames, mask_frames=None, max_depth=100, *, bgr: bool = False, counts: bool = False, stream=None):

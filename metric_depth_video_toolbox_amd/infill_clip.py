@@ -196,23 +196,28 @@ def run_chunks(inp, clip: Clip, batch: int, per_chunk, store_blended: bool = Tru
 
 # ---- one chunk: the device wrappers and the skeleton the chunked engines share ------------------------------------------------------
 
-def frames4(t, channels=3):
+def frames4(t, channels=3, name="frames", shape=None, device=None, output=False, disjoint=True):
+    """_lib.check_tensor for uint8 CUDA frames [N,H,W,3] (channels = 3) or planes [N,H,W] (channels = 1) with packed pixels, rows and
+    frames padded at will but not overlapping (the adapter and engine entry points take no stride below a frame; disjoint=False: any
+    stride); `shape` holds it to one size, `device` to a GPU (or a tensor's), `output` marks a tensor that is written."""
     import torch
-    ok = t.is_cuda and t.dtype == torch.uint8 and t.dim() == 3 + (channels == 3) and t.stride(-1) == 1
-    if channels == 3:
-        ok = ok and t.shape[-1] == 3 and t.stride(-2) == 3
-    assert ok, f"uint8 CUDA [N,H,W{',3' if channels == 3 else ''}] with packed pixels expected"
-    return t
+    if shape is None:
+        shape = (None, None, None, 3) if channels == 3 else (None, None, None)
+    return _lib.check_tensor(name, t, torch.uint8, shape, device=device, packed=2 if channels == 3 else 1, output=output, disjoint=disjoint)
 
 
 def composite_eye(model_frames, sbs_color, sbs_mask, eye: int, pasted, blended):
     """scr:151-188 (and, word for word, m2s:290-327) for one eye: the model's frames (uint8 CUDA [N,mh,mw,3]) resized back, pasted
     under the mask into that eye's half of `pasted` and blended along the holes' lower side into that eye's half of `blended` (both
-    uint8 CUDA [N,H,2W,3])."""
-    for t in (model_frames, sbs_color, sbs_mask, pasted, blended):
-        frames4(t)
+    uint8 CUDA [N,H,2W,3]).  All on one GPU, pixels packed; rows and frames may be strided, those of pasted and blended without overlap."""
+    frames4(sbs_color, name="sbs_color")
     N, H, W2 = (int(v) for v in sbs_color.shape[:3])
-    assert sbs_mask.shape == sbs_color.shape == pasted.shape == blended.shape and int(model_frames.shape[0]) == N
+    if W2 % 2:
+        raise ValueError(f"sbs_color must hold two eyes side by side, got a width of {W2}")
+    frames4(model_frames, name="model_frames", shape=(N, None, None, 3), device=sbs_color)
+    frames4(sbs_mask, name="sbs_mask", shape=tuple(sbs_color.shape), device=sbs_color)
+    frames4(pasted, name="pasted", shape=tuple(sbs_color.shape), device=sbs_color, output=True)
+    frames4(blended, name="blended", shape=tuple(sbs_color.shape), device=sbs_color, output=True)
     _lib.shared_context(sbs_color.device).call(
         "mdvt_adapter_composite_eye", W2 // 2, H, N, int(eye), model_frames.data_ptr(), int(model_frames.shape[2]), int(model_frames.shape[1]),
         model_frames.stride(1), model_frames.stride(0), sbs_color.data_ptr(), sbs_color.stride(1), sbs_color.stride(0),

@@ -43,8 +43,10 @@ def prepare_eye(sbs_color, sbs_mask, org, eye: int, image_size=(IMAGE_W, IMAGE_H
     """m2s:224-261 for one eye (0 = left, read mirrored; 1 = right) of uint8 CUDA [N,H,2W,3] colour and infill-mask frames and the
     original frames [N,oh,ow,3] -> (image [N,ih,iw,3], org_image [N,ih,iw,3], mask [N,mh,mw], hole counts int32 [N]), on the device."""
     import torch
-    frames4(sbs_color), frames4(sbs_mask), frames4(org)
-    assert sbs_color.shape == sbs_mask.shape and sbs_color.shape[2] % 2 == 0 and org.shape[0] == sbs_color.shape[0]
+    frames4(sbs_color, name="sbs_color"), frames4(sbs_mask, name="sbs_mask", shape=tuple(sbs_color.shape), device=sbs_color)
+    frames4(org, name="org", shape=(int(sbs_color.shape[0]), None, None, 3), device=sbs_color)
+    if sbs_color.shape[2] % 2:
+        raise ValueError(f"sbs_color must hold two eyes side by side, got a width of {int(sbs_color.shape[2])}")
     N, H, W2 = (int(v) for v in sbs_color.shape[:3])
     (iw, ih), (mw, mh) = image_size, mask_size
     dev = sbs_color.device

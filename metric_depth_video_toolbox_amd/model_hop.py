@@ -54,12 +54,13 @@ def build_depth_anything_v2(encoder: str = "vits", max_depth: int = 20, seed: in
 def depth_to_rgb_code(depth, max_depth: float, out=None):
     """f32 device tensor [N,H,W] metres -> uint8 [N,H,W,3] 16-bit depth code in R,G,B order
     (dfh:5-11 + dfh:48-61 with the channel order the render kernels read).  One launch for the batch:
-    the code is per pixel, so the batch is encoded as one (N*H) x W image."""
+    the code is per pixel, so the batch is encoded as one (N*H) x W image.  depth and out (where given, on depth's GPU) are contiguous."""
     import torch
-    assert depth.is_cuda and depth.dtype == torch.float32 and depth.dim() == 3 and depth.is_contiguous()
+    _lib.check_tensor("depth", depth, torch.float32, (None, None, None), contiguous=True)
     N, H, W = (int(v) for v in depth.shape)
     if out is None:
         out = torch.empty((N, H, W, 3), dtype=torch.uint8, device=depth.device)
+    _lib.check_tensor("out", out, torch.uint8, (N, H, W, 3), device=depth, contiguous=True)
     s = _lib.stream_arg(depth.device)
     group = max(1, 32767 // H)                      # a context takes at most 32767 rows
     for a in range(0, N, group):

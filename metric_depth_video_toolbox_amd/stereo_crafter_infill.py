@@ -43,8 +43,9 @@ def prepare_eye(sbs_color, sbs_mask, eye: int, model_size=(MODEL_W, MODEL_H)):
     """scr:101-126 for one eye (0 = left, read mirrored; 1 = right) of uint8 CUDA [N,H,2W,3] colour and infill-mask frames ->
     (image [N,mh,mw,3], mask [N,mh,mw], hole counts int32 [N]), all on the device."""
     import torch
-    frames4(sbs_color), frames4(sbs_mask)
-    assert sbs_color.shape == sbs_mask.shape and sbs_color.shape[2] % 2 == 0
+    frames4(sbs_color, name="sbs_color"), frames4(sbs_mask, name="sbs_mask", shape=tuple(sbs_color.shape), device=sbs_color)
+    if sbs_color.shape[2] % 2:
+        raise ValueError(f"sbs_color must hold two eyes side by side, got a width of {int(sbs_color.shape[2])}")
     N, H, W2 = (int(v) for v in sbs_color.shape[:3])
     mw, mh = model_size
     image = torch.empty((N, mh, mw, 3), dtype=torch.uint8, device=sbs_color.device)
@@ -64,11 +65,10 @@ def lhm_moments(frames, mask=None, out=None):
     frames4(frames)
     N, H, W = (int(v) for v in frames.shape[:3])
     if mask is not None:
-        frames4(mask, 1)
-        assert tuple(mask.shape) == (N, H, W)
+        frames4(mask, 1, name="mask", shape=(N, H, W), device=frames)
     if out is None:
         out = torch.empty((N, 10), dtype=torch.int64, device=frames.device)
-    assert out.is_contiguous() and out.dtype == torch.int64 and tuple(out.shape) == (N, 10)
+    _lib.check_tensor("out", out, torch.int64, (N, 10), device=frames, contiguous=True)
     _lib.shared_context(frames.device).call(
         "mdvt_lhm_moments", W, H, N, frames.data_ptr(), frames.stride(1), frames.stride(0),
         mask.data_ptr() if mask is not None else None, mask.stride(1) if mask is not None else 0, mask.stride(0) if mask is not None else 0,
@@ -108,14 +108,15 @@ def lhm_params(mom_x, mom_r, mom_r_all):
 
 
 def lhm_apply(frames, params, out=None):
-    """mdvt_lhm_apply: uint8 CUDA [N,H,W,3] and float64 CUDA [N,15] -> the matched frames."""
+    """mdvt_lhm_apply: uint8 CUDA [N,H,W,3] (rows and frames may be strided) and contiguous float64 CUDA [N,15] -> the matched
+    frames; out, where given: uint8 [N,H,W,3] on the same GPU, pixels packed, rows and frames strided without overlap."""
     import torch
     frames4(frames)
     N, H, W = (int(v) for v in frames.shape[:3])
-    assert params.is_cuda and params.dtype == torch.float64 and tuple(params.shape) == (N, 15) and params.is_contiguous()
+    _lib.check_tensor("params", params, torch.float64, (N, 15), device=frames, contiguous=True)
     if out is None:
         out = torch.empty((N, H, W, 3), dtype=torch.uint8, device=frames.device)
-    frames4(out)
+    frames4(out, name="out", shape=(N, H, W, 3), device=frames, output=True)
     _lib.shared_context(frames.device).call("mdvt_lhm_apply", W, H, N, frames.data_ptr(), frames.stride(1), frames.stride(0), params.data_ptr(),
                                             out.data_ptr(), out.stride(1), out.stride(0), _lib.stream_arg(frames.device))
     return out

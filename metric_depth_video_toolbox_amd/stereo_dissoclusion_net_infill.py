@@ -38,13 +38,13 @@ from .infill_clip import (add_common_flags, callable_from_spec, checked_model_fr
 
 def decode_depth_percent(depth_rgb, out=None):
     """decode_rgb_depth_frame(depth_rgb, 1.0, True) (sdn:95) per frame of uint8 CUDA [N,H,W,3] (rows and frames may be strided: an
-    eye's half of side-by-side frames) -> float32 [N,H,W]."""
+    eye's half of side-by-side frames) -> float32 [N,H,W]; out, where given, is that tensor, contiguous, on depth_rgb's GPU."""
     import torch
-    frames4(depth_rgb)
+    frames4(depth_rgb, name="depth_rgb", disjoint=False)      # (one call per frame: any frame stride)
     N, H, W = (int(v) for v in depth_rgb.shape[:3])
     if out is None:
         out = torch.empty((N, H, W), dtype=torch.float32, device=depth_rgb.device)
-    assert out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (N, H, W)
+    _lib.check_tensor("out", out, torch.float32, (N, H, W), device=depth_rgb, contiguous=True)
     ctx, stream = _lib.shared_context(depth_rgb.device, W, H), _lib.stream_arg(depth_rgb.device)
     for k in range(N):
         ctx.call("mdvt_decode_depth", depth_rgb[k].data_ptr(), depth_rgb.stride(1), out[k].data_ptr(), 4 * W, 1.0, 1.0, stream)
@@ -53,16 +53,15 @@ def decode_depth_percent(depth_rgb, out=None):
 
 def model_infill_finish(img, model, infill_mask, out=None):
     """mdvt_model_infill_finish (sdn:100-123 behind the model): uint8 CUDA [N,H,W,3] image, model image and infill mask (rows and
-    frames may be strided) -> the finished image; `img` itself is left untouched."""
+    frames may be strided; out's, where given, without overlap; all on one GPU) -> the finished image; `img` itself is left untouched."""
     import torch
-    for t in (img, model, infill_mask):
-        frames4(t)
-    assert img.shape == model.shape == infill_mask.shape
+    frames4(img, name="img")
+    frames4(model, name="model", shape=tuple(img.shape), device=img)
+    frames4(infill_mask, name="infill_mask", shape=tuple(img.shape), device=img)
     N, H, W = (int(v) for v in img.shape[:3])
     if out is None:
         out = torch.empty((N, H, W, 3), dtype=torch.uint8, device=img.device)
-    frames4(out)
-    assert out.shape == img.shape
+    frames4(out, name="out", shape=tuple(img.shape), device=img, output=True)
     _lib.shared_context(img.device).call(
         "mdvt_model_infill_finish", W, H, N, img.data_ptr(), img.stride(1), img.stride(0), model.data_ptr(), model.stride(1), model.stride(0),
         infill_mask.data_ptr(), infill_mask.stride(1), infill_mask.stride(0), out.data_ptr(), out.stride(1), out.stride(0), _lib.stream_arg(img.device))
@@ -71,7 +70,13 @@ def model_infill_finish(img, model, infill_mask, out=None):
 
 def sdiss_infill(img, infill_mask, depth_rgb, generate, out=None):
     """sdn:93-123 for one eye of a batch: uint8 CUDA [N,H,W,3] image, infill mask and coded depth (views of side-by-side frames are
-    fine) -> the infilled image.  Unlike the reference, `img` itself is left untouched."""
+    fine: pixels packed, rows and frames padded at will, not overlapping) -> the infilled image, in `out` where given (the same
+    layouts).  The model gets contiguous copies, the library the views themselves.  Unlike the reference, `img` itself is left untouched."""
+    frames4(img, name="img")                                  # (everything is held to its contract before the model runs)
+    frames4(infill_mask, name="infill_mask", shape=tuple(img.shape), device=img)
+    frames4(depth_rgb, name="depth_rgb", shape=tuple(img.shape), device=img, disjoint=False)
+    if out is not None:
+        frames4(out, name="out", shape=tuple(img.shape), device=img, output=True)
     image, mask = img.contiguous(), infill_mask.contiguous()
     predicted = checked_model_frames(generate(image, mask, decode_depth_percent(depth_rgb)), image)      # sdn:95-96
     return model_infill_finish(img, predicted, infill_mask, out)                              # sdn:100-123

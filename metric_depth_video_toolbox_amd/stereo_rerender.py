@@ -67,16 +67,19 @@ def master_fov_scale_depth(xfov, master_xfov):
 def infill_using_normals(color_img, hole_mask, normal_map, max_steps=400, out=None):
     """Device version of the reference's infill_using_normals (sr:155-240), same argument meaning:
     color_img uint8 [H,W,3], hole_mask bool/uint8 [H,W] (True = fill), normal_map float32 [H,W,3] whose XY
-    components give the march direction.  All CUDA tensors; returns a new uint8 [H,W,3] tensor."""
+    components give the march direction.  All tensors on one GPU, in any layout (a strided one is copied); returns a new uint8
+    [H,W,3] tensor, or `out` where given: a contiguous uint8 [H,W,3] tensor on that GPU."""
     import torch
-    assert color_img.is_cuda and color_img.dtype == torch.uint8 and color_img.dim() == 3 and color_img.shape[2] == 3
+    _lib.check_tensor("color_img", color_img, torch.uint8, (None, None, 3))
     H, W = int(color_img.shape[0]), int(color_img.shape[1])
+    _lib.check_tensor("hole_mask", hole_mask, (torch.bool, torch.uint8), (H, W), device=color_img)
+    _lib.check_tensor("normal_map", normal_map, torch.float32, (H, W, 3), device=color_img)
     color_img = color_img.contiguous()
     hole = hole_mask.to(torch.uint8).contiguous()
-    normal = normal_map.to(torch.float32).contiguous()
-    assert tuple(hole.shape) == (H, W) and tuple(normal.shape) == (H, W, 3)
+    normal = normal_map.contiguous()
     if out is None:
         out = torch.empty_like(color_img)
+    _lib.check_tensor("out", out, torch.uint8, (H, W, 3), device=color_img, contiguous=True)
     _lib.shared_context(color_img.device, W, H).call("mdvt_infill_using_normals", color_img.data_ptr(), 3 * W, hole.data_ptr(), W,
                                                      normal.data_ptr(), 12 * W, out.data_ptr(), 3 * W, int(max_steps),
                                                      _lib.stream_arg(color_img.device))
@@ -87,20 +90,21 @@ def infill_using_mask_normals(img, hole_mask, infill_mask, max_steps=400, out=No
     """sr:809-812 (--do_basic_infill) for whole batches: `infill_using_normals(image, bg_mask, infill_mask * 2 - 1)` with the
     normals taken straight from the finished infill-mask image ((u8 / 255) * 2 - 1 in f32, sr:808 + 810).  img, infill_mask: uint8
     CUDA [H,W,3] or [N,H,W,3]; hole_mask: uint8 / bool CUDA [H,W] or [N,H,W] (non-zero = hole); rows and images may be strided
-    (one half of side-by-side frames).  out None: a filled copy of img is returned; out given (may be img itself): filled in
+    (one half of side-by-side frames), pixels packed.  out None: a filled copy of img is returned; out given (may be img itself):
+    a uint8 tensor of img's shape on img's GPU, pixels packed, rows and images strided at will but not overlapping, filled in
     place after img has been copied into it."""
     import torch
-    assert img.is_cuda and img.dtype == torch.uint8 and img.dim() in (3, 4) and img.shape[-1] == 3
-    assert infill_mask.shape == img.shape and infill_mask.dtype == torch.uint8 and tuple(hole_mask.shape) == tuple(img.shape[:-1])
+    _lib.check_tensor("img", img, torch.uint8, (None, None, 3), ndim=(3, 4), packed=2)
+    _lib.check_tensor("infill_mask", infill_mask, torch.uint8, tuple(img.shape), device=img, packed=2)
+    _lib.check_tensor("hole_mask", hole_mask, (torch.bool, torch.uint8), tuple(img.shape[:-1]), device=img, packed=1)
     if hole_mask.dtype == torch.bool:
-        hole_mask = hole_mask.to(torch.uint8)
+        hole_mask = hole_mask.view(torch.uint8)
     if out is None:
-        out = img.clone()
-    elif out.data_ptr() != img.data_ptr():
-        out.copy_(img)
-    for t in (out, infill_mask):
-        assert t.stride(-1) == 1 and t.stride(-2) == 3, "pixels must be packed RGB"
-    assert hole_mask.stride(-1) == 1
+        out = img.clone(memory_format=torch.contiguous_format)
+    else:
+        _lib.check_tensor("out", out, torch.uint8, tuple(img.shape), device=img, packed=2, output=True)
+        if out.data_ptr() != img.data_ptr():
+            out.copy_(img)
     batched = img.dim() == 4
     N = int(img.shape[0]) if batched else 1
     H, W = int(img.shape[-3]), int(img.shape[-2])
@@ -115,13 +119,14 @@ def infill_using_mask_normals(img, hole_mask, infill_mask, max_steps=400, out=No
 def touchly_depth(depth, touchly_max_depth=5, touchly_min_depth=0, zero_is_far=False, out=None):
     """float32 CUDA depth [H,W] -> uint8 [H,W,3] Touchly reverse-depth plane (sr:549-551; with zero_is_far the
     variant used after a render, sr:689-691 / 825-829).  --touchly1 without a pose file is
-    vconcat([color_frame, touchly_depth(decode(depth_rgb) * scale)]) (sr:548-552)."""
+    vconcat([color_frame, touchly_depth(decode(depth_rgb) * scale)]) (sr:548-552).  The rows of depth may be strided; out, where
+    given, is a contiguous uint8 [H,W,3] tensor on depth's GPU."""
     import torch
-    assert depth.is_cuda and depth.dtype == torch.float32 and depth.dim() == 2 and depth.stride(1) == 1   # rows may be strided
+    _lib.check_tensor("depth", depth, torch.float32, (None, None), packed=1)                             # rows may be strided
     H, W = int(depth.shape[0]), int(depth.shape[1])
     if out is None:
         out = torch.empty((H, W, 3), dtype=torch.uint8, device=depth.device)
-    assert out.is_contiguous()
+    _lib.check_tensor("out", out, torch.uint8, (H, W, 3), device=depth, contiguous=True)
     _lib.shared_context(depth.device, W, H).call("mdvt_touchly_depth", depth.data_ptr(), 4 * depth.stride(0), out.data_ptr(), 3 * W,
                                                  float(touchly_max_depth), float(touchly_min_depth), int(bool(zero_is_far)),
                                                  _lib.stream_arg(depth.device))
@@ -148,14 +153,14 @@ def convert_to_equirectangular(image, input_fov=100, out=None):
     centred and everything outside the input fov black.  Rows / images may be strided views (e.g. one eye of a
     side-by-side buffer); pixels must be packed RGB."""
     import torch
-    assert image.is_cuda and image.dtype == torch.uint8 and image.dim() in (3, 4) and image.shape[-1] == 3
-    assert image.stride(-1) == 1 and image.stride(-2) == 3, "pixels must be packed RGB"
+    _lib.check_tensor("image", image, torch.uint8, (None, None, 3), ndim=(3, 4), packed=2)
     batched = image.dim() == 4
     N = int(image.shape[0]) if batched else 1
     H, W = int(image.shape[-3]), int(image.shape[-2])
     if out is None:
         out = torch.empty(tuple(image.shape), dtype=torch.uint8, device=image.device)
-    assert out.shape == image.shape and out.stride(-1) == 1 and out.stride(-2) == 3 and out.data_ptr() != image.data_ptr()
+    _lib.check_tensor("out", out, torch.uint8, tuple(image.shape), device=image, packed=2, output=True)
+    assert out.data_ptr() != image.data_ptr()
     key = (_lib.device_index(image.device), W, H, float(input_fov))
     if key not in _equirect_cache:
         mx, my = equirect_tables(W, H, input_fov)
@@ -171,12 +176,11 @@ def masked_blur(img, out=None):
     """Device version of the reference's masked_blur(img, ksize=(6,6), sigma=0) (sr:114-153): a 6x6 Gaussian that
     ignores pure black pixels.  uint8 CUDA [H,W,3] (rows may be strided) -> uint8 [H,W,3]."""
     import torch
-    assert img.is_cuda and img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == 3
-    assert img.stride(2) == 1 and img.stride(1) == 3, "pixels must be packed RGB"
+    _lib.check_tensor("img", img, torch.uint8, (None, None, 3), packed=2)
     H, W = int(img.shape[0]), int(img.shape[1])
     if out is None:
         out = torch.empty((H, W, 3), dtype=torch.uint8, device=img.device)
-    assert out.shape == img.shape and out.stride(2) == 1 and out.stride(1) == 3
+    _lib.check_tensor("out", out, torch.uint8, tuple(img.shape), device=img, packed=2, output=True)
     _lib.shared_context(img.device, W, H).call("mdvt_masked_blur", img.data_ptr(), img.stride(0), out.data_ptr(), out.stride(0),
                                                _lib.stream_arg(img.device))
     return out
@@ -433,27 +437,39 @@ class StereoRerenderer:
         Returns a PreparedRender whose launch() is a single C-ABI call -- use it when the same buffers
         are rendered into repeatedly (streaming loops, benchmarks).
         want_mask=False (with want_maskbits): no byte mask is written, the packed 1 bit/px mask is the hole mask -- where the
-        compaction is fused into the render kernel (pure-shift point frames; the library refuses elsewhere)."""
+        compaction is fused into the render kernel (pure-shift point frames; the library refuses elsewhere).
+        Every tensor is contiguous and on the renderer's GPU (the buffer table is written with the pitches of contiguous frames):
+        out_sbs uint8 [N,H,2W,3], out_mask uint8 [N,H,2W], out_depth float32 [N,H,2W] (used with want_depth), each with exactly the
+        N frames of depth_rgb -- for one [H,W,3] frame also without the leading 1.  All of this is checked here, once, and never
+        in launch()."""
         torch = self.torch
-        single = depth_rgb.dim() == 3
-        if single:
+        single = isinstance(depth_rgb, torch.Tensor) and depth_rgb.dim() == 3
+        if single and isinstance(color_rgb, torch.Tensor) and color_rgb.dim() == 3:
             depth_rgb, color_rgb = depth_rgb[None], color_rgb[None]
-        N, H, W = depth_rgb.shape[0], self.H, self.W
-        assert tuple(depth_rgb.shape) == (N, H, W, 3) and tuple(color_rgb.shape) == (N, H, W, 3), \
-            "color image and depth image need to have same width and height"          # sr:507
-        assert depth_rgb.dtype == torch.uint8 and color_rgb.dtype == torch.uint8
-        assert depth_rgb.is_cuda and color_rgb.is_cuda and depth_rgb.is_contiguous() and color_rgb.is_contiguous()
+        H, W = self.H, self.W
+        _lib.check_tensor("depth_rgb", depth_rgb, torch.uint8, (None, H, W, 3), device=self.device, contiguous=True)
+        N = int(depth_rgb.shape[0])
+        _lib.check_tensor("color_rgb", color_rgb, torch.uint8, (N, H, W, 3), device=self.device, contiguous=True)   # sr:507: same size
         arr = self.pack_params(params, N)
         dev = depth_rgb.device
-        sbs = out_sbs if out_sbs is not None else _lib.retry_after_release(lambda: torch.empty((N, H, 2 * W, 3), dtype=torch.uint8, device=dev))
-        assert want_mask or want_maskbits, "want_mask=False needs want_maskbits"
+
+        def given(name, t, dtype, shape):
+            if single and isinstance(t, torch.Tensor) and t.dim() == len(shape) - 1:
+                t = t[None]
+            return _lib.check_tensor(name, t, dtype, shape, device=self.device, contiguous=True, output=True)
+
+        sbs = given("out_sbs", out_sbs, torch.uint8, (N, H, 2 * W, 3)) if out_sbs is not None else \
+            _lib.retry_after_release(lambda: torch.empty((N, H, 2 * W, 3), dtype=torch.uint8, device=dev))
+        if not (want_mask or want_maskbits):
+            raise ValueError("want_mask=False needs want_maskbits")
         mask = None
         if want_mask:
-            mask = out_mask if out_mask is not None else _lib.retry_after_release(lambda: torch.empty((N, H, 2 * W), dtype=torch.uint8, device=dev))
-        assert tuple(sbs.shape[-3:]) == (H, 2 * W, 3) and (mask is None or tuple(mask.shape[-2:]) == (H, 2 * W))
+            mask = given("out_mask", out_mask, torch.uint8, (N, H, 2 * W)) if out_mask is not None else \
+                _lib.retry_after_release(lambda: torch.empty((N, H, 2 * W), dtype=torch.uint8, device=dev))
         zout = None
         if want_depth:
-            zout = out_depth if out_depth is not None else _lib.retry_after_release(lambda: torch.empty((N, H, 2 * W), dtype=torch.float32, device=dev))
+            zout = given("out_depth", out_depth, torch.float32, (N, H, 2 * W)) if out_depth is not None else \
+                _lib.retry_after_release(lambda: torch.empty((N, H, 2 * W), dtype=torch.float32, device=dev))
 
         io = _lib.MdvtIO()
         io.depth_rgb, io.depth_pitch, io.depth_stride = depth_rgb.data_ptr(), 3 * W, 3 * W * H
@@ -512,7 +528,8 @@ class StereoRerenderer:
     def finish_infill_mask_sbs(self, seed_sbs, out=None, max_rounds: int = 0, want_remaining: bool = False, no_host_wait: bool = False,
                                order: str = "levels"):
         """finish_infill_mask for side-by-side seed buffers [N,H,2W,3] (render(want_seed=True)["seed"]): both eyes of
-        all frames in one pass (mdvt_finish_infill_mask_stereo).  Returns [N,H,2W,3] (and, with want_remaining, an
+        all frames in one pass (mdvt_finish_infill_mask_stereo); seed_sbs and out are uint8 tensors on the renderer's GPU with packed
+        pixels, rows and frames strided at will (out's not overlapping).  Returns [N,H,2W,3] (and, with want_remaining, an
         int32 tensor [2,N]: left eyes, right eyes).  no_host_wait: the asynchronous form (max_rounds, default 256, levels are
         launched without reading the deepest level back: nothing waits on the stream).  order="heap": cv2.inpaint's own order
         (mdvt_finish_infill_mask_heap_stereo; see finish_infill_mask) in one context and one pass per launch."""
@@ -524,14 +541,13 @@ class StereoRerenderer:
         single = seed_sbs.dim() == 3
         if single:
             seed_sbs = seed_sbs[None]
-        assert seed_sbs.is_cuda and seed_sbs.dtype == torch.uint8 and tuple(seed_sbs.shape[1:]) == (H, 2 * W, 3)
-        assert seed_sbs.stride(-1) == 1 and seed_sbs.stride(-2) == 3, "pixels must be packed RGB"
+        _lib.check_tensor("seed_sbs", seed_sbs, torch.uint8, (None, H, 2 * W, 3), device=self.device, packed=2)
         N = int(seed_sbs.shape[0])
         if out is None:
             out = torch.empty((N, H, 2 * W, 3), dtype=torch.uint8, device=seed_sbs.device)
-        elif out.dim() == 3:
+        elif isinstance(out, torch.Tensor) and out.dim() == 3:
             out = out[None]
-        assert tuple(out.shape) == (N, H, 2 * W, 3) and out.stride(-1) == 1 and out.stride(-2) == 3
+        _lib.check_tensor("out", out, torch.uint8, (N, H, 2 * W, 3), device=self.device, packed=2, output=True)
         rem = torch.empty((2, N), dtype=torch.int32, device=seed_sbs.device) if want_remaining else None
         s = torch.cuda.current_stream(seed_sbs.device)
 
@@ -584,20 +600,19 @@ class StereoRerenderer:
         """sr:803-808 + 816 on the device: seed image(s) from render(want_seed=True) -> the finished infill-mask
         image(s): Telea-weighted inpaint of the key-coloured / black pixels (level by level, see include/mdvt.h),
         key-coloured pixels keep the inpainted normal, then masked_blur.  seed: uint8 CUDA [H,W,3] or [N,H,W,3],
-        rows / images may be strided (e.g. one eye of the side-by-side seed buffer).  Returns the image(s)
+        rows / images may be strided (e.g. one eye of the side-by-side seed buffer); out, where given, likewise: uint8 of seed's
+        shape on the renderer's GPU, pixels packed, no two rows or images overlapping.  Returns the image(s)
         (and, with want_remaining, an int32 tensor [N] of key-coloured pixels the front did not reach).
         order="heap": the inpaint in cv2.inpaint's own order, byte-exact to the reference's sequential heap
         (mdvt_finish_infill_mask_heap; opt-in, much slower than the default "levels"); no max_rounds."""
         self._check_order(order, max_rounds)
         torch = self.torch
-        assert seed.is_cuda and seed.dtype == torch.uint8 and seed.dim() in (3, 4) and seed.shape[-1] == 3
-        assert seed.stride(-1) == 1 and seed.stride(-2) == 3, "pixels must be packed RGB"
-        assert tuple(seed.shape[-3:-1]) == (self.H, self.W)
+        _lib.check_tensor("seed", seed, torch.uint8, (self.H, self.W, 3), ndim=(3, 4), device=self.device, packed=2)
         batched = seed.dim() == 4
         N = int(seed.shape[0]) if batched else 1
         if out is None:
             out = torch.empty(tuple(seed.shape), dtype=torch.uint8, device=seed.device)
-        assert out.shape == seed.shape and out.stride(-1) == 1 and out.stride(-2) == 3
+        _lib.check_tensor("out", out, torch.uint8, tuple(seed.shape), device=self.device, packed=2, output=True)
         rem = torch.empty(N, dtype=torch.int32, device=seed.device) if want_remaining else None
         s = _lib.stream_arg(seed.device)
         if order == "heap":
@@ -626,10 +641,10 @@ class StereoRerenderer:
 
     def edge_filter(self, depth_rgb, params, of_by_one: Optional[bool] = None, stream=None):
         """The filter part of dmt.get_mesh_from_depth_map(remove_edges=True) for one frame:
-        -> (tri_invalid u8[2(H-1)(W-1)] in draw order, unused u8[H*W])."""
+        depth_rgb a contiguous uint8 [H,W,3] tensor on the renderer's GPU -> (tri_invalid u8[2(H-1)(W-1)] in draw order, unused u8[H*W])."""
         torch = self.torch
         H, W = self.H, self.W
-        assert tuple(depth_rgb.shape) == (H, W, 3) and depth_rgb.is_cuda and depth_rgb.is_contiguous()
+        _lib.check_tensor("depth_rgb", depth_rgb, torch.uint8, (H, W, 3), device=self.device, contiguous=True)
         dev = depth_rgb.device
         tri = torch.empty(2 * (H - 1) * (W - 1), dtype=torch.uint8, device=dev)
         unused = torch.empty(H * W, dtype=torch.uint8, device=dev)
@@ -642,11 +657,11 @@ class StereoRerenderer:
 
     def edge_point_pixels(self, depth_rgb, params, how: int = 0, stream=None):
         """Where the edge point of every vertex of a frame lands (sr:589-606, 727-735, 745-750, 838-858) ->
-        int32[H*W, 2 eyes, 2 (x, y)], INT32_MIN outside the frame.  how = 0: the reference's f64 chain per vertex; 1: as the
+        int32[H*W, 2 eyes, 2 (x, y)], INT32_MIN outside the frame; depth_rgb a contiguous uint8 [H,W,3] tensor on the renderer's GPU.  how = 0: the reference's f64 chain per vertex; 1: as the
         row kernels of a pure-shift frame take it (mdvt.h)."""
         torch = self.torch
         H, W = self.H, self.W
-        assert tuple(depth_rgb.shape) == (H, W, 3) and depth_rgb.is_cuda and depth_rgb.is_contiguous()
+        _lib.check_tensor("depth_rgb", depth_rgb, torch.uint8, (H, W, 3), device=self.device, contiguous=True)
         px = torch.empty((H * W, 2, 2), dtype=torch.int32, device=depth_rgb.device)
         self.ctx.call("mdvt_edge_point_pixels", C.byref(params), depth_rgb.data_ptr(), 3 * W, int(how),
                       px.data_ptr(), _lib.stream_arg(depth_rgb.device, stream))

@@ -143,6 +143,10 @@ def centers(depth_rgb, params, renderer, *, stream=None):
         raise ValueError(f"depth frames are {int(depth_rgb.shape[2])}x{int(depth_rgb.shape[1])}, the renderer's {renderer.W}x{renderer.H}")
     if not (depth_rgb.stride(-1) == 1 and depth_rgb.stride(-2) == 3):
         raise ValueError("depth_rgb must have packed 3-byte pixels (rows and frames may be padded)")
+    if depth_rgb.stride(1) < 3 * renderer.W or (N > 1 and depth_rgb.stride(0) < renderer.H * depth_rgb.stride(1)):
+        raise ValueError(f"depth_rgb: rows or frames overlap (they may be padded, not folded: strides {tuple(depth_rgb.stride())})")
+    if depth_rgb.device.index != renderer.device:
+        raise ValueError(f"depth_rgb is on {depth_rgb.device}, the renderer on cuda:{renderer.device}")
     arr = renderer.pack_params(params, N)
     dev = depth_rgb.device
     s = torch.cuda.current_stream(dev) if stream is None else stream
@@ -186,6 +190,10 @@ def render_view(depth_rgb, color_rgb, views, params, renderer, *, want_mask: boo
     for name, t in (("depth_rgb", depth_rgb), ("color_rgb", color_rgb)):
         if not t.is_cuda or t.dtype != torch.uint8 or tuple(t.shape) != (N, H, W, 3) or not (t.stride(-1) == 1 and t.stride(-2) == 3):
             raise ValueError(f"{name} must be a uint8 CUDA tensor [N, {H}, {W}, 3] with packed pixels")
+        if t.stride(1) < 3 * W or (N > 1 and t.stride(0) < H * t.stride(1)):
+            raise ValueError(f"{name}: rows or frames overlap (they may be padded, not folded: strides {tuple(t.stride())})")
+        if t.device.index != renderer.device:
+            raise ValueError(f"{name} is on {t.device}, the renderer on cuda:{renderer.device}")
     arr = view_params(renderer.pack_params(params, N), views)
     dev = depth_rgb.device
     s = torch.cuda.current_stream(dev) if stream is None else stream

@@ -467,7 +467,7 @@ def test_errors_are_reported_not_swallowed(mods):
     with pytest.raises(ValueError):
         r.frame_params()
     bad = torch.zeros((48, 60, 3), dtype=torch.uint8, device="cuda")
-    with pytest.raises(AssertionError):
+    with pytest.raises(ValueError):
         r.render(bad, bad, r.frame_params(xfov=45.0))
     p = r.frame_params(xfov=45.0)
     p.Krender[2] = 100.0           # render size != frame size (--vr180) is not built
