@@ -1,4 +1,5 @@
-// mdvt_device.h -- device-side helpers shared by the kernel translation units (mdvt_kernels.hip, mdvt_mesh_*.hip, mdvt_formats.hip, ...).
+// mdvt_device.h -- device-side helpers shared by the kernel translation units (mdvt_points_edge_rows.hip, mdvt_general_paths.hip,
+// mdvt_mesh_*.hip, mdvt_formats.hip, ...).
 //
 // Arithmetic decree: every f32 expression below is one IEEE operation per node, the
 // translation unit is compiled with -ffp-contract=off and divisions are the correctly rounded ones --

@@ -173,7 +173,8 @@ struct MsaaArgs {
     int32_t mode, cull, pattern, resolve;     // mdvt_config: mode, cull, sample_pattern, sample_resolve
     uint32_t key_rgb;            // R | G<<8 | B<<16
 };
-// The rasterising translation units (mdvt_kernels.hip, mdvt_mesh_*.hip) are compiled once per sub-pixel grid;
+// The rasterising translation units (mdvt_points_edge_rows.hip, mdvt_general_paths.hip, mdvt_mesh_*.hip, mdvt_msaa.hip, mdvt_near_clip.hip)
+// and launch_render's dispatch (mdvt_render_dispatch.hip) are compiled once per sub-pixel grid;
 // what they define is declared in mdvt_grid_decls.h, once per grid namespace (below, after the shared declarations).
 // (mdvt_normal_infill.hip; workspace: normal_infill_workspace_bytes(1, W, H))
 hipError_t launch_infill_normals(const uint8_t* color, size_t color_pitch, const uint8_t* hole, size_t hole_pitch,

@@ -1,7 +1,7 @@
 // mdvt_mesh_band.hip -- MESH MODE, pure stereo shift: the reference's default draw mode (dmt:1243-1254 rendered by
 // dmt:1422-1572 after sr:724-725 / 832-836), one workgroup per (frame, band of output rows), z-buffer in LDS.
 //
-// Same results as k_mesh_rows (mdvt_kernels.hip) and the oracle -- the arithmetic decree of DESIGN.md section 3 is
+// Same results as k_mesh_rows (mdvt_mesh_rows.hip) and the oracle -- the arithmetic decree of DESIGN.md section 3 is
 // untouched -- but organised around what the pure shift makes cheap:
 //
 //   * every vertex row is a horizontal line on screen (v = grid y), so output scanline k is covered by exactly one row

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Is the device code of two sets of ISA listings the same?  For a change that only moves kernels between translation units.
-    make -C metric_depth_video_toolbox_amd/csrc asm SRC=mdvt_kernels [ASMFLAGS=-DMDVT_TUNING]     (one listing per unit and variant)
+    make -C metric_depth_video_toolbox_amd/csrc asm SRC=mdvt_mesh_rows [ASMFLAGS=-DMDVT_TUNING]     (one listing per unit and variant)
     python tools/isa_same.py before/ after/            (a set = directories of *.s and / or single listings, comma separated)
 Every function of a listing (kernels and the device functions the compiler did not inline) is compared by name: its text with
 comments stripped and the function-local label numbers (.LBB<n>_, .Ltmp<n>) normalised, and, for a kernel, every .amdhsa_ field
