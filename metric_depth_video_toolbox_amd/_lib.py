@@ -51,6 +51,10 @@ INFILL_ENGINE_SYMBOLS = ("mdvt_m2svid_prepare_eye", "mdvt_model_infill_finish")
 # the entry point include/mdvt_view.h declares (the free-camera viewer's vertex centres), likewise
 VIEW_SYMBOLS = ("mdvt_view_centers", "mdvt_render_view_batch")
 
+# the entry points include/mdvt_geometry.h declares (per-frame vertex and triangle lists, grey depth), likewise.  They are bound here
+# and have no wrapper in the package yet: tools/export_depth_geometry.py calls them
+GEOMETRY_SYMBOLS = ("mdvt_export_geometry_batch", "mdvt_depth_grey_batch")
+
 
 class MdvtError(RuntimeError):
     def __init__(self, code: int, text: str):
@@ -78,6 +82,18 @@ class MdvtViewIO(C.Structure):
                 ("mask", C.c_void_p), ("mask_pitch", C.c_size_t), ("mask_stride", C.c_size_t),
                 ("depth", C.c_void_p), ("zout_pitch", C.c_size_t), ("zout_stride", C.c_size_t),
                 ("hole_counts", C.c_void_p)]
+
+
+class MdvtGeometryOpts(C.Structure):
+    _fields_ = [("decode", C.c_int32), ("remove_edges", C.c_int32), ("reserved", C.c_int32 * 2), ("max_depth", C.c_double)]
+
+
+class MdvtGeometryIO(C.Structure):
+    _fields_ = [("depth_rgb", C.c_void_p), ("depth_pitch", C.c_size_t), ("depth_stride", C.c_size_t),
+                ("color_rgb", C.c_void_p), ("color_pitch", C.c_size_t), ("color_stride", C.c_size_t),
+                ("vertices", C.c_void_p), ("vertices_stride", C.c_size_t), ("triangles", C.c_void_p), ("triangles_stride", C.c_size_t),
+                ("used_index", C.c_void_p), ("used_stride", C.c_size_t), ("points", C.c_void_p), ("points_stride", C.c_size_t),
+                ("point_rgb", C.c_void_p), ("point_rgb_stride", C.c_size_t), ("counts", C.c_void_p)]
 
 
 class MdvtIO(C.Structure):
@@ -221,6 +237,10 @@ def load():
     L.mdvt_view_centers.argtypes = [vp, C.c_int, C.POINTER(MdvtFrameParams), vp, st, st, vp, vp]
     L.mdvt_render_view_batch.restype = C.c_int
     L.mdvt_render_view_batch.argtypes = [vp, C.c_int, C.POINTER(MdvtFrameParams), C.POINTER(MdvtViewIO), vp]
+    L.mdvt_export_geometry_batch.restype = C.c_int
+    L.mdvt_export_geometry_batch.argtypes = [vp, C.c_int, C.POINTER(MdvtFrameParams), C.POINTER(MdvtGeometryOpts), C.POINTER(MdvtGeometryIO), vp]
+    L.mdvt_depth_grey_batch.restype = C.c_int
+    L.mdvt_depth_grey_batch.argtypes = [vp, C.c_int, vp, st, st, C.c_double, C.c_int, vp, st, st, vp]
     # the HIP calls SharedContext orders its streams with, reached through the library's own link to the HIP runtime (dlsym
     # searches a library's dependencies), so the events belong to the runtime the kernels are launched by
     L.hipEventCreateWithFlags.restype = C.c_int

@@ -2,10 +2,12 @@
 // (ensure_workspace; its layout is mdvt_workspace.h), the multisampled and near-clipping renders, mdvt_render_stereo_batch as a list of
 // steps, and the entry points beside it that stage frame parameters (mdvt_edge_point_pixels, mdvt_edge_filter) or read the workspace
 // (mdvt_debug_read), and the viewer's two calls (include/mdvt_view.h): mdvt_render_view_batch, the batch render with one eye's work,
-// and mdvt_view_centers, which stages the parameters and runs the edge filter.  Host code only; compiled with -ffp-contract=off (the f64 composition of the eye matrices below is part of the
+// and mdvt_view_centers, which stages the parameters and runs the edge filter, and the geometry export's two calls (include/mdvt_geometry.h):
+// mdvt_export_geometry_batch, in launch sets on a scratch block of its own, and mdvt_depth_grey_batch.  Host code only; compiled with -ffp-contract=off (the f64 composition of the eye matrices below is part of the
 // arithmetic decree).
 #include "mdvt_context.h"
 #include "mdvt_view.h"
+#include "mdvt_geometry.h"
 
 #include <math.h>
 
@@ -900,6 +902,109 @@ int mdvt_view_centers(mdvt_ctx* c, int n_frames, const mdvt_frame_params* params
         MDVT_HIP(c, mdvt::launch_view_centers(a, s));
     }
     MDVT_HIP(c, hipEventRecord(slot->done, s));
+    return MDVT_OK;
+}
+
+// The geometry export (include/mdvt_geometry.h; mdvt_geometry.hip).  Launch sets: as many frames as the ctx's workspace budget affords.
+int mdvt_export_geometry_batch(mdvt_ctx* c, int n_frames, const mdvt_frame_params* params, const mdvt_geometry_opts* opts,
+                               const mdvt_geometry_io* io, void* stream)
+{
+    if (!c) return MDVT_ERR_INVALID_ARG;
+    if (n_frames < 1 || !params || !opts || !io) return fail(c, MDVT_ERR_INVALID_ARG, "n_frames/params/opts/io invalid");
+    if (!io->depth_rgb || !io->counts) return fail(c, MDVT_ERR_INVALID_ARG, "depth_rgb and counts are required");
+    if (io->point_rgb && !io->color_rgb) return fail(c, MDVT_ERR_INVALID_ARG, "point_rgb needs color_rgb");
+    const int W = c->W, H = c->H;
+    if (W < 2 || H < 2) return fail(c, MDVT_ERR_INVALID_ARG, "the geometry export needs at least a 2x2 frame");
+    if ((uint64_t)W * (uint64_t)H > ((uint64_t)1 << 28)) return fail(c, MDVT_ERR_UNSUPPORTED, "frame too large for the geometry export (%d x %d)", W, H);
+    if (opts->decode != 0 && opts->decode != 1) return fail(c, MDVT_ERR_UNSUPPORTED, "decode must be 0 (the exporter's) or 1 (the render's)");
+    if (opts->reserved[0] || opts->reserved[1]) return fail(c, MDVT_ERR_UNSUPPORTED, "mdvt_geometry_opts.reserved must be 0");
+    if (!(opts->max_depth > 0.0)) return fail(c, MDVT_ERR_INVALID_ARG, "max_depth must be > 0");
+    const size_t N = (size_t)W * (size_t)H, ncell = (size_t)(W - 1) * (size_t)(H - 1);
+    if (io->depth_pitch < (size_t)3 * W || (io->color_rgb && io->color_pitch < (size_t)3 * W)) return fail(c, MDVT_ERR_INVALID_ARG, "pitch smaller than one row");
+    const bool many = n_frames > 1;
+    if (many && (io->depth_stride < io->depth_pitch * (size_t)H || (io->color_rgb && io->color_stride < io->color_pitch * (size_t)H)))
+        return fail(c, MDVT_ERR_INVALID_ARG, "input stride smaller than one frame");
+    if (many && ((io->vertices && io->vertices_stride < 24 * N) || (io->triangles && io->triangles_stride < 24 * ncell) ||
+                 (io->used_index && io->used_stride < 4 * N) || (io->points && io->points_stride < 24 * N) ||
+                 (io->point_rgb && io->point_rgb_stride < 3 * N)))
+        return fail(c, MDVT_ERR_INVALID_ARG, "output stride smaller than a full frame's list");
+    if (!aligned(io->vertices, 8) || !aligned(io->points, 8) || (many && ((io->vertices && io->vertices_stride % 8) || (io->points && io->points_stride % 8))))
+        return fail(c, MDVT_ERR_INVALID_ARG, "vertices and points (and their strides) must be 8-byte aligned");
+    if (!aligned(io->triangles, 4) || !aligned(io->used_index, 4) || !aligned(io->counts, 4) ||
+        (many && ((io->triangles && io->triangles_stride % 4) || (io->used_index && io->used_stride % 4))))
+        return fail(c, MDVT_ERR_INVALID_ARG, "triangles, used_index and counts (and their strides) must be 4-byte aligned");
+    std::vector<FrameDev> fd((size_t)n_frames);
+    for (int k = 0; k < n_frames; ++k) {
+        const mdvt_frame_params& p = params[k];
+        FrameDev& f = fd[(size_t)k];
+        if (!(p.K[0] > 0.0) || !(p.K[4] > 0.0)) return fail(c, MDVT_ERR_INVALID_ARG, "camera matrix needs positive focal lengths");
+        if (!(p.depth_scale > 0.0)) return fail(c, MDVT_ERR_INVALID_ARG, "depth_scale must be > 0");
+        if (p.has_T && (fabs(p.T[12]) > 1e-12 || fabs(p.T[13]) > 1e-12 || fabs(p.T[14]) > 1e-12 || fabs(p.T[15] - 1.0) > 1e-12))
+            return fail(c, MDVT_ERR_UNSUPPORTED, "pose matrix must be affine (last row 0 0 0 1)");
+        memset(&f, 0, sizeof f);
+        f.mult = opts->decode ? (float)(opts->max_depth / 4228250625.0) : (float)(4228250625.0 / opts->max_depth);       // dfh:22; cmf:652 (the divisor)
+        f.scale = (float)p.depth_scale;
+        f.sx = (float)(((double)W + 1.0) / (double)W);
+        f.sy = (float)(((double)H + 1.0) / (double)H);
+        f.Kd[0] = p.K[0]; f.Kd[1] = p.K[4]; f.Kd[2] = p.K[2]; f.Kd[3] = p.K[5];
+        f.rKd[0] = 1.0 / p.K[0]; f.rKd[1] = 1.0 / p.K[4];
+        f.has_T = p.has_T ? 1 : 0;
+        if (p.has_T) memcpy(f.Td, p.T, sizeof f.Td);
+        f.div_slot = -1;
+    }
+    DeviceGuard g(c->device);
+    hipStream_t const s = (hipStream_t)stream;
+    mdvt::GeometryArgs a{};
+    a.npx = (uint32_t)N; a.ncell = (uint32_t)ncell;
+    a.nbt = (uint32_t)((2 * ncell + mdvt::kGeomBlock - 1) / mdvt::kGeomBlock);
+    a.nbv = (uint32_t)((N + mdvt::kGeomBlock - 1) / mdvt::kGeomBlock);
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t flag_bytes = opts->remove_edges ? up16(2 * ncell) : 0, total_bytes = up16(((size_t)a.nbt + a.nbv) * sizeof(uint32_t));
+    const int fchunk = slots_afforded(c, flag_bytes + total_bytes, n_frames < 4096 ? n_frames : 4096);
+    MDVT_HIP(c, scratch_reserve(c, c->scratch[SCR_GEOMETRY], (size_t)fchunk * (flag_bytes + total_bytes), s));
+    const FrameDev* dfp = nullptr;
+    ParamSlot* slot = nullptr;
+    if (int rc = stage_params(c, fd, s, &dfp, &slot)) return rc;
+    a.depth = io->depth_rgb; a.depth_pitch = io->depth_pitch; a.depth_stride = io->depth_stride;
+    a.color = io->color_rgb; a.color_pitch = io->color_pitch; a.color_stride = io->color_stride;
+    a.vertices = io->vertices; a.vertices_stride = io->vertices_stride;
+    a.triangles = io->triangles; a.triangles_stride = io->triangles_stride;
+    a.used_index = io->used_index; a.used_stride = io->used_stride;
+    a.points = io->points; a.points_stride = io->points_stride;
+    a.point_rgb = io->point_rgb; a.point_rgb_stride = io->point_rgb_stride;
+    a.counts = io->counts;
+    a.fp = dfp; a.W = W; a.H = H; a.decode = opts->decode;
+    a.totals = c->scratch[SCR_GEOMETRY].as<uint32_t>();
+    a.flags = opts->remove_edges ? c->scratch[SCR_GEOMETRY].p + (size_t)fchunk * total_bytes : nullptr;
+    a.flags_stride = flag_bytes;
+    for (int f0 = 0; f0 < n_frames; f0 += fchunk) {
+        a.frame0 = f0;
+        a.n_frames = n_frames - f0 < fchunk ? n_frames - f0 : fchunk;
+        MDVT_HIP(c, mdvt::launch_export_geometry(a, s));
+    }
+    MDVT_HIP(c, hipEventRecord(slot->done, s));
+    return MDVT_OK;
+}
+
+// The grey depth of cmf:752-760 (include/mdvt_geometry.h): no workspace, no frame parameters.
+int mdvt_depth_grey_batch(mdvt_ctx* c, int n_frames, const uint8_t* d_depth_rgb, size_t pitch, size_t stride, double max_depth, int bits,
+                          void* d_out, size_t out_pitch, size_t out_stride, void* stream)
+{
+    if (!c) return MDVT_ERR_INVALID_ARG;
+    if (n_frames < 1 || !d_depth_rgb || !d_out) return fail(c, MDVT_ERR_INVALID_ARG, "n_frames/buffers invalid");
+    if (bits != 8 && bits != 16) return fail(c, MDVT_ERR_INVALID_ARG, "bits must be 8 or 16");
+    if (!(max_depth > 0.0)) return fail(c, MDVT_ERR_INVALID_ARG, "max_depth must be > 0");
+    const int W = c->W, H = c->H;
+    const size_t out_row = bits == 16 ? (size_t)2 * W : (size_t)3 * W;
+    if (pitch < (size_t)3 * W || out_pitch < out_row) return fail(c, MDVT_ERR_INVALID_ARG, "pitch smaller than one row");
+    if (n_frames > 1 && (stride < pitch * (size_t)H || out_stride < out_pitch * (size_t)H)) return fail(c, MDVT_ERR_INVALID_ARG, "stride smaller than one frame");
+    if (bits == 16 && (!aligned(d_out, 2) || (H > 1 && out_pitch % 2) || (n_frames > 1 && out_stride % 2)))
+        return fail(c, MDVT_ERR_INVALID_ARG, "a 16-bit output (its pitch and stride) must be 2-byte aligned");
+    if ((uint64_t)W * (uint64_t)H > ((uint64_t)1 << 28)) return fail(c, MDVT_ERR_UNSUPPORTED, "frame too large for the grey depth (%d x %d)", W, H);
+    DeviceGuard g(c->device);
+    const float divisor = (float)(4228250625.0 / max_depth);                                              // cmf:652
+    const float mult = bits == 16 ? (float)(65025.0 / max_depth) : (float)(255.0 / max_depth);            // cmf:753, 757
+    MDVT_HIP(c, mdvt::launch_depth_grey(d_depth_rgb, pitch, stride, divisor, mult, bits, d_out, out_pitch, out_stride, W, H, n_frames, (hipStream_t)stream));
     return MDVT_OK;
 }
 

@@ -55,6 +55,7 @@ enum ScratchId {
     SCR_ADAPTER,                      // mdvt_adapter_composite_eye: the listed-pixel workspace of one eye-sized image, its marks image, grown plane and row-blurred plane
     SCR_FFV1_STREAM,                  // mdvt_decode_video_stream: per slice of the call its offset, payload bytes and cell claim, per frame its kind
     SCR_VIEW,                         // mdvt_view_centers: per frame of a launch set its chunk sums (24 B per 8192 vertices); parking: also the edge filter's vertex flags (1 B/px)
+    SCR_GEOMETRY,                     // mdvt_export_geometry_batch: per frame of a launch set the filter's triangle flags (2 B per cell) and the compaction's workgroup totals (4 B per 256 triangles / vertices)
     SCR_COUNT
 };
 

@@ -306,6 +306,29 @@ struct ViewCentersArgs {
     double* centers;                                               // the caller's, at the batch's first frame
 };
 hipError_t launch_view_centers(const ViewCentersArgs& a, hipStream_t s);
+// mdvt_geometry.hip: the geometry export (mdvt_export_geometry_batch, mdvt_depth_grey_batch; include/mdvt_geometry.h), one launch set
+constexpr uint32_t kGeomBlock = 256;                               // items (triangles, or vertices) a workgroup of the compaction counts and scatters
+constexpr uint32_t kGeomScan = 256;                                // workgroup totals one step of the scan takes
+struct GeometryArgs {
+    const uint8_t* depth; size_t depth_pitch, depth_stride;        // the batch's first frame
+    const uint8_t* color; size_t color_pitch, color_stride;        // likewise, or null
+    double* vertices; size_t vertices_stride;                      // the caller's outputs at the batch's first frame; each may be null
+    int32_t* triangles; size_t triangles_stride;
+    int32_t* used_index; size_t used_stride;
+    double* points; size_t points_stride;
+    uint8_t* point_rgb; size_t point_rgb_stride;
+    uint32_t* counts;                                              // [batch][2] = {U, M}
+    const FrameDev* fp;                                            // device array, one per frame of the batch: mult (decode 0: the divisor), scale, Kd, rKd, sx, sy, has_T, Td
+    int frame0, n_frames;                                          // the set's first frame within the batch, its frames
+    int W, H, decode;
+    uint32_t npx, ncell;                                           // vertices and cells of a frame (2 ncell triangles)
+    uint32_t nbt, nbv;                                             // workgroups of kGeomBlock triangles / vertices of a frame
+    uint8_t* flags; size_t flags_stride;                           // workspace [n_frames][2 ncell]: 1 = removed, in draw order; null: nothing is removed
+    uint32_t* totals;                                              // workspace [n_frames][nbt + nbv]: kept items per workgroup, after the scan those before it
+};
+hipError_t launch_export_geometry(const GeometryArgs& a, hipStream_t s);
+hipError_t launch_depth_grey(const uint8_t* depth, size_t pitch, size_t stride, float divisor, float mult, int bits, void* out,
+                             size_t out_pitch, size_t out_stride, int W, int H, int n_frames, hipStream_t s);
 // mdvt_metric_align.hip: the scale-and-shift fit and the metric depth codes (include/mdvt_metric_align.h)
 constexpr uint32_t kFitSetChunks = 1024;                           // chunks of 8192 elements per launch set of the fit
 struct FitPlane {

@@ -1,0 +1,281 @@
+#!/usr/bin/env python3
+"""The reference's convert_metric_depth_video_to_other_format.py (cmf:) on the device: per-frame point clouds (--save_ply) and meshes
+(--save_obj) of a depth video, and its grey depth (--bit8, --bit16), with the reference's flag names.
+
+    python tools/export_depth_geometry.py --depth_video x.mkv --xfov 60 --save_ply out_ply --save_obj out_obj --remove_edges
+
+The geometry comes from mdvt_export_geometry_batch and the grey depth from mdvt_depth_grey_batch (include/mdvt_geometry.h), bound in
+_lib.py; the package has no wrapper for them yet (its tensor contract record is the follow-up), so this tool hands the tensors over
+itself, as the other tools do.  Frames go up in batches; the lists come back by their counts only -- `counts` first, then U or M
+entries per frame -- and are written by metric_depth_video_toolbox_amd/geometry_files.py (its docstring states the files' layouts, a
+decree of this project: Open3D's exact bytes cannot be observed without Open3D).
+
+Frame bounds are the reference loop's own, quirks included (cmf:639-641, 765-766): with --min_frames m the frames 0 .. m are skipped
+(m + 1 frames, not m), and with --max_frames M the loop stops after frame M + 1 (exported_frames below)."""
+import argparse
+import contextlib
+import ctypes as C
+import json
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+REFUSED = {                                              # flag -> why the device path does not take it
+    "track_file": "--track_file starts the host 3D reconstruction from 2D tracks (cmf:609-614, 700-730, 773 ff.), which is not built",
+    "mask_video": "--mask_video filters the 2D tracks of --track_file (cmf:659-685), host reconstruction that is not built",
+    "strict_mask": "--strict_mask belongs to --mask_video and --track_file (cmf:675-683), host reconstruction that is not built",
+    "merge_close_points": "--merge_close_points merges tracked points on the host (cmf:719-724, 776-777), which is not built",
+    "save_alembic": "--save_alembic writes an Alembic file through Blender's exporter, which is not built",
+    "use_triangulated_points": "--use_triangulated_points needs the triangulation of --track_file, host reconstruction that is not built",
+    "save_rescaled_depth": "--save_rescaled_depth writes the depth rescaled to the triangulated points (cmf:612-614), which is not built",
+    "global_align": "--global_align aligns the depth to the triangulated depth on the host, which is not built",
+    "show_scene_point_clouds": "--show_scene_point_clouds opens an Open3D window",
+    "show_both_point_clouds": "--show_both_point_clouds opens an Open3D window",
+}
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description="Convert a rgb encoded metric depth video to point clouds, meshes or a grey depth video")
+    p.add_argument("--depth_video", type=str, required=True, help="video file to use as input (.mkv, or a .npy frame dump)")
+    p.add_argument("--bit16", action="store_true", help="write the 16-bit grey depth as <depth_video>_grey_depth.npy (uint16 [N, H, W]): the FFV1 "
+                   "writer has no 16-bit grey and the reader refuses grey video, so the frames are a dump, not an .mkv")
+    p.add_argument("--bit8", action="store_true", help="write the 8-bit grey depth as <depth_video>_grey_depth.mkv (.npy for a .npy input)")
+    p.add_argument("--max_depth", default=100, type=int, help="the max depth that the video uses")
+    p.add_argument("--save_ply", type=str, help="folder to save .ply pointcloud files in ({frame:07d}.ply)")
+    p.add_argument("--save_obj", type=str, help="folder to save .obj mesh files in ({frame:07d}.obj)")
+    p.add_argument("--color_video", type=str, help="video file to use as color input (default: the depth video's own bytes, cmf:636-637)")
+    p.add_argument("--xfov", type=float, help="fov in deg in the x-direction, calculated from aspectratio and yfov in not given")
+    p.add_argument("--yfov", type=float, help="fov in deg in the y-direction, calculated from aspectratio and xfov in not given")
+    p.add_argument("--min_frames", default=-1, type=int, help="start convertion after nr of frames; as the reference's loop has it the frames "
+                   "0 .. min_frames are skipped (min_frames + 1 of them)")
+    p.add_argument("--max_frames", default=-1, type=int, help="quit after max_frames nr of frames; as the reference's loop has it the last frame "
+                   "taken is max_frames + 1")
+    p.add_argument("--transformation_file", type=str, help="file with scene transformations from the aligner")
+    p.add_argument("--transformation_lock_frame", default=0, type=int, help="the frame that the transformation will use as a base")
+    p.add_argument("--remove_edges", action="store_true", help="Tries to remove edges that was not visible in image")
+    p.add_argument("--track_file", type=str, help="refused: host reconstruction")
+    p.add_argument("--strict_mask", default=False, action="store_true", help="refused: host reconstruction")
+    p.add_argument("--mask_video", type=str, help="refused: host reconstruction")
+    p.add_argument("--merge_close_points", action="store_true", help="refused: host reconstruction")
+    p.add_argument("--show_scene_point_clouds", action="store_true", help="refused: an Open3D window")
+    p.add_argument("--show_both_point_clouds", action="store_true", help="refused: an Open3D window")
+    p.add_argument("--save_alembic", action="store_true", help="refused: Blender's exporter")
+    p.add_argument("--use_triangulated_points", action="store_true", help="refused: host reconstruction")
+    p.add_argument("--tringulation_min_observations", default=5, type=int, help="unused: belongs to --track_file")
+    p.add_argument("--save_rescaled_depth", action="store_true", help="refused: host reconstruction")
+    p.add_argument("--global_align", action="store_true", help="refused: host reconstruction")
+    p.add_argument("--batch", default=8, type=int, help="not a reference flag: frames per device call")
+    p.add_argument("--video_decoder", choices=("host", "device", "device_all"), default="host", help="not a reference flag: where .mkv inputs are decoded")
+    return p
+
+
+def check_flags(a):
+    """NotImplementedError, naming the reason, for what only the host reconstruction, Blender or an Open3D window could do."""
+    for name, why in REFUSED.items():
+        v = getattr(a, name, None)
+        if v is not None and v is not False:
+            raise NotImplementedError(why)
+
+
+def exported_frames(n_frames, min_frames=-1, max_frames=-1):
+    """The frames the reference's loop takes from a video of n_frames (cmf:639-641, 765-766): frame f is skipped while
+    min_frames >= f, and the loop stops after the first taken frame f with max_frames < f."""
+    out = []
+    for f in range(int(n_frames)):
+        if min_frames >= f and min_frames != -1:
+            continue
+        out.append(f)
+        if max_frames < f and max_frames != -1:
+            break
+    return out
+
+
+def frame_params(_lib, K, transforms):
+    """MdvtFrameParams records of a batch: K, depth scale 1, the pose where there is one."""
+    arr = (_lib.MdvtFrameParams * len(transforms))()
+    for k, T in enumerate(transforms):
+        for i, v in enumerate(np.asarray(K, np.float64).reshape(9)):
+            arr[k].K[i] = arr[k].Krender[i] = v
+        arr[k].depth_scale = 1.0
+        if T is not None:
+            arr[k].has_T = 1
+            for i, v in enumerate(np.asarray(T, np.float64).reshape(16)):
+                arr[k].T[i] = v
+    return arr
+
+
+def export_batch(ctx, d_depth, d_color, K, transforms, *, max_depth, remove_edges, decode=0, want_ply=True, want_obj=True, stream=None):
+    """One call of mdvt_export_geometry_batch on uint8 CUDA [B, H, W, 3] frames -> per frame a dict of host arrays: points, point_rgb
+    (want_ply), vertices, triangles (want_obj), counts (U, M).  The lists come back by their counts: counts first, then U or M entries."""
+    import torch
+    from metric_depth_video_toolbox_amd import _lib
+    B, H, W = int(d_depth.shape[0]), int(d_depth.shape[1]), int(d_depth.shape[2])
+    N, ncell, dev = W * H, (W - 1) * (H - 1), d_depth.device
+    for name, t in (("depth", d_depth), ("color", d_color)):
+        _lib.check_tensor(name, t, torch.uint8, (B, H, W, 3), device=dev, contiguous=True)
+    opts = _lib.MdvtGeometryOpts(decode=int(decode), remove_edges=int(bool(remove_edges)), max_depth=float(max_depth))
+    io = _lib.MdvtGeometryIO()
+    io.depth_rgb, io.depth_pitch, io.depth_stride = d_depth.data_ptr(), 3 * W, 3 * W * H
+    io.color_rgb, io.color_pitch, io.color_stride = d_color.data_ptr(), 3 * W, 3 * W * H
+    counts = torch.empty((B, 2), dtype=torch.int32, device=dev)
+    io.counts = counts.data_ptr()
+    vertices = triangles = points = point_rgb = None
+    if want_obj:
+        vertices = torch.empty((B, N, 3), dtype=torch.float64, device=dev)
+        triangles = torch.empty((B, 2 * ncell, 3), dtype=torch.int32, device=dev)
+        io.vertices, io.vertices_stride = vertices.data_ptr(), 24 * N
+        io.triangles, io.triangles_stride = triangles.data_ptr(), 24 * ncell
+    if want_ply:
+        points = torch.empty((B, N, 3), dtype=torch.float64, device=dev)
+        point_rgb = torch.empty((B, N, 3), dtype=torch.uint8, device=dev)
+        io.points, io.points_stride = points.data_ptr(), 24 * N
+        io.point_rgb, io.point_rgb_stride = point_rgb.data_ptr(), 3 * N
+    ctx.call("mdvt_export_geometry_batch", B, frame_params(_lib, K, transforms), C.byref(opts), C.byref(io), _lib.stream_arg(dev, stream))
+    host_counts = counts.cpu().numpy()
+    out = []
+    for k in range(B):
+        U, M = int(host_counts[k, 0]), int(host_counts[k, 1])
+        f = {"counts": (U, M)}
+        if want_ply:
+            f["points"], f["point_rgb"] = points[k, :U].cpu().numpy(), point_rgb[k, :U].cpu().numpy()
+        if want_obj:
+            f["vertices"], f["triangles"] = vertices[k].cpu().numpy(), triangles[k, :M].cpu().numpy()
+        out.append(f)
+    return out
+
+
+def grey_batch(ctx, d_depth, *, max_depth, bits, stream=None):
+    """mdvt_depth_grey_batch on uint8 CUDA [B, H, W, 3] frames -> CUDA int16 [B, H, W] holding the uint16 bit patterns (bits 16: view
+    the host copy as np.uint16) or uint8 [B, H, W, 3] (bits 8)."""
+    import torch
+    from metric_depth_video_toolbox_amd import _lib
+    B, H, W = int(d_depth.shape[0]), int(d_depth.shape[1]), int(d_depth.shape[2])
+    _lib.check_tensor("depth", d_depth, torch.uint8, (B, H, W, 3), contiguous=True)
+    out = torch.empty((B, H, W) if bits == 16 else (B, H, W, 3), dtype=torch.int16 if bits == 16 else torch.uint8, device=d_depth.device)
+    row = 2 * W if bits == 16 else 3 * W
+    ctx.call("mdvt_depth_grey_batch", B, d_depth.data_ptr(), 3 * W, 3 * W * H, float(max_depth), int(bits), out.data_ptr(), row, row * H,
+             _lib.stream_arg(d_depth.device, stream))
+    return out
+
+
+def _batches(frames, batch):
+    """Runs of consecutive frame numbers, at most `batch` long."""
+    run = []
+    for f in frames:
+        if run and (f != run[-1] + 1 or len(run) == batch):
+            yield run
+            run = []
+        run.append(f)
+    if run:
+        yield run
+
+
+class Grey16Dump:
+    """The --bit16 output: uint16 [n, H, W] written as `final + ".tmp"`, renamed on a normal exit from the block, removed on an exception."""
+
+    def __init__(self, final, n, H, W):
+        self.final, self.tmp = final, final + ".tmp"
+        self.arr = np.lib.format.open_memmap(self.tmp, mode="w+", dtype=np.uint16, shape=(int(n), H, W))
+
+    def __enter__(self):
+        return self
+
+    def store(self, d_frames, a):
+        """Frames a, a + 1, ... from grey_batch's int16 CUDA tensor (the uint16 bit patterns)."""
+        self.arr[a:a + len(d_frames)] = d_frames.cpu().numpy().view(np.uint16)
+
+    def __exit__(self, failed, *exc):
+        if failed is None:
+            self.arr.flush()
+        self.arr = None
+        if failed is None:
+            os.replace(self.tmp, self.final)
+        elif os.path.exists(self.tmp):
+            os.remove(self.tmp)
+
+
+def run(a):
+    check_flags(a)
+    if a.bit8 and a.bit16:
+        raise ValueError("--bit8 and --bit16 write the same output name: pick one")
+    if (a.save_ply is not None or a.save_obj is not None) and a.xfov is None and a.yfov is None:
+        raise ValueError("Either --xfov or --yfov is required.")                                   # cmf:576-579
+    import torch
+    from metric_depth_video_toolbox_amd import _lib, geometry_files
+    from metric_depth_video_toolbox_amd import depth_map_tools, distributed
+    from metric_depth_video_toolbox_amd.clip_io import ClipInputs, ClipOutput, check_video_decoder, video_parts
+    written = []
+    with ClipInputs() as inp:
+        depth = inp.open(a.depth_video, "depth_video", Exception("input video does not exist"))
+        color = None if a.color_video is None else inp.open(a.color_video, "color_video", Exception("input color_video does not exist"))
+        video = bool(video_parts(depth))
+        check_video_decoder(a.video_decoder, video)
+        if depth.ndim != 4 or depth.shape[-1] != 3 or depth.dtype != np.uint8:
+            raise ValueError(f"{a.depth_video}: uint8 [N, H, W, 3] expected")
+        if color is not None and tuple(color.shape[1:]) != tuple(depth.shape[1:]):
+            raise ValueError("color image and depth image need to have same width and height")     # cmf:635
+        H, W = int(depth.shape[1]), int(depth.shape[2])
+        n = int(depth.shape[0]) if color is None else min(int(depth.shape[0]), int(color.shape[0]))
+        frames = exported_frames(n, a.min_frames, a.max_frames)
+        geometry = a.save_ply is not None or a.save_obj is not None
+        K = depth_map_tools.compute_camera_matrix(a.xfov, a.yfov, W, H) if geometry else None       # cmf:582
+        T = None
+        if a.transformation_file is not None:
+            if not os.path.isfile(a.transformation_file):
+                raise Exception("input transformation_file does not exist")                        # cmf:594-595
+            with open(a.transformation_file) as fh:
+                T = distributed.rebase_on_lock_frame(json.load(fh), a.transformation_lock_frame)   # cmf:599-603, on the host
+            if frames and len(T) <= frames[-1]:
+                raise ValueError("transformation file has fewer entries than frames")
+        for d in (a.save_ply, a.save_obj):
+            if d is not None:
+                os.makedirs(d, exist_ok=True)                                                      # cmf:556-562
+        inp.on_device(torch.device("cuda", torch.cuda.current_device()), a.video_decoder)
+        ctx = _lib.Context(inp.dev.index, W, H)
+        with contextlib.ExitStack() as stack:
+            stack.callback(ctx.close)
+            stack.enter_context(torch.cuda.device(inp.dev))
+            grey = None
+            if a.bit8:
+                ext = ".mkv" if video else ".npy"
+                fps = (video_parts(depth)[0][0].fps or 30.0) if video else None
+                grey = stack.enter_context(ClipOutput(a.depth_video + "_tmp_grey_depth" + ext, a.depth_video + "_grey_depth" + ext,
+                                                      len(frames), (H, W, 3), fps))
+                written.append(grey.final)
+            elif a.bit16:
+                grey = stack.enter_context(Grey16Dump(a.depth_video + "_grey_depth.npy", len(frames), H, W))
+                written.append(grey.final)
+            at = 0
+            for run_ in _batches(frames, max(1, int(a.batch))):
+                d_depth = inp.fetch(depth, run_[0], run_[-1] + 1).contiguous()
+                d_color = d_depth if color is None else inp.fetch(color, run_[0], run_[-1] + 1).contiguous()       # cmf:636-637
+                if geometry:
+                    got = export_batch(ctx, d_depth, d_color, K, [None if T is None else T[f] for f in run_], max_depth=a.max_depth,
+                                       remove_edges=a.remove_edges, want_ply=a.save_ply is not None, want_obj=a.save_obj is not None)
+                    host_color = d_color.cpu().numpy().reshape(len(run_), -1, 3) if a.save_obj is not None else None
+                    for k, f in enumerate(run_):
+                        if a.save_obj is not None:                                                 # cmf:732-742
+                            path = os.path.join(a.save_obj, f"{f:07d}.obj")
+                            geometry_files.write_obj(path, got[k]["vertices"], host_color[k], got[k]["triangles"])
+                            written.append(path)
+                        if a.save_ply is not None:                                                 # cmf:743-749
+                            path = os.path.join(a.save_ply, f"{f:07d}.ply")
+                            geometry_files.write_ply(path, got[k]["points"], got[k]["point_rgb"])
+                            written.append(path)
+                if a.bit8 or a.bit16:                                                              # cmf:752-760
+                    grey.store(grey_batch(ctx, d_depth, max_depth=a.max_depth, bits=16 if a.bit16 else 8), at)
+                at += len(run_)
+    return written
+
+
+def main(argv=None):
+    written = run(build_parser().parse_args(argv))
+    print(f"Done. Wrote {len(written)} file(s)" + (f": {written[0]} ..." if written else ""))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
