@@ -42,6 +42,10 @@ CONVERGENCE_SYMBOLS = ("mdvt_convergence_depths",)
 # the entry points include/mdvt_metric_align.h declares (relative depth to metric depth codes), listed apart in the same way
 METRIC_ALIGN_SYMBOLS = ("mdvt_scale_shift_fit", "mdvt_metric_depth_codes")
 
+# the entry point include/mdvt_depth_sink.h declares (metric depth planes to a depth video's codes), listed apart in the same way.  It is
+# bound here and has no wrapper in the package yet: tools/video_da3.py calls it
+DEPTH_SINK_SYMBOLS = ("mdvt_depth_video_codes",)
+
 # the entry points include/mdvt_infill_adapter.h declares (the frames around an in-painting model), listed apart in the same way
 INFILL_ADAPTER_SYMBOLS = ("mdvt_adapter_prepare_eye", "mdvt_lhm_moments", "mdvt_lhm_apply", "mdvt_adapter_composite_eye")
 
@@ -218,6 +222,9 @@ def load():
     L.mdvt_metric_depth_codes.restype = C.c_int
     L.mdvt_metric_depth_codes.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, C.c_size_t, vp, C.c_int, C.c_double, C.c_int, C.c_int,
                                           vp, C.c_size_t, C.c_size_t, C.c_int, vp, C.c_size_t, C.c_size_t, vp]
+    L.mdvt_depth_video_codes.restype = C.c_int
+    L.mdvt_depth_video_codes.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, C.c_size_t, vp, C.c_int, C.c_double, C.c_int, C.c_int,
+                                         vp, C.c_size_t, C.c_size_t, C.c_int, vp, C.c_size_t, C.c_size_t, vp]
     st = C.c_size_t
     L.mdvt_adapter_prepare_eye.restype = C.c_int
     L.mdvt_adapter_prepare_eye.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, st, st, vp, st, st, C.c_int, C.c_int, vp, st, st, vp, st, st, vp, vp]

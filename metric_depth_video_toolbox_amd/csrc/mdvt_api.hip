@@ -1,5 +1,5 @@
 // mdvt_api.hip -- the entry points of the C ABI of include/mdvt.h beside the render (mdvt_api_render.hip) and the context
-// (mdvt_context.hip): formats, equirect, blur, the infills, both infill-mask completions, FFV1 in both directions, convergence depths, the metric alignment, the infill adapter, the two further infill engines.
+// (mdvt_context.hip): formats, equirect, blur, the infills, both infill-mask completions, FFV1 in both directions, convergence depths, the metric alignment, the depth sink, the infill adapter, the two further infill engines.
 // Host code only; the kernels are in the other *.hip units.
 #include "mdvt_context.h"
 #include "mdvt_ffv1_core.h"
@@ -7,6 +7,7 @@
 #include "mdvt_ffv1_stream_decode.h"
 #include "mdvt_convergence.h"
 #include "mdvt_metric_align.h"
+#include "mdvt_depth_sink.h"
 #include "mdvt_infill_adapter.h"
 #include "mdvt_infill_engines.h"
 
@@ -746,6 +747,48 @@ int mdvt_metric_depth_codes(mdvt_ctx* c, int in_w, int in_h, int n_frames, const
     for (int f0 = 0; f0 < n_frames; f0 += 32768) {               // (the grid's second dimension holds the frames)
         a.frame0 = f0;
         MDVT_HIP(c, mdvt::launch_metric_codes(a, n_frames - f0 < 32768 ? n_frames - f0 : 32768, s));
+    }
+    return MDVT_OK;
+}
+
+// Metric depth planes to a depth video's codes (mdvt_depth_sink.hip; include/mdvt_depth_sink.h).  No scratch block: launches only.
+int mdvt_depth_video_codes(mdvt_ctx* c, int in_w, int in_h, int n_frames, const float* d_depth, size_t depth_pitch, size_t depth_stride,
+                           const float* d_scale, int nan_to_max, double max_depth, int out_w, int out_h,
+                           uint8_t* d_codes, size_t codes_pitch, size_t codes_stride, int order,
+                           float* d_plane, size_t plane_pitch, size_t plane_stride, void* stream)
+{
+    if (!c) return MDVT_ERR_INVALID_ARG;
+    if (!d_depth || !d_codes) return fail(c, MDVT_ERR_INVALID_ARG, "NULL buffer");
+    if (in_w < 1 || in_h < 1 || out_w < 1 || out_h < 1) return fail(c, MDVT_ERR_INVALID_ARG, "bad size %d x %d -> %d x %d", in_w, in_h, out_w, out_h);
+    if (n_frames < 1) return fail(c, MDVT_ERR_INVALID_ARG, "n_frames must be >= 1");
+    if (nan_to_max != 0 && nan_to_max != 1) return fail(c, MDVT_ERR_INVALID_ARG, "nan_to_max must be 0 or 1, got %d", nan_to_max);
+    if (order != 0 && order != 1) return fail(c, MDVT_ERR_INVALID_ARG, "order must be 0 (RGB) or 1 (BGR), got %d", order);
+    if (!(max_depth > 0.0)) return fail(c, MDVT_ERR_INVALID_ARG, "max_depth must be > 0");
+    if (depth_pitch < (size_t)in_w * 4u) return fail(c, MDVT_ERR_INVALID_ARG, "depth_pitch smaller than one row");
+    if (codes_pitch < (size_t)out_w * 3u) return fail(c, MDVT_ERR_INVALID_ARG, "codes_pitch smaller than one row");
+    if (d_plane && plane_pitch < (size_t)out_w * 4u) return fail(c, MDVT_ERR_INVALID_ARG, "plane_pitch smaller than one row");
+    if (n_frames > 1 && (depth_stride < depth_pitch * (size_t)in_h || codes_stride < codes_pitch * (size_t)out_h ||
+                         (d_plane && plane_stride < plane_pitch * (size_t)out_h)))
+        return fail(c, MDVT_ERR_INVALID_ARG, "stride smaller than one frame");
+    if ((uint64_t)out_w * (uint64_t)out_h >= ((uint64_t)1 << 31))
+        return fail(c, MDVT_ERR_UNSUPPORTED, "output frame too large (%d x %d)", out_w, out_h);
+    DeviceGuard g(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (n_frames == 1) depth_stride = codes_stride = plane_stride = 0;
+    mdvt::DepthSinkArgs a{};
+    a.src = reinterpret_cast<const uint8_t*>(d_depth); a.src_pitch = depth_pitch; a.src_stride = depth_stride; a.in_w = in_w; a.in_h = in_h;
+    a.src_vec = (uintptr_t)d_depth % 16 == 0 && depth_pitch % 16 == 0 && depth_stride % 16 == 0;
+    a.scale = d_scale; a.nan_to_max = nan_to_max; a.fmax = (float)max_depth; a.multi = 4228250625.0 / max_depth;
+    a.out_w = out_w; a.out_h = out_h; a.resize = in_w != out_w || in_h != out_h;
+    a.ratio_x = (double)in_w / (double)out_w; a.ratio_y = (double)in_h / (double)out_h;
+    a.codes = d_codes; a.codes_pitch = codes_pitch; a.codes_stride = codes_stride; a.bgr = order;
+    a.codes_vec = (uintptr_t)d_codes % 4 == 0 && codes_pitch % 4 == 0 && codes_stride % 4 == 0;
+    a.plane = reinterpret_cast<uint8_t*>(d_plane); a.plane_pitch = plane_pitch; a.plane_stride = plane_stride;
+    a.plane_vec = d_plane && (uintptr_t)d_plane % 16 == 0 && plane_pitch % 16 == 0 && plane_stride % 16 == 0;
+    a.gw = ((uint32_t)out_w + 3u) / 4u; a.groups = a.gw * (uint32_t)out_h;
+    for (int f0 = 0; f0 < n_frames; f0 += 32768) {               // (the grid's second dimension holds the frames)
+        a.frame0 = f0;
+        MDVT_HIP(c, mdvt::launch_depth_sink(a, n_frames - f0 < 32768 ? n_frames - f0 : 32768, s));
     }
     return MDVT_OK;
 }

@@ -26,12 +26,18 @@
 // clips and codes.  Four codes are 12 bytes: three dword stores where the image's address, pitch and stride are multiples of 4.
 #include "mdvt_internal.h"
 #include "mdvt_pairwise.h"
+#include "mdvt_depth_code.h"
 
 namespace mdvt {
 namespace {
 
 using pairwise::kChunk;
 using pairwise::kLeaf;
+using depth_code::clip_np;
+using depth_code::tap;
+using depth_code::pixel;
+using depth_code::store_pixels;
+using depth_code::store_plane;
 
 constexpr int kFitThreads = 256;
 constexpr int kTotalThreads = 5 * 64;              // k_fit_total: a wave per sum
@@ -263,13 +269,6 @@ __global__ void __launch_bounds__(kTotalThreads) k_fit_total(FitArgs a)
 
 // ---- the codes ----------------------------------------------------------------------------------------------------------------
 
-// NumPy's clip(d, 0, hi): a NaN stays, and so does -0
-__device__ __forceinline__ float clip_np(float d, float hi)
-{
-    const float lo = d < 0.0f ? 0.0f : d;
-    return lo > hi ? hi : lo;
-}
-
 template <int STYLE>
 __device__ __forceinline__ float reconstruct(float x, float scale, float shift, float fmax)
 {
@@ -281,20 +280,6 @@ __device__ __forceinline__ float reconstruct(float x, float scale, float shift, 
     if (inv == 0.0f) inv = 1e-4f;
     const float d = clip_np(1.0f / inv, fmax);
     return d != d ? fmax : d;
-}
-
-// source index and weight of output index d along an axis of n_in source values: cv2's INTER_LINEAR tables, restated
-__device__ __forceinline__ void tap(int d, double ratio, int n_in, int& s0, int& s1, float& w0, float& w1)
-{
-    float f = (float)(((double)d + 0.5) * ratio - 0.5);
-    int s = (int)floorf(f);
-    f -= (float)s;
-    if (s < 0) { s = 0; f = 0.0f; }
-    if (s >= n_in - 1) { s = n_in - 1; f = 0.0f; }
-    s0 = s;
-    s1 = s + 1 < n_in - 1 ? s + 1 : n_in - 1;
-    w0 = 1.0f - f;
-    w1 = f;
 }
 
 template <int STYLE>
@@ -343,34 +328,13 @@ __global__ void __launch_bounds__(256) k_metric_codes(MetricCodesArgs a)
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         d[k] = clip_np(d[k], a.fmax);
-        const double e = a.multi * (double)d[k];
-        const uint32_t code = (e >= 0.0 && e < 4294967296.0) ? (uint32_t)e : 0u;     // NaN -> 0
-        const uint32_t hi = code >> 24, lo = (code >> 16) & 0xFFu;
-        px[k] = a.bgr ? (lo | (hi << 8) | (hi << 16)) : (hi | (hi << 8) | (lo << 16));
+        px[k] = pixel(d[k], a.multi, a.bgr);
     }
     uint8_t* q = a.codes + f * a.codes_stride + (size_t)row * a.codes_pitch + (size_t)x0 * 3u;
-    if (a.codes_vec && nv == 4) {
-        uint32_t* w = reinterpret_cast<uint32_t*>(q);
-        w[0] = px[0] | (px[1] << 24);
-        w[1] = (px[1] >> 8) | (px[2] << 16);
-        w[2] = (px[2] >> 16) | (px[3] << 8);
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (k < nv) {
-                q[3 * k] = (uint8_t)px[k]; q[3 * k + 1] = (uint8_t)(px[k] >> 8); q[3 * k + 2] = (uint8_t)(px[k] >> 16);
-            }
-        }
-    }
+    store_pixels(q, px, nv, a.codes_vec);
     if (a.depth) {
         float* z = reinterpret_cast<float*>(a.depth + f * a.depth_stride + (size_t)row * a.depth_pitch) + x0;
-        if (a.depth_vec && nv == 4) {
-            *reinterpret_cast<float4*>(z) = make_float4(d[0], d[1], d[2], d[3]);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (k < nv) z[k] = d[k];
-        }
+        store_plane(z, d, nv, a.depth_vec);
     }
 }
 
