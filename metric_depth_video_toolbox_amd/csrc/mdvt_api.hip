@@ -1,6 +1,7 @@
-// mdvt_api.hip -- the entry points of the C ABI of include/mdvt.h beside the render (mdvt_api_render.hip) and the context
-// (mdvt_context.hip): formats, equirect, blur, the infills, both infill-mask completions, FFV1 in both directions, convergence depths, the metric alignment, the depth sink, the infill adapter, the two further infill engines.
-// Host code only; the kernels are in the other *.hip units.
+// mdvt_api.hip -- the entry points of the C ABI beside the render (mdvt_api_render.hip) and the context (mdvt_context.hip): include/mdvt.h's formats,
+// equirect, blur, infills and both infill-mask completions, then FFV1 in both directions, the convergence depths, the metric alignment, the depth sink, the
+// infill adapter and the two further infill engines (a header of include/ each).  An entry point's refusals stand in the order the caller meets their texts,
+// each fail(...) text at its check (tests/refusal_cases.py pins texts and order).  Host code only; the kernels are in the other *.hip units.
 #include "mdvt_context.h"
 #include "mdvt_ffv1_core.h"
 #include "mdvt_ffv1_decode.h"
@@ -19,21 +20,30 @@ using namespace mdvt::grid8;          // (the grid-independent launchers)
 
 namespace {
 
-// cv2.getGaussianKernel(6, 0) as published: sigma = 0.3*((n-1)*0.5 - 1) + 0.8, exp in f64, scaled by 1/sum; the
-// 2-D kernel is the f64 outer product (sr:124-125) rounded to f32 (what filter2D does for an f32 image).
+// cv2.getGaussianKernel(n, sigma) as published: exp in f64, the weights added from the first on, scaled by 1 / sum; g[n] stays f64 (the caller
+// rounds once to f32).  cv2's "sigma = 0" is 0.3 * ((n - 1) * 0.5 - 1) + 0.8, spelled by the caller as its reference spells it.
+void gaussian_weights(int n, double sigma, double* g)
+{
+    double sum = 0.0;
+    for (int i = 0; i < n; ++i) { const double x = (double)i - (n - 1) * 0.5; g[i] = exp(-0.5 / (sigma * sigma) * x * x); sum += g[i]; }
+    for (int i = 0; i < n; ++i) g[i] *= 1.0 / sum;
+}
+// cv2.getGaussianKernel(6, 0); the 2-D kernel is the f64 outer product (sr:124-125) rounded to f32 (what filter2D does for an f32 image).
 mdvt::BlurKernel masked_blur_kernel()
 {
-    double g[6], sum = 0.0;
-    const double sigma = 0.3 * ((6 - 1) * 0.5 - 1.0) + 0.8, scale2 = -0.5 / (sigma * sigma);
-    for (int i = 0; i < 6; ++i) { const double x = (double)i - (6 - 1) * 0.5; g[i] = exp(scale2 * x * x); sum += g[i]; }
-    sum = 1.0 / sum;
-    for (int i = 0; i < 6; ++i) g[i] *= sum;
+    double g[6];
+    gaussian_weights(6, 0.3 * ((6 - 1) * 0.5 - 1.0) + 0.8, g);
     mdvt::BlurKernel K;
     for (int y = 0; y < 6; ++y) for (int x = 0; x < 6; ++x) K.k[6 * y + x] = (float)(g[y] * g[x]);
     return K;
 }
 constexpr int kTeleaChunk = mdvt::kTeleaMaxImages;      // images per pass (14 B/px of workspace each)
 constexpr int kNormalInfillChunk = 16;       // images per launch set
+// FFV1's default state transition tables, built once per process
+const mdvt::Ffv1StateTables& ffv1_states() { static const mdvt::Ffv1StateTables tab = mdvt::ffv1_default_states(); return tab; }
+// What a vector path asks of an array: every pointer, pitch, stride (or row length) listed is a multiple of k; the pitch of a single row is never used.
+template <class... A> bool multiples_of(size_t k, A... a) { return (((uintptr_t)a % k == 0) && ...); }
+size_t pitch_in_use(size_t pitch, int rows) { return rows == 1 ? 0 : pitch; }
 
 // The n images (frames, when both eyes travel together) from i0 on of a caller's array.
 mdvt::ImageSet slice(const uint8_t* base, size_t pitch, size_t stride, int i0, int n, ptrdiff_t eye_offset = 0)
@@ -444,7 +454,6 @@ int mdvt_encode_video_frames(mdvt_ctx* c, int width, int height, int slices_h, i
     uint32_t* slice_n = reinterpret_cast<uint32_t*>(ws.p + head);
     uint8_t* scratch = ws.p + head + words;
     MDVT_HIP(c, hipMemsetAsync(used, 0, sizeof(unsigned long long), s));
-    static const mdvt::Ffv1StateTables tab = mdvt::ffv1_default_states();
     mdvt::Ffv1CodeArgs ca{};
     ca.pitch = pitch; ca.frame_stride = frame_stride; ca.channels = channels;
     ca.ri = channels == 1 ? 0 : (order == 1 ? 2 : 0); ca.gi = channels == 1 ? 0 : 1; ca.bi = channels == 1 ? 0 : (order == 1 ? 0 : 2);
@@ -453,7 +462,7 @@ int mdvt_encode_video_frames(mdvt_ctx* c, int width, int height, int slices_h, i
     for (int f0 = 0; f0 < n_frames; f0 += fchunk) {
         const int nf = n_frames - f0 < fchunk ? n_frames - f0 : fchunk;
         ca.src = d_src + (size_t)f0 * frame_stride;
-        MDVT_HIP(c, mdvt::launch_ffv1_code(ca, tab, nf * spf, s));
+        MDVT_HIP(c, mdvt::launch_ffv1_code(ca, ffv1_states(), nf * spf, s));
         const mdvt::Ffv1LayoutArgs la{slice_n, spf, nf, d_sizes + f0, reinterpret_cast<unsigned long long*>(d_offsets) + f0, used,
                                       (unsigned long long)packets_cap};
         MDVT_HIP(c, mdvt::launch_ffv1_layout(la, s));
@@ -548,7 +557,6 @@ int mdvt_decode_video_frames(mdvt_ctx* c, int width, int height, const uint8_t* 
     const size_t per_frame = (size_t)spf * 3 * sizeof(uint32_t);
     const int fchunk = slots_afforded(c, per_frame, n_frames);
     MDVT_HIP(c, scratch_reserve(c, c->scratch[SCR_FFV1_DEC], (size_t)fchunk * per_frame, s));
-    static const mdvt::Ffv1StateTables tab = mdvt::ffv1_default_states();
     for (int f0 = 0; f0 < n_frames; f0 += fchunk) {
         const int nf = n_frames - f0 < fchunk ? n_frames - f0 : fchunk;
         a.n_frames = nf;
@@ -557,7 +565,7 @@ int mdvt_decode_video_frames(mdvt_ctx* c, int width, int height, const uint8_t* 
         a.table = c->scratch[SCR_FFV1_DEC].as<uint32_t>();
         a.claims = a.table + (size_t)2 * nf * spf;
         MDVT_HIP(c, hipMemsetAsync(a.claims, 0, (size_t)nf * spf * sizeof(uint32_t), s));
-        MDVT_HIP(c, mdvt::launch_ffv1_decode(a, tab, s));
+        MDVT_HIP(c, mdvt::launch_ffv1_decode(a, ffv1_states(), s));
     }
     return MDVT_OK;
 }
@@ -579,7 +587,6 @@ int mdvt_decode_video_stream(mdvt_ctx* c, int width, int height, const uint8_t* 
     DeviceGuard g(c->device);
     hipStream_t s = (hipStream_t)stream;
     MDVT_HIP(c, scratch_reserve(c, c->scratch[SCR_FFV1_STREAM], (size_t)n_packets * per_frame, s));
-    static const mdvt::Ffv1StateTables tab = mdvt::ffv1_default_states();
     a.offsets = reinterpret_cast<const unsigned long long*>(d_offsets); a.sizes = d_sizes;
     a.n_frames = n_packets; a.first_out = first_out;
     a.dst = d_dst; a.status = d_status;
@@ -587,7 +594,7 @@ int mdvt_decode_video_stream(mdvt_ctx* c, int width, int height, const uint8_t* 
     a.claims = a.table + (size_t)2 * n_packets * spf;
     a.kind = a.claims + (size_t)n_packets * spf;
     MDVT_HIP(c, hipMemsetAsync(a.claims, 0, (size_t)n_packets * spf * sizeof(uint32_t), s));
-    MDVT_HIP(c, mdvt::launch_ffv1_stream_decode(a, tab, s));
+    MDVT_HIP(c, mdvt::launch_ffv1_stream_decode(a, ffv1_states(), s));
     return MDVT_OK;
 }
 
@@ -631,14 +638,11 @@ int mdvt_convergence_depths(mdvt_ctx* c, int width, int height, const uint8_t* d
     // rows without padding are one long row of npx pixels: no division per pixel, and the 12-byte loads need npx % 4 == 0 only
     const uint32_t depth_W = depth_pitch == (size_t)width * 3u ? npx : (uint32_t)width;
     const uint32_t mask_W = with_mask && mask_pitch == (size_t)width * 3u ? npx : (uint32_t)width;
-    auto vec_ok = [&](const uint8_t* p, uint32_t row, size_t pitch, size_t stride) {
-        return row % 4 == 0 && pitch % 4 == 0 && stride % 4 == 0 && (uintptr_t)p % 4 == 0;
-    };
     mdvt::ConvergenceArgs a{};
     a.depth_pitch = depth_pitch; a.depth_stride = depth_stride; a.depth_bgr = depth_order; a.depth_W = depth_W;
-    a.depth_vec = vec_ok(d_depth, depth_W, depth_pitch, depth_stride);
+    a.depth_vec = multiples_of(4, d_depth, depth_W, depth_pitch, depth_stride);
     a.mask_pitch = mask_pitch; a.mask_stride = mask_stride; a.mask_bgr = mask_order; a.mask_W = mask_W;
-    a.mask_vec = with_mask && vec_ok(d_mask, mask_W, mask_pitch, mask_stride);
+    a.mask_vec = with_mask && multiples_of(4, d_mask, mask_W, mask_pitch, mask_stride);
     a.npx = npx; a.nchunks = nchunks; a.nunits = nunits;
     a.div = (float)(4228250625.0 / max_depth);               // 255^4 / max_depth in double, rounded once (fcd:60)
     a.compact_stride = compact_stride;
@@ -735,14 +739,14 @@ int mdvt_metric_depth_codes(mdvt_ctx* c, int in_w, int in_h, int n_frames, const
     if (n_frames == 1) rel_stride = codes_stride = depth_stride = 0;
     mdvt::MetricCodesArgs a{};
     a.rel = reinterpret_cast<const uint8_t*>(d_rel); a.rel_pitch = rel_pitch; a.rel_stride = rel_stride; a.in_w = in_w; a.in_h = in_h;
-    a.rel_vec = (uintptr_t)d_rel % 16 == 0 && rel_pitch % 16 == 0 && rel_stride % 16 == 0;
+    a.rel_vec = multiples_of(16, d_rel, rel_pitch, rel_stride);
     a.scale_shift = d_scale_shift; a.style = style; a.fmax = (float)max_depth; a.multi = 4228250625.0 / max_depth;
     a.out_w = out_w; a.out_h = out_h; a.resize = in_w != out_w || in_h != out_h;
     a.ratio_x = (double)in_w / (double)out_w; a.ratio_y = (double)in_h / (double)out_h;
     a.codes = d_codes; a.codes_pitch = codes_pitch; a.codes_stride = codes_stride; a.bgr = order;
-    a.codes_vec = (uintptr_t)d_codes % 4 == 0 && codes_pitch % 4 == 0 && codes_stride % 4 == 0;
+    a.codes_vec = multiples_of(4, d_codes, codes_pitch, codes_stride);
     a.depth = reinterpret_cast<uint8_t*>(d_depth); a.depth_pitch = depth_pitch; a.depth_stride = depth_stride;
-    a.depth_vec = d_depth && (uintptr_t)d_depth % 16 == 0 && depth_pitch % 16 == 0 && depth_stride % 16 == 0;
+    a.depth_vec = d_depth && multiples_of(16, d_depth, depth_pitch, depth_stride);
     a.gw = ((uint32_t)out_w + 3u) / 4u; a.groups = a.gw * (uint32_t)out_h;
     for (int f0 = 0; f0 < n_frames; f0 += 32768) {               // (the grid's second dimension holds the frames)
         a.frame0 = f0;
@@ -777,14 +781,14 @@ int mdvt_depth_video_codes(mdvt_ctx* c, int in_w, int in_h, int n_frames, const 
     if (n_frames == 1) depth_stride = codes_stride = plane_stride = 0;
     mdvt::DepthSinkArgs a{};
     a.src = reinterpret_cast<const uint8_t*>(d_depth); a.src_pitch = depth_pitch; a.src_stride = depth_stride; a.in_w = in_w; a.in_h = in_h;
-    a.src_vec = (uintptr_t)d_depth % 16 == 0 && depth_pitch % 16 == 0 && depth_stride % 16 == 0;
+    a.src_vec = multiples_of(16, d_depth, depth_pitch, depth_stride);
     a.scale = d_scale; a.nan_to_max = nan_to_max; a.fmax = (float)max_depth; a.multi = 4228250625.0 / max_depth;
     a.out_w = out_w; a.out_h = out_h; a.resize = in_w != out_w || in_h != out_h;
     a.ratio_x = (double)in_w / (double)out_w; a.ratio_y = (double)in_h / (double)out_h;
     a.codes = d_codes; a.codes_pitch = codes_pitch; a.codes_stride = codes_stride; a.bgr = order;
-    a.codes_vec = (uintptr_t)d_codes % 4 == 0 && codes_pitch % 4 == 0 && codes_stride % 4 == 0;
+    a.codes_vec = multiples_of(4, d_codes, codes_pitch, codes_stride);
     a.plane = reinterpret_cast<uint8_t*>(d_plane); a.plane_pitch = plane_pitch; a.plane_stride = plane_stride;
-    a.plane_vec = d_plane && (uintptr_t)d_plane % 16 == 0 && plane_pitch % 16 == 0 && plane_stride % 16 == 0;
+    a.plane_vec = d_plane && multiples_of(16, d_plane, plane_pitch, plane_stride);
     a.gw = ((uint32_t)out_w + 3u) / 4u; a.groups = a.gw * (uint32_t)out_h;
     for (int f0 = 0; f0 < n_frames; f0 += 32768) {               // (the grid's second dimension holds the frames)
         a.frame0 = f0;
@@ -799,16 +803,13 @@ int mdvt_depth_video_codes(mdvt_ctx* c, int in_w, int in_h, int n_frames, const 
 
 namespace {
 
-// cv2.getGaussianKernel(15, 0) as the header restates it: sigma = 0.3 * ((15 - 1) * 0.5 - 1) + 0.8 = 2.6; exp in f64, the weights added
-// from the first on, scaled by 1 / sum, rounded once to f32
+// cv2.getGaussianKernel(15, 0) as the header restates it: sigma = 0.3 * ((15 - 1) * 0.5 - 1) + 0.8 = 2.6 (the literal); rounded once to f32
 mdvt::AdapterGauss adapter_gauss()
 {
-    double g[15], sum = 0.0;
-    const double sigma = 2.6, scale2 = -0.5 / (sigma * sigma);
-    for (int i = 0; i < 15; ++i) { const double x = (double)(i - 7); g[i] = exp(scale2 * x * x); sum += g[i]; }
-    sum = 1.0 / sum;
+    double g[15];
+    gaussian_weights(15, 2.6, g);
     mdvt::AdapterGauss K;
-    for (int i = 0; i < 15; ++i) K.w[i] = (float)(g[i] * sum);
+    for (int i = 0; i < 15; ++i) K.w[i] = (float)g[i];
     return K;
 }
 
@@ -878,8 +879,7 @@ int mdvt_lhm_moments(mdvt_ctx* c, int width, int height, int n_frames, const uin
     MDVT_HIP(c, hipMemsetAsync(d_out, 0, (size_t)n_frames * 10 * sizeof(uint64_t), s));
     mdvt::LhmMomentsArgs a{};
     a.W = width; a.H = height;
-    const size_t one_row = height == 1 ? 0 : ~(size_t)0;           // (the pitch of a single row is never used)
-    a.vec = (((uintptr_t)d_rgb | (pitch & one_row) | stride) & 3) == 0 && (!d_mask || (((uintptr_t)d_mask | (mask_pitch & one_row) | mask_stride) & 3) == 0);
+    a.vec = multiples_of(4, d_rgb, pitch_in_use(pitch, height), stride) && (!d_mask || multiples_of(4, d_mask, pitch_in_use(mask_pitch, height), mask_stride));
     for (int f0 = 0; f0 < n_frames; f0 += 32768) {
         a.img = {d_rgb + (size_t)f0 * stride, pitch, stride};
         a.mask = {d_mask ? d_mask + (size_t)f0 * mask_stride : nullptr, mask_pitch, mask_stride};
@@ -906,8 +906,7 @@ int mdvt_lhm_apply(mdvt_ctx* c, int width, int height, int n_frames, const uint8
     if (n_frames == 1) stride = out_stride = 0;
     mdvt::LhmApplyArgs a{};
     a.W = width; a.H = height; a.out_pitch = out_pitch; a.out_stride = out_stride;
-    const size_t one_row = height == 1 ? 0 : ~(size_t)0;           // (the pitch of a single row is never used)
-    a.vec = (((uintptr_t)d_rgb | (pitch & one_row) | stride | (uintptr_t)d_out | (out_pitch & one_row) | out_stride) & 3) == 0;
+    a.vec = multiples_of(4, d_rgb, pitch_in_use(pitch, height), stride, d_out, pitch_in_use(out_pitch, height), out_stride);
     for (int f0 = 0; f0 < n_frames; f0 += 32768) {
         a.img = {d_rgb + (size_t)f0 * stride, pitch, stride};
         a.params = d_params + (size_t)f0 * 15; a.out = d_out + (size_t)f0 * out_stride;
@@ -964,11 +963,7 @@ int mdvt_adapter_composite_eye(mdvt_ctx* c, int eye_w, int eye_h, int n_frames, 
     return MDVT_OK;
 }
 
-}  // extern "C"
-
 // ---- the m2svid and stereo_dissoclusion_net infill steps around their models (include/mdvt_infill_engines.h) ----
-
-extern "C" {
 
 int mdvt_m2svid_prepare_eye(mdvt_ctx* c, int eye_w, int eye_h, int n_frames, int eye,
                             const uint8_t* d_color, size_t color_pitch, size_t color_stride,
