@@ -46,6 +46,10 @@ METRIC_ALIGN_SYMBOLS = ("mdvt_scale_shift_fit", "mdvt_metric_depth_codes")
 # bound here and has no wrapper in the package yet: tools/video_da3.py calls it
 DEPTH_SINK_SYMBOLS = ("mdvt_depth_video_codes",)
 
+# the entry points include/mdvt_depth_engines.h declares (frames into a model, PromptDA's prompt, UniK3D's focal estimate), likewise.
+# They are bound here and have no wrapper in the package yet: tools/depth_engine_video.py and tools/upscale_depth_promptda.py call them
+DEPTH_ENGINE_SYMBOLS = ("mdvt_model_frames", "mdvt_depth_prompt", "mdvt_focal_from_points")
+
 # the entry points include/mdvt_infill_adapter.h declares (the frames around an in-painting model), listed apart in the same way
 INFILL_ADAPTER_SYMBOLS = ("mdvt_adapter_prepare_eye", "mdvt_lhm_moments", "mdvt_lhm_apply", "mdvt_adapter_composite_eye")
 
@@ -226,6 +230,12 @@ def load():
     L.mdvt_depth_video_codes.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, C.c_size_t, vp, C.c_int, C.c_double, C.c_int, C.c_int,
                                          vp, C.c_size_t, C.c_size_t, C.c_int, vp, C.c_size_t, C.c_size_t, vp]
     st = C.c_size_t
+    L.mdvt_model_frames.restype = C.c_int
+    L.mdvt_model_frames.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, st, st, C.c_int, C.c_int, C.c_int, C.c_int, vp, st, st, st, vp]
+    L.mdvt_depth_prompt.restype = C.c_int
+    L.mdvt_depth_prompt.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, st, st, C.c_int, C.c_double, C.c_int, C.c_int, vp, st, st, vp]
+    L.mdvt_focal_from_points.restype = C.c_int
+    L.mdvt_focal_from_points.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, st, st, st, vp, vp, vp]
     L.mdvt_adapter_prepare_eye.restype = C.c_int
     L.mdvt_adapter_prepare_eye.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, st, st, vp, st, st, C.c_int, C.c_int, vp, st, st, vp, st, st, vp, vp]
     L.mdvt_lhm_moments.restype = C.c_int

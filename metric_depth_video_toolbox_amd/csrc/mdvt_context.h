@@ -1,6 +1,6 @@
 // mdvt_context.h -- what the host units of the C ABI share: the context (mdvt_ctx), its error text, its device memory (the
 // process-wide pools of mdvt_context.hip, the scratch blocks and their one growth rule) and a few facts read off its
-// configuration.  Host only: included by mdvt_context.hip, mdvt_api_render.hip and mdvt_api.hip, never by a unit that defines kernels.
+// configuration.  Host only: included by mdvt_context.hip, mdvt_api_render.hip, mdvt_api.hip and mdvt_api_depth_engines.hip, never by a unit that defines kernels.
 #pragma once
 
 #include "mdvt_internal.h"
@@ -56,6 +56,7 @@ enum ScratchId {
     SCR_FFV1_STREAM,                  // mdvt_decode_video_stream: per slice of the call its offset, payload bytes and cell claim, per frame its kind
     SCR_VIEW,                         // mdvt_view_centers: per frame of a launch set its chunk sums (24 B per 8192 vertices); parking: also the edge filter's vertex flags (1 B/px)
     SCR_GEOMETRY,                     // mdvt_export_geometry_batch: per frame of a launch set the filter's triangle flags (2 B per cell) and the compaction's workgroup totals (4 B per 256 triangles / vertices)
+    SCR_FOCAL,                        // mdvt_focal_from_points: per frame of a launch set the selected values of both axes (8 B per point), their chunk sums, unit counts and offsets
     SCR_COUNT
 };
 

@@ -421,6 +421,37 @@ struct M2sPrepareArgs {
     uint32_t* holes;                                               // [n], zeroed before the launch
 };
 hipError_t launch_m2s_prepare(const M2sPrepareArgs& a, int n, hipStream_t s);
+// mdvt_depth_engines.hip: frames into a model, PromptDA's prompt and UniK3D's focal estimate (include/mdvt_depth_engines.h)
+struct ModelFramesArgs {
+    const uint8_t* src; size_t src_pitch, src_stride; int bgr, src_vec;       // _vec: four pixels of a row are three aligned dwords
+    AdapterResize rs;                                              // frame -> model
+    uint8_t* dst; size_t dst_pitch, dst_plane, dst_stride; int as_float, dst_vec;     // _vec: four values of a plane are one aligned store
+    uint32_t gw, groups;                                           // groups of four pixels per output row and per frame
+    int frame0;                                                    // the launch's first frame
+};
+hipError_t launch_model_frames(const ModelFramesArgs& a, int n_frames, hipStream_t s);
+struct DepthPromptArgs {
+    const uint8_t* src; size_t src_pitch, src_stride; int in_w, in_h, bgr, src_vec;
+    float mult;                                                    // float(max_depth / 255^4)
+    int out_w, out_h, resize; double ratio_x, ratio_y;             // in / out per axis
+    uint8_t* dst; size_t dst_pitch, dst_stride; int dst_vec;
+    uint32_t gw, groups;                                           // groups of four values per output row and per frame
+    int frame0;                                                    // the launch's first frame
+};
+hipError_t launch_depth_prompt(const DepthPromptArgs& a, int n_frames, hipStream_t s);
+constexpr uint32_t kFocalUnit = 2048;                              // points a wave counts / compacts
+struct FocalArgs {
+    const uint8_t* points; size_t pitch, stride;                   // the set's first frame; bytes between rows and frames
+    size_t chan_bytes, point_bytes;                                // bytes between the coordinates of a point, and between points of a row
+    uint32_t W, npx, nunits, nchunks;                              // points per row and per frame; units of 2048 points, chunks of 8192 values
+    float half_w, half_h;                                          // width / 2, height / 2 (exact)
+    int n_frames;                                                  // frames of the set; list 2 f is frame f's ex, list 2 f + 1 its ey
+    uint32_t *unit_cnt, *unit_off, *totals;                        // workspace [2 n_frames][nunits] twice, [2 n_frames]
+    float* compact; size_t compact_stride;                         // workspace [2 n_frames][compact_stride]: the selected values in order
+    float* sums;                                                   // workspace [2 n_frames][nchunks]
+    float* focal; uint32_t* counts;                                // the caller's, at the set's first frame; counts may be null
+};
+hipError_t launch_focal_from_points(const FocalArgs& a, hipStream_t s);
 hipError_t launch_selftest(int which, unsigned long long seed, unsigned long long* d_mism, hipStream_t s);
 hipError_t launch_coherence_test(uint32_t* blk, size_t dwords, uint32_t tag, uint32_t* d_xcc, uint32_t* d_out, hipStream_t s);     // (mdvt_selftest.hip; r05 diagnosis)
 
