@@ -63,6 +63,11 @@ VIEW_SYMBOLS = ("mdvt_view_centers", "mdvt_render_view_batch")
 # and have no wrapper in the package yet: tools/export_depth_geometry.py calls them
 GEOMETRY_SYMBOLS = ("mdvt_export_geometry_batch", "mdvt_depth_grey_batch")
 
+# the entry points include/mdvt_video_mask.h declares (Pillow's Lanczos resize, the mask network's input, the mask from its prediction),
+# likewise.  They are bound here and have no wrapper in the package yet: tools/generate_video_mask.py calls them
+VIDEO_MASK_SYMBOLS = ("mdvt_lanczos_resize_u8", "mdvt_mask_model_input", "mdvt_mask_from_prediction")
+LANCZOS_AUTO, LANCZOS_FUSED, LANCZOS_TWO_LAUNCH = 0, 1, 2
+
 
 class MdvtError(RuntimeError):
     def __init__(self, code: int, text: str):
@@ -236,6 +241,12 @@ def load():
     L.mdvt_depth_prompt.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, st, st, C.c_int, C.c_double, C.c_int, C.c_int, vp, st, st, vp]
     L.mdvt_focal_from_points.restype = C.c_int
     L.mdvt_focal_from_points.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, st, st, st, vp, vp, vp]
+    L.mdvt_lanczos_resize_u8.restype = C.c_int
+    L.mdvt_lanczos_resize_u8.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, st, st, C.c_int, C.c_int, vp, st, st, C.c_int, vp, vp]
+    L.mdvt_mask_model_input.restype = C.c_int
+    L.mdvt_mask_model_input.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, st, st, C.c_int, C.c_int, C.c_int, vp, vp, vp, st, st, st, vp]
+    L.mdvt_mask_from_prediction.restype = C.c_int
+    L.mdvt_mask_from_prediction.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, st, st, C.c_int, C.c_int, C.c_int, vp, st, st, vp]
     L.mdvt_adapter_prepare_eye.restype = C.c_int
     L.mdvt_adapter_prepare_eye.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, st, st, vp, st, st, C.c_int, C.c_int, vp, st, st, vp, st, st, vp, vp]
     L.mdvt_lhm_moments.restype = C.c_int

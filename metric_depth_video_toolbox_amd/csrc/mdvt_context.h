@@ -1,15 +1,17 @@
 // mdvt_context.h -- what the host units of the C ABI share: the context (mdvt_ctx), its error text, its device memory (the
 // process-wide pools of mdvt_context.hip, the scratch blocks and their one growth rule) and a few facts read off its
-// configuration.  Host only: included by mdvt_context.hip, mdvt_api_render.hip, mdvt_api.hip and mdvt_api_depth_engines.hip, never by a unit that defines kernels.
+// configuration.  Host only: included by mdvt_context.hip, mdvt_api_render.hip, mdvt_api.hip, mdvt_api_depth_engines.hip and mdvt_api_video_mask.hip, never by a unit that defines kernels.
 #pragma once
 
 #include "mdvt_internal.h"
+#include "mdvt_lanczos_table.h"
 
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <array>
+#include <map>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -57,6 +59,8 @@ enum ScratchId {
     SCR_VIEW,                         // mdvt_view_centers: per frame of a launch set its chunk sums (24 B per 8192 vertices); parking: also the edge filter's vertex flags (1 B/px)
     SCR_GEOMETRY,                     // mdvt_export_geometry_batch: per frame of a launch set the filter's triangle flags (2 B per cell) and the compaction's workgroup totals (4 B per 256 triangles / vertices)
     SCR_FOCAL,                        // mdvt_focal_from_points: per frame of a launch set the selected values of both axes (8 B per point), their chunk sums, unit counts and offsets
+    SCR_LANCZOS_TABLES,               // include/mdvt_video_mask.h: the resampler's bounds and coefficient tables of the latest size pair (ctx->lanczos_resident)
+    SCR_MASK_WS,                      // include/mdvt_video_mask.h: per frame of a launch set the intermediate image of the two-launch form, the resized frame or byte plane, the frame's maximum, table or minimum and maximum
     SCR_COUNT
 };
 
@@ -117,6 +121,10 @@ struct mdvt_ctx {
     hipStream_t side = nullptr;
     uint32_t* hugeq2 = nullptr;
     hipEvent_t ev_start = nullptr, ev_join = nullptr, ev_vert[2] = {nullptr, nullptr};
+    // Pillow's Lanczos tables (mdvt_api_video_mask.hip): built once per (in, out) pair and kept on the host; the pairs whose tables
+    // SCR_LANCZOS_TABLES holds on the device: (in_w, out_w, in_h, out_h), all 0 = none
+    std::map<std::pair<int, int>, mdvt::host::LanczosTable> lanczos_tables;
+    int lanczos_resident[4] = {0, 0, 0, 0};
 };
 
 namespace mdvt::host {

@@ -452,6 +452,38 @@ struct FocalArgs {
     float* focal; uint32_t* counts;                                // the caller's, at the set's first frame; counts may be null
 };
 hipError_t launch_focal_from_points(const FocalArgs& a, hipStream_t s);
+// mdvt_video_mask.hip: Pillow's 8-bit Lanczos resampler and the mask step's two normalisations (include/mdvt_video_mask.h)
+constexpr int kLzStrip = 8;                                        // output columns a workgroup of the fused form takes
+constexpr size_t kLzFusedLds = 65536;                              // the LDS a workgroup of the fused form may ask for
+struct LzAxis {                                                    // one axis' table on the device (mdvt_lanczos_table.h)
+    const int32_t* bounds;                                         // [out][2]: the first source sample, the number of taps
+    const int32_t* coef;                                           // [ksize][out]
+};
+struct LzArgs {
+    const uint8_t* src; size_t src_pitch, src_stride;              // the launch's first frame
+    uint8_t* dst; size_t dst_pitch, dst_stride;
+    int C, rep;                                                    // interleaved channels; 3 with C = 1: a value is written as three equal bytes
+    int in_w, in_h, out_w, out_h;                                  // a single pass leaves the other axis' sizes equal
+    LzAxis h, v;
+};
+hipError_t launch_lz_rows(const LzArgs& a, int n_frames, hipStream_t s);      // the horizontal pass: in_w -> out_w on in_h rows
+hipError_t launch_lz_cols(const LzArgs& a, int n_frames, hipStream_t s);      // the vertical pass: in_h -> out_h on out_w columns
+hipError_t launch_lz_copy(const LzArgs& a, int n_frames, hipStream_t s);      // both passes skipped
+hipError_t launch_lz_fused(const LzArgs& a, int n_frames, hipStream_t s);     // both passes, the intermediate strip in LDS
+struct MaskInputArgs {
+    const uint8_t* img; size_t img_pitch, img_stride; int w, h, bgr;          // the resized frames, packed 3 bytes per pixel
+    uint32_t* max_byte;                                            // workspace [n]: zeroed, then each frame's maximum byte
+    float* lut;                                                    // workspace [n][3][256]: plane c's value of byte v
+    double mean[3], std[3];
+    uint8_t* dst; size_t dst_pitch, dst_plane, dst_stride; int dst_vec;       // _vec: four values of a plane are one aligned 16-byte store
+};
+hipError_t launch_mask_model_input(const MaskInputArgs& a, int n_frames, hipStream_t s);
+struct MaskPredArgs {
+    const uint8_t* pred; size_t pred_pitch, pred_stride; int w, h;            // float32 planes
+    uint32_t* stats;                                               // workspace [n][4]: ordered keys of min and max, the non-finite flag
+    uint8_t* dst; size_t dst_pitch, dst_stride; int rep;           // the byte planes; rep as in LzArgs
+};
+hipError_t launch_mask_pred_bytes(const MaskPredArgs& a, int n_frames, hipStream_t s);
 hipError_t launch_selftest(int which, unsigned long long seed, unsigned long long* d_mism, hipStream_t s);
 hipError_t launch_coherence_test(uint32_t* blk, size_t dwords, uint32_t tag, uint32_t* d_xcc, uint32_t* d_out, hipStream_t s);     // (mdvt_selftest.hip; r05 diagnosis)
 
