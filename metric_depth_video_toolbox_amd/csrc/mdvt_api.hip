@@ -41,8 +41,7 @@ constexpr int kTeleaChunk = mdvt::kTeleaMaxImages;      // images per pass (14 B
 constexpr int kNormalInfillChunk = 16;       // images per launch set
 // FFV1's default state transition tables, built once per process
 const mdvt::Ffv1StateTables& ffv1_states() { static const mdvt::Ffv1StateTables tab = mdvt::ffv1_default_states(); return tab; }
-// What a vector path asks of an array: every pointer, pitch, stride (or row length) listed is a multiple of k; the pitch of a single row is never used.
-template <class... A> bool multiples_of(size_t k, A... a) { return (((uintptr_t)a % k == 0) && ...); }
+// (a vector path's multiples_of: the pitch of a single row is never used)
 size_t pitch_in_use(size_t pitch, int rows) { return rows == 1 ? 0 : pitch; }
 
 // The n images (frames, when both eyes travel together) from i0 on of a caller's array.
@@ -74,6 +73,54 @@ int copy_remaining(mdvt_ctx* c, uint32_t* d_remaining, const uint32_t* pass, int
     for (int e = 0; e < eyes; ++e)
         MDVT_HIP(c, hipMemcpyAsync(d_remaining + (size_t)e * n_frames + f0, pass + (size_t)e * nf, (size_t)nf * sizeof(uint32_t),
                                    hipMemcpyDeviceToDevice, s));
+    return MDVT_OK;
+}
+
+// What mdvt_metric_depth_codes (metric) and mdvt_depth_video_codes share: float32 source planes, a factor on the device and a 0 / 1
+// flag of their own (scale_shift and style: the factor is required; scale and nan_to_max: it may be null), codes and optional depth
+// planes out.  src_pitch_name, flag_name, plane_pitch_name: the caller's argument names for the refusals' texts.  No scratch block:
+// launches only.
+int depth_codes(mdvt_ctx* c, bool metric, int in_w, int in_h, int n_frames, const float* d_src, size_t src_pitch, size_t src_stride,
+                const char* src_pitch_name, const float* d_factor, int flag, const char* flag_name, double max_depth, int out_w, int out_h,
+                uint8_t* d_codes, size_t codes_pitch, size_t codes_stride, int order,
+                float* d_plane, size_t plane_pitch, size_t plane_stride, const char* plane_pitch_name, void* stream)
+{
+    if (!c) return MDVT_ERR_INVALID_ARG;
+    if (!d_src || (metric && !d_factor) || !d_codes) return fail(c, MDVT_ERR_INVALID_ARG, "NULL buffer");
+    if (in_w < 1 || in_h < 1 || out_w < 1 || out_h < 1) return fail(c, MDVT_ERR_INVALID_ARG, "bad size %d x %d -> %d x %d", in_w, in_h, out_w, out_h);
+    if (n_frames < 1) return fail(c, MDVT_ERR_INVALID_ARG, "n_frames must be >= 1");
+    if (flag != 0 && flag != 1) return fail(c, MDVT_ERR_INVALID_ARG, "%s must be 0 or 1, got %d", flag_name, flag);
+    if (order != 0 && order != 1) return fail(c, MDVT_ERR_INVALID_ARG, "order must be 0 (RGB) or 1 (BGR), got %d", order);
+    if (!(max_depth > 0.0)) return fail(c, MDVT_ERR_INVALID_ARG, "max_depth must be > 0");
+    if (src_pitch < (size_t)in_w * 4u) return fail(c, MDVT_ERR_INVALID_ARG, "%s smaller than one row", src_pitch_name);
+    if (codes_pitch < (size_t)out_w * 3u) return fail(c, MDVT_ERR_INVALID_ARG, "codes_pitch smaller than one row");
+    if (d_plane && plane_pitch < (size_t)out_w * 4u) return fail(c, MDVT_ERR_INVALID_ARG, "%s smaller than one row", plane_pitch_name);
+    if (n_frames > 1 && (src_stride < src_pitch * (size_t)in_h || codes_stride < codes_pitch * (size_t)out_h ||
+                         (d_plane && plane_stride < plane_pitch * (size_t)out_h)))
+        return fail(c, MDVT_ERR_INVALID_ARG, "stride smaller than one frame");
+    if ((uint64_t)out_w * (uint64_t)out_h >= ((uint64_t)1 << 31))
+        return fail(c, MDVT_ERR_UNSUPPORTED, "output frame too large (%d x %d)", out_w, out_h);
+    DeviceGuard g(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (n_frames == 1) src_stride = codes_stride = plane_stride = 0;
+    mdvt::DepthCodesArgs a{};
+    a.src = reinterpret_cast<const uint8_t*>(d_src); a.src_pitch = src_pitch; a.src_stride = src_stride; a.in_w = in_w; a.in_h = in_h;
+    a.src_vec = multiples_of(16, d_src, src_pitch, src_stride);
+    a.fmax = (float)max_depth; a.multi = 4228250625.0 / max_depth;
+    a.out_w = out_w; a.out_h = out_h; a.resize = in_w != out_w || in_h != out_h;
+    a.ratio_x = (double)in_w / (double)out_w; a.ratio_y = (double)in_h / (double)out_h;
+    a.codes = d_codes; a.codes_pitch = codes_pitch; a.codes_stride = codes_stride; a.bgr = order;
+    a.codes_vec = multiples_of(4, d_codes, codes_pitch, codes_stride);
+    a.plane = reinterpret_cast<uint8_t*>(d_plane); a.plane_pitch = plane_pitch; a.plane_stride = plane_stride;
+    a.plane_vec = d_plane && multiples_of(16, d_plane, plane_pitch, plane_stride);
+    a.gw = ((uint32_t)out_w + 3u) / 4u; a.groups = a.gw * (uint32_t)out_h;
+    if (metric) { a.scale_shift = d_factor; a.style = flag; }
+    else { a.scale = d_factor; a.nan_to_max = flag; }
+    for (int f0 = 0; f0 < n_frames; f0 += kGridFrames) {
+        a.frame0 = f0;
+        const int n = set_len(n_frames, f0, kGridFrames);
+        MDVT_HIP(c, metric ? mdvt::launch_metric_codes(a, n, s) : mdvt::launch_depth_sink(a, n, s));
+    }
     return MDVT_OK;
 }
 
@@ -310,7 +357,7 @@ static int finish_infill_mask(mdvt_ctx* c, const uint8_t* d_seed, const uint8_t*
     const mdvt::BlurKernel K = masked_blur_kernel();
     const int fchunk = kTeleaChunk / eyes;                   // frames per pass: both eyes of a frame travel together
     for (int f0 = 0; f0 < n_frames; f0 += fchunk) {
-        const int nf = n_frames - f0 < fchunk ? n_frames - f0 : fchunk, n = nf * eyes;
+        const int nf = set_len(n_frames, f0, fchunk), n = nf * eyes;
         const mdvt::ImageSet seed = slice(d_seed, seed_pitch, seed_stride, f0, nf, d_seed_right ? d_seed_right - d_seed : 0);
         const mdvt::ImageSet out = slice(d_out, out_pitch, out_stride, f0, nf, d_out_right ? d_out_right - d_out : 0);
         const mdvt::ImageSet work{ws.img, (size_t)3 * W, 3 * npx, 0, n};
@@ -373,7 +420,7 @@ static int finish_infill_mask_heap(mdvt_ctx* c, const uint8_t* d_seed, const uin
     const uint32_t key = packed_key_rgb(c);
     const mdvt::BlurKernel K = masked_blur_kernel();
     for (int f0 = 0; f0 < n_frames; f0 += fchunk) {
-        const int nf = n_frames - f0 < fchunk ? n_frames - f0 : fchunk, n = nf * eyes;
+        const int nf = set_len(n_frames, f0, fchunk), n = nf * eyes;
         const mdvt::ImageSet seed = slice(d_seed, seed_pitch, seed_stride, f0, nf, d_seed_right ? d_seed_right - d_seed : 0);
         const mdvt::ImageSet out = slice(d_out, out_pitch, out_stride, f0, nf, d_out_right ? d_out_right - d_out : 0);
         const mdvt::ImageSet work{heap.p + mdvt::telea_heap_img_offset(W, H), (size_t)3 * W, per_image, 0, n};
@@ -460,7 +507,7 @@ int mdvt_encode_video_frames(mdvt_ctx* c, int width, int height, int slices_h, i
     ca.W = width; ca.H = height; ca.nh = slices_h; ca.nv = slices_v;
     ca.scratch = scratch; ca.slice_stride = slice_stride; ca.cap = cap; ca.cap_is_24bit = cap == (uint32_t)limit; ca.slice_n = slice_n;
     for (int f0 = 0; f0 < n_frames; f0 += fchunk) {
-        const int nf = n_frames - f0 < fchunk ? n_frames - f0 : fchunk;
+        const int nf = set_len(n_frames, f0, fchunk);
         ca.src = d_src + (size_t)f0 * frame_stride;
         MDVT_HIP(c, mdvt::launch_ffv1_code(ca, ffv1_states(), nf * spf, s));
         const mdvt::Ffv1LayoutArgs la{slice_n, spf, nf, d_sizes + f0, reinterpret_cast<unsigned long long*>(d_offsets) + f0, used,
@@ -558,7 +605,7 @@ int mdvt_decode_video_frames(mdvt_ctx* c, int width, int height, const uint8_t* 
     const int fchunk = slots_afforded(c, per_frame, n_frames);
     MDVT_HIP(c, scratch_reserve(c, c->scratch[SCR_FFV1_DEC], (size_t)fchunk * per_frame, s));
     for (int f0 = 0; f0 < n_frames; f0 += fchunk) {
-        const int nf = n_frames - f0 < fchunk ? n_frames - f0 : fchunk;
+        const int nf = set_len(n_frames, f0, fchunk);
         a.n_frames = nf;
         a.offsets = reinterpret_cast<const unsigned long long*>(d_offsets) + f0; a.sizes = d_sizes + f0;
         a.dst = d_dst + (size_t)f0 * frame_stride; a.status = d_status + f0;
@@ -625,7 +672,6 @@ int mdvt_convergence_depths(mdvt_ctx* c, int width, int height, const uint8_t* d
     hipStream_t s = (hipStream_t)stream;
     const uint32_t npx = (uint32_t)width * (uint32_t)height;
     const uint32_t nchunks = (npx + 8191u) / 8192u, nunits = (npx + 2047u) / 2048u;
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
     // per frame of a set: the chunk sums; with a mask the ballot words (1 bit/px), the selected codes (2 B/px), unit counts and offsets, the count
     const size_t bits_bytes = with_mask ? (size_t)nunits * 32 * sizeof(unsigned long long) : 0;
     const size_t compact_stride = ((size_t)npx + 7) & ~(size_t)7;
@@ -647,14 +693,14 @@ int mdvt_convergence_depths(mdvt_ctx* c, int width, int height, const uint8_t* d
     a.div = (float)(4228250625.0 / max_depth);               // 255^4 / max_depth in double, rounded once (fcd:60)
     a.compact_stride = compact_stride;
     uint8_t* w = c->scratch[SCR_CONV].p;
-    a.bits = reinterpret_cast<unsigned long long*>(w); w += (size_t)fchunk * bits_bytes;
-    a.compact = reinterpret_cast<uint16_t*>(w); w += (size_t)fchunk * compact_bytes;
-    a.sums = reinterpret_cast<float*>(w); w += (size_t)fchunk * sums_bytes;
-    a.unit_cnt = reinterpret_cast<uint32_t*>(w); w += (size_t)fchunk * unit_bytes;
-    a.unit_off = reinterpret_cast<uint32_t*>(w); w += (size_t)fchunk * unit_bytes;
-    a.totals = reinterpret_cast<uint32_t*>(w);
+    a.bits = take<unsigned long long>(w, (size_t)fchunk * bits_bytes);
+    a.compact = take<uint16_t>(w, (size_t)fchunk * compact_bytes);
+    a.sums = take<float>(w, (size_t)fchunk * sums_bytes);
+    a.unit_cnt = take<uint32_t>(w, (size_t)fchunk * unit_bytes);
+    a.unit_off = take<uint32_t>(w, (size_t)fchunk * unit_bytes);
+    a.totals = take<uint32_t>(w, with_mask ? (size_t)fchunk * 16 : 0);
     for (int f0 = 0; f0 < n_frames; f0 += fchunk) {
-        a.n_frames = n_frames - f0 < fchunk ? n_frames - f0 : fchunk;
+        a.n_frames = set_len(n_frames, f0, fchunk);
         a.n_masked = n_mask_frames - f0 < 0 ? 0 : n_mask_frames - f0 < a.n_frames ? n_mask_frames - f0 : a.n_frames;
         a.depth = d_depth + (size_t)f0 * depth_stride;
         a.mask = a.n_masked ? d_mask + (size_t)f0 * mask_stride : nullptr;
@@ -719,82 +765,18 @@ int mdvt_metric_depth_codes(mdvt_ctx* c, int in_w, int in_h, int n_frames, const
                             uint8_t* d_codes, size_t codes_pitch, size_t codes_stride, int order,
                             float* d_depth, size_t depth_pitch, size_t depth_stride, void* stream)
 {
-    if (!c) return MDVT_ERR_INVALID_ARG;
-    if (!d_rel || !d_scale_shift || !d_codes) return fail(c, MDVT_ERR_INVALID_ARG, "NULL buffer");
-    if (in_w < 1 || in_h < 1 || out_w < 1 || out_h < 1) return fail(c, MDVT_ERR_INVALID_ARG, "bad size %d x %d -> %d x %d", in_w, in_h, out_w, out_h);
-    if (n_frames < 1) return fail(c, MDVT_ERR_INVALID_ARG, "n_frames must be >= 1");
-    if (style != 0 && style != 1) return fail(c, MDVT_ERR_INVALID_ARG, "style must be 0 or 1, got %d", style);
-    if (order != 0 && order != 1) return fail(c, MDVT_ERR_INVALID_ARG, "order must be 0 (RGB) or 1 (BGR), got %d", order);
-    if (!(max_depth > 0.0)) return fail(c, MDVT_ERR_INVALID_ARG, "max_depth must be > 0");
-    if (rel_pitch < (size_t)in_w * 4u) return fail(c, MDVT_ERR_INVALID_ARG, "rel_pitch smaller than one row");
-    if (codes_pitch < (size_t)out_w * 3u) return fail(c, MDVT_ERR_INVALID_ARG, "codes_pitch smaller than one row");
-    if (d_depth && depth_pitch < (size_t)out_w * 4u) return fail(c, MDVT_ERR_INVALID_ARG, "depth_pitch smaller than one row");
-    if (n_frames > 1 && (rel_stride < rel_pitch * (size_t)in_h || codes_stride < codes_pitch * (size_t)out_h ||
-                         (d_depth && depth_stride < depth_pitch * (size_t)out_h)))
-        return fail(c, MDVT_ERR_INVALID_ARG, "stride smaller than one frame");
-    if ((uint64_t)out_w * (uint64_t)out_h >= ((uint64_t)1 << 31))
-        return fail(c, MDVT_ERR_UNSUPPORTED, "output frame too large (%d x %d)", out_w, out_h);
-    DeviceGuard g(c->device);
-    hipStream_t s = (hipStream_t)stream;
-    if (n_frames == 1) rel_stride = codes_stride = depth_stride = 0;
-    mdvt::MetricCodesArgs a{};
-    a.rel = reinterpret_cast<const uint8_t*>(d_rel); a.rel_pitch = rel_pitch; a.rel_stride = rel_stride; a.in_w = in_w; a.in_h = in_h;
-    a.rel_vec = multiples_of(16, d_rel, rel_pitch, rel_stride);
-    a.scale_shift = d_scale_shift; a.style = style; a.fmax = (float)max_depth; a.multi = 4228250625.0 / max_depth;
-    a.out_w = out_w; a.out_h = out_h; a.resize = in_w != out_w || in_h != out_h;
-    a.ratio_x = (double)in_w / (double)out_w; a.ratio_y = (double)in_h / (double)out_h;
-    a.codes = d_codes; a.codes_pitch = codes_pitch; a.codes_stride = codes_stride; a.bgr = order;
-    a.codes_vec = multiples_of(4, d_codes, codes_pitch, codes_stride);
-    a.depth = reinterpret_cast<uint8_t*>(d_depth); a.depth_pitch = depth_pitch; a.depth_stride = depth_stride;
-    a.depth_vec = d_depth && multiples_of(16, d_depth, depth_pitch, depth_stride);
-    a.gw = ((uint32_t)out_w + 3u) / 4u; a.groups = a.gw * (uint32_t)out_h;
-    for (int f0 = 0; f0 < n_frames; f0 += 32768) {               // (the grid's second dimension holds the frames)
-        a.frame0 = f0;
-        MDVT_HIP(c, mdvt::launch_metric_codes(a, n_frames - f0 < 32768 ? n_frames - f0 : 32768, s));
-    }
-    return MDVT_OK;
+    return depth_codes(c, true, in_w, in_h, n_frames, d_rel, rel_pitch, rel_stride, "rel_pitch", d_scale_shift, style, "style", max_depth, out_w, out_h,
+                       d_codes, codes_pitch, codes_stride, order, d_depth, depth_pitch, depth_stride, "depth_pitch", stream);
 }
 
-// Metric depth planes to a depth video's codes (mdvt_depth_sink.hip; include/mdvt_depth_sink.h).  No scratch block: launches only.
+// Metric depth planes to a depth video's codes (mdvt_depth_sink.hip; include/mdvt_depth_sink.h).
 int mdvt_depth_video_codes(mdvt_ctx* c, int in_w, int in_h, int n_frames, const float* d_depth, size_t depth_pitch, size_t depth_stride,
                            const float* d_scale, int nan_to_max, double max_depth, int out_w, int out_h,
                            uint8_t* d_codes, size_t codes_pitch, size_t codes_stride, int order,
                            float* d_plane, size_t plane_pitch, size_t plane_stride, void* stream)
 {
-    if (!c) return MDVT_ERR_INVALID_ARG;
-    if (!d_depth || !d_codes) return fail(c, MDVT_ERR_INVALID_ARG, "NULL buffer");
-    if (in_w < 1 || in_h < 1 || out_w < 1 || out_h < 1) return fail(c, MDVT_ERR_INVALID_ARG, "bad size %d x %d -> %d x %d", in_w, in_h, out_w, out_h);
-    if (n_frames < 1) return fail(c, MDVT_ERR_INVALID_ARG, "n_frames must be >= 1");
-    if (nan_to_max != 0 && nan_to_max != 1) return fail(c, MDVT_ERR_INVALID_ARG, "nan_to_max must be 0 or 1, got %d", nan_to_max);
-    if (order != 0 && order != 1) return fail(c, MDVT_ERR_INVALID_ARG, "order must be 0 (RGB) or 1 (BGR), got %d", order);
-    if (!(max_depth > 0.0)) return fail(c, MDVT_ERR_INVALID_ARG, "max_depth must be > 0");
-    if (depth_pitch < (size_t)in_w * 4u) return fail(c, MDVT_ERR_INVALID_ARG, "depth_pitch smaller than one row");
-    if (codes_pitch < (size_t)out_w * 3u) return fail(c, MDVT_ERR_INVALID_ARG, "codes_pitch smaller than one row");
-    if (d_plane && plane_pitch < (size_t)out_w * 4u) return fail(c, MDVT_ERR_INVALID_ARG, "plane_pitch smaller than one row");
-    if (n_frames > 1 && (depth_stride < depth_pitch * (size_t)in_h || codes_stride < codes_pitch * (size_t)out_h ||
-                         (d_plane && plane_stride < plane_pitch * (size_t)out_h)))
-        return fail(c, MDVT_ERR_INVALID_ARG, "stride smaller than one frame");
-    if ((uint64_t)out_w * (uint64_t)out_h >= ((uint64_t)1 << 31))
-        return fail(c, MDVT_ERR_UNSUPPORTED, "output frame too large (%d x %d)", out_w, out_h);
-    DeviceGuard g(c->device);
-    hipStream_t s = (hipStream_t)stream;
-    if (n_frames == 1) depth_stride = codes_stride = plane_stride = 0;
-    mdvt::DepthSinkArgs a{};
-    a.src = reinterpret_cast<const uint8_t*>(d_depth); a.src_pitch = depth_pitch; a.src_stride = depth_stride; a.in_w = in_w; a.in_h = in_h;
-    a.src_vec = multiples_of(16, d_depth, depth_pitch, depth_stride);
-    a.scale = d_scale; a.nan_to_max = nan_to_max; a.fmax = (float)max_depth; a.multi = 4228250625.0 / max_depth;
-    a.out_w = out_w; a.out_h = out_h; a.resize = in_w != out_w || in_h != out_h;
-    a.ratio_x = (double)in_w / (double)out_w; a.ratio_y = (double)in_h / (double)out_h;
-    a.codes = d_codes; a.codes_pitch = codes_pitch; a.codes_stride = codes_stride; a.bgr = order;
-    a.codes_vec = multiples_of(4, d_codes, codes_pitch, codes_stride);
-    a.plane = reinterpret_cast<uint8_t*>(d_plane); a.plane_pitch = plane_pitch; a.plane_stride = plane_stride;
-    a.plane_vec = d_plane && multiples_of(16, d_plane, plane_pitch, plane_stride);
-    a.gw = ((uint32_t)out_w + 3u) / 4u; a.groups = a.gw * (uint32_t)out_h;
-    for (int f0 = 0; f0 < n_frames; f0 += 32768) {               // (the grid's second dimension holds the frames)
-        a.frame0 = f0;
-        MDVT_HIP(c, mdvt::launch_depth_sink(a, n_frames - f0 < 32768 ? n_frames - f0 : 32768, s));
-    }
-    return MDVT_OK;
+    return depth_codes(c, false, in_w, in_h, n_frames, d_depth, depth_pitch, depth_stride, "depth_pitch", d_scale, nan_to_max, "nan_to_max", max_depth,
+                       out_w, out_h, d_codes, codes_pitch, codes_stride, order, d_plane, plane_pitch, plane_stride, "plane_pitch", stream);
 }
 
 }  // extern "C"
@@ -853,11 +835,11 @@ int mdvt_adapter_prepare_eye(mdvt_ctx* c, int eye_w, int eye_h, int n_frames, in
     a.mirror = eye == 0;
     a.rs = mdvt::adapter_resize(eye_w, eye_h, model_w, model_h);
     a.image_pitch = image_pitch; a.image_stride = image_stride; a.mmask_pitch = model_mask_pitch; a.mmask_stride = model_mask_stride;
-    for (int f0 = 0; f0 < n_frames; f0 += 32768) {               // (the grid's third dimension holds the frames)
+    for (int f0 = 0; f0 < n_frames; f0 += kGridFrames) {
         a.color = {d_color + (size_t)eye * 3 * eye_w + (size_t)f0 * color_stride, color_pitch, color_stride};
         a.mask = {d_mask + (size_t)eye * 3 * eye_w + (size_t)f0 * mask_stride, mask_pitch, mask_stride};
         a.image = d_image + (size_t)f0 * image_stride; a.mmask = d_model_mask + (size_t)f0 * model_mask_stride; a.holes = d_hole_counts + f0;
-        MDVT_HIP(c, mdvt::launch_adapter_prepare(a, n_frames - f0 < 32768 ? n_frames - f0 : 32768, s));
+        MDVT_HIP(c, mdvt::launch_adapter_prepare(a, set_len(n_frames, f0, kGridFrames), s));
     }
     return MDVT_OK;
 }
@@ -880,11 +862,11 @@ int mdvt_lhm_moments(mdvt_ctx* c, int width, int height, int n_frames, const uin
     mdvt::LhmMomentsArgs a{};
     a.W = width; a.H = height;
     a.vec = multiples_of(4, d_rgb, pitch_in_use(pitch, height), stride) && (!d_mask || multiples_of(4, d_mask, pitch_in_use(mask_pitch, height), mask_stride));
-    for (int f0 = 0; f0 < n_frames; f0 += 32768) {
+    for (int f0 = 0; f0 < n_frames; f0 += kGridFrames) {
         a.img = {d_rgb + (size_t)f0 * stride, pitch, stride};
         a.mask = {d_mask ? d_mask + (size_t)f0 * mask_stride : nullptr, mask_pitch, mask_stride};
         a.out = reinterpret_cast<unsigned long long*>(d_out) + (size_t)f0 * 10;
-        MDVT_HIP(c, mdvt::launch_lhm_moments(a, n_frames - f0 < 32768 ? n_frames - f0 : 32768, s));
+        MDVT_HIP(c, mdvt::launch_lhm_moments(a, set_len(n_frames, f0, kGridFrames), s));
     }
     return MDVT_OK;
 }
@@ -907,10 +889,10 @@ int mdvt_lhm_apply(mdvt_ctx* c, int width, int height, int n_frames, const uint8
     mdvt::LhmApplyArgs a{};
     a.W = width; a.H = height; a.out_pitch = out_pitch; a.out_stride = out_stride;
     a.vec = multiples_of(4, d_rgb, pitch_in_use(pitch, height), stride, d_out, pitch_in_use(out_pitch, height), out_stride);
-    for (int f0 = 0; f0 < n_frames; f0 += 32768) {
+    for (int f0 = 0; f0 < n_frames; f0 += kGridFrames) {
         a.img = {d_rgb + (size_t)f0 * stride, pitch, stride};
         a.params = d_params + (size_t)f0 * 15; a.out = d_out + (size_t)f0 * out_stride;
-        MDVT_HIP(c, mdvt::launch_lhm_apply(a, n_frames - f0 < 32768 ? n_frames - f0 : 32768, s));
+        MDVT_HIP(c, mdvt::launch_lhm_apply(a, set_len(n_frames, f0, kGridFrames), s));
     }
     return MDVT_OK;
 }

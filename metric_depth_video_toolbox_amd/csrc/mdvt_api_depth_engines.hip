@@ -1,18 +1,11 @@
 // mdvt_api_depth_engines.hip -- the three entry points of include/mdvt_depth_engines.h: frames into a model, PromptDA's prompt and
 // UniK3D's focal estimate (kernels: mdvt_depth_engines.hip).  An entry point's refusals stand in the order the caller meets their
-// texts, each fail(...) text at its check, in the vocabulary of mdvt_api.hip.  Host code only.
+// texts, each fail(...) text at its check; the layout tests, set loops and the scratch carver are mdvt_context.h's.  Host code only.
 #include "mdvt_context.h"
 #include "mdvt_depth_engines.h"
 
 using namespace mdvt;
 using namespace mdvt::host;
-
-namespace {
-
-// What a vector path asks of an array: every pointer, pitch and stride listed is a multiple of k.
-template <class... A> bool multiples_of(size_t k, A... a) { return (((uintptr_t)a % k == 0) && ...); }
-
-}  // namespace
 
 extern "C" {
 
@@ -48,9 +41,9 @@ int mdvt_model_frames(mdvt_ctx* c, int in_w, int in_h, int n_frames, const uint8
     a.as_float = format;
     a.dst_vec = multiples_of(format ? 16 : 4, d_out, out_pitch, out_plane_stride, out_stride);
     a.gw = ((uint32_t)out_w + 3u) / 4u; a.groups = a.gw * (uint32_t)out_h;
-    for (int f0 = 0; f0 < n_frames; f0 += 32768) {               // (the grid's second dimension holds the frames)
+    for (int f0 = 0; f0 < n_frames; f0 += kGridFrames) {
         a.frame0 = f0;
-        MDVT_HIP(c, mdvt::launch_model_frames(a, n_frames - f0 < 32768 ? n_frames - f0 : 32768, s));
+        MDVT_HIP(c, mdvt::launch_model_frames(a, set_len(n_frames, f0, kGridFrames), s));
     }
     return MDVT_OK;
 }
@@ -88,9 +81,9 @@ int mdvt_depth_prompt(mdvt_ctx* c, int in_w, int in_h, int n_frames, const uint8
     a.dst = reinterpret_cast<uint8_t*>(d_prompt); a.dst_pitch = prompt_pitch; a.dst_stride = prompt_stride;
     a.dst_vec = multiples_of(16, d_prompt, prompt_pitch, prompt_stride);
     a.gw = ((uint32_t)out_w + 3u) / 4u; a.groups = a.gw * (uint32_t)out_h;
-    for (int f0 = 0; f0 < n_frames; f0 += 32768) {               // (the grid's second dimension holds the frames)
+    for (int f0 = 0; f0 < n_frames; f0 += kGridFrames) {
         a.frame0 = f0;
-        MDVT_HIP(c, mdvt::launch_depth_prompt(a, n_frames - f0 < 32768 ? n_frames - f0 : 32768, s));
+        MDVT_HIP(c, mdvt::launch_depth_prompt(a, set_len(n_frames, f0, kGridFrames), s));
     }
     return MDVT_OK;
 }
@@ -120,7 +113,6 @@ int mdvt_focal_from_points(mdvt_ctx* c, int width, int height, int n_frames, con
     if (n_frames == 1) points_stride = 0;
     const uint32_t npx = (uint32_t)width * (uint32_t)height;
     const uint32_t nchunks = (npx + 8191u) / 8192u, nunits = (npx + mdvt::kFocalUnit - 1u) / mdvt::kFocalUnit;
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
     // per list (a frame has two): the selected values (4 B per point), the chunk sums, the unit counts and offsets, the count
     const size_t compact_stride = ((size_t)npx + 3) & ~(size_t)3;
     const size_t compact_bytes = compact_stride * sizeof(float);
@@ -135,13 +127,13 @@ int mdvt_focal_from_points(mdvt_ctx* c, int width, int height, int n_frames, con
     a.half_w = (float)((double)width / 2.0); a.half_h = (float)((double)height / 2.0);
     a.compact_stride = compact_stride;
     uint8_t* w = c->scratch[SCR_FOCAL].p;
-    a.compact = reinterpret_cast<float*>(w); w += (size_t)fchunk * 2 * compact_bytes;
-    a.sums = reinterpret_cast<float*>(w); w += up16((size_t)fchunk * 2 * sums_bytes);
-    a.unit_cnt = reinterpret_cast<uint32_t*>(w); w += up16((size_t)fchunk * 2 * unit_bytes);
-    a.unit_off = reinterpret_cast<uint32_t*>(w); w += up16((size_t)fchunk * 2 * unit_bytes);
-    a.totals = reinterpret_cast<uint32_t*>(w);
+    a.compact = take<float>(w, (size_t)fchunk * 2 * compact_bytes);
+    a.sums = take<float>(w, up16((size_t)fchunk * 2 * sums_bytes));
+    a.unit_cnt = take<uint32_t>(w, up16((size_t)fchunk * 2 * unit_bytes));
+    a.unit_off = take<uint32_t>(w, up16((size_t)fchunk * 2 * unit_bytes));
+    a.totals = take<uint32_t>(w, (size_t)fchunk * 2 * 16);
     for (int f0 = 0; f0 < n_frames; f0 += fchunk) {
-        a.n_frames = n_frames - f0 < fchunk ? n_frames - f0 : fchunk;
+        a.n_frames = set_len(n_frames, f0, fchunk);
         a.points = reinterpret_cast<const uint8_t*>(d_points) + (size_t)f0 * points_stride;
         a.focal = d_focal + 2 * (size_t)f0; a.counts = d_counts ? d_counts + 2 * (size_t)f0 : nullptr;
         MDVT_HIP(c, mdvt::launch_focal_from_points(a, s));

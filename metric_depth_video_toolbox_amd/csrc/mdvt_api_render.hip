@@ -877,7 +877,6 @@ int mdvt_view_centers(mdvt_ctx* c, int n_frames, const mdvt_frame_params* params
     DeviceGuard g(c->device);
     hipStream_t const s = (hipStream_t)stream;
     const uint32_t npx = (uint32_t)W * (uint32_t)H, nchunks = (npx + 8191u) / 8192u;
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
     const size_t sums_bytes = up16((size_t)nchunks * mdvt::kViewSumBytes), flag_bytes = park ? up16((size_t)npx) : 0;
     const int fchunk = slots_afforded(c, sums_bytes + flag_bytes, n_frames < 4096 ? n_frames : 4096);
     MDVT_HIP(c, scratch_reserve(c, c->scratch[SCR_VIEW], (size_t)fchunk * (sums_bytes + flag_bytes), s));
@@ -894,7 +893,7 @@ int mdvt_view_centers(mdvt_ctx* c, int n_frames, const mdvt_frame_params* params
     a.centers = d_centers;
     for (int f0 = 0; f0 < n_frames; f0 += fchunk) {
         a.frame0 = f0;
-        a.n_frames = n_frames - f0 < fchunk ? n_frames - f0 : fchunk;
+        a.n_frames = set_len(n_frames, f0, fchunk);
         if (park) {
             MDVT_HIP(c, launch_zero_bytes(flags, (size_t)a.n_frames * flag_bytes, s));
             MDVT_HIP(c, launch_edge_filter(d_depth_rgb, depth_pitch, depth_stride, dfp, f0, a.n_frames, W, H, 0, nullptr, 0, flags, flag_bytes, s));
@@ -958,7 +957,6 @@ int mdvt_export_geometry_batch(mdvt_ctx* c, int n_frames, const mdvt_frame_param
     a.npx = (uint32_t)N; a.ncell = (uint32_t)ncell;
     a.nbt = (uint32_t)((2 * ncell + mdvt::kGeomBlock - 1) / mdvt::kGeomBlock);
     a.nbv = (uint32_t)((N + mdvt::kGeomBlock - 1) / mdvt::kGeomBlock);
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
     const size_t flag_bytes = opts->remove_edges ? up16(2 * ncell) : 0, total_bytes = up16(((size_t)a.nbt + a.nbv) * sizeof(uint32_t));
     const int fchunk = slots_afforded(c, flag_bytes + total_bytes, n_frames < 4096 ? n_frames : 4096);
     MDVT_HIP(c, scratch_reserve(c, c->scratch[SCR_GEOMETRY], (size_t)fchunk * (flag_bytes + total_bytes), s));
@@ -979,7 +977,7 @@ int mdvt_export_geometry_batch(mdvt_ctx* c, int n_frames, const mdvt_frame_param
     a.flags_stride = flag_bytes;
     for (int f0 = 0; f0 < n_frames; f0 += fchunk) {
         a.frame0 = f0;
-        a.n_frames = n_frames - f0 < fchunk ? n_frames - f0 : fchunk;
+        a.n_frames = set_len(n_frames, f0, fchunk);
         MDVT_HIP(c, mdvt::launch_export_geometry(a, s));
     }
     MDVT_HIP(c, hipEventRecord(slot->done, s));

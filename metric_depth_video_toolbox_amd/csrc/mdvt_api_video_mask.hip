@@ -1,7 +1,7 @@
 // mdvt_api_video_mask.hip -- the three entry points of include/mdvt_video_mask.h: Pillow's 8-bit Lanczos resize, rembg's normalize in
 // front of the mask network and its predict's tail behind it (kernels: mdvt_video_mask.hip; the tables: mdvt_lanczos_table.h).  An entry
-// point's refusals stand in the order the caller meets their texts, each fail(...) text at its check, in the vocabulary of
-// mdvt_api_depth_engines.hip.  Host code only.
+// point's refusals stand in the order the caller meets their texts, each fail(...) text at its check; the layout tests, set loops
+// and the scratch carver are mdvt_context.h's.  Host code only.
 #include "mdvt_context.h"
 #include "mdvt_video_mask.h"
 
@@ -10,9 +10,6 @@ using namespace mdvt::host;
 
 namespace {
 
-template <class... A> bool multiples_of(size_t k, A... a) { return (((uintptr_t)a % k == 0) && ...); }
-
-constexpr size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 constexpr size_t kTablePairs = 32;             // pairs the host keeps before it starts over
 
 // One resize as the entry points plan it: which passes run, in which form, and what a frame of a launch set needs for it.
@@ -91,7 +88,7 @@ int stage_tables(mdvt_ctx* c, ResizePlan& p, hipStream_t s)
 
 struct Image { const uint8_t* p; size_t pitch, stride; };
 
-// n frames (one launch set, at most 32768) of src through the plan to dst; tmp: n * p.tmp_bytes of workspace.
+// n frames (one launch set, at most kGridFrames) of src through the plan to dst; tmp: n * p.tmp_bytes of workspace.
 hipError_t resize_set(const ResizePlan& p, Image src, uint8_t* dst, size_t dst_pitch, size_t dst_stride, int rep, uint8_t* tmp, int n, hipStream_t s)
 {
     LzArgs a{};
@@ -111,10 +108,10 @@ hipError_t resize_set(const ResizePlan& p, Image src, uint8_t* dst, size_t dst_p
     return p.rows ? launch_lz_rows(a, n, s) : launch_lz_cols(a, n, s);
 }
 
-// the frames of a launch set: what the workspace budget affords of per_frame bytes each, at most 32768 (a grid dimension holds them)
+// the frames of a launch set: what the workspace budget affords of per_frame bytes each, at most kGridFrames
 int set_frames(const mdvt_ctx* c, size_t per_frame, int n_frames)
 {
-    const int cap = n_frames < 32768 ? n_frames : 32768;
+    const int cap = set_len(n_frames, 0, kGridFrames);
     return per_frame ? slots_afforded(c, per_frame, cap) : cap;
 }
 
@@ -150,7 +147,7 @@ int mdvt_lanczos_resize_u8(mdvt_ctx* c, int in_w, int in_h, int channels, int n_
     const int fchunk = set_frames(c, p.tmp_bytes, n_frames);
     if (p.tmp_bytes) MDVT_HIP(c, scratch_reserve(c, c->scratch[SCR_MASK_WS], (size_t)fchunk * p.tmp_bytes, s));
     for (int f0 = 0; f0 < n_frames; f0 += fchunk) {
-        const int n = n_frames - f0 < fchunk ? n_frames - f0 : fchunk;
+        const int n = set_len(n_frames, f0, fchunk);
         MDVT_HIP(c, resize_set(p, Image{d_in + (size_t)f0 * in_stride, in_pitch, in_stride}, d_out + (size_t)f0 * out_stride, out_pitch, out_stride, 1,
                                c->scratch[SCR_MASK_WS].p, n, s));
     }
@@ -191,17 +188,17 @@ int mdvt_mask_model_input(mdvt_ctx* c, int in_w, int in_h, int n_frames, const u
     const int fchunk = set_frames(c, per_frame, n_frames);
     MDVT_HIP(c, scratch_reserve(c, c->scratch[SCR_MASK_WS], (size_t)fchunk * per_frame, s));
     uint8_t* w = c->scratch[SCR_MASK_WS].p;
-    uint8_t* tmp = w; w += (size_t)fchunk * p.tmp_bytes;
-    uint8_t* img = w; w += (size_t)fchunk * img_bytes;
+    uint8_t* tmp = take<uint8_t>(w, (size_t)fchunk * p.tmp_bytes);
+    uint8_t* img = take<uint8_t>(w, (size_t)fchunk * img_bytes);
     MaskInputArgs a{};
-    a.lut = reinterpret_cast<float*>(w); w += (size_t)fchunk * 768 * sizeof(float);
-    a.max_byte = reinterpret_cast<uint32_t*>(w);
+    a.lut = take<float>(w, (size_t)fchunk * 768 * sizeof(float));
+    a.max_byte = take<uint32_t>(w, (size_t)fchunk * 16);
     a.w = model_w; a.h = model_h; a.bgr = order;
     for (int k = 0; k < 3; ++k) { a.mean[k] = h_mean[k]; a.std[k] = h_std[k]; }
     a.dst_pitch = out_pitch; a.dst_plane = out_plane_stride; a.dst_stride = out_stride;
     a.dst_vec = multiples_of(16, d_out, out_pitch, out_plane_stride, out_stride);
     for (int f0 = 0; f0 < n_frames; f0 += fchunk) {
-        const int n = n_frames - f0 < fchunk ? n_frames - f0 : fchunk;
+        const int n = set_len(n_frames, f0, fchunk);
         const Image src{d_frames + (size_t)f0 * frames_stride, frames_pitch, frames_stride};
         if (p.form) {
             MDVT_HIP(c, resize_set(p, src, img, img_pitch, img_bytes, 1, tmp, n, s));
@@ -241,13 +238,13 @@ int mdvt_mask_from_prediction(mdvt_ctx* c, int pred_w, int pred_h, int n_frames,
     const int fchunk = set_frames(c, per_frame, n_frames);
     MDVT_HIP(c, scratch_reserve(c, c->scratch[SCR_MASK_WS], (size_t)fchunk * per_frame, s));
     uint8_t* w = c->scratch[SCR_MASK_WS].p;
-    uint8_t* tmp = w; w += (size_t)fchunk * p.tmp_bytes;
-    uint8_t* plane = w; w += (size_t)fchunk * plane_bytes;
+    uint8_t* tmp = take<uint8_t>(w, (size_t)fchunk * p.tmp_bytes);
+    uint8_t* plane = take<uint8_t>(w, (size_t)fchunk * plane_bytes);
     MaskPredArgs a{};
-    a.stats = reinterpret_cast<uint32_t*>(w);
+    a.stats = take<uint32_t>(w, (size_t)fchunk * 16);
     a.pred_pitch = pred_pitch; a.pred_stride = pred_stride; a.w = pred_w; a.h = pred_h;
     for (int f0 = 0; f0 < n_frames; f0 += fchunk) {
-        const int n = n_frames - f0 < fchunk ? n_frames - f0 : fchunk;
+        const int n = set_len(n_frames, f0, fchunk);
         uint8_t* out = d_mask + (size_t)f0 * mask_stride;
         a.pred = reinterpret_cast<const uint8_t*>(d_pred) + (size_t)f0 * pred_stride;
         if (p.form) { a.dst = plane; a.dst_pitch = (size_t)pred_w; a.dst_stride = plane_bytes; a.rep = 1; }

@@ -157,6 +157,21 @@ inline int slots_afforded(const mdvt_ctx* c, size_t per_slot, int cap)
     return (size_t)cap > afford ? (afford < 1 ? 1 : (int)afford) : cap;
 }
 
+// ---- the entry points' vocabulary for layouts, launch sets and scratch blocks --------------------------------------------------
+// What a vector path asks of an array: every pointer, pitch, stride (or row length) listed is a multiple of k.
+template <class... A> bool multiples_of(size_t k, A... a) { return (((uintptr_t)a % k == 0) && ...); }
+constexpr size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
+constexpr int kGridFrames = 32768;    // frames of one launch where a grid's second or third dimension holds them
+// the frames of the launch set that starts at frame f0 of n, cap at the most
+inline int set_len(int n, int f0, int cap) { return n - f0 < cap ? n - f0 : cap; }
+// carves a scratch block: the next `bytes` bytes from w on as T*; w moves behind them (the caller rounds where its layout does)
+template <class T> T* take(uint8_t*& w, size_t bytes)
+{
+    T* p = reinterpret_cast<T*>(w);
+    w += bytes;
+    return p;
+}
+
 // ---- mdvt_context.hip: the process-wide pools (their reasons are told there) -------------------------------------------------
 // device memory owned by a context, accounted for mdvt_workspace_bytes; `s`: the stream the fresh-block fill goes to
 hipError_t ws_malloc(mdvt_ctx* c, void** p, size_t bytes, hipStream_t s);

@@ -14,7 +14,7 @@
 // Launches per launch set (frames that have a mask frame take all five, the others the last two):
 //   k_conv_select   one wave per unit of 2048 pixels of the mask: gray = (4899 R + 9617 G + 1868 B + 8192) >> 14 > 240 (OpenCV's 8-bit
 //                   BGR2GRAY), the selection as ballot words (lane l holds pixels 4 l .. 4 l + 3 of a group of 256) and the unit's count
-//   k_conv_scan     one wave per frame: exclusive scan of the unit counts, the frame's count
+//   k_conv_scan     one wave per frame: exclusive scan of the unit counts, the frame's count (mdvt_ordered_select.h: unit_scan)
 //   k_conv_compact  one wave per unit: the 16-bit codes R << 8 | B of the selected pixels, in row-major order, to their places; depth
 //                   pixels are loaded only by lanes that hold a selected one
 //   k_conv_reduce   one workgroup of four waves per chunk of 8192 values: the codes are staged in LDS (coalesced 12-byte loads of four
@@ -23,9 +23,11 @@
 //                   chunk is 64 leaf sums and a balanced tree of butterfly steps over the lanes, then over the waves (IEEE add is
 //                   commutative: both sides hold the same bits); a tail chunk is walked in the general shape (leaves listed by
 //                   thread 0, summed by a thread each, combined by thread 0)
-//   k_conv_mean     one wave per frame: the chunk sums in order, the division, the NaN of an empty selection, the count
+//   k_conv_mean     one wave per frame: the chunk sums in order, the division, the NaN of an empty selection (mdvt_ordered_select.h:
+//                   ordered_mean), the count
+// The scan and the mean are shared with the focal estimate of mdvt_depth_engines.hip; select, compact and reduce are this unit's own.
 #include "mdvt_internal.h"
-#include "mdvt_pairwise.h"
+#include "mdvt_ordered_select.h"
 
 namespace mdvt {
 namespace {
@@ -107,24 +109,8 @@ __global__ void __launch_bounds__(256) k_conv_select(ConvergenceArgs a)
 
 __global__ void __launch_bounds__(64) k_conv_scan(ConvergenceArgs a)
 {
-    const int lane = (int)threadIdx.x;
-    const int f = (int)blockIdx.x;
-    const uint32_t* cnt = a.unit_cnt + (size_t)f * a.nunits;
-    uint32_t* off = a.unit_off + (size_t)f * a.nunits;
-    uint32_t carry = 0;
-    for (uint32_t base = 0; base < a.nunits; base += 64u) {
-        const uint32_t i = base + (uint32_t)lane;
-        const uint32_t v = i < a.nunits ? cnt[i] : 0u;
-        uint32_t s = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t t = __shfl_up(s, d);
-            if (lane >= d) s += t;
-        }
-        if (i < a.nunits) off[i] = carry + s - v;
-        carry += __shfl(s, 63);
-    }
-    if (lane == 0) a.totals[f] = carry;
+    const size_t f = blockIdx.x;
+    ordered_select::unit_scan(a.unit_cnt + f * a.nunits, a.unit_off + f * a.nunits, a.nunits, a.totals + f);
 }
 
 __global__ void __launch_bounds__(256) k_conv_compact(ConvergenceArgs a)
@@ -241,19 +227,11 @@ __global__ void __launch_bounds__(kReduceThreads) k_conv_reduce(ConvergenceArgs 
 
 __global__ void __launch_bounds__(64) k_conv_mean(ConvergenceArgs a)
 {
-    const int lane = (int)threadIdx.x;
     const int f = (int)blockIdx.x;
     const uint32_t total = f < a.n_masked ? a.totals[f] : a.npx;
-    const uint32_t nch = (total + (uint32_t)kChunk - 1u) / (uint32_t)kChunk;
-    const float* sums = a.sums + (size_t)f * a.nchunks;
-    float acc = 0.f;
-    for (uint32_t base = 0; base < nch; base += 64u) {
-        const float s = base + (uint32_t)lane < nch ? sums[base + (uint32_t)lane] : 0.f;
-        const int m = (int)(nch - base < 64u ? nch - base : 64u);
-        for (int j = 0; j < m; ++j) acc += __shfl(s, j);
-    }
-    if (lane == 0) {
-        a.means[f] = total ? acc / (float)total : __builtin_nanf("");
+    const float mean = ordered_select::ordered_mean(a.sums + (size_t)f * a.nchunks, total, __builtin_nanf(""));
+    if (threadIdx.x == 0) {
+        a.means[f] = mean;
         if (a.counts) a.counts[f] = total;
     }
 }

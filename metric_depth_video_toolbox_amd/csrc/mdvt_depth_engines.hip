@@ -2,35 +2,39 @@
 // (include/mdvt_depth_engines.h): packed video frames to a model's planar input (mdvt_model_frames), a coded depth video to PromptDA's
 // low-resolution prompt (mdvt_depth_prompt) and UniK3D's focal estimate from its point map (mdvt_focal_from_points).
 //
-// The unit is compiled with -ffp-contract=off, IEEE division and without fast-math (Makefile), like the units it shares
-// mdvt_depth_code.h (the float32 resize tables), mdvt_adapter_resize.h (the u8 resize) and mdvt_pairwise.h (NumPy's order of
-// summation) with: every `*`, `+`, `-` and `/` below is one IEEE operation, rounded before the next.
+// The unit is compiled with -ffp-contract=off, IEEE division and without fast-math (Makefile): every `*`, `+`, `-` and `/` below is
+// one IEEE operation, rounded before the next.  Shared with other units: mdvt_depth_code.h (the four-pixel frame quad_of, and for the
+// prompt the float32 gather quad_gather over this unit's CodeSource), mdvt_adapter_resize.h (the u8 resize), mdvt_pairwise.h (NumPy's
+// order of summation) and mdvt_ordered_select.h (the scan of the unit counts and the mean from the chunk sums, as in
+// mdvt_convergence.hip).
 //
-// k_model_frames, k_depth_prompt: a thread per four output pixels of a row, a frame per blockIdx.y; k_depth_sink is the model.  Packed
+// k_model_frames, k_depth_prompt: a thread per four output pixels of a row, a frame per blockIdx.y.  Packed
 // 3-byte pixels are read as 12 bytes per lane where nothing is resized and the source is aligned to 4: the three dwords are adjacent, so
 // the lanes of a wave read one run of 768 bytes and every byte of a cache line is used; the planar stores are 4 or 16 bytes per lane,
 // neighbouring lanes neighbouring addresses.  Resized pixels gather their taps byte by byte: the taps of neighbouring pixels are
 // neighbours or the same, and the caches serve them.  A value's arithmetic does not depend on which loads and stores it takes.
 //
-// The focal estimate per launch set, modelled on mdvt_convergence.hip:
+// The focal estimate per launch set (count, compact and reduce are this unit's own: both lists of a frame from one walk, float values):
 //   k_focal_count    one wave per unit of 2048 points: both selections as ballots, the unit's two counts
 //   k_focal_scan     one wave per list (a frame's ex, or its ey): exclusive scan of the unit counts, the list's count
 //   k_focal_compact  one wave per unit: the points again, ex and ey of the selected ones in row-major order to their places
 //   k_focal_reduce   one workgroup per chunk of 8192 values of a list: the chunk in LDS (a padding dword per 128 values, so that the
 //                    leaves' threads read different banks), walked in the general shape of mdvt_pairwise.h -- a full chunk is that
 //                    shape's balanced tree over 64 leaves of 128 values
-//   k_focal_mean     one thread per list: the chunk sums in order, the division, the 0 of an empty selection, the count
+//   k_focal_mean     one wave per list: the chunk sums in order, the division, the 0 of an empty selection, the count
 // Every sum has a fixed shape: no floating-point atomics, no dependence on the launch geometry.
 #include "mdvt_internal.h"
 #include "mdvt_adapter_resize.h"
 #include "mdvt_depth_code.h"
-#include "mdvt_pairwise.h"
+#include "mdvt_ordered_select.h"
 
 namespace mdvt {
 namespace {
 
 using depth_code::store_plane;
-using depth_code::tap;
+using depth_code::Quad;
+using depth_code::quad_of;
+using depth_code::quad_gather;
 using pairwise::kChunk;
 
 // ---- mdvt_model_frames ---------------------------------------------------------------------------------------------------------
@@ -38,13 +42,11 @@ using pairwise::kChunk;
 template <bool AS_FLOAT>
 __global__ void __launch_bounds__(256) k_model_frames(ModelFramesArgs a)
 {
-    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-    if (t >= a.groups) return;
-    const uint32_t row = t / a.gw, g = t - row * a.gw;
-    const int x0 = (int)(4u * g);
-    const int nv = a.rs.out_w - x0 < 4 ? a.rs.out_w - x0 : 4;
-    const size_t f = (size_t)a.frame0 + blockIdx.y;
-    const uint8_t* src = a.src + f * a.src_stride;
+    Quad q;
+    if (!quad_of(a.groups, a.gw, a.rs.out_w, a.frame0, q)) return;
+    const uint32_t row = q.row;
+    const int x0 = q.x0, nv = q.nv;
+    const uint8_t* src = a.src + q.f * a.src_stride;
     const size_t pitch = a.src_pitch;
     uint32_t px[4] = {0u, 0u, 0u, 0u};                              // byte 0 | byte 1 << 8 | byte 2 << 16 as stored
     if (a.rs.mode == 0 && a.src_vec && nv == 4) {
@@ -55,7 +57,7 @@ __global__ void __launch_bounds__(256) k_model_frames(ModelFramesArgs a)
         for (int k = 0; k < 4; ++k)
             if (k < nv) px[k] = adapter_resize_px(a.rs, x0 + k, (int)row, [&](int sx, int sy) { return load_px_bytes(src + (size_t)sy * pitch, sx); });
     }
-    uint8_t* out = a.dst + f * a.dst_stride + (size_t)row * a.dst_pitch + (size_t)x0 * (AS_FLOAT ? 4u : 1u);
+    uint8_t* out = a.dst + q.f * a.dst_stride + (size_t)row * a.dst_pitch + (size_t)x0 * (AS_FLOAT ? 4u : 1u);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {                                   // planes R, G, B
         const int shift = 8 * (a.bgr ? 2 - c : c);
@@ -86,49 +88,30 @@ __device__ __forceinline__ float decode_px(uint32_t px, int bgr, float mult)
     return (float)code * mult;
 }
 
+// a coded depth frame as a source of the gather (mdvt_depth_code.h): a pixel decoded, four pixels through the three-dword load
+struct CodeSource {
+    static constexpr size_t kBytes = 3;
+    int bgr; float mult;
+    __device__ __forceinline__ float at(const uint8_t* p, int x) const { return decode_px(load_px_bytes(p, x), bgr, mult); }
+    __device__ __forceinline__ void four(const uint8_t* p, float (&d)[4]) const
+    {
+        const uint32_t* w = reinterpret_cast<const uint32_t*>(p);
+        uint32_t px[4];
+        unpack4(w[0], w[1], w[2], px);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) d[k] = decode_px(px[k], bgr, mult);
+    }
+};
+
 template <bool RESIZE>
 __global__ void __launch_bounds__(256) k_depth_prompt(DepthPromptArgs a)
 {
-    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-    if (t >= a.groups) return;
-    const uint32_t row = t / a.gw, g = t - row * a.gw;
-    const int x0 = (int)(4u * g);
-    const int nv = a.out_w - x0 < 4 ? a.out_w - x0 : 4;
-    const size_t f = (size_t)a.frame0 + blockIdx.y;
-    const uint8_t* src = a.src + f * a.src_stride;
+    Quad q;
+    if (!quad_of(a.groups, a.gw, a.out_w, a.frame0, q)) return;
     float d[4] = {0.f, 0.f, 0.f, 0.f};
-    if (!RESIZE) {
-        const uint8_t* r = src + (size_t)row * a.src_pitch;
-        if (a.src_vec && nv == 4) {
-            const uint32_t* q = reinterpret_cast<const uint32_t*>(r + (size_t)x0 * 3u);
-            uint32_t px[4];
-            unpack4(q[0], q[1], q[2], px);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) d[k] = decode_px(px[k], a.bgr, a.mult);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (k < nv) d[k] = decode_px(load_px_bytes(r, x0 + k), a.bgr, a.mult);
-        }
-    } else {
-        int y0, y1;
-        float b0, b1;
-        tap((int)row, a.ratio_y, a.in_h, y0, y1, b0, b1);
-        const uint8_t* r0 = src + (size_t)y0 * a.src_pitch;
-        const uint8_t* r1 = src + (size_t)y1 * a.src_pitch;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (k < nv) {
-                int s0, s1;
-                float a0, a1;
-                tap(x0 + k, a.ratio_x, a.in_w, s0, s1, a0, a1);
-                const float h0 = decode_px(load_px_bytes(r0, s0), a.bgr, a.mult) * a0 + decode_px(load_px_bytes(r0, s1), a.bgr, a.mult) * a1;
-                const float h1 = decode_px(load_px_bytes(r1, s0), a.bgr, a.mult) * a0 + decode_px(load_px_bytes(r1, s1), a.bgr, a.mult) * a1;
-                d[k] = h0 * b0 + h1 * b1;
-            }
-        }
-    }
-    store_plane(reinterpret_cast<float*>(a.dst + f * a.dst_stride + (size_t)row * a.dst_pitch) + x0, d, nv, a.dst_vec != 0);
+    quad_gather(d, a.src + q.f * a.src_stride, a.src_pitch, a.src_vec != 0, q, RESIZE, a.ratio_x, a.ratio_y, a.in_w, a.in_h,
+                CodeSource{a.bgr, a.mult});
+    store_plane(reinterpret_cast<float*>(a.dst + q.f * a.dst_stride + (size_t)q.row * a.dst_pitch) + q.x0, d, q.nv, a.dst_vec != 0);
 }
 
 // ---- mdvt_focal_from_points ----------------------------------------------------------------------------------------------------
@@ -180,24 +163,8 @@ __global__ void __launch_bounds__(256) k_focal_count(FocalArgs a)
 
 __global__ void __launch_bounds__(64) k_focal_scan(FocalArgs a)
 {
-    const int lane = (int)threadIdx.x;
     const size_t l = blockIdx.x;                                     // the list
-    const uint32_t* cnt = a.unit_cnt + l * a.nunits;
-    uint32_t* off = a.unit_off + l * a.nunits;
-    uint32_t carry = 0;
-    for (uint32_t base = 0; base < a.nunits; base += 64u) {
-        const uint32_t i = base + (uint32_t)lane;
-        const uint32_t v = i < a.nunits ? cnt[i] : 0u;
-        uint32_t s = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t t = __shfl_up(s, d);
-            if (lane >= d) s += t;
-        }
-        if (i < a.nunits) off[i] = carry + s - v;
-        carry += __shfl(s, 63);
-    }
-    if (lane == 0) a.totals[l] = carry;
+    ordered_select::unit_scan(a.unit_cnt + l * a.nunits, a.unit_off + l * a.nunits, a.nunits, a.totals + l);
 }
 
 __global__ void __launch_bounds__(256) k_focal_compact(FocalArgs a)
@@ -254,15 +221,13 @@ __global__ void __launch_bounds__(kFocalReduceThreads) k_focal_reduce(FocalArgs 
 
 __global__ void __launch_bounds__(64) k_focal_mean(FocalArgs a)
 {
-    const uint32_t l = blockIdx.x * 64u + threadIdx.x;
-    if (l >= 2u * (uint32_t)a.n_frames) return;
+    const size_t l = blockIdx.x;                                     // the list
     const uint32_t total = a.totals[l];
-    const uint32_t nch = (total + (uint32_t)kChunk - 1u) / (uint32_t)kChunk;
-    const float* sums = a.sums + (size_t)l * a.nchunks;
-    float acc = 0.f;
-    for (uint32_t j = 0; j < nch; ++j) acc += sums[j];
-    a.focal[l] = total ? acc / (float)total : 0.0f;                  // unik3d_video.py:98-99
-    if (a.counts) a.counts[l] = total;
+    const float mean = ordered_select::ordered_mean(a.sums + l * a.nchunks, total, 0.0f);      // unik3d_video.py:98-99
+    if (threadIdx.x == 0) {
+        a.focal[l] = mean;
+        if (a.counts) a.counts[l] = total;
+    }
 }
 
 }  // namespace
@@ -291,7 +256,7 @@ hipError_t launch_focal_from_points(const FocalArgs& a, hipStream_t s)
     hipLaunchKernelGGL(k_focal_scan, dim3(lists), dim3(64), 0, s, a);
     hipLaunchKernelGGL(k_focal_compact, units, dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_focal_reduce, dim3(a.nchunks, lists), dim3(kFocalReduceThreads), 0, s, a);
-    hipLaunchKernelGGL(k_focal_mean, dim3((lists + 63u) / 64u), dim3(64), 0, s, a);
+    hipLaunchKernelGGL(k_focal_mean, dim3(lists), dim3(64), 0, s, a);
     return hipGetLastError();
 }
 

@@ -2,10 +2,12 @@
 // include/mdvt_depth_sink.h): depth_frames_helper.save_depth_video (dfh:125-161) behind an optional NaN rule (moge_video.py:171) and an
 // optional factor that lives on the device (video_da3.py:193), bit for bit.  The sink of every metric-depth script of the reference.
 //
-// The unit is compiled with -ffp-contract=off and without fast-math (Makefile), like mdvt_metric_align.hip, whose resize tables, clip
-// and code it shares through mdvt_depth_code.h: every `*` and `+` below is one IEEE operation, rounded before the next.
+// The unit is compiled with -ffp-contract=off and without fast-math (Makefile): every `*` and `+` below is one IEEE operation,
+// rounded before the next.  Shared with mdvt_metric_align.hip's k_metric_codes through mdvt_depth_code.h: the frame (quad_of), the
+// float32 gather with its resize tables (quad_values) and the tail (codes_out: clip, code, packed stores).  This unit's own: prepare,
+// the function of a source value, and the LDS-staged upscale.
 //
-// k_depth_sink: a thread per four output pixels of a row, a frame per blockIdx.y; k_metric_codes (mdvt_metric_align.hip) is the model.
+// k_depth_sink: a thread per four output pixels of a row, a frame per blockIdx.y.
 // Same size: one 16-byte load of four source values where the plane's address, pitch and stride are multiples of 16, element by element
 // otherwise.  Resized: each output pixel prepares its up to four source values, filters horizontally then vertically; where the
 // source is no wider than the output (the usual direction) k_depth_sink_up stages the two source rows of a workgroup in LDS first.
@@ -18,11 +20,11 @@
 namespace mdvt {
 namespace {
 
-using depth_code::clip_np;
 using depth_code::tap;
-using depth_code::pixel;
-using depth_code::store_pixels;
-using depth_code::store_plane;
+using depth_code::Quad;
+using depth_code::quad_of;
+using depth_code::quad_values;
+using depth_code::codes_out;
 
 // steps 1 and 2 of the header on a source value
 __device__ __forceinline__ float prepare(float x, bool nan_to_max, bool scaled, float s, float fmax)
@@ -32,55 +34,16 @@ __device__ __forceinline__ float prepare(float x, bool nan_to_max, bool scaled, 
 }
 
 template <bool RESIZE>
-__global__ void __launch_bounds__(256) k_depth_sink(DepthSinkArgs a)
+__global__ void __launch_bounds__(256) k_depth_sink(DepthCodesArgs a)
 {
-    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-    if (t >= a.groups) return;
-    const uint32_t row = t / a.gw, g = t - row * a.gw;
-    const int x0 = (int)(4u * g);
-    const int nv = a.out_w - x0 < 4 ? a.out_w - x0 : 4;
-    const size_t f = (size_t)a.frame0 + blockIdx.y;
+    Quad q;
+    if (!quad_of(a.groups, a.gw, a.out_w, a.frame0, q)) return;
     const bool ntm = a.nan_to_max != 0, scaled = a.scale != nullptr;
-    const float s = scaled ? *a.scale : 1.0f;
-    const uint8_t* src = a.src + f * a.src_stride;
+    const float s = scaled ? *a.scale : 1.0f, fmax = a.fmax;
     float d[4] = {0.f, 0.f, 0.f, 0.f};
-    if (!RESIZE) {
-        const float* x = reinterpret_cast<const float*>(src + (size_t)row * a.src_pitch) + x0;
-        if (a.src_vec && nv == 4) {
-            const float4 v = *reinterpret_cast<const float4*>(x);
-            d[0] = prepare(v.x, ntm, scaled, s, a.fmax); d[1] = prepare(v.y, ntm, scaled, s, a.fmax);
-            d[2] = prepare(v.z, ntm, scaled, s, a.fmax); d[3] = prepare(v.w, ntm, scaled, s, a.fmax);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (k < nv) d[k] = prepare(x[k], ntm, scaled, s, a.fmax);
-        }
-    } else {
-        int y0, y1;
-        float b0, b1;
-        tap((int)row, a.ratio_y, a.in_h, y0, y1, b0, b1);
-        const float* r0 = reinterpret_cast<const float*>(src + (size_t)y0 * a.src_pitch);
-        const float* r1 = reinterpret_cast<const float*>(src + (size_t)y1 * a.src_pitch);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (k < nv) {
-                int s0, s1;
-                float a0, a1;
-                tap(x0 + k, a.ratio_x, a.in_w, s0, s1, a0, a1);
-                const float h0 = prepare(r0[s0], ntm, scaled, s, a.fmax) * a0 + prepare(r0[s1], ntm, scaled, s, a.fmax) * a1;
-                const float h1 = prepare(r1[s0], ntm, scaled, s, a.fmax) * a0 + prepare(r1[s1], ntm, scaled, s, a.fmax) * a1;
-                d[k] = h0 * b0 + h1 * b1;
-            }
-        }
-    }
-    uint32_t px[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        d[k] = clip_np(d[k], a.fmax);
-        px[k] = pixel(d[k], a.multi, a.bgr);
-    }
-    store_pixels(a.codes + f * a.codes_stride + (size_t)row * a.codes_pitch + (size_t)x0 * 3u, px, nv, a.codes_vec);
-    if (a.plane) store_plane(reinterpret_cast<float*>(a.plane + f * a.plane_stride + (size_t)row * a.plane_pitch) + x0, d, nv, a.plane_vec);
+    quad_values(d, a.src + q.f * a.src_stride, a.src_pitch, a.src_vec != 0, q, RESIZE, a.ratio_x, a.ratio_y, a.in_w, a.in_h,
+                [=](float x) { return prepare(x, ntm, scaled, s, fmax); });
+    codes_out(d, q, a);
 }
 
 // The resize where a source row is no longer than an output row (in_w <= out_w: the models' sizes to a video's).  A workgroup takes up
@@ -96,7 +59,7 @@ __global__ void __launch_bounds__(256) k_depth_sink(DepthSinkArgs a)
 // floor differs by at most 1024, the second tap adds 1, so a span holds at most 1026 values.
 constexpr int kUpSpan = 1032;
 
-__global__ void __launch_bounds__(256) k_depth_sink_up(DepthSinkArgs a)
+__global__ void __launch_bounds__(256) k_depth_sink_up(DepthCodesArgs a)
 {
     __shared__ float s_r0[kUpSpan], s_r1[kUpSpan];
     const uint32_t cpr = (a.gw + 255u) / 256u;                      // workgroups per output row
@@ -126,12 +89,11 @@ __global__ void __launch_bounds__(256) k_depth_sink_up(DepthSinkArgs a)
     __syncthreads();
     if (threadIdx.x >= ng) return;
     const int x0 = x_first + 4 * (int)threadIdx.x;
-    const int nv = a.out_w - x0 < 4 ? a.out_w - x0 : 4;
+    const Quad q{row, x0, a.out_w - x0 < 4 ? a.out_w - x0 : 4, f};
     float d[4] = {0.f, 0.f, 0.f, 0.f};
-    uint32_t px[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        if (k < nv) {
+        if (k < q.nv) {
             int s0, s1;
             float a0, a1;
             tap(x0 + k, a.ratio_x, a.in_w, s0, s1, a0, a1);
@@ -140,16 +102,13 @@ __global__ void __launch_bounds__(256) k_depth_sink_up(DepthSinkArgs a)
             const float h1 = s_r1[s0] * a0 + s_r1[s1] * a1;
             d[k] = h0 * b0 + h1 * b1;
         }
-        d[k] = clip_np(d[k], a.fmax);
-        px[k] = pixel(d[k], a.multi, a.bgr);
     }
-    store_pixels(a.codes + f * a.codes_stride + (size_t)row * a.codes_pitch + (size_t)x0 * 3u, px, nv, a.codes_vec);
-    if (a.plane) store_plane(reinterpret_cast<float*>(a.plane + f * a.plane_stride + (size_t)row * a.plane_pitch) + x0, d, nv, a.plane_vec);
+    codes_out(d, q, a);
 }
 
 }  // namespace
 
-hipError_t launch_depth_sink(const DepthSinkArgs& a, int n_frames, hipStream_t s)
+hipError_t launch_depth_sink(const DepthCodesArgs& a, int n_frames, hipStream_t s)
 {
     if (a.resize && a.in_w <= a.out_w && a.in_w < (1 << 22)) {
         const dim3 grid(((a.gw + 255u) / 256u) * (unsigned)a.out_h, (unsigned)n_frames);

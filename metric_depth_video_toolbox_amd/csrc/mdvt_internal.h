@@ -346,28 +346,24 @@ struct FitArgs {
     float* out;                                                    // the caller's 8 floats
 };
 hipError_t launch_scale_shift_fit(const FitArgs& a, hipStream_t s);
-struct MetricCodesArgs {
-    const uint8_t* rel; size_t rel_pitch, rel_stride; int in_w, in_h, rel_vec;
-    const float* scale_shift; int style; float fmax; double multi; // float(max_depth), 255^4 / max_depth
-    int out_w, out_h, resize; double ratio_x, ratio_y;             // in / out per axis
-    uint8_t* codes; size_t codes_pitch, codes_stride; int bgr, codes_vec;
-    uint8_t* depth; size_t depth_pitch, depth_stride; int depth_vec;          // null: no depth planes
-    uint32_t gw, groups;                                           // groups of four pixels per output row and per image
-    int frame0;                                                    // the launch's first frame
-};
-hipError_t launch_metric_codes(const MetricCodesArgs& a, int n_frames, hipStream_t s);
-// mdvt_depth_sink.hip: metric depth planes to a depth video's codes (mdvt_depth_video_codes; include/mdvt_depth_sink.h)
-struct DepthSinkArgs {
-    const uint8_t* src; size_t src_pitch, src_stride; int in_w, in_h, src_vec;
-    const float* scale;                                            // one float on the device, or null: no factor
-    int nan_to_max; float fmax; double multi;                      // float(max_depth), 255^4 / max_depth
+// what the two steps that write a depth video's codes share (mdvt_depth_code.h); each one's own pair, a factor on the device and a
+// 0 / 1 flag, stands in the same place
+struct DepthCodesArgs {
+    const uint8_t* src; size_t src_pitch, src_stride; int in_w, in_h, src_vec;       // float32 planes; _vec: 16-byte loads are aligned
+    union { const float* scale_shift;                              // mdvt_metric_depth_codes: the fit's two floats
+            const float* scale; };                                 // mdvt_depth_video_codes: one float, or null: no factor
+    union { int style; int nan_to_max; };                          // likewise
+    float fmax; double multi;                                      // float(max_depth), 255^4 / max_depth
     int out_w, out_h, resize; double ratio_x, ratio_y;             // in / out per axis
     uint8_t* codes; size_t codes_pitch, codes_stride; int bgr, codes_vec;
     uint8_t* plane; size_t plane_pitch, plane_stride; int plane_vec;          // null: no depth planes
     uint32_t gw, groups;                                           // groups of four pixels per output row and per image
     int frame0;                                                    // the launch's first frame
 };
-hipError_t launch_depth_sink(const DepthSinkArgs& a, int n_frames, hipStream_t s);
+// mdvt_metric_align.hip: relative planes to metric depth codes (include/mdvt_metric_align.h)
+hipError_t launch_metric_codes(const DepthCodesArgs& a, int n_frames, hipStream_t s);
+// mdvt_depth_sink.hip: metric depth planes to a depth video's codes (mdvt_depth_video_codes; include/mdvt_depth_sink.h)
+hipError_t launch_depth_sink(const DepthCodesArgs& a, int n_frames, hipStream_t s);
 // mdvt_normal_infill.hip: the six cross dilations of normal_infill (bni:112) on their own.  marks: an image as mdvt_mark_lower_side
 // writes it ((0,0,255) at a mark); grown: H rows of W bytes without padding, zeroed here, 1 within L1 distance 6 of a mark.
 hipError_t launch_grow_marks(const uint8_t* marks, size_t marks_pitch, uint8_t* grown, int W, int H, hipStream_t s);

@@ -20,10 +20,12 @@
 //   k_fit_total   one workgroup of five waves, a wave per sum: the set's chunk sums added in order onto the running totals; after the
 //                 last set det, scale and shift.
 //
-// The codes.  k_metric_codes: a thread per four output pixels of a row.  Same size: reconstruct, clip, code.  Resized: each output
-// pixel reconstructs its up to four source values (they come from L1/L2: a 2 x upscale reads every source value four times, but the
-// kernel's traffic to memory stays the algorithmic 4 B per source and 3 B per output pixel), filters horizontally then vertically,
-// clips and codes.  Four codes are 12 bytes: three dword stores where the image's address, pitch and stride are multiples of 4.
+// The codes.  k_metric_codes: a thread per four output pixels of a row, in the frame, gather and tail of mdvt_depth_code.h (quad_of,
+// quad_values, codes_out), which mdvt_depth_sink.hip uses too; this unit's own is reconstruct, the function of a source value.  Same
+// size: reconstruct, clip, code.  Resized: each output pixel reconstructs its up to four source values (they come from L1/L2: a 2 x
+// upscale reads every source value four times, but the kernel's traffic to memory stays the algorithmic 4 B per source and 3 B per
+// output pixel), filters horizontally then vertically, clips and codes.  Four codes are 12 bytes: three dword stores where the
+// image's address, pitch and stride are multiples of 4.
 #include "mdvt_internal.h"
 #include "mdvt_pairwise.h"
 #include "mdvt_depth_code.h"
@@ -34,10 +36,10 @@ namespace {
 using pairwise::kChunk;
 using pairwise::kLeaf;
 using depth_code::clip_np;
-using depth_code::tap;
-using depth_code::pixel;
-using depth_code::store_pixels;
-using depth_code::store_plane;
+using depth_code::Quad;
+using depth_code::quad_of;
+using depth_code::quad_values;
+using depth_code::codes_out;
 
 constexpr int kFitThreads = 256;
 constexpr int kTotalThreads = 5 * 64;              // k_fit_total: a wave per sum
@@ -283,59 +285,19 @@ __device__ __forceinline__ float reconstruct(float x, float scale, float shift, 
 }
 
 template <int STYLE>
-__global__ void __launch_bounds__(256) k_metric_codes(MetricCodesArgs a)
+__global__ void __launch_bounds__(256) k_metric_codes(DepthCodesArgs a)
 {
-    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-    if (t >= a.groups) return;
-    const uint32_t row = t / a.gw, g = t - row * a.gw;
-    const int x0 = (int)(4u * g);
-    const int nv = a.out_w - x0 < 4 ? a.out_w - x0 : 4;
-    const size_t f = (size_t)a.frame0 + blockIdx.y;
-    const float scale = a.scale_shift[0], shift = a.scale_shift[1];
-    const uint8_t* src = a.rel + f * a.rel_stride;
+    Quad q;
+    if (!quad_of(a.groups, a.gw, a.out_w, a.frame0, q)) return;
+    const float scale = a.scale_shift[0], shift = a.scale_shift[1], fmax = a.fmax;
     float d[4] = {0.f, 0.f, 0.f, 0.f};
-    if (!a.resize) {
-        const float* x = reinterpret_cast<const float*>(src + (size_t)row * a.rel_pitch) + x0;
-        if (a.rel_vec && nv == 4) {
-            const float4 v = *reinterpret_cast<const float4*>(x);
-            d[0] = reconstruct<STYLE>(v.x, scale, shift, a.fmax); d[1] = reconstruct<STYLE>(v.y, scale, shift, a.fmax);
-            d[2] = reconstruct<STYLE>(v.z, scale, shift, a.fmax); d[3] = reconstruct<STYLE>(v.w, scale, shift, a.fmax);
-        } else {
+    quad_values(d, a.src + q.f * a.src_stride, a.src_pitch, a.src_vec != 0, q, a.resize != 0, a.ratio_x, a.ratio_y, a.in_w, a.in_h,
+                [=](float x) { return reconstruct<STYLE>(x, scale, shift, fmax); });
+    if (STYLE == 1 && a.resize) {                                // (style 1 clips the filtered value too)
 #pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (k < nv) d[k] = reconstruct<STYLE>(x[k], scale, shift, a.fmax);
-        }
-    } else {
-        int y0, y1;
-        float b0, b1;
-        tap((int)row, a.ratio_y, a.in_h, y0, y1, b0, b1);
-        const float* r0 = reinterpret_cast<const float*>(src + (size_t)y0 * a.rel_pitch);
-        const float* r1 = reinterpret_cast<const float*>(src + (size_t)y1 * a.rel_pitch);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (k < nv) {
-                int s0, s1;
-                float a0, a1;
-                tap(x0 + k, a.ratio_x, a.in_w, s0, s1, a0, a1);
-                const float h0 = reconstruct<STYLE>(r0[s0], scale, shift, a.fmax) * a0 + reconstruct<STYLE>(r0[s1], scale, shift, a.fmax) * a1;
-                const float h1 = reconstruct<STYLE>(r1[s0], scale, shift, a.fmax) * a0 + reconstruct<STYLE>(r1[s1], scale, shift, a.fmax) * a1;
-                const float v = h0 * b0 + h1 * b1;
-                d[k] = STYLE == 1 ? clip_np(v, a.fmax) : v;
-            }
-        }
+        for (int k = 0; k < 4; ++k) d[k] = clip_np(d[k], fmax);
     }
-    uint32_t px[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        d[k] = clip_np(d[k], a.fmax);
-        px[k] = pixel(d[k], a.multi, a.bgr);
-    }
-    uint8_t* q = a.codes + f * a.codes_stride + (size_t)row * a.codes_pitch + (size_t)x0 * 3u;
-    store_pixels(q, px, nv, a.codes_vec);
-    if (a.depth) {
-        float* z = reinterpret_cast<float*>(a.depth + f * a.depth_stride + (size_t)row * a.depth_pitch) + x0;
-        store_plane(z, d, nv, a.depth_vec);
-    }
+    codes_out(d, q, a);
 }
 
 }  // namespace
@@ -347,7 +309,7 @@ hipError_t launch_scale_shift_fit(const FitArgs& a, hipStream_t s)
     return hipGetLastError();
 }
 
-hipError_t launch_metric_codes(const MetricCodesArgs& a, int n_frames, hipStream_t s)
+hipError_t launch_metric_codes(const DepthCodesArgs& a, int n_frames, hipStream_t s)
 {
     const dim3 grid((a.groups + 255u) / 256u, (unsigned)n_frames);
     if (a.style == 0) hipLaunchKernelGGL(k_metric_codes<0>, grid, dim3(256), 0, s, a);

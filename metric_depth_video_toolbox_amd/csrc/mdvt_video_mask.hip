@@ -171,12 +171,11 @@ __global__ void __launch_bounds__(256) k_mask_lut(MaskInputArgs a)
 __global__ void __launch_bounds__(256) k_mask_planar(MaskInputArgs a)
 {
     const uint32_t gw = ((uint32_t)a.w + 3u) / 4u;
-    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-    if (t >= gw * (uint32_t)a.h) return;
-    const uint32_t row = t / gw, g = t - row * gw;
-    const int x0 = (int)(4u * g);
-    const int nv = a.w - x0 < 4 ? a.w - x0 : 4;
-    const size_t f = blockIdx.y;
+    depth_code::Quad q;
+    if (!depth_code::quad_of(gw * (uint32_t)a.h, gw, a.w, 0, q)) return;
+    const uint32_t row = q.row;
+    const int x0 = q.x0, nv = q.nv;
+    const size_t f = q.f;
     const uint8_t* r = a.img + f * a.img_stride + (size_t)row * a.img_pitch + (size_t)x0 * 3u;
     uint8_t px[12];
 #pragma unroll
