@@ -68,6 +68,10 @@ GEOMETRY_SYMBOLS = ("mdvt_export_geometry_batch", "mdvt_depth_grey_batch")
 VIDEO_MASK_SYMBOLS = ("mdvt_lanczos_resize_u8", "mdvt_mask_model_input", "mdvt_mask_from_prediction")
 LANCZOS_AUTO, LANCZOS_FUSED, LANCZOS_TWO_LAUNCH = 0, 1, 2
 
+# the entry points include/mdvt_mvsa.h declares (torch's bilinear resize into the multi-view model, two nearest resizes to depth codes,
+# the masked median ratio), likewise.  They are bound here and have no wrapper in the package yet: tools/video_mvsa.py calls them
+MVSA_SYMBOLS = ("mdvt_bilinear_model_frames", "mdvt_nearest_depth_codes", "mdvt_ratio_median")
+
 
 class MdvtError(RuntimeError):
     def __init__(self, code: int, text: str):
@@ -247,6 +251,14 @@ def load():
     L.mdvt_mask_model_input.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, st, st, C.c_int, C.c_int, C.c_int, vp, vp, vp, st, st, st, vp]
     L.mdvt_mask_from_prediction.restype = C.c_int
     L.mdvt_mask_from_prediction.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, st, st, C.c_int, C.c_int, C.c_int, vp, st, st, vp]
+    L.mdvt_bilinear_model_frames.restype = C.c_int
+    L.mdvt_bilinear_model_frames.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, st, st, C.c_int, C.c_int, C.c_int, vp, st, st, st, vp]
+    L.mdvt_nearest_depth_codes.restype = C.c_int
+    L.mdvt_nearest_depth_codes.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, st, st, C.c_int, C.c_int, vp, st, C.c_double, C.c_int, C.c_int,
+                                           vp, st, st, C.c_int, vp, st, st, vp]
+    L.mdvt_ratio_median.restype = C.c_int
+    L.mdvt_ratio_median.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, st, st, C.c_int, C.c_int, vp, st, st, C.c_int, C.c_int, vp, st, st,
+                                    vp, vp, vp]
     L.mdvt_adapter_prepare_eye.restype = C.c_int
     L.mdvt_adapter_prepare_eye.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, st, st, vp, st, st, C.c_int, C.c_int, vp, st, st, vp, st, st, vp, vp]
     L.mdvt_lhm_moments.restype = C.c_int

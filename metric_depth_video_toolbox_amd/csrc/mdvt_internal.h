@@ -480,6 +480,33 @@ struct MaskPredArgs {
     uint8_t* dst; size_t dst_pitch, dst_stride; int rep;           // the byte planes; rep as in LzArgs
 };
 hipError_t launch_mask_pred_bytes(const MaskPredArgs& a, int n_frames, hipStream_t s);
+// mdvt_mvsa.hip: torch's bilinear resize into a model, two nearest resizes to depth codes and the masked median ratio (include/mdvt_mvsa.h)
+struct NearAxis { float to_mid, to_src; int mid, src; };           // an output index -> near(near(x, mid, out), src, mid): the two scales, the two clamps
+struct BilinearFramesArgs {
+    const uint8_t* src; size_t src_pitch, src_stride; int in_w, in_h, bgr;
+    float scale_x, scale_y;                                        // fl(float(in) / float(out)) per axis
+    int small;                                                     // out_w + out_h <= 128: torch's CPU kernel for small outputs, four weights summed in order
+    uint8_t* dst; size_t dst_pitch, dst_plane, dst_stride; int out_w, dst_vec;        // _vec: four values of a plane are one aligned 16-byte store
+    uint32_t gw, groups;                                           // groups of four pixels per output row and per frame
+    int frame0;                                                    // the launch's first frame
+};
+hipError_t launch_bilinear_frames(const BilinearFramesArgs& a, int n_frames, hipStream_t s);
+struct NearestCodesArgs {
+    DepthCodesArgs c;                                              // the source planes and the tail's outputs; resize, ratio_x, ratio_y and scale unused
+    NearAxis x, y;
+    const uint8_t* scales; size_t scales_stride;                   // frame k's factor at scales + k * scales_stride; null: no factor
+};
+hipError_t launch_nearest_codes(const NearestCodesArgs& a, int n_frames, hipStream_t s);
+constexpr uint32_t kMedianFrameWords = 260;                        // a frame's scratch: 256 histogram words, then prefix, sought index, count, unused
+struct RatioMedianArgs {
+    const uint8_t* cv; size_t cv_pitch, cv_stride; uint32_t cv_w, npx;                // the set's first frame; npx = cv_w * cv_h
+    const uint8_t* ref; size_t ref_pitch, ref_stride; float ref_sx, ref_sy; int ref_w, ref_h;     // near(x, ref_w, cv_w): the scale and the clamp
+    const uint8_t* mask; size_t mask_pitch, mask_stride; float mask_sx, mask_sy; int mask_w, mask_h;      // null: every pixel counts
+    uint32_t* work;                                                // workspace [n_frames][kMedianFrameWords], zeroed before the first pass
+    int n_frames;
+    float* median; uint32_t* counts;                               // the caller's, at the set's first frame; counts may be null
+};
+hipError_t launch_ratio_median(const RatioMedianArgs& a, hipStream_t s);
 hipError_t launch_selftest(int which, unsigned long long seed, unsigned long long* d_mism, hipStream_t s);
 hipError_t launch_coherence_test(uint32_t* blk, size_t dwords, uint32_t tag, uint32_t* d_xcc, uint32_t* d_out, hipStream_t s);     // (mdvt_selftest.hip; r05 diagnosis)
 
