@@ -539,12 +539,12 @@ class ClipInputs:
         self.opened.append((name, frames))
         return frames
 
-    def on_device(self, dev, video_decoder: str = "host", video_encoder: str = "host"):
-        """Reads go to `dev` from here on.  With a "device" codec this makes the context the decoder and the encoder run in (its
-        own workspace; the render size does not matter to them); video_decoder "device" / "device_all" switches every video part
-        over whose stream is in that decoder's class."""
+    def on_device(self, dev, video_decoder: str = "host", video_encoder: str = "host", *, own_context: bool = False):
+        """Reads go to `dev` from here on.  With a "device" codec -- or own_context, for a script whose own calls need one whatever
+        the codecs -- this makes the context the decoder and the encoder run in (its own workspace; the render size does not
+        matter to them); video_decoder "device" / "device_all" switches every video part over whose stream is in that decoder's class."""
         self.dev = dev
-        if video_decoder in ("device", "device_all") or video_encoder == "device":
+        if own_context or video_decoder in ("device", "device_all") or video_encoder == "device":
             self.ctx = _lib.Context(dev.index, 16, 16)
         if video_decoder in ("device", "device_all"):
             self.dec_ctx = self.ctx

@@ -16,14 +16,13 @@ and promptda are not available to this project."""
 from __future__ import annotations
 
 import argparse
-import json
 import math
 
 import numpy as np
 
 from . import video_da3
-from .clip_io import VIDEO_DECODERS, VIDEO_ENCODERS
 from .depth_map_tools import compute_camera_matrix, fov_from_camera_matrix
+from .step_clip import add_device_flags, clips_from_argument, frames_to_write, output_pair, write_float_list  # noqa: F401 (exported)
 
 ENGINES = ("unik3d", "moge", "depthpro")
 PROMPT_W, PROMPT_H = 256, 192                            # pda:37: rescale_height, rescale_width = 192, 256
@@ -46,12 +45,7 @@ def check_engine(engine: str):
     return engine
 
 
-def _add_device_flags(p, default_batch):
-    p.add_argument("--batch", default=default_batch, type=int, help="not a reference flag: frames per read, per call of the model and per read-back")
-    p.add_argument("--video_decoder", choices=VIDEO_DECODERS, default="host",
-                   help="not a reference flag: where an .mkv input is FFV1-decoded -- 'host' (default), 'device' or 'device_all'")
-    p.add_argument("--video_encoder", choices=VIDEO_ENCODERS, default="host",
-                   help="not a reference flag: where the .mkv output is FFV1-encoded -- 'host' (default) or 'device' (the same bytes)")
+BATCH_HELP = "frames per read, per call of the model and per read-back"
 
 
 def build_engine_parser():
@@ -68,8 +62,7 @@ def build_engine_parser():
     p.add_argument("--generator", default=None, type=str,
                    help="not a reference flag: the model, by default the engine's own (needs its package), or pkg.module:callable with "
                         "infer(frames, camera_or_fov) -> dict of CUDA tensors (INTEGRATION.md states the contract)")
-    _add_device_flags(p, 8)
-    return p
+    return add_device_flags(p, 8, BATCH_HELP)
 
 
 def build_promptda_parser():
@@ -82,8 +75,7 @@ def build_promptda_parser():
     p.add_argument("--generator", default="promptda", type=str,
                    help="not a reference flag: the model, 'promptda' (default; needs the promptda package) or pkg.module:callable with "
                         "upscale(rgb, prompt) -> depth: rgb float32 CUDA [n,3,h14,w14], prompt float32 CUDA [n,1,192,256], depth float32 CUDA [n,h14,w14]")
-    _add_device_flags(p, 4)
-    return p
+    return add_device_flags(p, 4, BATCH_HELP)
 
 
 def check_engine_flags(a):
@@ -95,13 +87,6 @@ def check_engine_flags(a):
         raise ValueError(f"--batch must be at least 1, got {a.batch}")
 
 
-def frames_to_write(n_in_file: int, max_frames: int) -> int:
-    """How many frames each script's loop writes (u3d:155-163, mge:149-157, dpr:134-142, pda:43-58): all of them with -1, else the
-    first max_frames; the loops test `max_frames < frame_n` after counting the frame, so N gives exactly N and 0 gives none."""
-    n = int(n_in_file)
-    return n if int(max_frames) == -1 else max(0, min(n, int(max_frames)))
-
-
 # ---- files ----------------------------------------------------------------------------------------------------------------------
 def engine_output_paths(color_video: str, video: bool = True):
     """(tmp, final, xfovs): u3d:149-151.  moge and depthpro write the final name at once (mge:141, dpr:129); this project writes every
@@ -111,16 +96,10 @@ def engine_output_paths(color_video: str, video: bool = True):
 
 def promptda_output_paths(depth_video: str, video: bool = True):
     """(tmp, final): pda:84 names the final file; tmp is this project's."""
-    ext = ".mkv" if video else ".npy"
-    return depth_video + "_tmp_upscaled" + ext, depth_video + "_upscaled" + ext
+    return output_pair(depth_video, video, "upscaled")
 
 
-def write_xfovs(path: str, xfovs):
-    with open(path, "w") as fh:
-        fh.write(json.dumps([float(v) for v in xfovs]))
-
-
-clips_from_argument = video_da3.clips_from_argument
+write_xfovs = write_float_list
 
 
 def closest_higher_multiple(x, base=14):

@@ -14,8 +14,7 @@ import json
 
 import numpy as np
 
-from .clip_io import VIDEO_DECODERS, VIDEO_ENCODERS
-from .infill_clip import callable_from_spec, is_txt, read_list_file
+from .step_clip import add_device_flags, callable_from_spec, clips_from_argument, output_pair, write_float_list  # noqa: F401 (exported)
 
 REFUSED = {                                              # flag -> why the step does not take it: the reference itself cannot run it
     "xfov": "--xfov cannot run in the reference either: video_da3.py:102 reads cam_matrix before it is assigned, and video_da3.py:47-50 "
@@ -47,11 +46,7 @@ def build_parser():
                    help="not a reference flag: the depth model, 'da3' (default; needs the depth_anything_3 package) or pkg.module:callable with "
                         "infer(frames, resolution) -> (depth, extrinsics, intrinsics): frames uint8 CUDA [T,H,W,3] RGB, depth float32 CUDA "
                         "[T,h,w], extrinsics [T,3,4] world-to-camera and intrinsics [T,3,3] of any float dtype on either side")
-    p.add_argument("--video_decoder", choices=VIDEO_DECODERS, default="host",
-                   help="not a reference flag: where an .mkv --color_video is FFV1-decoded -- 'host' (default), 'device' or 'device_all'")
-    p.add_argument("--video_encoder", choices=VIDEO_ENCODERS, default="host",
-                   help="not a reference flag: where the .mkv output is FFV1-encoded -- 'host' (default) or 'device' (the same bytes)")
-    return p
+    return add_device_flags(p)
 
 
 def check_flags(a):
@@ -189,21 +184,14 @@ class PoseTrack:
 # ---- files ----------------------------------------------------------------------------------------------------------------------
 def output_paths(color_video: str, video: bool = True):
     """(tmp, final, xfovs, transformations): vd3:74-77; a .npy frame dump gives .npy depth frames."""
-    ext = ".mkv" if video else ".npy"
-    final = color_video + "_depth" + ext
-    return color_video + "_tmp_depth" + ext, final, final + "_xfovs.json", final + "_transformations.json"
+    tmp, final = output_pair(color_video, video)
+    return tmp, final, final + "_xfovs.json", final + "_transformations.json"
 
 
 def write_json_files(xfov_file: str, transformations_file: str, xfovs, transformations):
-    with open(xfov_file, "w") as fh:
-        fh.write(json.dumps([float(v) for v in xfovs]))
+    write_float_list(xfov_file, xfovs)
     with open(transformations_file, "w") as fh:
         fh.write(json.dumps([np.asarray(t, np.float64).tolist() for t in transformations]))
-
-
-def clips_from_argument(color_video: str):
-    """The clip, or the entries of a .txt list (vd3:301-307)."""
-    return read_list_file(color_video) if is_txt(color_video) else [color_video]
 
 
 # ---- the model ------------------------------------------------------------------------------------------------------------------

@@ -10,8 +10,7 @@ from __future__ import annotations
 
 import argparse
 
-from .clip_io import VIDEO_DECODERS, VIDEO_ENCODERS
-from .infill_clip import callable_from_spec, is_txt, read_list_file
+from .step_clip import add_device_flags, callable_from_spec, clips_from_argument, frames_to_write, output_pair  # noqa: F401 (exported)
 
 # rembg's U2netSession.predict: normalize(img, (0.485, 0.456, 0.406), (0.229, 0.224, 0.225), (320, 320)); other rembg models differ in
 # these numbers only
@@ -33,11 +32,7 @@ def build_parser():
     p.add_argument("--generator", default=DEFAULT_GENERATOR, type=str,
                    help=f"not a reference flag: the model, '{DEFAULT_GENERATOR}' (default; needs rembg and onnxruntime) or pkg.module:callable "
                         "with infer(x) -> pred: x float32 CUDA [n,3,S,S], pred float32 CUDA [n,h,w] or [n,1,h,w] (INTEGRATION.md states the contract)")
-    p.add_argument("--video_decoder", choices=VIDEO_DECODERS, default="host",
-                   help="not a reference flag: where an .mkv input is FFV1-decoded -- 'host' (default), 'device' or 'device_all'")
-    p.add_argument("--video_encoder", choices=VIDEO_ENCODERS, default="host",
-                   help="not a reference flag: where the .mkv output is FFV1-encoded -- 'host' (default) or 'device' (the same bytes)")
-    return p
+    return add_device_flags(p)
 
 
 def check_flags(a):
@@ -50,22 +45,9 @@ def check_flags(a):
         raise ValueError(f"--max_frames must be -1 (no limit) or a count, got {a.max_frames}")
 
 
-def frames_to_write(n_in_file: int, max_frames: int) -> int:
-    """How many frames gvm:85-109 writes: all of them with -1, else the first max_frames (the loop tests `frame_n > max_frames` after
-    counting the frame, so N gives exactly N)."""
-    n = int(n_in_file)
-    return n if int(max_frames) == -1 else max(0, min(n, int(max_frames)))
-
-
 def output_paths(color_video: str, video: bool = True):
     """(tmp, final): gvm:66-67; a .npy frame dump gives a .npy mask."""
-    ext = ".mkv" if video else ".npy"
-    return color_video + "_tmp_mask" + ext, color_video + "_mask" + ext
-
-
-def clips_from_argument(color_video: str):
-    """The clip, or the entries of a .txt list (gvm:47-62, 150-155)."""
-    return read_list_file(color_video) if is_txt(color_video) else [color_video]
+    return output_pair(color_video, video, "mask")
 
 
 class RembgU2NetGenerator:

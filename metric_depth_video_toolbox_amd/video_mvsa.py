@@ -15,9 +15,8 @@ import json
 
 import numpy as np
 
-from .clip_io import VIDEO_DECODERS, VIDEO_ENCODERS
 from .depth_map_tools import compute_camera_matrix
-from .infill_clip import callable_from_spec, is_txt, read_list_file
+from .step_clip import add_device_flags, callable_from_spec, clips_from_argument, output_pair, write_float_list  # noqa: F401 (exported)
 
 MVSA_CONFIG_PATH = "mvsanywhere/configs/models/mvsanywhere_model.yaml"          # mvs:16-17
 MVSA_WEIGHTS_PATH = "mvsanywhere/weights/mvsanywhere_hero.ckpt"
@@ -40,15 +39,10 @@ def build_parser():
                         "(video_mvsa.py:283-297); this project's reading of the author's intent, not the reference's output")
     p.add_argument("--save_cost_volume_scales", action="store_true",
                    help="not a reference flag: write the per-frame median ratios to x.mkv_depth.mkv_cv_scales.json")
-    p.add_argument("--batch", default=8, type=int, help="not a reference flag: frames per read and per resize call")
     p.add_argument("--generator", default="mvsanywhere", type=str,
                    help="not a reference flag: the model, 'mvsanywhere' (default; needs the mvsanywhere package) or pkg.module:callable with "
                         "infer(cur_data, src_data, fast_cost_volume) -> dict of CUDA tensors (INTEGRATION.md states the contract)")
-    p.add_argument("--video_decoder", choices=VIDEO_DECODERS, default="host",
-                   help="not a reference flag: where an .mkv input is FFV1-decoded -- 'host' (default), 'device' or 'device_all'")
-    p.add_argument("--video_encoder", choices=VIDEO_ENCODERS, default="host",
-                   help="not a reference flag: where the .mkv output is FFV1-encoded -- 'host' (default) or 'device' (the same bytes)")
-    return p
+    return add_device_flags(p, 8, "frames per read and per resize call")
 
 
 def check_flags(a):
@@ -166,19 +160,11 @@ def intrinsics(xfov, yfov, width: int, height: int, resize_w: int):
 def output_paths(color_video: str, video: bool = True):
     """(tmp, final, scales): mvs:303 names the final file; tmp and the scales' file are this project's.  A .npy frame dump gives .npy
     depth frames."""
-    ext = ".mkv" if video else ".npy"
-    final = color_video + "_depth" + ext
-    return color_video + "_tmp_depth" + ext, final, final + "_cv_scales.json"
+    tmp, final = output_pair(color_video, video)
+    return tmp, final, final + "_cv_scales.json"
 
 
-def write_scales(path: str, scales):
-    with open(path, "w") as fh:
-        fh.write(json.dumps([float(v) for v in scales]))
-
-
-def clips_from_argument(color_video: str):
-    """The clip, or the entries of a .txt list."""
-    return read_list_file(color_video) if is_txt(color_video) else [color_video]
+write_scales = write_float_list
 
 
 # ---- the model ------------------------------------------------------------------------------------------------------------------

@@ -9,8 +9,9 @@ metric conversion.
 writes x.mkv_depth.mkv (tmp x.mkv_tmp_depth.mkv, renamed when its frame count is right) and x.mkv_depth.mkv_xfovs.json.  A .txt list
 runs each entry; a .npy frame dump gives .npy depth frames.  INTEGRATION.md states the generator's contract.
 
-The parsers, the file names and the x-fov arithmetic are host logic in metric_depth_video_toolbox_amd/depth_engines.py.  Here is what
-touches the device, per batch: the decoded frames go through mdvt_model_frames to the planar tensor the model takes (uint8 for unik3d
+The parsers, the file names and the x-fov arithmetic are host logic in metric_depth_video_toolbox_amd/depth_engines.py; the opening
+of the clip with its checks, the context, the output file and the list loop are step_clip.py's.  Here is what touches the device,
+per batch: the decoded frames go through mdvt_model_frames to the planar tensor the model takes (uint8 for unik3d
 and depthpro, float32 / 255 for moge), the model is called, unik3d's point map goes through mdvt_focal_from_points, ONE read-back
 brings the batch's focal lengths (8 bytes per frame) or intrinsics to the host for the x-fov list, and the depth goes through
 mdvt_depth_video_codes (with moge's NaN rule, mge:171) to the writer or the device FFV1 encoder.
@@ -47,16 +48,12 @@ def model_frames(ctx, frames, out_size=None, *, as_float=False, bgr=False, strea
     [N, 3, h, w] in R, G, B plane order at out_size = (w, h) (default: the frames' own size), uint8, or float32 v / 255 with as_float.
     Only enqueues, on `stream`."""
     import torch
-    from metric_depth_video_toolbox_amd import _lib
+    from metric_depth_video_toolbox_amd import _lib, step_clip
     _lib.check_tensor("frames", frames, torch.uint8, (None, None, None, 3), packed=2, disjoint=True)
-    N, H, W = (int(v) for v in frames.shape[:3])
-    if N < 1 or H < 1 or W < 1:
-        raise ValueError(f"frames holds no pixel: shape {tuple(frames.shape)}")
-    w, h = (W, H) if out_size is None else (int(out_size[0]), int(out_size[1]))
-    if w < 1 or h < 1:
-        raise ValueError(f"out_size must be (width, height) with both at least 1, got {out_size!r}")
+    N, H, W = step_clip.non_empty("frames", frames, "pixel")
+    w, h = (W, H) if out_size is None else step_clip.size_arg(out_size, "out_size")
     dev = frames.device
-    s = torch.cuda.current_stream(dev) if stream is None else stream
+    s = step_clip.stream_or_current(dev, stream)
     with torch.cuda.stream(s):
         out = torch.empty((N, 3, h, w), dtype=torch.float32 if as_float else torch.uint8, device=dev)
     e = out.element_size()
@@ -69,18 +66,14 @@ def depth_prompt(ctx, codes, max_depth, out_size, *, bgr=False, stream=None):
     """mdvt_depth_prompt on uint8 CUDA depth frames [N, H, W, 3] (R, G, B; B, G, R with bgr) -> float32 [N, h, w] at out_size = (w, h):
     the decoded depth, resized like cv2.resize(INTER_LINEAR).  Only enqueues, on `stream`."""
     import torch
-    from metric_depth_video_toolbox_amd import _lib
+    from metric_depth_video_toolbox_amd import _lib, step_clip
     if not (float(max_depth) > 0):
         raise ValueError("max_depth must be > 0")
     _lib.check_tensor("codes", codes, torch.uint8, (None, None, None, 3), packed=2, disjoint=True)
-    N, H, W = (int(v) for v in codes.shape[:3])
-    if N < 1 or H < 1 or W < 1:
-        raise ValueError(f"codes holds no pixel: shape {tuple(codes.shape)}")
-    w, h = int(out_size[0]), int(out_size[1])
-    if w < 1 or h < 1:
-        raise ValueError(f"out_size must be (width, height) with both at least 1, got {out_size!r}")
+    N, H, W = step_clip.non_empty("codes", codes, "pixel")
+    w, h = step_clip.size_arg(out_size, "out_size")
     dev = codes.device
-    s = torch.cuda.current_stream(dev) if stream is None else stream
+    s = step_clip.stream_or_current(dev, stream)
     with torch.cuda.stream(s):
         out = torch.empty((N, h, w), dtype=torch.float32, device=dev)
     ctx.call("mdvt_depth_prompt", W, H, N, codes.data_ptr(), codes.stride(1), codes.stride(0), int(bool(bgr)), float(max_depth), w, h,
@@ -93,22 +86,21 @@ def focal_from_points(ctx, points, *, want_counts=False, stream=None):
     former, as u3d:46-52 reads it; rows, planes and frames may be strided) -> float32 [N, 2] = (fx, fy) per frame and, with
     want_counts, the int32 tensor [N, 2] = (nx, ny) of the library's uint32 counts (at most 2^28 each).  Only enqueues, on `stream`."""
     import torch
-    from metric_depth_video_toolbox_amd import _lib
+    from metric_depth_video_toolbox_amd import _lib, step_clip
     _lib.check_tensor("points", points, torch.float32, ndim=4)
     if points.shape[-1] == 3:
         _lib.check_tensor("points", points, torch.float32, ndim=4, packed=2, disjoint=True)
-        layout, (N, H, W) = 1, (int(v) for v in points.shape[:3])
+        layout, dims = 1, points.shape[:3]
         pitch, plane, stride = 4 * points.stride(1), 0, 4 * points.stride(0)
     elif points.shape[1] == 3:
         _lib.check_tensor("points", points, torch.float32, ndim=4, packed=1, disjoint=True)
-        layout, N, (H, W) = 0, int(points.shape[0]), (int(v) for v in points.shape[2:])
+        layout, dims = 0, (points.shape[0], *points.shape[2:])
         pitch, plane, stride = 4 * points.stride(2), 4 * points.stride(1), 4 * points.stride(0)
     else:
         raise ValueError(f"points must be [N, H, W, 3] or [N, 3, H, W], got shape {tuple(points.shape)}")
-    if N < 1 or H < 1 or W < 1:
-        raise ValueError(f"points holds no point: shape {tuple(points.shape)}")
+    N, H, W = step_clip.non_empty("points", points, "point", dims)
     dev = points.device
-    s = torch.cuda.current_stream(dev) if stream is None else stream
+    s = step_clip.stream_or_current(dev, stream)
     with torch.cuda.stream(s):
         focal = torch.empty((N, 2), dtype=torch.float32, device=dev)
         counts = torch.empty((N, 2), dtype=torch.int32, device=dev) if want_counts else None
@@ -143,69 +135,42 @@ def checked_prediction(got, engine, n, W, H):
 
 def run_clip(args, color_video, infer):
     """u3d:132-191 / mge:124-177 / dpr:113-164 for one clip -> the depth video's path."""
-    import torch
-    from metric_depth_video_toolbox_amd import _lib, depth_engines as host
-    from metric_depth_video_toolbox_amd.clip_io import ClipInputs, ClipOutput, check_video_decoder, check_video_encoder, video_parts
+    from metric_depth_video_toolbox_amd import depth_engines as host, step_clip
     da3_tool = sibling_tool("video_da3")
     engine = args.engine
-    with ClipInputs() as inp:
-        color = inp.open(color_video, "color_video", Exception("input color_video does not exist"))      # u3d:132-133
-        video = bool(video_parts(color))
-        check_video_decoder(args.video_decoder, video)
-        check_video_encoder(args.video_encoder, video)
-        if color.ndim != 4 or color.shape[-1] != 3 or color.dtype != np.uint8:
-            raise ValueError(f"{color_video}: uint8 [N, H, W, 3] expected")
-        H, W = int(color.shape[1]), int(color.shape[2])
-        n = host.frames_to_write(int(color.shape[0]), args.max_frames)
-        if n < 1:
-            raise ValueError("No frames read")
-        fps = (video_parts(color)[0][0].fps or 30.0) if video else None
-        tmp, final, xfov_file = host.engine_output_paths(color_video, video)
+    with step_clip.StepClip() as clip:
+        color, = clip.open_checked([(color_video, "color_video", Exception("input color_video does not exist"))],       # u3d:132-133
+                                   args.video_decoder, args.video_encoder, lambda n: host.frames_to_write(n, args.max_frames))
+        n, H, W = clip.n, clip.H, clip.W
+        tmp, final, xfov_file = host.engine_output_paths(color_video, clip.video)
         cam = host.requested_camera(args.xfov, args.yfov, W, H)
         if engine == "moge" and cam is not None:
             cam = np.float32(host.xfov_moge(cam))                                                       # mge:136: the model takes fov_x
-        inp.on_device(torch.device("cuda", torch.cuda.current_device()), args.video_decoder, args.video_encoder)
-        dev = inp.dev
-        ctx = inp.ctx if inp.ctx is not None else _lib.Context(dev.index, 16, 16)
         xfovs = []
-        try:
-            with torch.cuda.device(dev), ClipOutput(tmp, final, n, (H, W, 3), fps, args.video_encoder, ctx) as out:
-                for a in range(0, n, int(args.batch)):
-                    b = min(n, a + int(args.batch))
-                    frames = model_frames(ctx, inp.fetch(color, a, b), as_float=engine == "moge")
-                    depth, extra = checked_prediction(infer(frames, cam), engine, b - a, W, H)
-                    if engine == "unik3d":
-                        focal = focal_from_points(ctx, extra).cpu().numpy()                              # the batch's one read-back: 8 B per frame
-                        xfovs += [host.xfov_unik3d(fx, fy, W, H) for fx, fy in focal]
-                    elif engine == "moge":
-                        xfovs += [host.xfov_moge(K) for K in extra.cpu().numpy()]
-                    else:
-                        xfovs += [host.xfov_depthpro(f, W, H) for f in extra.cpu().numpy()]
-                    out.store(da3_tool.depth_video_codes(ctx, depth, args.max_depth, (W, H), nan_to_max=engine == "moge"), a)
-                # the x-fov list first, then the depth video's rename, as u3d:185-191 orders them: a depth video never stands without
-                # its list, and a list that cannot be written leaves no depth video
-                host.write_xfovs(xfov_file, xfovs)
-        finally:
-            if ctx is not inp.ctx:
-                ctx.close()
+        with clip.device(tmp, final) as (ctx, fetch, store):
+            for a in range(0, n, int(args.batch)):
+                b = min(n, a + int(args.batch))
+                frames = model_frames(ctx, fetch(color, a, b), as_float=engine == "moge")
+                depth, extra = checked_prediction(infer(frames, cam), engine, b - a, W, H)
+                if engine == "unik3d":
+                    focal = focal_from_points(ctx, extra).cpu().numpy()                                  # the batch's one read-back: 8 B per frame
+                    xfovs += [host.xfov_unik3d(fx, fy, W, H) for fx, fy in focal]
+                elif engine == "moge":
+                    xfovs += [host.xfov_moge(K) for K in extra.cpu().numpy()]
+                else:
+                    xfovs += [host.xfov_depthpro(f, W, H) for f in extra.cpu().numpy()]
+                store(da3_tool.depth_video_codes(ctx, depth, args.max_depth, (W, H), nan_to_max=engine == "moge"), a)
+            # the x-fov list first, then the depth video's rename, as u3d:185-191 orders them: a depth video never stands without
+            # its list, and a list that cannot be written leaves no depth video
+            host.write_xfovs(xfov_file, xfovs)
     return final
 
 
 def run(args, infer=None):
     """The step for --color_video, or for each entry of a .txt list.  infer: the generator (default: the one --generator names,
     loaded once).  -> the depth videos' paths."""
-    from metric_depth_video_toolbox_amd import depth_engines as host
-    from metric_depth_video_toolbox_amd.infill_clip import is_txt
-    host.check_engine_flags(args)                                   # before any file is opened
-    clips = host.clips_from_argument(args.color_video)
-    if infer is None:
-        infer = host.load_generator(args.generator, args.engine)
-    written = []
-    for k, path in enumerate(clips, start=1):
-        if len(clips) > 1 or is_txt(args.color_video):
-            print(f"\n##### [{k}/{len(clips)}] Processing {path} #####")
-        written.append(run_clip(args, path, infer))
-    return written
+    from metric_depth_video_toolbox_amd import depth_engines as host, step_clip
+    return step_clip.run_list(args, infer, host.check_engine_flags, lambda: host.load_generator(args.generator, args.engine), run_clip)
 
 
 def main(argv=None):

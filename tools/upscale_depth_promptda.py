@@ -14,11 +14,10 @@ called, and mdvt_depth_video_codes resizes its output to (W, H) and codes it (pd
 save_depth_video's, which then has nothing left to do, are that one resize).  The model's size is less than 14 pixels above the frame's, so from
 14 x 14 frames on the sink meets no exact-2x case; a depth video of exactly 512 x 384 would be one for the prompt and is refused by mdvt_depth_prompt.
 
-The loop ends with the shorter of the two videos (pda:51-58)."""
+The loop ends with the shorter of the two videos (pda:51-58): step_clip.py's clip session opens both, holds them to one kind and
+counts the shorter one."""
 import os
 import sys
-
-import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
@@ -34,47 +33,29 @@ def checked_upscale(got, n, h14, w14):
 
 def run(args, upscale=None):
     """pda:30-84 for one pair of clips -> the upscaled depth video's path."""
-    import torch
     from depth_engine_video import depth_prompt, model_frames, sibling_tool
-    from metric_depth_video_toolbox_amd import _lib, depth_engines as host
-    from metric_depth_video_toolbox_amd.clip_io import ClipInputs, ClipOutput, check_video_decoder, check_video_encoder, video_parts
+    from metric_depth_video_toolbox_amd import depth_engines as host, step_clip
     da3_tool = sibling_tool("video_da3")
     if int(args.batch) < 1:
         raise ValueError(f"--batch must be at least 1, got {args.batch}")
     if upscale is None:
         upscale = host.load_generator(args.generator, "promptda")
-    with ClipInputs() as inp:
-        color = inp.open(args.color_video, "color_video", Exception("input color_video does not exist"))
-        depth = inp.open(args.depth_video, "depth_video", Exception("input depth_video does not exist"))
-        video = bool(video_parts(color))
-        if bool(video_parts(depth)) != video:
-            raise ValueError("--color_video and --depth_video must both be .mkv videos or both .npy frame dumps")
-        check_video_decoder(args.video_decoder, video)
-        check_video_encoder(args.video_encoder, video)
-        for name, v in (("color_video", color), ("depth_video", depth)):
-            if v.ndim != 4 or v.shape[-1] != 3 or v.dtype != np.uint8:
-                raise ValueError(f"--{name}: uint8 [N, H, W, 3] expected")
-        H, W = int(color.shape[1]), int(color.shape[2])
-        n = host.frames_to_write(min(int(color.shape[0]), int(depth.shape[0])), args.max_frames)
-        if n < 1:
-            raise ValueError("No frames read")
-        fps = (video_parts(color)[0][0].fps or 30.0) if video else None                      # pda:33: the colour video's rate
+    with step_clip.StepClip() as clip:
+        # the session's checks for two inputs: both .mkv or both .npy; the shorter of the two counts (pda:51-58); the colour video's rate (pda:33)
+        color, depth = clip.open_checked([(args.color_video, "color_video", Exception("input color_video does not exist")),
+                                          (args.depth_video, "depth_video", Exception("input depth_video does not exist"))],
+                                         args.video_decoder, args.video_encoder, lambda n: host.frames_to_write(n, args.max_frames),
+                                         label="--{name}")
+        n, H, W = clip.n, clip.H, clip.W
         h14, w14 = host.closest_higher_multiple(H), host.closest_higher_multiple(W)          # pda:38
-        tmp, final = host.promptda_output_paths(args.depth_video, video)
-        inp.on_device(torch.device("cuda", torch.cuda.current_device()), args.video_decoder, args.video_encoder)
-        dev = inp.dev
-        ctx = inp.ctx if inp.ctx is not None else _lib.Context(dev.index, 16, 16)
-        try:
-            with torch.cuda.device(dev), ClipOutput(tmp, final, n, (H, W, 3), fps, args.video_encoder, ctx) as out:
-                for a in range(0, n, int(args.batch)):
-                    b = min(n, a + int(args.batch))
-                    rgb = model_frames(ctx, inp.fetch(color, a, b), (w14, h14), as_float=True)
-                    prompt = depth_prompt(ctx, inp.fetch(depth, a, b), args.max_depth, (host.PROMPT_W, host.PROMPT_H))
-                    up = checked_upscale(upscale(rgb, prompt.unsqueeze(1)), b - a, h14, w14)
-                    out.store(da3_tool.depth_video_codes(ctx, up, args.max_depth, (W, H)), a)
-        finally:
-            if ctx is not inp.ctx:
-                ctx.close()
+        tmp, final = host.promptda_output_paths(args.depth_video, clip.video)
+        with clip.device(tmp, final) as (ctx, fetch, store):
+            for a in range(0, n, int(args.batch)):
+                b = min(n, a + int(args.batch))
+                rgb = model_frames(ctx, fetch(color, a, b), (w14, h14), as_float=True)
+                prompt = depth_prompt(ctx, fetch(depth, a, b), args.max_depth, (host.PROMPT_W, host.PROMPT_H))
+                up = checked_upscale(upscale(rgb, prompt.unsqueeze(1)), b - a, h14, w14)
+                store(da3_tool.depth_video_codes(ctx, up, args.max_depth, (W, H)), a)
     return final
 
 

@@ -9,8 +9,9 @@ writes x.mkv_depth.mkv (tmp x.mkv_tmp_depth.mkv, then verify_and_move), x.mkv_de
 x.mkv_depth.mkv_transformations.json, the three files the render takes.  A .txt list runs each entry; a .npy frame dump gives .npy
 depth frames.  INTEGRATION.md states the generator's contract.
 
-The schedule, the pose alignment, the parser and the file names are host logic in metric_depth_video_toolbox_amd/video_da3.py.  Here
-is what touches the device: the frames are gathered there (the reference frames are decoded once and kept), the model is called, the
+The schedule, the pose alignment, the parser and the file names are host logic in metric_depth_video_toolbox_amd/video_da3.py; the
+opening of the clip with its checks, the context, the output file and the list loop are step_clip.py's, shared with the other model
+steps.  Here is what touches the device: the frames are gathered there (the reference frames are decoded once and kept), the model is called, the
 factor that aligns a batch to the one before comes from the fit's float32 sums (video_metric_convert.compute_scale_and_shift_full)
 and stays on the device, and the new planes go through mdvt_depth_video_codes (include/mdvt_depth_sink.h) with that factor to the
 video's size and on to the writer or the device FFV1 encoder.  One 4-byte read-back of the factor per batch scales the translations
@@ -33,22 +34,18 @@ def depth_video_codes(ctx, planes, max_depth, out_size=None, *, scale=None, nan_
     CUDA tensor every value is multiplied by first, read on the device; nan_to_max: NaN becomes max_depth before that.  want_plane:
     also the float32 [N, H, W] planes of the coded depth.  out: the codes' tensor to fill.  Only enqueues, on `stream`."""
     import torch
-    from metric_depth_video_toolbox_amd import _lib
+    from metric_depth_video_toolbox_amd import _lib, step_clip
     if not (float(max_depth) > 0):
         raise ValueError("max_depth must be > 0")
     _lib.check_tensor("planes", planes, torch.float32, ndim=3, packed=1, disjoint=True)
-    N, h, w = (int(v) for v in planes.shape)
-    if N < 1 or h < 1 or w < 1:
-        raise ValueError(f"planes holds no value: shape {tuple(planes.shape)}")
-    W, H = (w, h) if out_size is None else (int(out_size[0]), int(out_size[1]))
-    if W < 1 or H < 1:
-        raise ValueError(f"out_size must be (width, height) with both at least 1, got {out_size!r}")
+    N, h, w = step_clip.non_empty("planes", planes, "value")
+    W, H = (w, h) if out_size is None else step_clip.size_arg(out_size, "out_size")
     dev = planes.device
     if scale is not None:
         _lib.check_tensor("scale", scale, torch.float32, device=dev, contiguous=True)
         if scale.numel() != 1:
             raise ValueError(f"scale must hold one value, got shape {tuple(scale.shape)}")
-    s = torch.cuda.current_stream(dev) if stream is None else stream
+    s = step_clip.stream_or_current(dev, stream)
     with torch.cuda.stream(s):
         codes = torch.empty((N, H, W, 3), dtype=torch.uint8, device=dev) if out is None else out
         plane = torch.empty((N, H, W), dtype=torch.float32, device=dev) if want_plane else None
@@ -115,52 +112,35 @@ def save_depth_video(frames, path, fps, max_depth, W, H, *, nan_to_max=False, vi
 def run_clip(args, color_video, infer):
     """vd3:68-263 for one clip -> the depth video's path."""
     import torch
-    from metric_depth_video_toolbox_amd import _lib, video_da3 as host
-    from metric_depth_video_toolbox_amd.clip_io import ClipInputs, ClipOutput, check_video_decoder, check_video_encoder, video_parts
-    with ClipInputs() as inp:
-        color = inp.open(color_video, "color_video", Exception("video file: " + color_video + " does not exist"))      # dfh:257-258
-        video = bool(video_parts(color))
-        check_video_decoder(args.video_decoder, video)
-        check_video_encoder(args.video_encoder, video)
-        if color.ndim != 4 or color.shape[-1] != 3 or color.dtype != np.uint8:
-            raise ValueError(f"{color_video}: uint8 [N, H, W, 3] expected")
-        n, H, W = int(color.shape[0]), int(color.shape[1]), int(color.shape[2])
-        if args.max_frames > 0:                                                                 # dfh:273: the first max_frames frames
-            n = min(n, args.max_frames)
-        if n < 1:
-            raise ValueError("No frames read")                                                  # dfh:278
-        fps = (video_parts(color)[0][0].fps or 30.0) if video else None
-        schedule = host.batch_schedule(n, args.images_per_batch, args.batch_overlap, args.nr_of_ref_frames)
-        tmp, final, xfov_file, transformations_file = host.output_paths(color_video, video)
-        inp.on_device(torch.device("cuda", torch.cuda.current_device()), args.video_decoder, args.video_encoder)
-        dev = inp.dev
-        ctx = inp.ctx if inp.ctx is not None else _lib.Context(dev.index, 16, 16)
-        try:
-            with torch.cuda.device(dev), ClipOutput(tmp, final, n, (H, W, 3), fps, args.video_encoder, ctx) as out:
-                n_refs = schedule[0][1]
-                ref_frames = [inp.fetch(color, i, i + 1) for i in schedule[0][0][:n_refs]]       # decoded once, kept
-                poses = host.PoseTrack(args.batch_overlap)
-                first_ref_depths = last_frames = last_depths = None
-                at = 0
-                for ids, used in schedule:
-                    n_new = len(ids) - used
-                    new_frames = inp.fetch(color, ids[used], ids[-1] + 1)
-                    frames = torch.cat(ref_frames + ([last_frames] if last_frames is not None else []) + [new_frames])
-                    depth, ext, intr = checked_prediction(infer(frames, args.da3_resolution), len(ids))
-                    if first_ref_depths is None:
-                        first_ref_depths = depth[:used].clone()                                 # vd3:178-179
-                    scale = None
-                    if last_depths is not None:                                                 # vd3:183-193
-                        scale = batch_scale(torch.cat([first_ref_depths, last_depths]), depth[:used])
-                    out.store(depth_video_codes(ctx, depth[used:], args.max_depth, (W, H), scale=scale), at)
-                    at += n_new
-                    handed = len(ids[used:][-args.batch_overlap:])          # the frames the next batch sees again (vd3:239-241)
-                    last_frames = new_frames[-handed:]
-                    last_depths = depth[-handed:] if scale is None else depth[-handed:] * scale
-                    poses.add(ext, intr, used, None if scale is None else float(scale.item()))  # the batch's one read-back (vd3:192)
-        finally:
-            if ctx is not inp.ctx:
-                ctx.close()
+    from metric_depth_video_toolbox_amd import step_clip, video_da3 as host
+    with step_clip.StepClip() as clip:
+        color, = clip.open_checked([(color_video, "color_video", Exception("video file: " + color_video + " does not exist"))],     # dfh:257-258
+                                   args.video_decoder, args.video_encoder,
+                                   lambda n: min(n, args.max_frames) if args.max_frames > 0 else n)                             # dfh:273
+        schedule = host.batch_schedule(clip.n, args.images_per_batch, args.batch_overlap, args.nr_of_ref_frames)
+        tmp, final, xfov_file, transformations_file = host.output_paths(color_video, clip.video)
+        with clip.device(tmp, final) as (ctx, fetch, store):
+            n_refs = schedule[0][1]
+            ref_frames = [fetch(color, i, i + 1) for i in schedule[0][0][:n_refs]]               # decoded once, kept
+            poses = host.PoseTrack(args.batch_overlap)
+            first_ref_depths = last_frames = last_depths = None
+            at = 0
+            for ids, used in schedule:
+                n_new = len(ids) - used
+                new_frames = fetch(color, ids[used], ids[-1] + 1)
+                frames = torch.cat(ref_frames + ([last_frames] if last_frames is not None else []) + [new_frames])
+                depth, ext, intr = checked_prediction(infer(frames, args.da3_resolution), len(ids))
+                if first_ref_depths is None:
+                    first_ref_depths = depth[:used].clone()                                     # vd3:178-179
+                scale = None
+                if last_depths is not None:                                                     # vd3:183-193
+                    scale = batch_scale(torch.cat([first_ref_depths, last_depths]), depth[:used])
+                store(depth_video_codes(ctx, depth[used:], args.max_depth, (clip.W, clip.H), scale=scale), at)
+                at += n_new
+                handed = len(ids[used:][-args.batch_overlap:])              # the frames the next batch sees again (vd3:239-241)
+                last_frames = new_frames[-handed:]
+                last_depths = depth[-handed:] if scale is None else depth[-handed:] * scale
+                poses.add(ext, intr, used, None if scale is None else float(scale.item()))      # the batch's one read-back (vd3:192)
     host.write_json_files(xfov_file, transformations_file, poses.xfovs(), poses.transformations())
     return final
 
@@ -168,18 +148,12 @@ def run_clip(args, color_video, infer):
 def run(args, infer=None):
     """The step for --color_video, or for each entry of a .txt list.  infer: the generator (default: the one --generator names,
     loaded once).  -> the depth videos' paths."""
-    from metric_depth_video_toolbox_amd import video_da3 as host
-    host.check_flags(args)                                          # before any file is opened
-    host.check_schedule_args(args.images_per_batch, args.batch_overlap, args.nr_of_ref_frames)
-    clips = host.clips_from_argument(args.color_video)
-    if infer is None:
-        infer = host.load_generator(args.generator)
-    written = []
-    for k, path in enumerate(clips, start=1):
-        if len(clips) > 1 or host.is_txt(args.color_video):
-            print(f"\n##### [{k}/{len(clips)}] Processing {path} #####")
-        written.append(run_clip(args, path, infer))
-    return written
+    from metric_depth_video_toolbox_amd import step_clip, video_da3 as host
+
+    def check(a):                                                   # before any file is opened
+        host.check_flags(a)
+        host.check_schedule_args(a.images_per_batch, a.batch_overlap, a.nr_of_ref_frames)
+    return step_clip.run_list(args, infer, check, lambda: host.load_generator(args.generator), run_clip)
 
 
 def main(argv=None):

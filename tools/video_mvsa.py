@@ -11,7 +11,8 @@ x.mkv_depth.mkv_cv_scales.json.  A .txt list runs each entry; a .npy frame dump 
 generator's contract.
 
 The parser, the transformation file's three forms, the window, the sizes and the intrinsics are host logic in
-metric_depth_video_toolbox_amd/video_mvsa.py.  Here is what touches the device.  Each decoded batch goes ONCE through
+metric_depth_video_toolbox_amd/video_mvsa.py; the opening of the clip with its checks, the context, the output file and the list loop
+are step_clip.py's.  Here is what touches the device.  Each decoded batch goes ONCE through
 mdvt_bilinear_model_frames into a ring of 2 * half_w + 1 + batch planar frames (the reference resizes a frame again for every window
 it falls into, up to `window` times, on the CPU); per target frame the two dicts of mvs:171-231 are built from views of the ring, the
 model is called, and its refined depth goes through mdvt_nearest_depth_codes to the writer or the device FFV1 encoder.
@@ -26,8 +27,6 @@ records are the follow-up), so this tool hands the tensors over itself, as tools
 import os
 import sys
 
-import numpy as np
-
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 
@@ -37,16 +36,12 @@ def bilinear_model_frames(ctx, frames, out_size=None, *, bgr=False, out=None, st
     planar tensor [N, 3, h, w] in R, G, B plane order at out_size = (w, h) (default: the frames' own size): v / 255 through torch's
     bilinear resize, unfused.  out: the tensor to fill (rows, planes and frames may be strided).  Only enqueues, on `stream`."""
     import torch
-    from metric_depth_video_toolbox_amd import _lib
+    from metric_depth_video_toolbox_amd import _lib, step_clip
     _lib.check_tensor("frames", frames, torch.uint8, (None, None, None, 3), packed=2, disjoint=True)
-    N, H, W = (int(v) for v in frames.shape[:3])
-    if N < 1 or H < 1 or W < 1:
-        raise ValueError(f"frames holds no pixel: shape {tuple(frames.shape)}")
-    w, h = (W, H) if out_size is None else (int(out_size[0]), int(out_size[1]))
-    if w < 1 or h < 1:
-        raise ValueError(f"out_size must be (width, height) with both at least 1, got {out_size!r}")
+    N, H, W = step_clip.non_empty("frames", frames, "pixel")
+    w, h = (W, H) if out_size is None else step_clip.size_arg(out_size, "out_size")
     dev = frames.device
-    s = torch.cuda.current_stream(dev) if stream is None else stream
+    s = step_clip.stream_or_current(dev, stream)
     if out is None:
         with torch.cuda.stream(s):
             out = torch.empty((N, 3, h, w), dtype=torch.float32, device=dev)
@@ -62,13 +57,11 @@ def nearest_depth_codes(ctx, planes, mid_size, max_depth, out_size, *, scale=Non
     of one factor for all frames or of N, read on the device.  want_plane: also the float32 [N, H, W] planes of the coded depth.
     out: the codes' tensor to fill.  Only enqueues, on `stream`."""
     import torch
-    from metric_depth_video_toolbox_amd import _lib
+    from metric_depth_video_toolbox_amd import _lib, step_clip
     if not (float(max_depth) > 0):
         raise ValueError("max_depth must be > 0")
     _lib.check_tensor("planes", planes, torch.float32, ndim=3, packed=1, disjoint=True)
-    N, h, w = (int(v) for v in planes.shape)
-    if N < 1 or h < 1 or w < 1:
-        raise ValueError(f"planes holds no value: shape {tuple(planes.shape)}")
+    N, h, w = step_clip.non_empty("planes", planes, "value")
     (mw, mh), (W, H) = (int(v) for v in mid_size), (int(v) for v in out_size)
     if min(mw, mh, W, H) < 1:
         raise ValueError(f"mid_size and out_size must be (width, height) with both at least 1, got {mid_size!r}, {out_size!r}")
@@ -79,7 +72,7 @@ def nearest_depth_codes(ctx, planes, mid_size, max_depth, out_size, *, scale=Non
         if scale.numel() not in (1, N):
             raise ValueError(f"scale must hold one value or one per frame, got shape {tuple(scale.shape)}")
         scale_stride = 4 if scale.numel() == N and N > 1 else 0
-    s = torch.cuda.current_stream(dev) if stream is None else stream
+    s = step_clip.stream_or_current(dev, stream)
     with torch.cuda.stream(s):
         codes = torch.empty((N, H, W, 3), dtype=torch.uint8, device=dev) if out is None else out
         plane = torch.empty((N, H, W), dtype=torch.float32, device=dev) if want_plane else None
@@ -96,7 +89,7 @@ def ratio_median(ctx, cv, ref, mask=None, *, want_counts=False, out=None, stream
     [N, h_m, w_m] (non-zero = true) -> the float32 [N] lower medians of the valid ratios cv / (ref + 1e-6), 1.0 where none is valid,
     and with want_counts the int32 [N] counts.  out: the float32 [N] tensor to fill.  Only enqueues, on `stream`."""
     import torch
-    from metric_depth_video_toolbox_amd import _lib
+    from metric_depth_video_toolbox_amd import _lib, step_clip
     _lib.check_tensor("cv", cv, torch.float32, ndim=3, packed=1, disjoint=True)
     N = int(cv.shape[0])
     dev = cv.device
@@ -105,9 +98,8 @@ def ratio_median(ctx, cv, ref, mask=None, *, want_counts=False, out=None, stream
         raise ValueError(f"cv or ref holds no value: shapes {tuple(cv.shape)}, {tuple(ref.shape)}")
     if mask is not None:
         _lib.check_tensor("mask", mask, torch.uint8, (N, None, None), device=dev, packed=1, disjoint=True)
-        if min(mask.shape[1:]) < 1:
-            raise ValueError(f"mask holds no value: shape {tuple(mask.shape)}")
-    s = torch.cuda.current_stream(dev) if stream is None else stream
+        step_clip.non_empty("mask", mask, "value")
+    s = step_clip.stream_or_current(dev, stream)
     with torch.cuda.stream(s):
         median = torch.empty((N,), dtype=torch.float32, device=dev) if out is None else out
         counts = torch.empty((N,), dtype=torch.int32, device=dev) if want_counts else None
@@ -148,21 +140,12 @@ def checked_prediction(got):
 def run_clip(args, color_video, infer):
     """mvs:81-307 for one clip -> the depth video's path."""
     import torch
-    from metric_depth_video_toolbox_amd import _lib, video_mvsa as host
-    from metric_depth_video_toolbox_amd.clip_io import ClipInputs, ClipOutput, check_video_decoder, check_video_encoder, video_parts
-    with ClipInputs() as inp:
-        color = inp.open(color_video, "color_video", Exception("input video missing"))                 # mvs:81
-        video = bool(video_parts(color))
-        check_video_decoder(args.video_decoder, video)
-        check_video_encoder(args.video_encoder, video)
-        if color.ndim != 4 or color.shape[-1] != 3 or color.dtype != np.uint8:
-            raise ValueError(f"{color_video}: uint8 [N, H, W, 3] expected")
-        H, W = int(color.shape[1]), int(color.shape[2])
-        n = host.frames_to_read(int(color.shape[0]), args.max_frames)
-        if n < 1:
-            raise ValueError("No frames read")                                                          # mvs:99
-        fps = (video_parts(color)[0][0].fps or 30.0) if video else None
-        tmp, final, scales_file = host.output_paths(color_video, video)
+    from metric_depth_video_toolbox_amd import step_clip, video_mvsa as host
+    with step_clip.StepClip() as clip:
+        color, = clip.open_checked([(color_video, "color_video", Exception("input video missing"))],   # mvs:81
+                                   args.video_decoder, args.video_encoder, lambda n: host.frames_to_read(n, args.max_frames))
+        n, H, W = clip.n, clip.H, clip.W
+        tmp, final, scales_file = host.output_paths(color_video, clip.video)
         new_w, new_h, _ = host.model_size(W, H, args.resize_w)
         if new_w < 1 or new_h < 1:
             raise ValueError(f"--resize_w {args.resize_w} gives a model size of {new_w} x {new_h} for {W} x {H} frames")
@@ -171,82 +154,70 @@ def run_clip(args, color_video, infer):
         world_T_cam = torch.stack([torch.inverse(cam_T_world[i]) for i in range(n)])                    # mvs:168-169, on the CPU
         half, batch = host.half_window(args.window), int(args.batch)
         want_scales = bool(args.apply_cost_volume_scale or args.save_cost_volume_scales)
-        inp.on_device(torch.device("cuda", torch.cuda.current_device()), args.video_decoder, args.video_encoder)
-        dev = inp.dev
-        ctx = inp.ctx if inp.ctx is not None else _lib.Context(dev.index, 16, 16)
-        try:
-            with torch.cuda.device(dev), ClipOutput(tmp, final, n, (H, W, 3), fps, args.video_encoder, ctx) as out:
-                cap = 2 * half + 1 + batch
-                ring = torch.empty((cap, 3, new_h, new_w), dtype=torch.float32, device=dev)
-                cam_T_world, world_T_cam = cam_T_world.to(dev), world_T_cam.to(dev)
-                Kd, iKd, Ksd, iKsd = (t.unsqueeze(0).to(dev) for t in (K44, invK44, K44_s, invK44_s))  # [1, 4, 4] each
-                full_res = torch.zeros(1, 1, H, W, device=dev)                                          # mvs:191, allocated once
-                scales = torch.ones((n,), dtype=torch.float32, device=dev) if want_scales else None
-                loaded = 0
-                codes, first = None, 0
-                for i in range(n):
-                    while loaded < min(n, i + half + 1):                                                # the frames the window needs
-                        b = min(n, loaded + batch)
-                        frames = inp.fetch(color, loaded, b)
-                        at = loaded % cap
-                        k = min(b - loaded, cap - at)                                                   # the ring's end splits a batch
-                        bilinear_model_frames(ctx, frames[:k], (new_w, new_h), out=ring[at:at + k])
-                        if k < b - loaded:
-                            bilinear_model_frames(ctx, frames[k:], (new_w, new_h), out=ring[:b - loaded - k])
-                        loaded = b
-                    ref_idx = host.reference_indices(i, n, args.window)
-                    R = len(ref_idx)
-                    cur_data = {                                                                        # mvs:171-192
-                        "image_b3hw": ring[i % cap].unsqueeze(0),
-                        "K_s0_b44": Ksd, "invK_s0_b44": iKsd, "K_matching_b44": Ksd, "invK_matching_b44": iKsd,
-                        "K_full_depth_b44": Kd, "invK_full_depth_b44": iKd,
-                        "cam_T_world_b44": cam_T_world[i].unsqueeze(0), "world_T_cam_b44": world_T_cam[i].unsqueeze(0),
-                        "frame_id_string": [f"{i:06d}"],
-                        "full_res_depth_b1hw": full_res,
-                    }
-                    src_T_cw = cam_T_world[ref_idx]                                                     # [R, 4, 4]
-                    src_data = {                                                                        # mvs:218-231
-                        "image_b3hw": torch.stack([ring[j % cap] for j in ref_idx]).unsqueeze(0),
-                        "K_s0_b44": Ksd.expand(R, 4, 4).unsqueeze(0), "invK_s0_b44": iKsd.expand(R, 4, 4).unsqueeze(0),
-                        "K_matching_b44": Ksd.expand(R, 4, 4).unsqueeze(0), "invK_matching_b44": iKsd.expand(R, 4, 4).unsqueeze(0),
-                        "K_full_depth_b44": Kd.expand(R, 4, 4).contiguous().unsqueeze(0),
-                        "invK_full_depth_b44": iKd.expand(R, 4, 4).contiguous().unsqueeze(0),
-                        "cam_T_world_b44": src_T_cw.unsqueeze(0), "world_T_cam_b44": torch.inverse(src_T_cw).unsqueeze(0),     # mvs:215
-                        "frame_id_string": [f"{j:06d}" for j in ref_idx],
-                    }
-                    depth, cv, mask = checked_prediction(infer(cur_data, src_data, bool(args.fast_cost_volume)))
-                    if want_scales:
-                        ratio_median(ctx, cv, depth, mask, out=scales[i:i + 1])                         # mvs:283-293, kept on the device
-                    if codes is None:
-                        first, codes = i, torch.empty((min(batch, n - i), H, W, 3), dtype=torch.uint8, device=dev)
-                    nearest_depth_codes(ctx, depth, (cv.shape[2], cv.shape[1]), args.max_depth, (W, H),
-                                        scale=scales[i:i + 1] if args.apply_cost_volume_scale else None, out=codes[i - first:i - first + 1])
-                    if i - first + 1 == codes.shape[0]:
-                        out.store(codes, first)
-                        codes = None
-                if args.save_cost_volume_scales:
-                    host.write_scales(scales_file, scales.cpu().numpy())                                # the clip's one read-back
-        finally:
-            if ctx is not inp.ctx:
-                ctx.close()
+        with clip.device(tmp, final) as (ctx, fetch, store):
+            dev = clip.dev
+            cap = 2 * half + 1 + batch
+            ring = torch.empty((cap, 3, new_h, new_w), dtype=torch.float32, device=dev)
+            cam_T_world, world_T_cam = cam_T_world.to(dev), world_T_cam.to(dev)
+            Kd, iKd, Ksd, iKsd = (t.unsqueeze(0).to(dev) for t in (K44, invK44, K44_s, invK44_s))  # [1, 4, 4] each
+            full_res = torch.zeros(1, 1, H, W, device=dev)                                          # mvs:191, allocated once
+            scales = torch.ones((n,), dtype=torch.float32, device=dev) if want_scales else None
+            loaded = 0
+            codes, first = None, 0
+            for i in range(n):
+                while loaded < min(n, i + half + 1):                                                # the frames the window needs
+                    b = min(n, loaded + batch)
+                    frames = fetch(color, loaded, b)
+                    at = loaded % cap
+                    k = min(b - loaded, cap - at)                                                   # the ring's end splits a batch
+                    bilinear_model_frames(ctx, frames[:k], (new_w, new_h), out=ring[at:at + k])
+                    if k < b - loaded:
+                        bilinear_model_frames(ctx, frames[k:], (new_w, new_h), out=ring[:b - loaded - k])
+                    loaded = b
+                ref_idx = host.reference_indices(i, n, args.window)
+                R = len(ref_idx)
+                cur_data = {                                                                        # mvs:171-192
+                    "image_b3hw": ring[i % cap].unsqueeze(0),
+                    "K_s0_b44": Ksd, "invK_s0_b44": iKsd, "K_matching_b44": Ksd, "invK_matching_b44": iKsd,
+                    "K_full_depth_b44": Kd, "invK_full_depth_b44": iKd,
+                    "cam_T_world_b44": cam_T_world[i].unsqueeze(0), "world_T_cam_b44": world_T_cam[i].unsqueeze(0),
+                    "frame_id_string": [f"{i:06d}"],
+                    "full_res_depth_b1hw": full_res,
+                }
+                src_T_cw = cam_T_world[ref_idx]                                                     # [R, 4, 4]
+                src_data = {                                                                        # mvs:218-231
+                    "image_b3hw": torch.stack([ring[j % cap] for j in ref_idx]).unsqueeze(0),
+                    "K_s0_b44": Ksd.expand(R, 4, 4).unsqueeze(0), "invK_s0_b44": iKsd.expand(R, 4, 4).unsqueeze(0),
+                    "K_matching_b44": Ksd.expand(R, 4, 4).unsqueeze(0), "invK_matching_b44": iKsd.expand(R, 4, 4).unsqueeze(0),
+                    "K_full_depth_b44": Kd.expand(R, 4, 4).contiguous().unsqueeze(0),
+                    "invK_full_depth_b44": iKd.expand(R, 4, 4).contiguous().unsqueeze(0),
+                    "cam_T_world_b44": src_T_cw.unsqueeze(0), "world_T_cam_b44": torch.inverse(src_T_cw).unsqueeze(0),     # mvs:215
+                    "frame_id_string": [f"{j:06d}" for j in ref_idx],
+                }
+                depth, cv, mask = checked_prediction(infer(cur_data, src_data, bool(args.fast_cost_volume)))
+                if want_scales:
+                    ratio_median(ctx, cv, depth, mask, out=scales[i:i + 1])                         # mvs:283-293, kept on the device
+                if codes is None:
+                    first, codes = i, torch.empty((min(batch, n - i), H, W, 3), dtype=torch.uint8, device=dev)
+                nearest_depth_codes(ctx, depth, (cv.shape[2], cv.shape[1]), args.max_depth, (W, H),
+                                    scale=scales[i:i + 1] if args.apply_cost_volume_scale else None, out=codes[i - first:i - first + 1])
+                if i - first + 1 == codes.shape[0]:
+                    store(codes, first)
+                    codes = None
+            if args.save_cost_volume_scales:
+                host.write_scales(scales_file, scales.cpu().numpy())                                # the clip's one read-back
     return final
 
 
 def run(args, infer=None):
     """The step for --color_video, or for each entry of a .txt list.  infer: the generator (default: the one --generator names,
     loaded once).  -> the depth videos' paths."""
-    from metric_depth_video_toolbox_amd import video_mvsa as host
-    host.check_flags(args)                                          # before any file is opened for writing
-    host.check_transformation_file(args.transformation_file)
-    clips = host.clips_from_argument(args.color_video)
-    if infer is None:
-        infer = host.load_generator(args.generator)
-    written = []
-    for k, path in enumerate(clips, start=1):
-        if len(clips) > 1 or host.is_txt(args.color_video):
-            print(f"\n##### [{k}/{len(clips)}] Processing {path} #####")
-        written.append(run_clip(args, path, infer))
-    return written
+    from metric_depth_video_toolbox_amd import step_clip, video_mvsa as host
+
+    def check(a):                                                   # before any file is opened for writing
+        host.check_flags(a)
+        host.check_transformation_file(a.transformation_file)
+    return step_clip.run_list(args, infer, check, lambda: host.load_generator(args.generator), run_clip)
 
 
 def main(argv=None):
