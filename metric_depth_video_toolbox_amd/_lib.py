@@ -42,12 +42,12 @@ CONVERGENCE_SYMBOLS = ("mdvt_convergence_depths",)
 # the entry points include/mdvt_metric_align.h declares (relative depth to metric depth codes), listed apart in the same way
 METRIC_ALIGN_SYMBOLS = ("mdvt_scale_shift_fit", "mdvt_metric_depth_codes")
 
-# the entry point include/mdvt_depth_sink.h declares (metric depth planes to a depth video's codes), listed apart in the same way.  It is
-# bound here and has no wrapper in the package yet: tools/video_da3.py calls it
+# the entry point include/mdvt_depth_sink.h declares (metric depth planes to a depth video's codes), listed apart in the same way.  Its
+# wrapper is step_device.depth_video_codes
 DEPTH_SINK_SYMBOLS = ("mdvt_depth_video_codes",)
 
 # the entry points include/mdvt_depth_engines.h declares (frames into a model, PromptDA's prompt, UniK3D's focal estimate), likewise.
-# They are bound here and have no wrapper in the package yet: tools/depth_engine_video.py and tools/upscale_depth_promptda.py call them
+# Their wrappers are step_device.model_frames, depth_prompt and focal_from_points
 DEPTH_ENGINE_SYMBOLS = ("mdvt_model_frames", "mdvt_depth_prompt", "mdvt_focal_from_points")
 
 # the entry points include/mdvt_infill_adapter.h declares (the frames around an in-painting model), listed apart in the same way
@@ -59,17 +59,17 @@ INFILL_ENGINE_SYMBOLS = ("mdvt_m2svid_prepare_eye", "mdvt_model_infill_finish")
 # the entry point include/mdvt_view.h declares (the free-camera viewer's vertex centres), likewise
 VIEW_SYMBOLS = ("mdvt_view_centers", "mdvt_render_view_batch")
 
-# the entry points include/mdvt_geometry.h declares (per-frame vertex and triangle lists, grey depth), likewise.  They are bound here
-# and have no wrapper in the package yet: tools/export_depth_geometry.py calls them
+# the entry points include/mdvt_geometry.h declares (per-frame vertex and triangle lists, grey depth), likewise.  Their wrappers are
+# geometry_device.enqueue_export (export_batch reads its lists back) and grey_batch
 GEOMETRY_SYMBOLS = ("mdvt_export_geometry_batch", "mdvt_depth_grey_batch")
 
 # the entry points include/mdvt_video_mask.h declares (Pillow's Lanczos resize, the mask network's input, the mask from its prediction),
-# likewise.  They are bound here and have no wrapper in the package yet: tools/generate_video_mask.py calls them
+# likewise.  Their wrappers are step_device.lanczos_resize, mask_model_input and mask_from_prediction
 VIDEO_MASK_SYMBOLS = ("mdvt_lanczos_resize_u8", "mdvt_mask_model_input", "mdvt_mask_from_prediction")
 LANCZOS_AUTO, LANCZOS_FUSED, LANCZOS_TWO_LAUNCH = 0, 1, 2
 
 # the entry points include/mdvt_mvsa.h declares (torch's bilinear resize into the multi-view model, two nearest resizes to depth codes,
-# the masked median ratio), likewise.  They are bound here and have no wrapper in the package yet: tools/video_mvsa.py calls them
+# the masked median ratio), likewise.  Their wrappers are step_device.bilinear_model_frames, nearest_depth_codes and ratio_median
 MVSA_SYMBOLS = ("mdvt_bilinear_model_frames", "mdvt_nearest_depth_codes", "mdvt_ratio_median")
 
 

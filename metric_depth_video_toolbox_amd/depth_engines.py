@@ -1,8 +1,8 @@
 """The host side of the reference's per-frame depth engines -- unik3d_video.py (u3d:), moge_video.py (mge:), depthpro_video.py (dpr:)
 -- and of its PromptDA upscaler, upscale_depth_promptda.py (pda:): the command lines, the file names, the `--generator` loader and the
 x-fov arithmetic exactly as each script does it on the host.  Plain host logic: no tensor's address is taken here.
-tools/depth_engine_video.py and tools/upscale_depth_promptda.py run the steps on the device with these pieces and the three entry
-points of include/mdvt_depth_engines.h.
+tools/depth_engine_video.py and tools/upscale_depth_promptda.py run the steps on the device with these pieces and step_device.py's
+wrappers of the three entry points of include/mdvt_depth_engines.h.
 
 The x-fov of all three engines is fov_from_camera_matrix (dmt:1640; mge:21-30 and dpr:51-60 carry copies of it); what differs is the
 matrix it is given:

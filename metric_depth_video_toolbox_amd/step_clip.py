@@ -2,7 +2,7 @@
 video_mvsa.py) share one level above clip_io's frame I/O, as infill_clip.py does for the infill scripts: the host helpers their host
 modules export, the clip session in its two phases, the list loop, and the argument helpers of the tools' device wrappers.  A tool
 configures these with what is its own: the exception of a missing file, the rule for the frame count, the frame rate of a file that
-states none, the banner.  No tensor's address is taken here: the device wrappers stay in the tools.
+states none, the banner.  No tensor's address is taken here: the device wrappers are step_device.py's.
 """
 from __future__ import annotations
 

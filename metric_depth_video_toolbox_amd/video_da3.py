@@ -1,7 +1,8 @@
 """The host side of the reference's video_da3.py (vd3:), the depth step movie_2_3D.py picks when no engine is named: the command
 line, the batch schedule with its reference frames and overlap, the alignment of a batch's camera poses to the batches before, the
 file names and the `--generator` loader.  Plain host logic: no tensor's address is taken here.  tools/video_da3.py runs the step on
-the device with these pieces (the batch factor from mdvt_scale_shift_fit's sums, the depth video through mdvt_depth_video_codes).
+the device with these pieces (the batch factor from mdvt_scale_shift_fit's sums, the depth video through
+step_device.depth_video_codes, the wrapper of mdvt_depth_video_codes).
 
 Two pieces of Depth-Anything-3 that the reference calls cannot be observed without DA3 and are DECREES of this project:
 the batch factor (least_squares_scale_scalar: its documented formula, this project's order of summation) and the pose alignment

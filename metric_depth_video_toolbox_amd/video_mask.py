@@ -1,7 +1,7 @@
 """The host side of the reference's generate_video_mask.py (gvm:), step 3 of movie_2_3D.py: the command line, the file names with
 their tmp -> rename step, the frame count of --max_frames, the `--generator` loader and U2-Net's constants.  Plain host logic: no
-tensor's address is taken here.  tools/generate_video_mask.py runs the step on the device with these pieces and the three entry points
-of include/mdvt_video_mask.h.
+tensor's address is taken here.  tools/generate_video_mask.py runs the step on the device with these pieces and step_device.py's
+wrappers of the three entry points of include/mdvt_video_mask.h.
 
 The step is rembg's remove(only_mask=True) around a U2-Net (gvm:21).  rembg is not available to this project: what it does around the
 network is stated in include/mdvt_video_mask.h from its source (sessions/base.py: normalize, sessions/u2net.py: predict), and the

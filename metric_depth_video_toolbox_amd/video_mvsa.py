@@ -1,8 +1,8 @@
 """The host side of the reference's video_mvsa.py (mvs:), the MVSAnywhere depth step that takes camera poses on the way in: the command
 line, the three forms of a transformation file, the window of reference frames with its quirks, the model's size, the intrinsics and
 their inverses exactly as the script computes them, the file names and the `--generator` loader.  Plain host logic: no tensor's
-address is taken here.  tools/video_mvsa.py runs the step on the device with these pieces and the three entry points of
-include/mdvt_mvsa.h.
+address is taken here.  tools/video_mvsa.py runs the step on the device with these pieces and step_device.py's wrappers of the three
+entry points of include/mdvt_mvsa.h.
 
 Three DECREES of this project: the frames go into the model through the unfused float32 bilinear formula, because torch's
 CPU bilinear has no single set of bits; the two nearest resizes and the median are held to torch's CPU kernels, because CUDA's cannot

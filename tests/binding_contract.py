@@ -25,7 +25,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # the modules whose wrappers the table covers (every module of the package that hands a tensor's address to the library)
 MODULES = ("stereo_rerender", "depth_frames_helper", "infill_common", "basic_nomal_infill", "stereo_dissoclusion_net_infill",
            "stereo_crafter_infill", "m2svid_infill", "infill_clip", "find_convergence_depth", "video_metric_convert", "view_depthfile",
-           "ffv1_device", "model_hop")
+           "ffv1_device", "model_hop", "step_device", "geometry_device")
 
 SIZES = ((33, 5), (36, 6), (6, 6))          # W x H: odd and across a 32-pixel mask word; a multiple of 4 (vector paths); square
 N_FRAMES = 3
@@ -103,25 +103,29 @@ def owned_bytes(t):
 
 @dataclass
 class Touch:
-    """What the library touches for one pointer group: `n` frames `stride` bytes apart, `rows` rows `pitch` bytes apart in each,
-    `row_bytes` bytes in each row from `ptr` on."""
+    """What the library touches for one pointer group: `n` frames `stride` bytes apart, `planes` planes `plane` bytes apart in each
+    (a planar tensor's three; one for every other), `rows` rows `pitch` bytes apart in each plane, `row_bytes` bytes in each row from
+    `ptr` on."""
     ptr: int
     pitch: int
     stride: int
     n: int
     row_bytes: int
     rows: int
+    planes: int = 1
+    plane: int = 0
 
     def addresses(self):
-        """Every touched address, one entry per (frame, row, byte): an address two rows share is there twice."""
-        f = np.arange(self.n, dtype=np.int64)[:, None, None] * int(self.stride if self.n > 1 else 0)
-        r = np.arange(self.rows, dtype=np.int64)[None, :, None] * int(self.pitch if self.rows > 1 else 0)
-        b = np.arange(self.row_bytes, dtype=np.int64)[None, None, :]
-        return (int(self.ptr) + f + r + b).reshape(-1)
+        """Every touched address, one entry per (frame, plane, row, byte): an address two rows share is there twice."""
+        f = np.arange(self.n, dtype=np.int64)[:, None, None, None] * int(self.stride if self.n > 1 else 0)
+        p = np.arange(self.planes, dtype=np.int64)[None, :, None, None] * int(self.plane if self.planes > 1 else 0)
+        r = np.arange(self.rows, dtype=np.int64)[None, None, :, None] * int(self.pitch if self.rows > 1 else 0)
+        b = np.arange(self.row_bytes, dtype=np.int64)[None, None, None, :]
+        return (int(self.ptr) + f + p + r + b).reshape(-1)
 
     def where(self, address):
-        f, r, b = np.unravel_index(int(np.argmax(self.addresses() == address)), (self.n, self.rows, self.row_bytes))
-        return f"(frame {f}, row {r}, byte {b})"
+        f, p, r, b = np.unravel_index(int(np.argmax(self.addresses() == address)), (self.n, self.planes, self.rows, self.row_bytes))
+        return f"(frame {f}, {f'plane {p}, ' if self.planes > 1 else ''}row {r}, byte {b})"
 
 
 def check_groups(what, tensor, touches, output, partial=False):
@@ -143,7 +147,7 @@ def check_groups(what, tensor, touches, output, partial=False):
             problems.append(f"{what}, group {k}: {stray.size} touched byte(s) the tensor does not own, the lowest at {t.where(lo)} = "
                             f"{lo - int(own[0]):+d} bytes from the tensor's first byte (the tensor owns {own.size} bytes over "
                             f"{int(own[-1]) - int(own[0]) + 1}; ptr {t.ptr - int(own[0]):+d}, pitch {t.pitch}, stride {t.stride}, n {t.n}, "
-                            f"{t.rows} rows of {t.row_bytes} bytes)")
+                            f"{f'{t.planes} planes {t.plane} apart, ' if t.planes > 1 else ''}{t.rows} rows of {t.row_bytes} bytes)")
     if not touches:
         return [f"{what}: no pointer group was recorded"]
     allgot = np.concatenate(got)
@@ -163,7 +167,8 @@ def check_groups(what, tensor, touches, output, partial=False):
 # ------------------------------------------------------------------------------------------------------------------------------------
 @dataclass(frozen=True)
 class Arg:
-    """One tensor argument.  kind "rgb": uint8-like [N,]h,w,3; "plane": [N,]h,w; "vec": `shape`, contiguous, no pixels.
+    """One tensor argument.  kind "rgb": uint8-like [N,]h,w,3; "plane": [N,]h,w; "planar": [N,]3,h,w (a plane level between frame
+    and row); "vec": `shape`, contiguous, no pixels.
     layout: what the docstring promises to take -- "strided" (pixels packed, rows and frames at any pitch), "contiguous" (no pitch
     of the tensor is passed on), "copied" (any layout: the wrapper works on a contiguous copy)."""
     name: str
@@ -189,18 +194,19 @@ class Arg:
             return tuple(self.shape(env))
         h, w = self.hw(env) if self.hw else (env.H, self.wide * env.W)
         lead = ((env.N if n is None else n),) if self.batched else ()
-        return lead + (h, w) + ((3,) if self.kind == "rgb" else ())
+        return lead + ((3,) if self.kind == "planar" else ()) + (h, w) + ((3,) if self.kind == "rgb" else ())
 
     @property
     def packed(self):
-        return {"rgb": 2, "plane": 1, "vec": 0}[self.kind]
+        return {"rgb": 2, "plane": 1, "planar": 1, "vec": 0}[self.kind]
 
 
 @dataclass(frozen=True)
 class G:
     """One pointer group of a C call: where in the recorded arguments (positions after the entry point's name; a string names a field
     of the call's MdvtIO / MdvtViewIO; ("=", v) is a literal) pointer, pitch, stride and count stand, and the bytes per row and rows
-    as functions of the environment.  `arg` names the record's argument -- or, with out=None or for returned buffers, the result --
+    as functions of the environment; `plane`, `planes`: where a planar tensor's plane distance stands, and how many planes it has.
+    `arg` names the record's argument -- or, with out=None or for returned buffers, the result --
     the group must stay inside; `offset`: bytes from the recorded pointer to the first touched one (the eye's half of a row)."""
     arg: str
     entry: str
@@ -212,6 +218,8 @@ class G:
     rows: Callable = lambda e: e.H
     offset: Callable = lambda e: 0
     partial: bool = False
+    plane: object = None
+    planes: int = 1
 
 
 @dataclass
@@ -405,6 +413,115 @@ ONE = lambda e: 1                            # noqa: E731
 _M3 = lambda e: 3 * e.MW                     # noqa: E731
 _MROWS = lambda e: e.MH                      # noqa: E731
 
+
+# ---- step_device and geometry_device: the wrappers take the clip's context first; a size the clip does not fix is the model's
+# (8 x 6), the mask's (4 x 3: MVSAnywhere's cost volume and its mask) or the original's (9 x 7: the video's), never W x H ----
+_M4 = lambda e: 4 * e.MW                     # noqa: E731
+_O3 = lambda e: 3 * e.OW                     # noqa: E731
+_O4 = lambda e: 4 * e.OW                     # noqa: E731
+_OROWS = lambda e: e.OH                      # noqa: E731
+_MASK = lambda e: (e.KH, e.KW)               # noqa: E731
+_NVEC = lambda e: 4 * e.N                    # noqa: E731
+
+
+def _ctx(e, sized=False):
+    """The context the step wrappers take first (the geometry wrappers': of the frames' size, which the entry points read from it)."""
+    return mod("_lib").shared_context(e.device, e.W, e.H) if sized else mod("_lib").shared_context(e.device)
+
+
+def _frames_in(name="frames"):
+    return _rgb(name, leads=True, expand=False)
+
+
+def _planes_in(name="planes", **kw):
+    return _plane(name, "float32", expand=False, **kw)
+
+
+def _sink(e, a):
+    codes, plane = mod("step_device").depth_video_codes(_ctx(e), a["planes"], 100.0, (e.OW, e.OH), scale=a["scale"], want_plane=True, out=a["out"])
+    return {"out": codes, "plane": plane}
+
+
+def _model_frames(as_float):
+    entry, el = "mdvt_model_frames", 4 if as_float else 1
+    return Record(f"step_device.model_frames[{'float' if as_float else 'u8'}]", ("step_device.model_frames",), (_frames_in(),),
+                  lambda e, a: {"out": mod("step_device").model_frames(_ctx(e), a["frames"], (e.MW, e.MH), as_float=as_float)},
+                  (G("frames", entry, 3, 4, 5, 2, R3), G("out", entry, 10, 11, 13, 2, lambda e: el * e.MW, _MROWS, plane=12, planes=3)))
+
+
+def _focal(planar):
+    entry = "mdvt_focal_from_points"
+
+    def call(e, a):
+        focal, counts = mod("step_device").focal_from_points(_ctx(e), a["points"], want_counts=True)
+        return {"focal": focal, "counts": counts}
+    points = Arg("points", "planar", "float32", leads=True, expand=False) if planar else _rgb("points", dtype="float32", leads=True, expand=False)
+    group = G("points", entry, 3, 5, 7, 2, R4, plane=6, planes=3) if planar else G("points", entry, 3, 5, 7, 2, lambda e: 12 * e.W)
+    return Record(f"step_device.focal_from_points[{'N3HW' if planar else 'NHW3'}]", ("step_device.focal_from_points",), (points,), call,
+                  (group, G("focal", entry, 8, row_bytes=lambda e: 8 * e.N, rows=ONE), G("counts", entry, 9, row_bytes=lambda e: 8 * e.N, rows=ONE)))
+
+
+def _lanczos(ch):
+    entry = "mdvt_lanczos_resize_u8"
+
+    def call(e, a):
+        out, form = mod("step_device").lanczos_resize(_ctx(e), a["images"], (e.MW, e.MH))
+        return {"out": out} if e.recorder is not None else {"out": out, "form": form}      # (recorded only, no form comes back)
+    images = _frames_in("images") if ch == 3 else _plane("images", leads=True, expand=False)
+    return Record(f"step_device.lanczos_resize[{'RGB' if ch == 3 else 'L'}]", ("step_device.lanczos_resize",), (images,), call,
+                  (G("images", entry, 4, 5, 6, 3, lambda e: ch * e.W), G("out", entry, 9, 10, 11, 3, lambda e: ch * e.MW, _MROWS)))
+
+
+def _mask_from_prediction(ch):
+    entry = "mdvt_mask_from_prediction"
+    return Record(f"step_device.mask_from_prediction[{ch}]", ("step_device.mask_from_prediction",), (_planes_in("pred", leads=True),),
+                  lambda e, a: {"out": mod("step_device").mask_from_prediction(_ctx(e), a["pred"], (e.OW, e.OH), channels=ch)},
+                  (G("pred", entry, 3, 4, 5, 2, R4), G("out", entry, 9, 10, 11, 2, lambda e: ch * e.OW, _OROWS)))
+
+
+def _nearest(e, a):
+    codes, plane = mod("step_device").nearest_depth_codes(_ctx(e), a["planes"], (e.KW, e.KH), 100.0, (e.OW, e.OH), scale=a["scale"], want_plane=True,
+                                                          out=a["out"])
+    return {"out": codes, "plane": plane}
+
+
+def _ratio_median(e, a):
+    median, counts = mod("step_device").ratio_median(_ctx(e), a["cv"], a["ref"], a["mask"], want_counts=True, out=a["out"])
+    return {"out": median, "counts": counts}
+
+
+def _export(e, a):
+    """The enqueueing half of export_batch.  Recorded: the five buffers as they are; launched: what export_batch reads of them --
+    the counts, every vertex, and of the other lists the entries the counts name (the rest is never written)."""
+    K = ((40.0, 0.0, e.W / 2), (0.0, 40.0, e.H / 2), (0.0, 0.0, 1.0))
+    got = mod("geometry_device").enqueue_export(_ctx(e, True), a["depth"], a["color"], K, [None] * e.N, max_depth=100.0, remove_edges=True)
+    res = dict(zip(("counts", "vertices", "triangles", "points", "point_rgb"), got))
+    if e.recorder is None:
+        import torch
+        c = res["counts"].cpu().numpy()
+        res["triangles"] = torch.cat([res["triangles"][k, :c[k, 1]] for k in range(e.N)])
+        for name in ("points", "point_rgb"):
+            res[name] = torch.cat([res[name][k, :c[k, 0]] for k in range(e.N)])
+    return res
+
+
+def _export_io():
+    entry = "mdvt_export_geometry_batch"
+
+    def lists(name, per_frame):
+        return G(name, entry, name, None, name + "_stride", 0, per_frame, ONE)
+    return (G("depth", entry, "depth_rgb", "depth_pitch", "depth_stride", 0, R3), G("color", entry, "color_rgb", "color_pitch", "color_stride", 0, R3),
+            G("counts", entry, "counts", row_bytes=lambda e: 8 * e.N, rows=ONE),
+            lists("vertices", lambda e: 24 * e.W * e.H), lists("triangles", lambda e: 24 * (e.W - 1) * (e.H - 1)),
+            lists("points", lambda e: 24 * e.W * e.H), lists("point_rgb", lambda e: 3 * e.W * e.H))
+
+
+def _grey(bits):
+    entry = "mdvt_depth_grey_batch"
+    return Record(f"geometry_device.grey_batch[{bits}]", ("geometry_device.grey_batch",), (_rgb("depth", layout="contiguous", leads=True, fixed=True),),
+                  lambda e, a: {"out": mod("geometry_device").grey_batch(_ctx(e, True), a["depth"], max_depth=100.0, bits=bits)},
+                  (G("depth", entry, 1, 2, 3, 0, R3), G("out", entry, 6, 7, 8, 0, lambda e: (2 if bits == 16 else 3) * e.W)))
+
 RECORDS = (
     # ---- stereo_rerender: module functions ------------------------------------------------------------------------------------------
     Record("stereo_rerender.infill_using_normals", ("stereo_rerender.infill_using_normals",),
@@ -551,6 +668,39 @@ RECORDS = (
            (_plane("depth", "float32", layout="contiguous", leads=True), _out(layout="contiguous")),
            lambda e, a: {"out": mod("model_hop").depth_to_rgb_code(a["depth"], 100.0, out=a["out"])},
            (G("depth", "mdvt_encode_depth", 0, 1, row_bytes=R4, rows=lambda e: e.N * e.H), G("out", "mdvt_encode_depth", 2, 3, row_bytes=R3, rows=lambda e: e.N * e.H))),
+    # ---- step_device: the model steps' wrappers (no entry point of theirs takes a stride below a frame: expand=False) ---------------
+    Record("step_device.depth_video_codes", ("step_device.depth_video_codes",),
+           (_planes_in(leads=True), Arg("scale", "vec", "float32", layout="contiguous", shape=lambda e: (1,)), _out(hw=_ORG)), _sink,
+           (G("planes", "mdvt_depth_video_codes", 3, 4, 5, 2, R4), G("scale", "mdvt_depth_video_codes", 6, row_bytes=lambda e: 4, rows=ONE),
+            G("out", "mdvt_depth_video_codes", 11, 12, 13, 2, _O3, _OROWS), G("plane", "mdvt_depth_video_codes", 15, 16, 17, 2, _O4, _OROWS))),
+    _model_frames(False), _model_frames(True),
+    Record("step_device.depth_prompt", ("step_device.depth_prompt",), (_frames_in("codes"),),
+           lambda e, a: {"out": mod("step_device").depth_prompt(_ctx(e), a["codes"], 100.0, (e.MW, e.MH))},
+           (G("codes", "mdvt_depth_prompt", 3, 4, 5, 2, R3), G("out", "mdvt_depth_prompt", 10, 11, 12, 2, _M4, _MROWS))),
+    _focal(False), _focal(True), _lanczos(1), _lanczos(3),
+    Record("step_device.mask_model_input", ("step_device.mask_model_input",), (_frames_in(),),
+           lambda e, a: {"out": mod("step_device").mask_model_input(_ctx(e), a["frames"], (e.MW, e.MH), (0.485, 0.456, 0.406), (0.229, 0.224, 0.225))},
+           (G("frames", "mdvt_mask_model_input", 3, 4, 5, 2, R3), G("out", "mdvt_mask_model_input", 11, 12, 14, 2, _M4, _MROWS, plane=13, planes=3))),
+    _mask_from_prediction(1), _mask_from_prediction(3),
+    # (out: a slice of the tool's ring of planar model frames)
+    Record("step_device.bilinear_model_frames", ("step_device.bilinear_model_frames",), (_frames_in(), _out("out", "planar", "float32", hw=_MODEL)),
+           lambda e, a: {"out": mod("step_device").bilinear_model_frames(_ctx(e), a["frames"], (e.MW, e.MH), out=a["out"])},
+           (G("frames", "mdvt_bilinear_model_frames", 3, 4, 5, 2, R3),
+            G("out", "mdvt_bilinear_model_frames", 9, 10, 12, 2, _M4, _MROWS, plane=11, planes=3))),
+    Record("step_device.nearest_depth_codes", ("step_device.nearest_depth_codes",),
+           (_planes_in(leads=True), Arg("scale", "vec", "float32", layout="contiguous", shape=lambda e: (e.N,)), _out(hw=_ORG)), _nearest,
+           (G("planes", "mdvt_nearest_depth_codes", 3, 4, 5, 2, R4), G("scale", "mdvt_nearest_depth_codes", 8, None, 9, 2, lambda e: 4, ONE),
+            G("out", "mdvt_nearest_depth_codes", 13, 14, 15, 2, _O3, _OROWS), G("plane", "mdvt_nearest_depth_codes", 17, 18, 19, 2, _O4, _OROWS))),
+    Record("step_device.ratio_median", ("step_device.ratio_median",),
+           (_planes_in("cv", leads=True), _planes_in("ref", hw=_MODEL, free_hw=True), _plane("mask", hw=_MASK, free_hw=True, expand=False),
+            _out("out", "vec", "float32", layout="contiguous", shape=lambda e: (e.N,))), _ratio_median,
+           (G("cv", "mdvt_ratio_median", 3, 4, 5, 0, R4), G("ref", "mdvt_ratio_median", 8, 9, 10, 0, _M4, _MROWS),
+            G("mask", "mdvt_ratio_median", 13, 14, 15, 0, lambda e: e.KW, lambda e: e.KH),
+            G("out", "mdvt_ratio_median", 16, row_bytes=_NVEC, rows=ONE), G("counts", "mdvt_ratio_median", 17, row_bytes=_NVEC, rows=ONE))),
+    # ---- geometry_device: the context fixes W x H, the library is told no pitch of the tensors' own ---------------------------------
+    Record("geometry_device.enqueue_export", ("geometry_device.enqueue_export",),
+           (_rgb("depth", layout="contiguous", leads=True, fixed=True), _rgb("color", layout="contiguous")), _export, _export_io()),
+    _grey(8), _grey(16),
 )
 
 BY_NAME = {r.name: r for r in RECORDS}
@@ -812,7 +962,7 @@ def touches_of(record, calls, env):
             stride = resolve(g.stride, c, env)
             n = int(resolve(g.n, c, env))
             out.setdefault(g.arg, []).append(Touch(int(ptr or 0) + int(g.offset(env)), int(rb if pitch is None else pitch),
-                                                   int(0 if stride is None else stride), n, rb, rows))
+                                                   int(0 if stride is None else stride), n, rb, rows, g.planes, int(resolve(g.plane, c, env) or 0)))
     return out
 
 

@@ -75,7 +75,7 @@ def test_every_record_names_its_tensors_and_groups_consistently():
         names = [a.name for a in r.args]
         assert len(set(names)) == len(names) and r.groups, r.name
         for a in r.args:
-            assert a.kind in ("rgb", "plane", "vec") and a.role in ("in", "out") and a.layout in ("strided", "contiguous", "copied"), (r.name, a.name)
+            assert a.kind in ("rgb", "plane", "planar", "vec") and a.role in ("in", "out") and a.layout in ("strided", "contiguous", "copied"), (r.name, a.name)
             assert a.kind != "vec" or (a.layout == "contiguous" and a.shape is not None), (r.name, a.name)
             if (r.name, a.name) not in UNGROUPED:
                 assert a.name in {g.arg for g in r.groups}, f"{r.name}: argument {a.name} has no pointer group"
@@ -97,6 +97,16 @@ def _touch(t, **kw):
     batched = t.dim() == 4
     d = dict(ptr=t.data_ptr(), pitch=t.stride(-3) * e, stride=t.stride(0) * e if batched else 0, n=int(t.shape[0]) if batched else 1,
              row_bytes=int(t.shape[-2]) * int(t.shape[-1]) * e, rows=int(t.shape[-3]))
+    d.update(kw)
+    return bc.Touch(**d)
+
+
+def _planar_touch(t, **kw):
+    """The right recording of a planar tensor [N, 3, H, W] (or [3, H, W]): its pointer and its three byte distances."""
+    e = t.element_size()
+    batched = t.dim() == 4
+    d = dict(ptr=t.data_ptr(), pitch=t.stride(-2) * e, plane=t.stride(-3) * e, planes=int(t.shape[-3]), stride=t.stride(0) * e if batched else 0,
+             n=int(t.shape[0]) if batched else 1, row_bytes=int(t.shape[-1]) * e, rows=int(t.shape[-2]))
     d.update(kw)
     return bc.Touch(**d)
 
@@ -133,6 +143,11 @@ def test_a_correct_recording_passes(torch):
     assert bc.check_groups("ok", z, [_touch(z)], True) == []
     padded = torch.zeros((N, H, W + 5, 1), dtype=torch.float32)[:, :, :W]
     assert bc.check_groups("ok", padded, [_touch(padded)], True) == []
+    # a planar tensor [N, 3, H, W] has a plane level: contiguous, with padded rows, and a slice of a ring of model frames
+    ring = torch.zeros((5, 3, H, W + 5), dtype=torch.float32)
+    for view in (ring, ring[:, :, :, :W], ring[1:1 + N], ring[1:1 + N, :, :, :W], ring[2]):
+        for output in (False, True):
+            assert bc.check_groups("ok", view, [_planar_touch(view)], output) == [], tuple(view.stride())
 
 
 def test_the_slips_the_checker_exists_for_are_reported(torch):
@@ -140,6 +155,8 @@ def test_the_slips_the_checker_exists_for_are_reported(torch):
     right = sbs[:, :, W:]
     z = torch.zeros((N, H, W, 1), dtype=torch.float32)
     gapped = torch.zeros((N, H * W * 3 + 11), dtype=torch.uint8)[:, :H * W * 3].view(N, H, W, 3)
+    planar = torch.zeros((5, 3, H, W), dtype=torch.float32)[1:1 + N]
+    padded_planar = torch.zeros((5, 3, H, W + 5), dtype=torch.float32)[1:1 + N, :, :, :W]
     slips = {
         # an element stride where bytes are wanted, float32: pitch W instead of 4 W -- as an input (nothing out of bounds: part of
         # the tensor would be read four times over) and as an output
@@ -159,6 +176,11 @@ def test_the_slips_the_checker_exists_for_are_reported(torch):
         "contiguous frame stride for a gapped batch, input": (gapped, [_touch(gapped, stride=3 * W * H)], False, "would not be read"),
         # rows that fold onto one another in an output
         "folded rows": (sbs[0, :, :W], [_touch(sbs[0, :, :W], pitch=3 * W - 2)], True, "more than once"),
+        # an element stride where the plane's byte distance is wanted: H W instead of 4 H W, on out=ring[at:at + k] of the MVSA ring
+        "element stride for the plane distance, input": (planar, [_planar_touch(planar, plane=planar.stride(1))], False, "would not be read"),
+        "element stride for the plane distance, output": (planar, [_planar_touch(planar, plane=planar.stride(1))], True, "would not be written"),
+        # the contiguous plane distance for a view with padded rows
+        "contiguous plane distance for padded rows": (padded_planar, [_planar_touch(padded_planar, plane=4 * H * W)], True, "does not own"),
     }
     for name, (tensor, touches, output, text) in slips.items():
         problems = bc.check_groups(name, tensor, touches, output)
@@ -166,6 +188,9 @@ def test_the_slips_the_checker_exists_for_are_reported(torch):
     # a last row that ends inside the storage but outside the view is named by frame, row and byte
     text = bc.check_groups("t", right, [_touch(right, pitch=3 * W, stride=3 * W * H)], True)[0]
     assert "(frame 0, row 1, byte 0)" in text and "pitch 21" in text, text
+    text = bc.check_groups("t", padded_planar, [_planar_touch(padded_planar, plane=4 * H * W)], True)[0]
+    # (plane 1 is told to start 4 H W = 112 bytes in: 16 bytes into the view's third row, which owns 12 more)
+    assert "(frame 0, plane 1, row 0, byte 12)" in text and f"3 planes {4 * H * W} apart" in text, text
     assert bc.check_groups("none", sbs, [], True) == ["none: no pointer group was recorded"]
     # `partial` excuses unread bytes, never stray ones
     assert bc.check_groups("p", sbs, [_touch(sbs, row_bytes=3 * W)], False, partial=True) == []

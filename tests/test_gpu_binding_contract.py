@@ -12,7 +12,11 @@ the table, the recorder and the extent checker), in three passes kept apart:
       layout that failed (b) is reported as failed here, without a launch.
 
 Sizes: 33 x 5 (odd, across a 32-pixel word of the packed mask), 36 x 6 (a multiple of 4: the vector paths), 6 x 6 (square: a
-transposed view keeps its shape), 3 frames; the model-sized buffers of the adapter and m2svid steps are 8 x 6 and 4 x 3.
+transposed view keeps its shape), 3 frames; the model-sized buffers of the adapter and m2svid steps are 8 x 6 and 4 x 3.  The
+model-step wrappers of step_device.py take the same: every size the clip does not fix differs from W x H -- the model's input and
+PromptDA's prompt 8 x 6, MVSAnywhere's cost volume and its mask 4 x 3, the video a depth or a mask is resized to 9 x 7 -- and the
+planar tensors [N, 3, h, w] bring a third byte distance, the plane's.  geometry_device.py's wrappers read W x H from the context,
+so theirs is made for the frames' size.
 Every comparison is equality of bytes (floats: the same bits, or both NaN)."""
 import pytest
 

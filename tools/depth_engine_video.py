@@ -20,8 +20,8 @@ moge and depthpro write through their own save_24bit (mge:68-102, dpr:62-96), wh
 every depth in [0, max_depth] and has no defined result outside (a float64 out of uint32's range).  DECREE: those depths take the
 sink's clip, like every other depth video of this project.
 
-The three entry points of include/mdvt_depth_engines.h are bound in _lib.py and have no wrapper in the package yet (their tensor
-contract records are the follow-up), so this tool hands the tensors over itself, as tools/video_da3.py does."""
+model_frames, depth_prompt and focal_from_points, the wrappers of include/mdvt_depth_engines.h's three entry points, are
+metric_depth_video_toolbox_amd/step_device.py's; they stay reachable under this module's name."""
 import importlib.util
 import os
 import sys
@@ -30,6 +30,8 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
+
+from metric_depth_video_toolbox_amd.step_device import depth_prompt, focal_from_points, model_frames      # noqa: E402, F401
 
 
 def sibling_tool(name):
@@ -41,72 +43,6 @@ def sibling_tool(name):
         sys.modules[key] = mod
         spec.loader.exec_module(mod)
     return sys.modules[key]
-
-
-def model_frames(ctx, frames, out_size=None, *, as_float=False, bgr=False, stream=None):
-    """mdvt_model_frames on uint8 CUDA frames [N, H, W, 3] (rows and frames may be strided; B, G, R with bgr) -> the planar tensor
-    [N, 3, h, w] in R, G, B plane order at out_size = (w, h) (default: the frames' own size), uint8, or float32 v / 255 with as_float.
-    Only enqueues, on `stream`."""
-    import torch
-    from metric_depth_video_toolbox_amd import _lib, step_clip
-    _lib.check_tensor("frames", frames, torch.uint8, (None, None, None, 3), packed=2, disjoint=True)
-    N, H, W = step_clip.non_empty("frames", frames, "pixel")
-    w, h = (W, H) if out_size is None else step_clip.size_arg(out_size, "out_size")
-    dev = frames.device
-    s = step_clip.stream_or_current(dev, stream)
-    with torch.cuda.stream(s):
-        out = torch.empty((N, 3, h, w), dtype=torch.float32 if as_float else torch.uint8, device=dev)
-    e = out.element_size()
-    ctx.call("mdvt_model_frames", W, H, N, frames.data_ptr(), frames.stride(1), frames.stride(0), int(bool(bgr)), w, h, int(bool(as_float)),
-             out.data_ptr(), e * w, e * w * h, e * w * h * 3, _lib.stream_arg(dev, s))
-    return out
-
-
-def depth_prompt(ctx, codes, max_depth, out_size, *, bgr=False, stream=None):
-    """mdvt_depth_prompt on uint8 CUDA depth frames [N, H, W, 3] (R, G, B; B, G, R with bgr) -> float32 [N, h, w] at out_size = (w, h):
-    the decoded depth, resized like cv2.resize(INTER_LINEAR).  Only enqueues, on `stream`."""
-    import torch
-    from metric_depth_video_toolbox_amd import _lib, step_clip
-    if not (float(max_depth) > 0):
-        raise ValueError("max_depth must be > 0")
-    _lib.check_tensor("codes", codes, torch.uint8, (None, None, None, 3), packed=2, disjoint=True)
-    N, H, W = step_clip.non_empty("codes", codes, "pixel")
-    w, h = step_clip.size_arg(out_size, "out_size")
-    dev = codes.device
-    s = step_clip.stream_or_current(dev, stream)
-    with torch.cuda.stream(s):
-        out = torch.empty((N, h, w), dtype=torch.float32, device=dev)
-    ctx.call("mdvt_depth_prompt", W, H, N, codes.data_ptr(), codes.stride(1), codes.stride(0), int(bool(bgr)), float(max_depth), w, h,
-             out.data_ptr(), 4 * w, 4 * w * h, _lib.stream_arg(dev, s))
-    return out
-
-
-def focal_from_points(ctx, points, *, want_counts=False, stream=None):
-    """mdvt_focal_from_points on float32 CUDA point maps [N, H, W, 3] or [N, 3, H, W] (a last dimension of 3 is read as the
-    former, as u3d:46-52 reads it; rows, planes and frames may be strided) -> float32 [N, 2] = (fx, fy) per frame and, with
-    want_counts, the int32 tensor [N, 2] = (nx, ny) of the library's uint32 counts (at most 2^28 each).  Only enqueues, on `stream`."""
-    import torch
-    from metric_depth_video_toolbox_amd import _lib, step_clip
-    _lib.check_tensor("points", points, torch.float32, ndim=4)
-    if points.shape[-1] == 3:
-        _lib.check_tensor("points", points, torch.float32, ndim=4, packed=2, disjoint=True)
-        layout, dims = 1, points.shape[:3]
-        pitch, plane, stride = 4 * points.stride(1), 0, 4 * points.stride(0)
-    elif points.shape[1] == 3:
-        _lib.check_tensor("points", points, torch.float32, ndim=4, packed=1, disjoint=True)
-        layout, dims = 0, (points.shape[0], *points.shape[2:])
-        pitch, plane, stride = 4 * points.stride(2), 4 * points.stride(1), 4 * points.stride(0)
-    else:
-        raise ValueError(f"points must be [N, H, W, 3] or [N, 3, H, W], got shape {tuple(points.shape)}")
-    N, H, W = step_clip.non_empty("points", points, "point", dims)
-    dev = points.device
-    s = step_clip.stream_or_current(dev, stream)
-    with torch.cuda.stream(s):
-        focal = torch.empty((N, 2), dtype=torch.float32, device=dev)
-        counts = torch.empty((N, 2), dtype=torch.int32, device=dev) if want_counts else None
-    ctx.call("mdvt_focal_from_points", W, H, N, points.data_ptr(), layout, pitch, plane, stride, focal.data_ptr(),
-             counts.data_ptr() if want_counts else None, _lib.stream_arg(dev, s))
-    return (focal, counts) if want_counts else focal
 
 
 def checked_prediction(got, engine, n, W, H):

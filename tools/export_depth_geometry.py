@@ -4,9 +4,9 @@
 
     python tools/export_depth_geometry.py --depth_video x.mkv --xfov 60 --save_ply out_ply --save_obj out_obj --remove_edges
 
-The geometry comes from mdvt_export_geometry_batch and the grey depth from mdvt_depth_grey_batch (include/mdvt_geometry.h), bound in
-_lib.py; the package has no wrapper for them yet (its tensor contract record is the follow-up), so this tool hands the tensors over
-itself, as the other tools do.  Frames go up in batches; the lists come back by their counts only -- `counts` first, then U or M
+The geometry comes from mdvt_export_geometry_batch and the grey depth from mdvt_depth_grey_batch (include/mdvt_geometry.h); their
+wrappers export_batch and grey_batch are metric_depth_video_toolbox_amd/geometry_device.py's and stay reachable under this module's
+name.  Frames go up in batches; the lists come back by their counts only -- `counts` first, then U or M
 entries per frame -- and are written by metric_depth_video_toolbox_amd/geometry_files.py (its docstring states the files' layouts, a
 decree of this project: Open3D's exact bytes cannot be observed without Open3D).
 
@@ -14,7 +14,6 @@ Frame bounds are the reference loop's own, quirks included (cmf:639-641, 765-766
 (m + 1 frames, not m), and with --max_frames M the loop stops after frame M + 1 (exported_frames below)."""
 import argparse
 import contextlib
-import ctypes as C
 import json
 import os
 import sys
@@ -22,6 +21,8 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from metric_depth_video_toolbox_amd.geometry_device import export_batch, frame_params, grey_batch      # noqa: E402, F401
 
 REFUSED = {                                              # flag -> why the device path does not take it
     "track_file": "--track_file starts the host 3D reconstruction from 2D tracks (cmf:609-614, 700-730, 773 ff.), which is not built",
@@ -90,74 +91,6 @@ def exported_frames(n_frames, min_frames=-1, max_frames=-1):
         out.append(f)
         if max_frames < f and max_frames != -1:
             break
-    return out
-
-
-def frame_params(_lib, K, transforms):
-    """MdvtFrameParams records of a batch: K, depth scale 1, the pose where there is one."""
-    arr = (_lib.MdvtFrameParams * len(transforms))()
-    for k, T in enumerate(transforms):
-        for i, v in enumerate(np.asarray(K, np.float64).reshape(9)):
-            arr[k].K[i] = arr[k].Krender[i] = v
-        arr[k].depth_scale = 1.0
-        if T is not None:
-            arr[k].has_T = 1
-            for i, v in enumerate(np.asarray(T, np.float64).reshape(16)):
-                arr[k].T[i] = v
-    return arr
-
-
-def export_batch(ctx, d_depth, d_color, K, transforms, *, max_depth, remove_edges, decode=0, want_ply=True, want_obj=True, stream=None):
-    """One call of mdvt_export_geometry_batch on uint8 CUDA [B, H, W, 3] frames -> per frame a dict of host arrays: points, point_rgb
-    (want_ply), vertices, triangles (want_obj), counts (U, M).  The lists come back by their counts: counts first, then U or M entries."""
-    import torch
-    from metric_depth_video_toolbox_amd import _lib
-    B, H, W = int(d_depth.shape[0]), int(d_depth.shape[1]), int(d_depth.shape[2])
-    N, ncell, dev = W * H, (W - 1) * (H - 1), d_depth.device
-    for name, t in (("depth", d_depth), ("color", d_color)):
-        _lib.check_tensor(name, t, torch.uint8, (B, H, W, 3), device=dev, contiguous=True)
-    opts = _lib.MdvtGeometryOpts(decode=int(decode), remove_edges=int(bool(remove_edges)), max_depth=float(max_depth))
-    io = _lib.MdvtGeometryIO()
-    io.depth_rgb, io.depth_pitch, io.depth_stride = d_depth.data_ptr(), 3 * W, 3 * W * H
-    io.color_rgb, io.color_pitch, io.color_stride = d_color.data_ptr(), 3 * W, 3 * W * H
-    counts = torch.empty((B, 2), dtype=torch.int32, device=dev)
-    io.counts = counts.data_ptr()
-    vertices = triangles = points = point_rgb = None
-    if want_obj:
-        vertices = torch.empty((B, N, 3), dtype=torch.float64, device=dev)
-        triangles = torch.empty((B, 2 * ncell, 3), dtype=torch.int32, device=dev)
-        io.vertices, io.vertices_stride = vertices.data_ptr(), 24 * N
-        io.triangles, io.triangles_stride = triangles.data_ptr(), 24 * ncell
-    if want_ply:
-        points = torch.empty((B, N, 3), dtype=torch.float64, device=dev)
-        point_rgb = torch.empty((B, N, 3), dtype=torch.uint8, device=dev)
-        io.points, io.points_stride = points.data_ptr(), 24 * N
-        io.point_rgb, io.point_rgb_stride = point_rgb.data_ptr(), 3 * N
-    ctx.call("mdvt_export_geometry_batch", B, frame_params(_lib, K, transforms), C.byref(opts), C.byref(io), _lib.stream_arg(dev, stream))
-    host_counts = counts.cpu().numpy()
-    out = []
-    for k in range(B):
-        U, M = int(host_counts[k, 0]), int(host_counts[k, 1])
-        f = {"counts": (U, M)}
-        if want_ply:
-            f["points"], f["point_rgb"] = points[k, :U].cpu().numpy(), point_rgb[k, :U].cpu().numpy()
-        if want_obj:
-            f["vertices"], f["triangles"] = vertices[k].cpu().numpy(), triangles[k, :M].cpu().numpy()
-        out.append(f)
-    return out
-
-
-def grey_batch(ctx, d_depth, *, max_depth, bits, stream=None):
-    """mdvt_depth_grey_batch on uint8 CUDA [B, H, W, 3] frames -> CUDA int16 [B, H, W] holding the uint16 bit patterns (bits 16: view
-    the host copy as np.uint16) or uint8 [B, H, W, 3] (bits 8)."""
-    import torch
-    from metric_depth_video_toolbox_amd import _lib
-    B, H, W = int(d_depth.shape[0]), int(d_depth.shape[1]), int(d_depth.shape[2])
-    _lib.check_tensor("depth", d_depth, torch.uint8, (B, H, W, 3), contiguous=True)
-    out = torch.empty((B, H, W) if bits == 16 else (B, H, W, 3), dtype=torch.int16 if bits == 16 else torch.uint8, device=d_depth.device)
-    row = 2 * W if bits == 16 else 3 * W
-    ctx.call("mdvt_depth_grey_batch", B, d_depth.data_ptr(), 3 * W, 3 * W * H, float(max_depth), int(bits), out.data_ptr(), row, row * H,
-             _lib.stream_arg(d_depth.device, stream))
     return out
 
 

@@ -15,73 +15,15 @@ to the planar float32 tensor the network takes, the generator is called, its pre
 save_grayscale_video's frame, dfh:221-230) to the writer or the device FFV1 encoder.  Nothing is read back but the coded packets or,
 with the host encoder, the finished mask frames.
 
-The three entry points of include/mdvt_video_mask.h are bound in _lib.py and have no wrapper in the package yet (their tensor contract
-records are the follow-up), so this tool hands the tensors over itself, as tools/depth_engine_video.py does."""
-import ctypes as C
+lanczos_resize, mask_model_input and mask_from_prediction, the wrappers of include/mdvt_video_mask.h's three entry points, are
+metric_depth_video_toolbox_amd/step_device.py's; they stay reachable under this module's name."""
 import os
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 
-
-def lanczos_resize(ctx, images, out_size, *, form=0, stream=None):
-    """mdvt_lanczos_resize_u8 on uint8 CUDA images [N, H, W] (mode L) or [N, H, W, 3] (rows and frames may be strided) -> (the images
-    at out_size = (w, h): Image.resize(out_size, LANCZOS) byte for byte, the form the call took: _lib.LANCZOS_FUSED,
-    _lib.LANCZOS_TWO_LAUNCH or 0 for a copy).  Only enqueues, on `stream`."""
-    import torch
-    from metric_depth_video_toolbox_amd import _lib, step_clip
-    _lib.check_tensor("images", images, torch.uint8, ndim=(3, 4))
-    ch = 1 if images.dim() == 3 else 3
-    _lib.check_tensor("images", images, torch.uint8, (None, None, None) + ((3,) if ch == 3 else ()), packed=2 if ch == 3 else 1, disjoint=True)
-    N, H, W = step_clip.non_empty("images", images, "pixel")
-    w, h = step_clip.size_arg(out_size, "out_size")
-    dev = images.device
-    s = step_clip.stream_or_current(dev, stream)
-    with torch.cuda.stream(s):
-        out = torch.empty((N, h, w) + ((3,) if ch == 3 else ()), dtype=torch.uint8, device=dev)
-    took = C.c_int(-1)
-    ctx.call("mdvt_lanczos_resize_u8", W, H, ch, N, images.data_ptr(), images.stride(1), images.stride(0), w, h,
-             out.data_ptr(), ch * w, ch * w * h, int(form), C.cast(C.byref(took), C.c_void_p), _lib.stream_arg(dev, s))
-    return out, int(took.value)
-
-
-def mask_model_input(ctx, frames, model_size, mean, std, *, bgr=False, stream=None):
-    """mdvt_mask_model_input on uint8 CUDA frames [N, H, W, 3] (rows and frames may be strided; B, G, R with bgr) -> float32
-    [N, 3, h, w] at model_size = (w, h), planes R, G, B: rembg's normalize.  Only enqueues, on `stream`."""
-    import torch
-    from metric_depth_video_toolbox_amd import _lib, step_clip
-    _lib.check_tensor("frames", frames, torch.uint8, (None, None, None, 3), packed=2, disjoint=True)
-    N, H, W = step_clip.non_empty("frames", frames, "pixel")
-    w, h = step_clip.size_arg(model_size, "model_size")
-    d3 = C.c_double * 3
-    h_mean, h_std = d3(*(float(v) for v in mean)), d3(*(float(v) for v in std))
-    dev = frames.device
-    s = step_clip.stream_or_current(dev, stream)
-    with torch.cuda.stream(s):
-        out = torch.empty((N, 3, h, w), dtype=torch.float32, device=dev)
-    ctx.call("mdvt_mask_model_input", W, H, N, frames.data_ptr(), frames.stride(1), frames.stride(0), int(bool(bgr)), w, h,
-             C.cast(h_mean, C.c_void_p), C.cast(h_std, C.c_void_p), out.data_ptr(), 4 * w, 4 * w * h, 12 * w * h, _lib.stream_arg(dev, s))
-    return out
-
-
-def mask_from_prediction(ctx, pred, out_size, *, channels=3, stream=None):
-    """mdvt_mask_from_prediction on float32 CUDA planes [N, h, w] (rows and frames may be strided) -> uint8 [N, H, W, 3] (three equal
-    bytes: the mask video's frame) or, with channels=1, [N, H, W] at out_size = (W, H).  Only enqueues, on `stream`."""
-    import torch
-    from metric_depth_video_toolbox_amd import _lib, step_clip
-    if channels not in (1, 3):
-        raise ValueError(f"channels must be 1 or 3, got {channels!r}")
-    _lib.check_tensor("pred", pred, torch.float32, (None, None, None), packed=1, disjoint=True)
-    N, ph, pw = step_clip.non_empty("pred", pred, "value")
-    W, H = step_clip.size_arg(out_size, "out_size")
-    dev = pred.device
-    s = step_clip.stream_or_current(dev, stream)
-    with torch.cuda.stream(s):
-        out = torch.empty((N, H, W) + ((3,) if channels == 3 else ()), dtype=torch.uint8, device=dev)
-    ctx.call("mdvt_mask_from_prediction", pw, ph, N, pred.data_ptr(), 4 * pred.stride(1), 4 * pred.stride(0), W, H, int(channels),
-             out.data_ptr(), channels * W, channels * W * H, _lib.stream_arg(dev, s))
-    return out
+from metric_depth_video_toolbox_amd.step_device import lanczos_resize, mask_from_prediction, mask_model_input      # noqa: E402, F401
 
 
 def checked_prediction(got, n, device):

@@ -15,13 +15,12 @@ save_depth_video's, which then has nothing left to do, are that one resize).  Th
 14 x 14 frames on the sink meets no exact-2x case; a depth video of exactly 512 x 384 would be one for the prompt and is refused by mdvt_depth_prompt.
 
 The loop ends with the shorter of the two videos (pda:51-58): step_clip.py's clip session opens both, holds them to one kind and
-counts the shorter one."""
+counts the shorter one; the three device wrappers are metric_depth_video_toolbox_amd/step_device.py's."""
 import os
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, HERE)
 
 
 def checked_upscale(got, n, h14, w14):
@@ -33,9 +32,8 @@ def checked_upscale(got, n, h14, w14):
 
 def run(args, upscale=None):
     """pda:30-84 for one pair of clips -> the upscaled depth video's path."""
-    from depth_engine_video import depth_prompt, model_frames, sibling_tool
     from metric_depth_video_toolbox_amd import depth_engines as host, step_clip
-    da3_tool = sibling_tool("video_da3")
+    from metric_depth_video_toolbox_amd.step_device import depth_prompt, depth_video_codes, model_frames
     if int(args.batch) < 1:
         raise ValueError(f"--batch must be at least 1, got {args.batch}")
     if upscale is None:
@@ -55,7 +53,7 @@ def run(args, upscale=None):
                 rgb = model_frames(ctx, fetch(color, a, b), (w14, h14), as_float=True)
                 prompt = depth_prompt(ctx, fetch(depth, a, b), args.max_depth, (host.PROMPT_W, host.PROMPT_H))
                 up = checked_upscale(upscale(rgb, prompt.unsqueeze(1)), b - a, h14, w14)
-                store(da3_tool.depth_video_codes(ctx, up, args.max_depth, (W, H)), a)
+                store(depth_video_codes(ctx, up, args.max_depth, (W, H)), a)
     return final
 
 

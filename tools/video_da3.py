@@ -15,8 +15,8 @@ steps.  Here is what touches the device: the frames are gathered there (the refe
 factor that aligns a batch to the one before comes from the fit's float32 sums (video_metric_convert.compute_scale_and_shift_full)
 and stays on the device, and the new planes go through mdvt_depth_video_codes (include/mdvt_depth_sink.h) with that factor to the
 video's size and on to the writer or the device FFV1 encoder.  One 4-byte read-back of the factor per batch scales the translations
-(vd3:192).  mdvt_depth_video_codes is bound in _lib.py and has no wrapper in the package yet (its tensor contract record is the
-follow-up), so this tool hands the tensors over itself, as tools/export_depth_geometry.py does.
+(vd3:192).  depth_video_codes, the wrapper of mdvt_depth_video_codes, is metric_depth_video_toolbox_amd/step_device.py's; it stays
+reachable under this module's name.
 
 save_depth_video below is the sink alone (dfh:125-161), for any metric model's float32 CUDA planes."""
 import os
@@ -26,35 +26,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-
-def depth_video_codes(ctx, planes, max_depth, out_size=None, *, scale=None, nan_to_max=False, bgr=False, want_plane=False, out=None,
-                      stream=None):
-    """mdvt_depth_video_codes on float32 CUDA planes [N, h, w] (rows and frames may be strided) -> the uint8 [N, H, W, 3] codes of a
-    depth video at out_size = (W, H) (default: the planes' own size), R, G, B order (B, G, R with bgr).  scale: a one-element float32
-    CUDA tensor every value is multiplied by first, read on the device; nan_to_max: NaN becomes max_depth before that.  want_plane:
-    also the float32 [N, H, W] planes of the coded depth.  out: the codes' tensor to fill.  Only enqueues, on `stream`."""
-    import torch
-    from metric_depth_video_toolbox_amd import _lib, step_clip
-    if not (float(max_depth) > 0):
-        raise ValueError("max_depth must be > 0")
-    _lib.check_tensor("planes", planes, torch.float32, ndim=3, packed=1, disjoint=True)
-    N, h, w = step_clip.non_empty("planes", planes, "value")
-    W, H = (w, h) if out_size is None else step_clip.size_arg(out_size, "out_size")
-    dev = planes.device
-    if scale is not None:
-        _lib.check_tensor("scale", scale, torch.float32, device=dev, contiguous=True)
-        if scale.numel() != 1:
-            raise ValueError(f"scale must hold one value, got shape {tuple(scale.shape)}")
-    s = step_clip.stream_or_current(dev, stream)
-    with torch.cuda.stream(s):
-        codes = torch.empty((N, H, W, 3), dtype=torch.uint8, device=dev) if out is None else out
-        plane = torch.empty((N, H, W), dtype=torch.float32, device=dev) if want_plane else None
-    _lib.check_tensor("out", codes, torch.uint8, (N, H, W, 3), device=dev, packed=2, output=True)
-    ctx.call("mdvt_depth_video_codes", w, h, N, planes.data_ptr(), 4 * planes.stride(1), 4 * planes.stride(0),
-             scale.data_ptr() if scale is not None else None, int(bool(nan_to_max)), float(max_depth), W, H,
-             codes.data_ptr(), codes.stride(1), codes.stride(0), int(bool(bgr)),
-             plane.data_ptr() if want_plane else None, 4 * W, 4 * W * H, _lib.stream_arg(dev, s))
-    return (codes, plane) if want_plane else codes
+from metric_depth_video_toolbox_amd.step_device import depth_video_codes      # noqa: E402
 
 
 def batch_scale(earlier, again):

@@ -22,93 +22,15 @@ the codes as their factor, with no read-back: the `* s` that mvs:297 comments ou
 intent ("Not sure if this is right rescaling", mvs:259), not the reference's output.  --save_cost_volume_scales reads the clip's
 medians back once, at its end.
 
-The three entry points of include/mdvt_mvsa.h are bound in _lib.py and have no wrapper in the package yet (their tensor contract
-records are the follow-up), so this tool hands the tensors over itself, as tools/depth_engine_video.py does."""
+bilinear_model_frames, nearest_depth_codes and ratio_median, the wrappers of include/mdvt_mvsa.h's three entry points, are
+metric_depth_video_toolbox_amd/step_device.py's; they stay reachable under this module's name."""
 import os
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 
-
-def bilinear_model_frames(ctx, frames, out_size=None, *, bgr=False, out=None, stream=None):
-    """mdvt_bilinear_model_frames on uint8 CUDA frames [N, H, W, 3] (rows and frames may be strided; B, G, R with bgr) -> the float32
-    planar tensor [N, 3, h, w] in R, G, B plane order at out_size = (w, h) (default: the frames' own size): v / 255 through torch's
-    bilinear resize, unfused.  out: the tensor to fill (rows, planes and frames may be strided).  Only enqueues, on `stream`."""
-    import torch
-    from metric_depth_video_toolbox_amd import _lib, step_clip
-    _lib.check_tensor("frames", frames, torch.uint8, (None, None, None, 3), packed=2, disjoint=True)
-    N, H, W = step_clip.non_empty("frames", frames, "pixel")
-    w, h = (W, H) if out_size is None else step_clip.size_arg(out_size, "out_size")
-    dev = frames.device
-    s = step_clip.stream_or_current(dev, stream)
-    if out is None:
-        with torch.cuda.stream(s):
-            out = torch.empty((N, 3, h, w), dtype=torch.float32, device=dev)
-    _lib.check_tensor("out", out, torch.float32, (N, 3, h, w), device=dev, packed=1, output=True)
-    ctx.call("mdvt_bilinear_model_frames", W, H, N, frames.data_ptr(), frames.stride(1), frames.stride(0), int(bool(bgr)), w, h,
-             out.data_ptr(), 4 * out.stride(2), 4 * out.stride(1), 4 * out.stride(0), _lib.stream_arg(dev, s))
-    return out
-
-
-def nearest_depth_codes(ctx, planes, mid_size, max_depth, out_size, *, scale=None, bgr=False, want_plane=False, out=None, stream=None):
-    """mdvt_nearest_depth_codes on float32 CUDA planes [N, h, w] (rows and frames may be strided) -> the uint8 [N, H, W, 3] codes of a
-    depth video at out_size = (W, H), sampled through two nearest maps, first to mid_size = (w_cv, h_cv).  scale: a float32 CUDA tensor
-    of one factor for all frames or of N, read on the device.  want_plane: also the float32 [N, H, W] planes of the coded depth.
-    out: the codes' tensor to fill.  Only enqueues, on `stream`."""
-    import torch
-    from metric_depth_video_toolbox_amd import _lib, step_clip
-    if not (float(max_depth) > 0):
-        raise ValueError("max_depth must be > 0")
-    _lib.check_tensor("planes", planes, torch.float32, ndim=3, packed=1, disjoint=True)
-    N, h, w = step_clip.non_empty("planes", planes, "value")
-    (mw, mh), (W, H) = (int(v) for v in mid_size), (int(v) for v in out_size)
-    if min(mw, mh, W, H) < 1:
-        raise ValueError(f"mid_size and out_size must be (width, height) with both at least 1, got {mid_size!r}, {out_size!r}")
-    dev = planes.device
-    scale_stride = 0
-    if scale is not None:
-        _lib.check_tensor("scale", scale, torch.float32, device=dev, contiguous=True)
-        if scale.numel() not in (1, N):
-            raise ValueError(f"scale must hold one value or one per frame, got shape {tuple(scale.shape)}")
-        scale_stride = 4 if scale.numel() == N and N > 1 else 0
-    s = step_clip.stream_or_current(dev, stream)
-    with torch.cuda.stream(s):
-        codes = torch.empty((N, H, W, 3), dtype=torch.uint8, device=dev) if out is None else out
-        plane = torch.empty((N, H, W), dtype=torch.float32, device=dev) if want_plane else None
-    _lib.check_tensor("out", codes, torch.uint8, (N, H, W, 3), device=dev, packed=2, output=True)
-    ctx.call("mdvt_nearest_depth_codes", w, h, N, planes.data_ptr(), 4 * planes.stride(1), 4 * planes.stride(0), mw, mh,
-             scale.data_ptr() if scale is not None else None, scale_stride, float(max_depth), W, H,
-             codes.data_ptr(), codes.stride(1), codes.stride(0), int(bool(bgr)),
-             plane.data_ptr() if want_plane else None, 4 * W, 4 * W * H, _lib.stream_arg(dev, s))
-    return (codes, plane) if want_plane else codes
-
-
-def ratio_median(ctx, cv, ref, mask=None, *, want_counts=False, out=None, stream=None):
-    """mdvt_ratio_median on float32 CUDA planes cv [N, h_cv, w_cv] and ref [N, h_ref, w_ref] and an optional uint8 CUDA mask
-    [N, h_m, w_m] (non-zero = true) -> the float32 [N] lower medians of the valid ratios cv / (ref + 1e-6), 1.0 where none is valid,
-    and with want_counts the int32 [N] counts.  out: the float32 [N] tensor to fill.  Only enqueues, on `stream`."""
-    import torch
-    from metric_depth_video_toolbox_amd import _lib, step_clip
-    _lib.check_tensor("cv", cv, torch.float32, ndim=3, packed=1, disjoint=True)
-    N = int(cv.shape[0])
-    dev = cv.device
-    _lib.check_tensor("ref", ref, torch.float32, (N, None, None), device=dev, packed=1, disjoint=True)
-    if N < 1 or min(cv.shape[1:]) < 1 or min(ref.shape[1:]) < 1:
-        raise ValueError(f"cv or ref holds no value: shapes {tuple(cv.shape)}, {tuple(ref.shape)}")
-    if mask is not None:
-        _lib.check_tensor("mask", mask, torch.uint8, (N, None, None), device=dev, packed=1, disjoint=True)
-        step_clip.non_empty("mask", mask, "value")
-    s = step_clip.stream_or_current(dev, stream)
-    with torch.cuda.stream(s):
-        median = torch.empty((N,), dtype=torch.float32, device=dev) if out is None else out
-        counts = torch.empty((N,), dtype=torch.int32, device=dev) if want_counts else None
-    _lib.check_tensor("out", median, torch.float32, (N,), device=dev, contiguous=True, output=True)
-    m = (int(mask.shape[2]), int(mask.shape[1]), mask.data_ptr(), mask.stride(1), mask.stride(0)) if mask is not None else (0, 0, None, 0, 0)
-    ctx.call("mdvt_ratio_median", N, int(cv.shape[2]), int(cv.shape[1]), cv.data_ptr(), 4 * cv.stride(1), 4 * cv.stride(0),
-             int(ref.shape[2]), int(ref.shape[1]), ref.data_ptr(), 4 * ref.stride(1), 4 * ref.stride(0), *m,
-             median.data_ptr(), counts.data_ptr() if want_counts else None, _lib.stream_arg(dev, s))
-    return (median, counts) if want_counts else median
+from metric_depth_video_toolbox_amd.step_device import bilinear_model_frames, nearest_depth_codes, ratio_median      # noqa: E402
 
 
 def checked_prediction(got):
