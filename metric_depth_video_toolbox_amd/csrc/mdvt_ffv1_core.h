@@ -1,12 +1,15 @@
-// mdvt_ffv1_core.h -- the parts of FFV1 (RFC 9043) that the device encoder (mdvt_ffv1.hip), the two device decode kernels
-// (mdvt_ffv1_decode.hip, mdvt_ffv1_stream_decode.hip), the C ABI (mdvt_api.hip) and the host test programs share: the tables, the
-// CRC algebra, the slice-table walk, the configuration record's parser and the decoder of one slice.  Plain C++: it compiles for
-// the host alone (g++, where the tests run it under the sanitizers) and for host + device under hipcc; no HIP intrinsic, no
-// allocation, no recursion.
+// mdvt_ffv1_core.h -- the project's one definition of the FFV1 (RFC 9043) primitives: the tables, the CRC, the range decoder and
+// its integer binarisation, the bit reader, the Golomb-Rice symbol reader with its context state, the run-length exponents, the
+// predictor, the pixel stores, the slice-table walk and the key-frame bit.  The host codec (csrc_host/, libmdvt_video.so), the device
+// encoder (mdvt_ffv1.hip), the two device decode kernels (mdvt_ffv1_decode.hip, mdvt_ffv1_stream_decode.hip), the C ABI
+// (mdvt_api.hip) and the host test programs are all built on it.  Plain C++: it compiles for the host alone (g++, where the tests
+// run it under the sanitizers) and for host + device under hipcc; no HIP intrinsic, no recursion, and no allocation.  What is
+// marked (host) is not compiled for the device.
 //
-// The decoder side restates csrc_host/mdvt_video.cpp (RacDec, BitReader, get_symbol, get_vlc_symbol, Decoder::decode_frame /
-// decode_slice) for version 3, RGB (JPEG 2000 RCT), 8 bits, no alpha, the default 666-context quantisation tables.  There is one
-// record parser and one slice decoder, SliceDec; the two entry points ask them for different classes of that format:
+// On top of the primitives it holds the device's decoder: SliceDec and parse_stream_class, for version 3, RGB (JPEG 2000 RCT) or
+// YCbCr, 8 bits, no alpha, the default 666-context quantisation tables.  The host's decoder (csrc_host/mdvt_ffv1_dec.cpp) is the
+// general one -- any quantisation tables, initial states, alpha, versions 0 and 1 -- over the same primitives, and every GPU decode
+// test holds SliceDec to its bytes.  The two entry points ask the record parser and SliceDec for different classes of the format:
 //   intra    (mdvt_decode_video_frames)   the range coder with the default state table, key frames only: every slice of every
 //                                         frame starts from fresh context state
 //   stream   (mdvt_decode_video_stream)   Golomb-Rice or the range coder, key and inter frames: the context state carries from
@@ -39,7 +42,7 @@ constexpr int kMaxSlices = 1024;                           // slices per frame t
 // mdvt_decode_video_stream's alone (include/mdvt_ffv1_stream_decode.h)
 enum : uint32_t { kOk = 0, kCrcMismatch = 1, kBadSliceHeader = 2, kDamaged = 3, kBadPacket = 4, kNoKeyFrame = 5, kBrokenRun = 6 };
 
-// FFmpeg's quant11 (the host's quant11_of): the 11-level quantisation of (difference & 0xFF), with the i == 128 entry at -5
+// FFmpeg's quant11 (ffv1enc.c): the 11-level quantisation of (difference & 0xFF), with the i == 128 entry at -5
 MDVT_HD int quant11(int i)
 {
     const int d = i < 128 ? i : i - 256;
@@ -54,7 +57,8 @@ MDVT_HD int median3(int a, int b, int c)
     return a > b ? (b > c ? b : (a > c ? c : a)) : (a > c ? a : (b > c ? c : b));
 }
 
-// the default state-transition table (RFC 9043 section 3.8.1.3), built as the host encoder builds it
+// the default state-transition table (RFC 9043 section 3.8.1.3), generated the way FFmpeg's ff_build_rac_states(0.05 * 2^32, 256 - 8)
+// generates it; tests/test_ffv1_cpu.py checks it against the RFC's table
 inline void default_states(uint8_t* zero, uint8_t* one_state)
 {
     const long long one = 1LL << 32;
@@ -82,12 +86,45 @@ inline void default_states(uint8_t* zero, uint8_t* one_state)
     for (int k = 1; k < 255; ++k) zero[k] = (uint8_t)(256 - one_state[256 - k]);
 }
 
+// (host) RacDec's table, next[s] = zero_state[s] | one_state[s] << 8, of the default states
+inline const uint16_t* default_next_states()
+{
+    static const struct Table {
+        uint16_t next[256];
+        Table()
+        {
+            uint8_t zero[256], one[256];
+            default_states(zero, one);
+            for (int k = 0; k < 256; ++k) next[k] = (uint16_t)(zero[k] | (one[k] << 8));
+        }
+    } table;
+    return table.next;
+}
+
+// (host) ... and of a stream's own one_state[1 .. 255] (coder_type 2): zero_state[s] = 256 - one_state[256 - s]
+inline void custom_next_states(const uint8_t* one_state, uint16_t* next)
+{
+    next[0] = (uint16_t)(one_state[0] << 8);
+    for (int k = 1; k < 256; ++k) next[k] = (uint16_t)((uint8_t)(256 - one_state[256 - k]) | (one_state[k] << 8));
+}
+
 // ---- CRC-32, generator 0x04C11DB7, most significant bit first, initial value 0, no final XOR ----
 MDVT_HD uint32_t crc_table_entry(uint32_t k)
 {
     uint32_t v = k << 24;
     for (int b = 0; b < 8; ++b) v = (v << 1) ^ ((v & 0x80000000u) ? 0x04C11DB7u : 0u);
     return v;
+}
+
+// (host) the CRC of n more bytes, through the table of crc_table_entry
+inline uint32_t crc32_msb(uint32_t crc, const uint8_t* p, size_t n)
+{
+    static const struct Table {
+        uint32_t t[256];
+        Table() { for (uint32_t k = 0; k < 256; ++k) t[k] = crc_table_entry(k); }
+    } table;
+    for (size_t i = 0; i < n; ++i) crc = (crc << 8) ^ table.t[(crc >> 24) ^ p[i]];
+    return crc;
 }
 
 // a(x) * b(x) mod P(x), P = 0x104C11DB7, most significant bit = highest power
@@ -133,13 +170,24 @@ MDVT_HD uint32_t walk_slices(Byte byte, uint32_t size, int n, int ec, uint32_t* 
     return end ? kBadPacket : kOk;                                               // "stray bytes before the first slice"
 }
 
-// ---- the range decoder (the host's RacDec) over a byte source: Src::byte(k) for k < avail ----
+// ---- the range decoder over a byte source: Src::byte(k) for k < avail ----
 template <class Src>
 struct RacDec {
     Src src;
     uint32_t pos, end;             // next byte, and the first byte that reads as zero
     int low, range, overread;
     const uint16_t* next;          // next[s] = zero_state[s] | one_state[s] << 8: one lookup per decision, whatever the bit
+
+    // (host) starts the coder on the `size` bytes of s: false when there are fewer than two.  (SliceDec::begin does the same by hand,
+    // as the first slice's coder starts on the whole packet)
+    bool init(Src s, uint32_t size, const uint16_t* next_)
+    {
+        if (size < 2u) return false;
+        src = s; next = next_; pos = 2; end = size; range = 0xFF00; overread = 0;
+        low = ((int)s.byte(0) << 8) | (int)s.byte(1);
+        if (low >= 0xFF00) { low = 0xFF00; end = 2; }
+        return true;
+    }
 
     MDVT_HD int get(uint8_t* state)
     {
@@ -186,7 +234,7 @@ MDVT_HD int key_frame_bit(uint8_t b0, uint8_t b1)
 
 MDVT_HD int clz32(uint32_t v) { return v ? __builtin_clz(v) : 32; }
 
-// The host's BitReader over a byte source: bits [0, 8 * nbytes) of the bytes from `base` on, most significant bit first; every bit
+// The bit reader over a byte source: bits [0, 8 * nbytes) of the bytes from `base` on, most significant bit first; every bit
 // past them is zero.  A 64-bit accumulator holds the next `n` bits at its top, refilled a byte at a time through Src::byte (which
 // keeps its own window of aligned words on the device).
 template <class Src>
@@ -225,7 +273,7 @@ struct BitReader {
     }
 };
 
-// one context of the Golomb-Rice coder (the host's VlcState)
+// one context of the Golomb-Rice coder; vlc_reset gives its initial value
 struct VlcState { int16_t drift; uint16_t error_sum; int8_t bias; uint8_t count; };
 constexpr int kVlcBytes = kContexts * (int)sizeof(VlcState);       // one set: 666 x 6 bytes
 MDVT_HD void vlc_reset(VlcState* v) { v->drift = 0; v->error_sum = 4; v->bias = 0; v->count = 1; }
@@ -256,7 +304,7 @@ MDVT_HD int get_sr_golomb(BitReader<Src>& gb, int k, Stats& stats)
     return (int)(v >> 1) ^ -(int)(v & 1u);
 }
 
-// the host's get_vlc_symbol with update_vlc_state, for samples of kBits bits
+// one Golomb-Rice coded sample difference of kBits bits, with update_vlc_state
 template <int kBits, class Src, class Stats>
 MDVT_HD int get_vlc_symbol(BitReader<Src>& gb, VlcState* st, Stats& stats)
 {
@@ -294,7 +342,8 @@ MDVT_HD void store_rct_pixel(int y, int cb, int cr, uint8_t* o, int ri, int gi, 
     o[ri] = (uint8_t)r; o[gi] = (uint8_t)g; o[bi] = (uint8_t)b;
 }
 
-// YCbCr -> the bytes o[ri], o[gi], o[bi] as include/mdvt_video.h decrees it (BT.601 limited range, the host's store_ycbcr_pixel)
+// YCbCr -> the bytes o[ri], o[gi], o[bi] as include/mdvt_video.h decrees it: BT.601 limited range in integers (a decree of this
+// project's, not a claim about swscale's bits)
 MDVT_HD uint8_t clip8(int v) { return (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v); }
 MDVT_HD void store_ycbcr_pixel(int y, int u, int v, uint8_t* o, int ri, int gi, int bi)
 {
@@ -507,17 +556,11 @@ struct StreamClass { int version, micro, nh, nv, ec, coder, intra, planar, hs, v
 inline const char* parse_stream_class(const uint8_t* data, size_t size, bool stream, StreamClass* out)
 {
     if (!data || size < 6 || size > (1u << 20)) return "configuration record: missing or of an impossible size";
-    uint32_t crc = 0;
-    for (size_t i = 0; i < size; ++i) crc = (crc << 8) ^ crc_table_entry((crc >> 24) ^ data[i]);
-    uint8_t zero[256], one[256], state[32];
-    uint16_t next[256];
-    default_states(zero, one);
-    for (int k = 0; k < 256; ++k) next[k] = (uint16_t)(zero[k] | (one[k] << 8));
+    const uint32_t crc = crc32_msb(0, data, size);
+    uint8_t state[32];
     for (int k = 0; k < 32; ++k) state[k] = 128;
     RacDec<PtrSrc> c;
-    c.src = PtrSrc{data}; c.next = next; c.range = 0xFF00; c.overread = 0; c.pos = 2; c.end = (uint32_t)size;
-    c.low = (data[0] << 8) | data[1];
-    if (c.low >= 0xFF00) { c.low = 0xFF00; c.end = 2; }
+    c.init(PtrSrc{data}, (uint32_t)size, default_next_states());
     bool bad = false;
     const int version = c.symbol(state, false, &bad);
     if (bad || version != 3) return "version: only FFV1 version 3 is decoded on the device";
@@ -552,7 +595,7 @@ inline const char* parse_stream_class(const uint8_t* data, size_t size, bool str
     const int qcount = c.symbol(state, false, &bad);
     if (bad || qcount != 1) return "quant_table_set_count: only one quantisation table set is decoded on the device";
     int scale = 1;
-    for (int t = 0; t < 5; ++t) {                            // the host's read_quant_tables, compared with the default set
+    for (int t = 0; t < 5; ++t) {                            // the host decoder's read_quant_tables, compared with the default set
         uint8_t qs[32];
         for (int k = 0; k < 32; ++k) qs[k] = 128;
         int i = 0, v = 0;

@@ -1,6 +1,6 @@
 """FFV1-in-Matroska files, the reference's on-disk format (cv2.VideoCapture / cv2.VideoWriter with fourcc 'FFV1',
 stereo_rerender.py:326-341, 426-444, 941; depth_frames_helper.py:125-161): ctypes binding of libmdvt_video.so
-(include/mdvt_video.h, csrc_host/mdvt_video.cpp -- host C++, written from RFC 9043 / RFC 9559; no FFmpeg in the image).
+(include/mdvt_video.h, csrc_host/ -- host C++, written from RFC 9043 / RFC 9559; no FFmpeg in the image).
 
     with VideoReader("x_depth.mkv") as r:            # frames come back as H x W x 3 uint8, RGB unless bgr=True
         for frame in r: ...

@@ -313,8 +313,8 @@ def test_the_bench_tools_writer_is_byte_identical_to_the_reference(tmp_path):
     if not gxx:
         pytest.skip("no g++")
     exe = str(tmp_path / "ffv1_ycbcr_writer")
-    subprocess.check_call([gxx, "-O1", "-std=c++17", "-pthread", "-Wno-subobject-linkage", "-I", os.path.join(REPO, "include"), "-o", exe,
-                           os.path.join(REPO, "tools", "ffv1_ycbcr_writer.cpp")])
+    subprocess.check_call([gxx, "-O1", "-std=c++17", "-pthread", "-Wno-subobject-linkage", "-I", os.path.join(REPO, "include"), "-I", os.path.join(REPO, "metric_depth_video_toolbox_amd", "csrc"), "-o", exe,
+                           os.path.join(REPO, "tools", "ffv1_ycbcr_writer.cpp"), os.path.join(REPO, "metric_depth_video_toolbox_amd", "csrc_host", "mdvt_ffv1_enc.cpp")])
     raw, out = str(tmp_path / "planes.raw"), str(tmp_path / "packets.bin")
     for pix, (hs, vs) in yr.PIX_FMTS.items():
         for W, H, nh, nv in ((64, 48, 2, 2), (33, 21, 1, 1), (33, 21, 2, 2)):

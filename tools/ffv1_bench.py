@@ -130,7 +130,9 @@ def ycbcr_stream(frames, pix_fmt, slices, tmp):
     exe = os.path.join(tmp, "ffv1_ycbcr_writer")
     if not os.path.exists(exe):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-pthread", "-Wno-subobject-linkage", "-I", os.path.join(os.path.dirname(here), "include"),
-                               "-o", exe, os.path.join(here, "ffv1_ycbcr_writer.cpp")])
+                               "-I", os.path.join(os.path.dirname(here), "metric_depth_video_toolbox_amd", "csrc"), "-o", exe,
+                               os.path.join(here, "ffv1_ycbcr_writer.cpp"),
+                               os.path.join(os.path.dirname(here), "metric_depth_video_toolbox_amd", "csrc_host", "mdvt_ffv1_enc.cpp")])
     hs, vs = PIX_SHIFTS[pix_fmt]
     N, H, W = frames.shape[:3]
     if any((sx * W // slices[0]) % (1 << hs) for sx in range(slices[0])) or any((sy * H // slices[1]) % (1 << vs) for sy in range(slices[1])):

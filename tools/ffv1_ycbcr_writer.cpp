@@ -1,27 +1,29 @@
 // tools/ffv1_ycbcr_writer.cpp -- makes YCbCr FFV1 streams at full size in reasonable time, for measurements (tools/ffv1_bench.py
 // --pix-fmt): version 3.4, Golomb-Rice with run mode, intra = 0, a key frame every `gop` frames, CRC-32 parities, 8 bits, chroma
 // subsampled by 2^hs x 2^vs -- the class FFmpeg writes by default for a movie.  NOT a product writer: the library writes RGB only.
-// It reuses the library's own coder parts (range coder, bit writer, Golomb-Rice states, quantisation tables, CRC) by including its
-// source, and is byte for byte tests/ffv1_ycbcr_ref.py's Encoder (tests/test_ffv1_ycbcr_cpu.py).
+// It is built on the library's own encoder parts (mdvt_ffv1_host.h: the Golomb-Rice slice start, line encoder and slice closing,
+// compiled together with csrc_host/mdvt_ffv1_enc.cpp), and is byte for byte tests/ffv1_ycbcr_ref.py's Encoder
+// (tests/test_ffv1_ycbcr_cpu.py).
 //
 //   ffv1_ycbcr_writer <planes file> <W> <H> <frames> <hs> <vs> <nh> <nv> <gop> <out file>
 // planes file: per frame the Y plane (W x H bytes), then Cb and Cr (ceil(W / 2^hs) x ceil(H / 2^vs) bytes each)
 // out file:    u32 bytes of the configuration record, the record, then per frame u32 bytes of the packet and the packet
-#include "../metric_depth_video_toolbox_amd/csrc_host/mdvt_video.cpp"
+#include "../metric_depth_video_toolbox_amd/csrc_host/mdvt_ffv1_host.h"
+
+#include <stdlib.h>
+
+using namespace mdvt_host;
 
 namespace {
 
 struct PlaneView { const uint8_t* p; int w, h; size_t pitch; };
 
+// one plane of a slice: 8-bit samples, the run index restarting with the plane
 void encode_plane(BitWriter& bw, std::vector<VlcState>& vlc, const PlaneView& pl, std::vector<int16_t>& buf)
 {
     std::fill(buf.begin(), buf.end(), (int16_t)0);
     int16_t* sample[2] = {buf.data() + 3, buf.data() + buf.size() / 2 + 3};
-    const LineCtx lc{g_enc_tables.q, false};
     int run_index = 0;
-    auto flush_run = [&](int& run_count) {
-        while (run_count >= (1 << kLog2Run[run_index])) { run_count -= 1 << kLog2Run[run_index]; if (run_index < 40) ++run_index; bw.put(1, 1); }
-    };
     for (int y = 0; y < pl.h; ++y) {
         std::swap(sample[0], sample[1]);
         int16_t* cur = sample[1];
@@ -30,28 +32,7 @@ void encode_plane(BitWriter& bw, std::vector<VlcState>& vlc, const PlaneView& pl
         for (int x = 0; x < pl.w; ++x) cur[x] = src[x];
         cur[-1] = last[0];
         last[pl.w] = last[pl.w - 1];
-        int run_count = 0, run_mode = 0;
-        for (int x = 0; x < pl.w; ++x) {
-            int context = get_context(lc, cur + x, last + x, cur + x);
-            int diff = cur[x] - median3(cur[x - 1], last[x], cur[x - 1] + last[x] - last[x - 1]);
-            if (context < 0) { context = -context; diff = -diff; }
-            diff = fold(diff, 8);
-            if (context == 0) run_mode = 1;
-            if (run_mode) {
-                if (diff) {
-                    flush_run(run_count);
-                    bw.put(1 + kLog2Run[run_index], (uint32_t)run_count);
-                    if (run_index) --run_index;
-                    run_count = 0; run_mode = 0;
-                    if (diff > 0) --diff;
-                } else ++run_count;
-            }
-            if (run_mode == 0) put_vlc_symbol(bw, vlc[(size_t)context], diff, 8);
-        }
-        if (run_mode) {
-            flush_run(run_count);
-            if (run_count) bw.put(1, 1);
-        }
+        encode_line_golomb<8>(bw, vlc.data(), cur, last, pl.w, run_index);
     }
 }
 
@@ -83,32 +64,18 @@ int main(int argc, char** argv)
             const int x0 = (int)((int64_t)sx * W / nh), y0 = (int)((int64_t)sy * H / nv);
             const int sw = (int)((int64_t)(sx + 1) * W / nh) - x0, sh = (int)((int64_t)(sy + 1) * H / nv) - y0;
             if ((x0 & ((1 << hs) - 1)) || (y0 & ((1 << vs) - 1))) { fprintf(stderr, "slice grid off the chroma grid\n"); return 2; }
-            RacEnc c;
-            c.init();
-            c.ensure(1024);
-            if (i == 0) { uint8_t keystate = 128; c.put(&keystate, key ? 1 : 0); }
-            uint8_t hstate[kContextSize];
-            memset(hstate, 128, sizeof hstate);
-            const int header[9] = {sx, sy, 0, 0, 0, 0, 3, 0, 0};
-            for (int v : header) put_symbol(c, hstate, v, false);
-            c.terminate(true);
+            std::vector<uint8_t> sl = golomb_slice_start(sx, sy, i == 0, key);
             GolombSliceState& ss = states[(size_t)i];
-            if (key || ss.vlc[0].empty())
-                for (auto& v : ss.vlc) v.assign((size_t)g_enc_tables.context_count, VlcState());
+            begin_golomb_run(ss, key);
             BitWriter bw;
             const int cw = (sw + (1 << hs) - 1) >> hs, ch = (sh + (1 << vs) - 1) >> vs;
             encode_plane(bw, ss.vlc[0], PlaneView{Y.data() + (size_t)y0 * W + x0, sw, sh, (size_t)W}, buf);
             for (int p = 0; p < 2; ++p)
                 encode_plane(bw, ss.vlc[1], PlaneView{C[p].data() + (size_t)(y0 >> vs) * CW + (x0 >> hs), cw, ch, (size_t)CW}, buf);
             bw.flush();
-            std::vector<uint8_t> sl = c.out;
             sl.insert(sl.end(), bw.out.begin(), bw.out.end());
-            const size_t payload = sl.size();
-            if (payload >= (1u << 24)) { fprintf(stderr, "a slice of %zu bytes: use more slices\n", payload); return 2; }
-            sl.push_back((uint8_t)(payload >> 16)); sl.push_back((uint8_t)(payload >> 8)); sl.push_back((uint8_t)payload);
-            sl.push_back(0);
-            const uint32_t crc = crc32_msb(0, sl.data(), sl.size());
-            sl.push_back((uint8_t)(crc >> 24)); sl.push_back((uint8_t)(crc >> 16)); sl.push_back((uint8_t)(crc >> 8)); sl.push_back((uint8_t)crc);
+            if (sl.size() >= (1u << 24)) { fprintf(stderr, "a slice of %zu bytes: use more slices\n", sl.size()); return 2; }
+            close_slice(sl);
             packet.insert(packet.end(), sl.begin(), sl.end());
         }
         const uint32_t ps = (uint32_t)packet.size();
