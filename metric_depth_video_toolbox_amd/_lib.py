@@ -72,6 +72,10 @@ LANCZOS_AUTO, LANCZOS_FUSED, LANCZOS_TWO_LAUNCH = 0, 1, 2
 # the masked median ratio), likewise.  Their wrappers are step_device.bilinear_model_frames, nearest_depth_codes and ratio_median
 MVSA_SYMBOLS = ("mdvt_bilinear_model_frames", "mdvt_nearest_depth_codes", "mdvt_ratio_median")
 
+# the entry points include/mdvt_scene.h declares (the frame difference sums behind scene detection), likewise.  The wrapper is
+# tools/scene_detect.py's frame_sums
+SCENE_SYMBOLS = ("mdvt_scene_frame_sums", "mdvt_scene_vector_path")
+
 
 class MdvtError(RuntimeError):
     def __init__(self, code: int, text: str):
@@ -259,6 +263,10 @@ def load():
     L.mdvt_ratio_median.restype = C.c_int
     L.mdvt_ratio_median.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, st, st, C.c_int, C.c_int, vp, st, st, C.c_int, C.c_int, vp, st, st,
                                     vp, vp, vp]
+    L.mdvt_scene_frame_sums.restype = C.c_int
+    L.mdvt_scene_frame_sums.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, st, st, C.c_int, vp, st, C.c_int, vp, vp]
+    L.mdvt_scene_vector_path.restype = C.c_int
+    L.mdvt_scene_vector_path.argtypes = [C.c_int, vp, st, st, vp, st, C.c_int]
     L.mdvt_adapter_prepare_eye.restype = C.c_int
     L.mdvt_adapter_prepare_eye.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, st, st, vp, st, st, C.c_int, C.c_int, vp, st, st, vp, st, st, vp, vp]
     L.mdvt_lhm_moments.restype = C.c_int

@@ -1,6 +1,6 @@
 // mdvt_context.h -- what the host units of the C ABI share: the context (mdvt_ctx), its error text, its device memory (the
 // process-wide pools of mdvt_context.hip, the scratch blocks and their one growth rule) and a few facts read off its
-// configuration.  Host only: included by mdvt_context.hip, mdvt_api_render.hip, mdvt_api.hip, mdvt_api_depth_engines.hip, mdvt_api_video_mask.hip and mdvt_api_mvsa.hip, never by a unit that defines kernels.
+// configuration.  Host only: included by mdvt_context.hip, mdvt_api_render.hip, mdvt_api.hip, mdvt_api_depth_engines.hip, mdvt_api_video_mask.hip, mdvt_api_mvsa.hip and mdvt_api_scene.hip, never by a unit that defines kernels.
 #pragma once
 
 #include "mdvt_internal.h"

@@ -371,6 +371,16 @@ hipError_t launch_grow_marks(const uint8_t* marks, size_t marks_pitch, uint8_t* 
 struct AdapterImage { const uint8_t* p; size_t pitch, stride; };   // frame k at p + k * stride; u8 RGB rows unless said otherwise
 struct AdapterResize { int in_w, in_h, out_w, out_h, mode; double rx, ry; };     // mode 0 copy, 1 the 2 x 2 area mean, 2 linear; rx, ry = in / out
 AdapterResize adapter_resize(int in_w, int in_h, int out_w, int out_h);
+// mdvt_scene.hip: the hue, saturation and value difference sums of consecutive frames (mdvt_scene_frame_sums, include/mdvt_scene.h)
+struct SceneArgs {
+    const uint8_t* frames; size_t pitch, stride;                   // n_frames frames of W x H packed pixels
+    const uint8_t* prev; size_t prev_pitch;                        // the frame before them, or null
+    int n_frames, bgr;
+    uint32_t W, gw, units;                                         // vector kernel: groups of 16 pixels per row, groups of a frame; pixel kernel: units = analysed pixels
+    AdapterResize rs;                                              // frame -> analysed image (mode 0 where factor is 1)
+    unsigned long long* sums;                                      // the caller's [pairs][3], zeroed before the launch
+};
+hipError_t launch_scene_sums(const SceneArgs& a, bool vec, hipStream_t s);
 struct AdapterPrepareArgs {
     AdapterImage color, mask;                                      // the eye's half of the side-by-side frames (p at the eye's first column)
     int mirror;                                                    // the eye is read right to left
