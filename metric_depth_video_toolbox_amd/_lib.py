@@ -76,6 +76,11 @@ MVSA_SYMBOLS = ("mdvt_bilinear_model_frames", "mdvt_nearest_depth_codes", "mdvt_
 # tools/scene_detect.py's frame_sums
 SCENE_SYMBOLS = ("mdvt_scene_frame_sums", "mdvt_scene_vector_path")
 
+# the entry points include/mdvt_megasam.h declares (cv2's area resize, torch's nearest-exact and bilinear resizes into the camera
+# tracker, its planes out to video frames), likewise.  Their wrappers are tools/megasam_device.py's
+MEGASAM_SYMBOLS = ("mdvt_area_model_frames", "mdvt_megasam_vector_path", "mdvt_tracker_depth", "mdvt_tracker_mask", "mdvt_tracker_outputs")
+TRACKER_DEPTH_VIDEO, TRACKER_GREY_VIDEO = 0, 1
+
 
 class MdvtError(RuntimeError):
     def __init__(self, code: int, text: str):
@@ -267,6 +272,16 @@ def load():
     L.mdvt_scene_frame_sums.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, st, st, C.c_int, vp, st, C.c_int, vp, vp]
     L.mdvt_scene_vector_path.restype = C.c_int
     L.mdvt_scene_vector_path.argtypes = [C.c_int, vp, st, st, vp, st, C.c_int]
+    L.mdvt_area_model_frames.restype = C.c_int
+    L.mdvt_area_model_frames.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, st, st, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, st, st, st, vp]
+    L.mdvt_megasam_vector_path.restype = C.c_int
+    L.mdvt_megasam_vector_path.argtypes = [C.c_int, C.c_int, vp, st, st]
+    L.mdvt_tracker_depth.restype = C.c_int
+    L.mdvt_tracker_depth.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, st, st, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, vp, st, st, vp]
+    L.mdvt_tracker_mask.restype = C.c_int
+    L.mdvt_tracker_mask.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, st, st, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, st, st, vp]
+    L.mdvt_tracker_outputs.restype = C.c_int
+    L.mdvt_tracker_outputs.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, st, st, C.c_double, C.c_int, C.c_int, vp, st, st, C.c_int, vp]
     L.mdvt_adapter_prepare_eye.restype = C.c_int
     L.mdvt_adapter_prepare_eye.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, st, st, vp, st, st, C.c_int, C.c_int, vp, st, st, vp, st, st, vp, vp]
     L.mdvt_lhm_moments.restype = C.c_int

@@ -1,10 +1,11 @@
 // mdvt_context.h -- what the host units of the C ABI share: the context (mdvt_ctx), its error text, its device memory (the
 // process-wide pools of mdvt_context.hip, the scratch blocks and their one growth rule) and a few facts read off its
-// configuration.  Host only: included by mdvt_context.hip, mdvt_api_render.hip, mdvt_api.hip, mdvt_api_depth_engines.hip, mdvt_api_video_mask.hip, mdvt_api_mvsa.hip and mdvt_api_scene.hip, never by a unit that defines kernels.
+// configuration.  Host only: included by mdvt_context.hip, mdvt_api_render.hip, mdvt_api.hip, mdvt_api_depth_engines.hip, mdvt_api_video_mask.hip, mdvt_api_mvsa.hip, mdvt_api_scene.hip and mdvt_api_megasam.hip, never by a unit that defines kernels.
 #pragma once
 
 #include "mdvt_internal.h"
 #include "mdvt_lanczos_table.h"
+#include "mdvt_area_table.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -62,6 +63,7 @@ enum ScratchId {
     SCR_LANCZOS_TABLES,               // include/mdvt_video_mask.h: the resampler's bounds and coefficient tables of the latest size pair (ctx->lanczos_resident)
     SCR_MASK_WS,                      // include/mdvt_video_mask.h: per frame of a launch set the intermediate image of the two-launch form, the resized frame or byte plane, the frame's maximum, table or minimum and maximum
     SCR_MVSA,                         // mdvt_ratio_median: per frame of a launch set the 256 histogram words of a radix pass and the selection's state (1040 B)
+    SCR_AREA_TABLES,                  // include/mdvt_megasam.h: the area resize's first, count and weight tables of the latest size pair (ctx->area_resident)
     SCR_COUNT
 };
 
@@ -126,6 +128,9 @@ struct mdvt_ctx {
     // SCR_LANCZOS_TABLES holds on the device: (in_w, out_w, in_h, out_h), all 0 = none
     std::map<std::pair<int, int>, mdvt::host::LanczosTable> lanczos_tables;
     int lanczos_resident[4] = {0, 0, 0, 0};
+    // cv2's area tables (mdvt_api_megasam.hip), kept and uploaded by the same rule: SCR_AREA_TABLES, (in_w, out_w, in_h, out_h)
+    std::map<std::pair<int, int>, mdvt::host::AreaTable> area_tables;
+    int area_resident[4] = {0, 0, 0, 0};
 };
 
 namespace mdvt::host {

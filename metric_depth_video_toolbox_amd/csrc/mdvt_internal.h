@@ -517,6 +517,38 @@ struct RatioMedianArgs {
     float* median; uint32_t* counts;                               // the caller's, at the set's first frame; counts may be null
 };
 hipError_t launch_ratio_median(const RatioMedianArgs& a, hipStream_t s);
+// mdvt_megasam.hip: cv2's area resize, torch's nearest-exact and bilinear resizes into the camera tracker and its planes out to video
+// frames (include/mdvt_megasam.h)
+constexpr size_t kAreaLds = 65536;                                 // the LDS a workgroup of the area kernel may ask for
+struct AreaAxis {                                                  // one axis' table on the device (mdvt_area_table.h)
+    const int32_t* first; const int32_t* count; const float* w; int ktaps;
+};
+struct AreaFramesArgs {
+    const uint8_t* src; size_t src_pitch, src_stride; int in_w, bgr, src_vec;        // _vec: rows are staged with aligned 16-byte loads
+    AreaAxis x, y;
+    uint8_t* dst; size_t dst_pitch, dst_plane, dst_stride; int out_w, out_h;         // the cropped size
+    int tile_w;                                                    // output columns of a workgroup
+    uint32_t lds_row;                                              // bytes a staged source row may take in LDS (a multiple of 16)
+    int frame0;                                                    // the launch's first frame
+};
+hipError_t launch_area_frames(const AreaFramesArgs& a, int n_frames, hipStream_t s);
+struct TrackerPlaneArgs {                                          // packed frames -> a float32 plane through one of torch's resizes and a crop
+    const uint8_t* src; size_t src_pitch, src_stride; int in_w, in_h, bgr;
+    float scale_x, scale_y;                                        // fl(float(in) / float(mid)) per axis
+    int small;                                                     // the mask: mid_w + mid_h <= 128 (BilinearFramesArgs.small)
+    float divisor;                                                 // the depth: float32(255^4 / max_depth)
+    uint8_t* dst; size_t dst_pitch, dst_stride; int out_w, dst_vec;
+    uint32_t gw, groups;                                           // groups of four pixels per output row and per frame
+    int frame0;
+};
+hipError_t launch_tracker_depth(const TrackerPlaneArgs& a, int n_frames, hipStream_t s);
+hipError_t launch_tracker_mask(const TrackerPlaneArgs& a, int n_frames, hipStream_t s);
+struct TrackerOutArgs {
+    DepthCodesArgs c;                                              // the source planes and the frames (codes); mode 1: resize, ratio_x, ratio_y, fmax = m
+    float scale_x, scale_y;                                        // mode 0: fl(float(in) / float(out)) per axis
+};
+hipError_t launch_tracker_codes(const TrackerOutArgs& a, int n_frames, hipStream_t s);      // mode 0: nearest-exact, clip, the 16-bit code
+hipError_t launch_tracker_grey(const TrackerOutArgs& a, int n_frames, hipStream_t s);       // mode 1: linear resize, clip / m * 255, three equal bytes
 hipError_t launch_selftest(int which, unsigned long long seed, unsigned long long* d_mism, hipStream_t s);
 hipError_t launch_coherence_test(uint32_t* blk, size_t dwords, uint32_t tag, uint32_t* d_xcc, uint32_t* d_out, hipStream_t s);     // (mdvt_selftest.hip; r05 diagnosis)
 

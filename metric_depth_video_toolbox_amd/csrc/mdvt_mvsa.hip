@@ -22,6 +22,7 @@
 #include "mdvt_internal.h"
 #include "mdvt_device.h"
 #include "mdvt_depth_code.h"
+#include "mdvt_torch_resize.h"
 
 namespace mdvt {
 namespace {
@@ -30,6 +31,8 @@ using depth_code::store_plane;
 using depth_code::Quad;
 using depth_code::quad_of;
 using depth_code::codes_out;
+using torch_resize::lin_tap;                                        // the bilinear taps and the two forms of their sum: mdvt_torch_resize.h
+using torch_resize::lin_mix;
 
 // torch's CPU nearest map (include/mdvt_mvsa.h): index x of n_out values -> its source among n_in, scale = fl(float(n_in) / float(n_out))
 __device__ __forceinline__ int near_idx(uint32_t x, float scale, int n_in)
@@ -44,20 +47,6 @@ __device__ __forceinline__ int near_twice(uint32_t x, const NearAxis& ax)
 }
 
 // ---- mdvt_bilinear_model_frames ------------------------------------------------------------------------------------------------
-
-// torch's bilinear source index and weights of output index x along an axis of n_in values (align_corners=False), unfused
-__device__ __forceinline__ void lin_tap(int x, float scale, int n_in, int& i0, int& i1, float& w0, float& w1)
-{
-    float src = scale * ((float)x + 0.5f) - 0.5f;
-    src = src < 0.0f ? 0.0f : src;
-    i0 = src >= (float)(n_in - 1) ? n_in - 1 : (int)src;
-    i1 = i0 + 1 < n_in - 1 ? i0 + 1 : n_in - 1;
-    float lam = src - (float)i0;
-    lam = lam < 0.0f ? 0.0f : lam;
-    lam = lam > 1.0f ? 1.0f : lam;
-    w0 = 1.0f - lam;
-    w1 = lam;
-}
 
 __global__ void __launch_bounds__(256) k_bilinear_frames(BilinearFramesArgs a)
 {
@@ -86,13 +75,7 @@ __global__ void __launch_bounds__(256) k_bilinear_frames(BilinearFramesArgs a)
                 const int shift = 8 * (a.bgr ? 2 - c : c);
                 const float v00 = s_unit[(p00 >> shift) & 0xFFu], v01 = s_unit[(p01 >> shift) & 0xFFu];
                 const float v10 = s_unit[(p10 >> shift) & 0xFFu], v11 = s_unit[(p11 >> shift) & 0xFFu];
-                if (a.small) {                                      // (uniform) torch's kernel for small outputs: four weights, summed in order
-                    v[c][k] = (((wy0 * wx0) * v00 + (wy0 * wx1) * v01) + (wy1 * wx0) * v10) + (wy1 * wx1) * v11;
-                } else {                                            // its kernel otherwise: the two rows, then the column
-                    const float t0 = wx0 * v00 + wx1 * v01;
-                    const float t1 = wx0 * v10 + wx1 * v11;
-                    v[c][k] = wy0 * t0 + wy1 * t1;
-                }
+                v[c][k] = lin_mix(a.small != 0, wy0, wy1, wx0, wx1, v00, v01, v10, v11);
             }
         }
     }
