@@ -81,6 +81,12 @@ SCENE_SYMBOLS = ("mdvt_scene_frame_sums", "mdvt_scene_vector_path")
 MEGASAM_SYMBOLS = ("mdvt_area_model_frames", "mdvt_megasam_vector_path", "mdvt_tracker_depth", "mdvt_tracker_mask", "mdvt_tracker_outputs")
 TRACKER_DEPTH_VIDEO, TRACKER_GREY_VIDEO = 0, 1
 
+# the entry points include/mdvt_inspatio.h declares (the InSpatio-World infill step's masked alignment), likewise.  The wrapper is
+# tools/inspatio_device.py's masked_shift_grid and flow_warp
+INSPATIO_SYMBOLS = ("mdvt_masked_shift_grid", "mdvt_masked_shift_path", "mdvt_flow_warp", "mdvt_inspatio_prepare_eye",
+                    "mdvt_inspatio_model_frames", "mdvt_inspatio_composite_eye")
+SHIFT_PATH_AUTO, SHIFT_PATH_DIRECT, SHIFT_PATH_TRANSFORM = 0, 1, 2
+
 
 class MdvtError(RuntimeError):
     def __init__(self, code: int, text: str):
@@ -282,6 +288,19 @@ def load():
     L.mdvt_tracker_mask.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, st, st, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, st, st, vp]
     L.mdvt_tracker_outputs.restype = C.c_int
     L.mdvt_tracker_outputs.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, st, st, C.c_double, C.c_int, C.c_int, vp, st, st, C.c_int, vp]
+    L.mdvt_masked_shift_grid.restype = C.c_int
+    L.mdvt_masked_shift_grid.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, st, st, vp, st, st, vp, st, st, C.c_int, vp, vp, vp, vp]
+    L.mdvt_inspatio_prepare_eye.restype = C.c_int
+    L.mdvt_inspatio_prepare_eye.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, st, st, vp, st, st, C.c_int, C.c_int, vp, st, st, vp, st, st,
+                                            vp, st, st, vp, st, st, vp, vp]
+    L.mdvt_inspatio_composite_eye.restype = C.c_int
+    L.mdvt_inspatio_composite_eye.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, st, st, vp, st, st, vp, st, st, vp, st, st, vp, st, st, vp]
+    L.mdvt_inspatio_model_frames.restype = C.c_int
+    L.mdvt_inspatio_model_frames.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, st, st, C.c_int, C.c_int, vp, st, st, vp]
+    L.mdvt_flow_warp.restype = C.c_int
+    L.mdvt_flow_warp.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, st, st, vp, st, st, vp]
+    L.mdvt_masked_shift_path.restype = C.c_int
+    L.mdvt_masked_shift_path.argtypes = [C.c_int, C.c_int]
     L.mdvt_adapter_prepare_eye.restype = C.c_int
     L.mdvt_adapter_prepare_eye.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, st, st, vp, st, st, C.c_int, C.c_int, vp, st, st, vp, st, st, vp, vp]
     L.mdvt_lhm_moments.restype = C.c_int

@@ -1,6 +1,6 @@
 // mdvt_context.h -- what the host units of the C ABI share: the context (mdvt_ctx), its error text, its device memory (the
 // process-wide pools of mdvt_context.hip, the scratch blocks and their one growth rule) and a few facts read off its
-// configuration.  Host only: included by mdvt_context.hip, mdvt_api_render.hip, mdvt_api.hip, mdvt_api_depth_engines.hip, mdvt_api_video_mask.hip, mdvt_api_mvsa.hip, mdvt_api_scene.hip and mdvt_api_megasam.hip, never by a unit that defines kernels.
+// configuration.  Host only: included by mdvt_context.hip, mdvt_api_render.hip, mdvt_api.hip, mdvt_api_depth_engines.hip, mdvt_api_video_mask.hip, mdvt_api_mvsa.hip, mdvt_api_scene.hip, mdvt_api_megasam.hip and mdvt_api_inspatio.hip, never by a unit that defines kernels.
 #pragma once
 
 #include "mdvt_internal.h"
@@ -64,6 +64,7 @@ enum ScratchId {
     SCR_MASK_WS,                      // include/mdvt_video_mask.h: per frame of a launch set the intermediate image of the two-launch form, the resized frame or byte plane, the frame's maximum, table or minimum and maximum
     SCR_MVSA,                         // mdvt_ratio_median: per frame of a launch set the 256 histogram words of a radix pass and the selection's state (1040 B)
     SCR_AREA_TABLES,                  // include/mdvt_megasam.h: the area resize's first, count and weight tables of the latest size pair (ctx->area_resident)
+    SCR_INSPATIO,                     // mdvt_masked_shift_grid: 64 B per cell of the call, the largest rounding distance, then per interior cell of a launch set three complex float64 planes
     SCR_COUNT
 };
 

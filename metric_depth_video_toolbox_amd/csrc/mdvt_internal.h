@@ -549,6 +549,65 @@ struct TrackerOutArgs {
 };
 hipError_t launch_tracker_codes(const TrackerOutArgs& a, int n_frames, hipStream_t s);      // mode 0: nearest-exact, clip, the 16-bit code
 hipError_t launch_tracker_grey(const TrackerOutArgs& a, int n_frames, hipStream_t s);       // mode 1: linear resize, clip / m * 255, three equal bytes
+// mdvt_inspatio.hip: the 4 x 4 grid of masked cross-correlation shifts (mdvt_masked_shift_grid, include/mdvt_inspatio.h)
+constexpr int kShiftMaxCell = 1024;                                // the longest cell side
+constexpr int kShiftDirectPixels = 16384;                          // the largest cell the direct kernel holds in LDS
+constexpr int kShiftAutoDirectPixels = 4096;                       // the largest cell MDVT_SHIFT_PATH_AUTO sums directly
+struct ShiftCellState {                                            // one cell of the call, zeroed before the first launch
+    unsigned long long max_den, max_n, max_c, count;               // the bits of max den, max N, the key of max c, the maxima of c
+    long long sum_dy, sum_dx;                                      // the maxima's index sums
+    uint32_t n_valid, active, pad[2];
+};
+struct ShiftGridArgs {
+    const uint8_t* render; size_t render_pitch, render_stride;
+    const uint8_t* infilled; size_t infilled_pitch, infilled_stride;
+    const uint8_t* valid; size_t valid_pitch, valid_stride;
+    int W, H, n_frames;
+    int hmax, wmax;                                                // the largest cell: ceil(H / 4) x ceil(W / 4)
+    int transform;                                                 // 0: the direct kernel, Ly = 2 hmax - 1, Lx = 2 wmax - 1; 1: powers of two
+    int Ly, Lx, log_ly, log_lx;
+    size_t plane;                                                  // Ly * Lx
+    double2* planes;                                               // [unit of the set][3][plane]
+    ShiftCellState* state;                                         // [n_frames][16]
+    unsigned long long* round_err;                                 // the bits of the largest |x - rint(x)|, zeroed before the first launch
+    unsigned long long* round_err_out;                             // the caller's, or null
+    int unit0, n_units;                                            // the launch set: interior cells unit0 .. unit0 + n_units - 1 of 8 per frame
+    double* shift; uint8_t* status;                                // the caller's
+};
+// columns a workgroup of the column pass transforms at once (its LDS: (lines * L + L / 2) * 16 bytes <= 48 KiB)
+inline int shift_fft_lines(int L) { return L >= 2048 ? 1 : (L >= 1024 ? 2 : 4); }
+hipError_t launch_shift_gate(const ShiftGridArgs& a, hipStream_t s);        // the gate and the border columns, all frames
+hipError_t launch_shift_units(const ShiftGridArgs& a, hipStream_t s);       // one launch set of interior cells: sums, then maxima
+hipError_t launch_shift_finish(const ShiftGridArgs& a, hipStream_t s);      // all frames: shift and status
+struct FlowWarpArgs {                                              // mdvt_flow_warp
+    const float* grids; const uint8_t* has_grid;                   // [n][4][4][2] (dx, dy); [n]
+    const uint8_t* src; size_t src_pitch, src_stride;
+    uint8_t* dst; size_t dst_pitch, dst_stride;
+    int W, H, frame0;
+};
+hipError_t launch_flow_warp(const FlowWarpArgs& a, int n_frames, hipStream_t s);
+struct InspatioPrepareArgs {                                       // mdvt_inspatio_prepare_eye; mask.p null: mdvt_inspatio_model_frames
+    AdapterImage color, mask;                                      // the eye's half of the side-by-side frames (p at the eye's first column), or whole frames
+    AdapterResize rs;                                              // eye -> model
+    uint8_t* valid; size_t valid_pitch, valid_stride;              // the eye's validity plane, one byte per pixel
+    uint8_t* render; size_t render_pitch, render_stride;           // the eye's render, holes black
+    uint8_t* m_valid; size_t m_valid_pitch, m_valid_stride;        // both at the model's size
+    uint8_t* m_render; size_t m_render_pitch, m_render_stride;
+    uint32_t* holes;                                               // [n], zeroed before the launch
+    int frame0;
+};
+hipError_t launch_inspatio_prepare(const InspatioPrepareArgs& a, int n_frames, hipStream_t s);
+struct InspatioCompositeArgs {                                     // mdvt_inspatio_composite_eye, one frame of one eye
+    const uint8_t* aligned; size_t aligned_pitch;                  // the aligned frame at the eye's size
+    const uint8_t* color; size_t color_pitch;                      // the eye's half of the render and of the infill mask
+    const uint8_t* mask; size_t mask_pitch;
+    const uint8_t* grown;                                          // [H][W] 0 / 1 (blending)
+    uint8_t* pasted; size_t pasted_pitch;                          // the eye's half of the outputs; blended null: no blending
+    uint8_t* blended; size_t blended_pitch;
+    int W, H;
+};
+hipError_t launch_inspatio_grow(const uint8_t* marks, size_t marks_pitch, uint8_t* grown, int W, int H, hipStream_t s);
+hipError_t launch_inspatio_composite(const InspatioCompositeArgs& a, hipStream_t s);
 hipError_t launch_selftest(int which, unsigned long long seed, unsigned long long* d_mism, hipStream_t s);
 hipError_t launch_coherence_test(uint32_t* blk, size_t dwords, uint32_t tag, uint32_t* d_xcc, uint32_t* d_out, hipStream_t s);     // (mdvt_selftest.hip; r05 diagnosis)
 

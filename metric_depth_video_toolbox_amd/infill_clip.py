@@ -141,15 +141,17 @@ def run_batches(inp, clip: Clip, batch: int, per_batch):
             out.store(per_batch(d_color, fetch_mask(inp, mask, a, b), *d_extras), a)
 
 
-def chunk_schedule(n_frames: int):
+def chunk_schedule(n_frames: int, chunk: int = FRAMES_CHUNK):
     """The calls of the chunk schedule (above) for a clip of n_frames: [(first, last, frame of the buffer's index 0, buffered frames,
-    (a, b))], where [a, b) are the clip's frames the call writes."""
+    (a, b))], where [a, b) are the clip's frames the call writes.  chunk: the frames per chunk (inspatio_world_infill: 225)."""
     if n_frames < 1:
         raise ValueError("a clip needs at least one frame")
+    if chunk <= OVERLAP:
+        raise ValueError(f"a chunk must be longer than the {OVERLAP} frames kept between chunks")
     calls, first, base, held = [], True, 0, 0
     for t in range(n_frames):
         held += 1
-        if held >= FRAMES_CHUNK:
+        if held >= chunk:
             start = 0 if first else 3
             calls.append((first, False, base, held, (base + start, base + held - 3)))
             first, base, held = False, base + held - OVERLAP, OVERLAP
@@ -158,21 +160,21 @@ def chunk_schedule(n_frames: int):
     return calls
 
 
-def run_chunks(inp, clip: Clip, batch: int, per_chunk, store_blended: bool = True):
+def run_chunks(inp, clip: Clip, batch: int, per_chunk, store_blended: bool = True, chunk: int = FRAMES_CHUNK):
     """The chunk schedule (above) over the clip, read `batch` frames at a time: per call,
     per_chunk(first, last, fps, colour, mask, *further inputs) -> (start, pasted, blended) as infill_chunk returns them.  The file
     gets the blended frames or the pasted ones; the pasted ones feed the overlap either way (m2s:308, 332).  The generator is told
-    30 frames per second for frame dumps."""
+    30 frames per second for frame dumps.  chunk: the frames per chunk."""
     import torch
     color, mask, *extras = clip.frames
     batch = max(1, int(batch))
     fps = clip.fps if clip.video else 30.0
     with ClipOutput(clip.tmp, clip.final, clip.n, color.shape[1:], clip.fps, clip.encoder, inp.ctx) as out, torch.cuda.device(inp.dev):
-        buf_c = torch.empty((FRAMES_CHUNK,) + tuple(int(v) for v in color.shape[1:]), dtype=torch.uint8, device=inp.dev)
+        buf_c = torch.empty((chunk,) + tuple(int(v) for v in color.shape[1:]), dtype=torch.uint8, device=inp.dev)
         buf_m = torch.zeros_like(buf_c)
-        buf_x = [torch.empty((FRAMES_CHUNK,) + tuple(int(v) for v in x.shape[1:]), dtype=torch.uint8, device=inp.dev) for x in extras]
+        buf_x = [torch.empty((chunk,) + tuple(int(v) for v in x.shape[1:]), dtype=torch.uint8, device=inp.dev) for x in extras]
         read = 0
-        for first, last, base, held, (wa, wb) in chunk_schedule(clip.n):
+        for first, last, base, held, (wa, wb) in chunk_schedule(clip.n, chunk):
             have = read - base                                     # the overlap is in the buffer already
             while have < held:
                 k = min(batch, held - have)
