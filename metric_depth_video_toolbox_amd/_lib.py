@@ -73,16 +73,16 @@ LANCZOS_AUTO, LANCZOS_FUSED, LANCZOS_TWO_LAUNCH = 0, 1, 2
 MVSA_SYMBOLS = ("mdvt_bilinear_model_frames", "mdvt_nearest_depth_codes", "mdvt_ratio_median")
 
 # the entry points include/mdvt_scene.h declares (the frame difference sums behind scene detection), likewise.  The wrapper is
-# tools/scene_detect.py's frame_sums
+# step_device.frame_sums
 SCENE_SYMBOLS = ("mdvt_scene_frame_sums", "mdvt_scene_vector_path")
 
 # the entry points include/mdvt_megasam.h declares (cv2's area resize, torch's nearest-exact and bilinear resizes into the camera
-# tracker, its planes out to video frames), likewise.  Their wrappers are tools/megasam_device.py's
+# tracker, its planes out to video frames), likewise.  Their wrappers are megasam_device.py's
 MEGASAM_SYMBOLS = ("mdvt_area_model_frames", "mdvt_megasam_vector_path", "mdvt_tracker_depth", "mdvt_tracker_mask", "mdvt_tracker_outputs")
 TRACKER_DEPTH_VIDEO, TRACKER_GREY_VIDEO = 0, 1
 
-# the entry points include/mdvt_inspatio.h declares (the InSpatio-World infill step's masked alignment), likewise.  The wrapper is
-# tools/inspatio_device.py's masked_shift_grid and flow_warp
+# the entry points include/mdvt_inspatio.h declares (the InSpatio-World infill step's masked alignment), likewise.  Their wrappers are
+# inspatio_device.py's
 INSPATIO_SYMBOLS = ("mdvt_masked_shift_grid", "mdvt_masked_shift_path", "mdvt_flow_warp", "mdvt_inspatio_prepare_eye",
                     "mdvt_inspatio_model_frames", "mdvt_inspatio_composite_eye")
 SHIFT_PATH_AUTO, SHIFT_PATH_DIRECT, SHIFT_PATH_TRANSFORM = 0, 1, 2

@@ -1,13 +1,18 @@
-"""The device wrappers of the InSpatio-World infill step's alignment: the functions that hand tensors' addresses to
-mdvt_inspatio_prepare_eye, mdvt_inspatio_model_frames, mdvt_masked_shift_grid, mdvt_flow_warp and mdvt_inspatio_composite_eye (include/mdvt_inspatio.h).  Each takes the clip's context first, refuses a tensor its docstring does not promise
-to take before the library sees an address (_lib.check_tensor), and only enqueues on `stream`.  torch is imported inside the functions.
-They live next to the tools, as tools/megasam_device.py does: the tensor-contract table of the package's wrappers is a test helper this
-leaves alone."""
-import os
-import sys
+"""The device wrappers of the InSpatio-World infill step's alignment (tools/inspatio_world_infill.py, tools/inspatio_bench.py): the
+five functions that hand tensors' addresses to mdvt_inspatio_prepare_eye, mdvt_inspatio_model_frames, mdvt_masked_shift_grid,
+mdvt_flow_warp and mdvt_inspatio_composite_eye (include/mdvt_inspatio.h).  Each takes the clip's context first, refuses a tensor its
+docstring does not promise to take before the library sees an address (tests/binding_contract.py holds every one to its record), and
+only enqueues on `stream`.  torch is imported inside the functions: importing this module, or a tool, needs none.  model_frames here
+is this step's u8 resize, not step_device.model_frames."""
+from . import _lib
+from .step_clip import size_arg, stream_or_current
+from .step_device import frames_on_context
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
+
+def _eye(eye):
+    if eye not in (0, 1):
+        raise ValueError(f"eye must be 0 or 1, got {eye!r}")
+    return int(eye)
 
 
 def masked_shift_grid(ctx, render, infilled, valid, *, path=0, stream=None):
@@ -16,17 +21,12 @@ def masked_shift_grid(ctx, render, infilled, valid, *, path=0, stream=None):
     largest distance from an integer the transform path rounded, 0 on the direct path).  path: 0 as mdvt_masked_shift_path says, 1
     direct, 2 transform.  Only enqueues, on `stream`: nothing is read back."""
     import torch
-    from metric_depth_video_toolbox_amd import _lib, step_clip
     if path not in (_lib.SHIFT_PATH_AUTO, _lib.SHIFT_PATH_DIRECT, _lib.SHIFT_PATH_TRANSFORM):
         raise ValueError(f"path must be 0 (auto), 1 (direct) or 2 (transform), got {path!r}")
-    _lib.check_tensor("render", render, torch.uint8, (None, None, None, 3), ndim=4, packed=2, disjoint=True)
-    if render.device.index != ctx.device:
-        raise ValueError(f"render is on {render.device}, the context on cuda:{ctx.device}")
-    dev = render.device
-    N, H, W = step_clip.non_empty("render", render, "pixel")
+    dev, N, H, W = frames_on_context(ctx, "render", render)
     _lib.check_tensor("infilled", infilled, torch.uint8, (N, H, W, 3), ndim=4, device=dev, packed=2, disjoint=True)
     _lib.check_tensor("valid", valid, torch.uint8, (N, H, W), ndim=3, device=dev, packed=1, disjoint=True)
-    s = step_clip.stream_or_current(dev, stream)
+    s = stream_or_current(dev, stream)
     with torch.cuda.stream(s):
         shift = torch.empty((N, 4, 4, 2), dtype=torch.float64, device=dev)
         status = torch.empty((N, 4, 4), dtype=torch.uint8, device=dev)
@@ -42,15 +42,10 @@ def flow_warp(ctx, grids, has_grid, infilled, *, out=None, stream=None):
     frames uint8 CUDA [N, H, W, 3] (rows and frames may be strided) -> the aligned frames [N, H, W, 3]; a frame without a grid is
     copied.  out: the tensor to fill (it must not overlap infilled).  Only enqueues, on `stream`."""
     import torch
-    from metric_depth_video_toolbox_amd import _lib, step_clip
-    _lib.check_tensor("infilled", infilled, torch.uint8, (None, None, None, 3), ndim=4, packed=2, disjoint=True)
-    if infilled.device.index != ctx.device:
-        raise ValueError(f"infilled is on {infilled.device}, the context on cuda:{ctx.device}")
-    dev = infilled.device
-    N, H, W = (int(v) for v in step_clip.non_empty("infilled", infilled, "pixel"))
+    dev, N, H, W = frames_on_context(ctx, "infilled", infilled)
     _lib.check_tensor("grids", grids, torch.float32, (N, 4, 4, 2), ndim=4, device=dev, contiguous=True)
     _lib.check_tensor("has_grid", has_grid, torch.uint8, (N,), ndim=1, device=dev, contiguous=True)
-    s = step_clip.stream_or_current(dev, stream)
+    s = stream_or_current(dev, stream)
     with torch.cuda.stream(s):
         frames = torch.empty((N, H, W, 3), dtype=torch.uint8, device=dev) if out is None else out
     _lib.check_tensor("out", frames, torch.uint8, (N, H, W, 3), device=dev, packed=2, output=True)
@@ -64,27 +59,21 @@ def prepare_eye(ctx, sbs_color, sbs_mask, eye, model_size, *, stream=None):
     render [N, H, W, 3] with the holes black, model_valid [N, mh, mw], model_render [N, mh, mw, 3], hole_counts int32 [N] on the
     device); eye 0 is the left half, 1 the right; model_size = (mw, mh).  Only enqueues, on `stream`."""
     import torch
-    from metric_depth_video_toolbox_amd import _lib, step_clip
-    if eye not in (0, 1):
-        raise ValueError(f"eye must be 0 or 1, got {eye!r}")
-    _lib.check_tensor("sbs_color", sbs_color, torch.uint8, (None, None, None, 3), ndim=4, packed=2, disjoint=True)
-    if sbs_color.device.index != ctx.device:
-        raise ValueError(f"sbs_color is on {sbs_color.device}, the context on cuda:{ctx.device}")
-    dev = sbs_color.device
-    N, H, W2 = (int(v) for v in step_clip.non_empty("sbs_color", sbs_color, "pixel"))
+    eye = _eye(eye)
+    dev, N, H, W2 = frames_on_context(ctx, "sbs_color", sbs_color)
     if W2 % 2:
         raise ValueError(f"sbs_color must have an even width, got {W2}")
     _lib.check_tensor("sbs_mask", sbs_mask, torch.uint8, (N, H, W2, 3), ndim=4, device=dev, packed=2, disjoint=True)
     W = W2 // 2
-    mw, mh = step_clip.size_arg(model_size, "model_size")
-    s = step_clip.stream_or_current(dev, stream)
+    mw, mh = size_arg(model_size, "model_size")
+    s = stream_or_current(dev, stream)
     with torch.cuda.stream(s):
         valid = torch.empty((N, H, W), dtype=torch.uint8, device=dev)
         render = torch.empty((N, H, W, 3), dtype=torch.uint8, device=dev)
         m_valid = torch.empty((N, mh, mw), dtype=torch.uint8, device=dev)
         m_render = torch.empty((N, mh, mw, 3), dtype=torch.uint8, device=dev)
         holes = torch.empty((N,), dtype=torch.int32, device=dev)
-    ctx.call("mdvt_inspatio_prepare_eye", W, H, N, int(eye), sbs_color.data_ptr(), sbs_color.stride(1), sbs_color.stride(0),
+    ctx.call("mdvt_inspatio_prepare_eye", W, H, N, eye, sbs_color.data_ptr(), sbs_color.stride(1), sbs_color.stride(0),
              sbs_mask.data_ptr(), sbs_mask.stride(1), sbs_mask.stride(0), mw, mh, valid.data_ptr(), W, W * H, render.data_ptr(), 3 * W, 3 * W * H,
              m_valid.data_ptr(), mw, mw * mh, m_render.data_ptr(), 3 * mw, 3 * mw * mh, holes.data_ptr(), _lib.stream_arg(dev, s))
     return valid, render, m_valid, m_render, holes
@@ -94,14 +83,9 @@ def model_frames(ctx, frames, size, *, stream=None):
     """mdvt_inspatio_model_frames: uint8 CUDA frames [N, H, W, 3] (rows and frames may be strided) through the u8 resize to size =
     (w, h) -> [N, h, w, 3].  Only enqueues, on `stream`."""
     import torch
-    from metric_depth_video_toolbox_amd import _lib, step_clip
-    _lib.check_tensor("frames", frames, torch.uint8, (None, None, None, 3), ndim=4, packed=2, disjoint=True)
-    if frames.device.index != ctx.device:
-        raise ValueError(f"frames is on {frames.device}, the context on cuda:{ctx.device}")
-    dev = frames.device
-    N, H, W = (int(v) for v in step_clip.non_empty("frames", frames, "pixel"))
-    w, h = step_clip.size_arg(size, "size")
-    s = step_clip.stream_or_current(dev, stream)
+    dev, N, H, W = frames_on_context(ctx, "frames", frames)
+    w, h = size_arg(size, "size")
+    s = stream_or_current(dev, stream)
     with torch.cuda.stream(s):
         out = torch.empty((N, h, w, 3), dtype=torch.uint8, device=dev)
     ctx.call("mdvt_inspatio_model_frames", W, H, N, frames.data_ptr(), frames.stride(1), frames.stride(0), w, h, out.data_ptr(), 3 * w, 3 * w * h,
@@ -114,23 +98,16 @@ def composite_eye(ctx, aligned, sbs_color, sbs_mask, eye, pasted, blended=None, 
     side-by-side frames [N, H, 2W, 3] into `pasted`, and, where `blended` is given, blended along the holes' lower side into it (both
     uint8 CUDA [N, H, 2W, 3]; the eye's half is written).  Rows and frames may be strided.  Only enqueues, on `stream`."""
     import torch
-    from metric_depth_video_toolbox_amd import _lib, step_clip
-    if eye not in (0, 1):
-        raise ValueError(f"eye must be 0 or 1, got {eye!r}")
-    _lib.check_tensor("aligned", aligned, torch.uint8, (None, None, None, 3), ndim=4, packed=2, disjoint=True)
-    if aligned.device.index != ctx.device:
-        raise ValueError(f"aligned is on {aligned.device}, the context on cuda:{ctx.device}")
-    dev = aligned.device
-    N, H, W = (int(v) for v in step_clip.non_empty("aligned", aligned, "pixel"))
+    eye = _eye(eye)
+    dev, N, H, W = frames_on_context(ctx, "aligned", aligned)
     _lib.check_tensor("sbs_color", sbs_color, torch.uint8, (N, H, 2 * W, 3), ndim=4, device=dev, packed=2, disjoint=True)
     _lib.check_tensor("sbs_mask", sbs_mask, torch.uint8, (N, H, 2 * W, 3), ndim=4, device=dev, packed=2, disjoint=True)
     _lib.check_tensor("pasted", pasted, torch.uint8, (N, H, 2 * W, 3), ndim=4, device=dev, packed=2, output=True)
     if blended is not None:
         _lib.check_tensor("blended", blended, torch.uint8, (N, H, 2 * W, 3), ndim=4, device=dev, packed=2, output=True)
-    s = step_clip.stream_or_current(dev, stream)
-    ctx.call("mdvt_inspatio_composite_eye", W, H, N, int(eye), aligned.data_ptr(), aligned.stride(1), aligned.stride(0),
+    s = stream_or_current(dev, stream)
+    b = (None, 0, 0) if blended is None else (blended.data_ptr(), blended.stride(1), blended.stride(0))
+    ctx.call("mdvt_inspatio_composite_eye", W, H, N, eye, aligned.data_ptr(), aligned.stride(1), aligned.stride(0),
              sbs_color.data_ptr(), sbs_color.stride(1), sbs_color.stride(0), sbs_mask.data_ptr(), sbs_mask.stride(1), sbs_mask.stride(0),
-             pasted.data_ptr(), pasted.stride(1), pasted.stride(0),
-             None if blended is None else blended.data_ptr(), 0 if blended is None else blended.stride(1), 0 if blended is None else blended.stride(0),
-             _lib.stream_arg(dev, s))
+             pasted.data_ptr(), pasted.stride(1), pasted.stride(0), *b, _lib.stream_arg(dev, s))
     return pasted, blended

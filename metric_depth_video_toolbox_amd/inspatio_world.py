@@ -1,5 +1,5 @@
 """The host side of the reference's InSpatio-World infill step (inspatio_world_infill.py, iwi:) around the device's masked alignment
-(include/mdvt_inspatio.h; the wrapper that hands tensors to it is tools/inspatio_device.py's).  No torch and no tensor address here:
+(include/mdvt_inspatio.h; the wrapper that hands tensors to it is inspatio_device.py's).  No torch and no tensor address here:
 NumPy on what one read-back per chunk and eye brings -- the 4 x 4 shifts and their status bytes.
 
   pad_to_valid_T   the frame count the video model is handed (iwi:225-236)

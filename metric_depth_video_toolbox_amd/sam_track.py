@@ -2,7 +2,7 @@
 the command line, the file names, the tracker's image size, the scaled intrinsics, which frames the reference's look-ahead loop hands
 over, the poses' way into a transformation file and the `--generator` loader.  Plain host logic in NumPy: torch is not imported here
 and no tensor's address is taken.  tools/sam_track_video.py runs the step on the device with these pieces and
-tools/megasam_device.py's wrappers of the four entry points of include/mdvt_megasam.h.
+megasam_device.py's wrappers of the four entry points of include/mdvt_megasam.h.
 
 DECREES of this project: the pose conversion is the closed form in float64, because lietorch's
 SE3(...).inv().matrix() cannot be observed; the JSON holds t + 1 matrices, the identity first (stv:240); frame_plan reproduces the

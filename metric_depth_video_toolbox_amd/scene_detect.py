@@ -1,7 +1,7 @@
 """Host side of scene detection (step 0 of the reference's movie_2_3D.py, m23d:209-222, which runs PySceneDetect's
 `scenedetect -i movie list-scenes`): the integer sums of include/mdvt_scene.h's entry point to scores, cuts, a scene list and
 PySceneDetect's `<video stem>-Scenes.csv`.  Importable without torch; no tensor's address is taken here (the device wrapper is
-tools/scene_detect.py's).
+step_device.frame_sums).
 
 PySceneDetect is not observed by this project: what follows restates its 0.6.x defaults from its documentation and is a DECREE of
 this project (README, DESIGN.md "Scene detection"), not a measured equality.  All arithmetic is float64.

@@ -1,8 +1,9 @@
 """The device wrappers of the model-step tools (tools/video_da3.py, depth_engine_video.py, upscale_depth_promptda.py,
-generate_video_mask.py and video_mvsa.py): the ten functions that hand a tensor's address to the entry points of
-include/mdvt_depth_sink.h, mdvt_depth_engines.h, mdvt_video_mask.h and mdvt_mvsa.h.  Each takes the clip's context first, refuses a
-tensor its docstring does not promise to take before the library sees an address (tests/binding_contract.py holds every one to its
-record), and only enqueues on `stream`.  torch is imported inside the functions: importing this module, or a tool, needs none.
+generate_video_mask.py, video_mvsa.py and scene_detect.py): the eleven functions that hand a tensor's address to the entry points of
+include/mdvt_depth_sink.h, mdvt_depth_engines.h, mdvt_video_mask.h, mdvt_mvsa.h and mdvt_scene.h.  Each takes the clip's context
+first, refuses a tensor its docstring does not promise to take before the library sees an address (tests/binding_contract.py holds
+every one to its record), and only enqueues on `stream`.  torch is imported inside the functions: importing this module, or a tool,
+needs none.  on_context and frames_on_context are also megasam_device.py's and inspatio_device.py's.
 """
 from __future__ import annotations
 
@@ -12,11 +13,19 @@ from . import _lib
 from .step_clip import non_empty, size_arg, stream_or_current
 
 
-def _on_context(ctx, name: str, t):
+def on_context(ctx, name: str, t):
     """The device of a checked tensor, which must be the context's (ffv1_device.enqueue's refusal)."""
     if t.device.index != ctx.device:
         raise ValueError(f"{name} is on {t.device}, the context on cuda:{ctx.device}")
     return t.device
+
+
+def frames_on_context(ctx, name: str, frames, noun: str = "pixel", ndim=4):
+    """A packed uint8 frame batch [N, H, W, 3] (rows and frames at any pitch, none overlapping) on the context's GPU, checked ->
+    (device, N, H, W).  ndim=None words a wrong number of dimensions as a wrong shape."""
+    import torch
+    _lib.check_tensor(name, frames, torch.uint8, (None, None, None, 3), ndim=ndim, packed=2, disjoint=True)
+    return (on_context(ctx, name, frames),) + non_empty(name, frames, noun)
 
 
 # ---- include/mdvt_depth_sink.h ------------------------------------------------------------------------------------------------------
@@ -31,7 +40,7 @@ def depth_video_codes(ctx, planes, max_depth, out_size=None, *, scale=None, nan_
     if not (float(max_depth) > 0):
         raise ValueError("max_depth must be > 0")
     _lib.check_tensor("planes", planes, torch.float32, ndim=3, packed=1, disjoint=True)
-    dev = _on_context(ctx, "planes", planes)
+    dev = on_context(ctx, "planes", planes)
     N, h, w = non_empty("planes", planes, "value")
     W, H = (w, h) if out_size is None else size_arg(out_size, "out_size")
     if scale is not None:
@@ -57,9 +66,7 @@ def model_frames(ctx, frames, out_size=None, *, as_float=False, bgr=False, strea
     [N, 3, h, w] in R, G, B plane order at out_size = (w, h) (default: the frames' own size), uint8, or float32 v / 255 with as_float.
     Only enqueues, on `stream`."""
     import torch
-    _lib.check_tensor("frames", frames, torch.uint8, (None, None, None, 3), packed=2, disjoint=True)
-    dev = _on_context(ctx, "frames", frames)
-    N, H, W = non_empty("frames", frames, "pixel")
+    dev, N, H, W = frames_on_context(ctx, "frames", frames, ndim=None)
     w, h = (W, H) if out_size is None else size_arg(out_size, "out_size")
     s = stream_or_current(dev, stream)
     with torch.cuda.stream(s):
@@ -76,9 +83,7 @@ def depth_prompt(ctx, codes, max_depth, out_size, *, bgr=False, stream=None):
     import torch
     if not (float(max_depth) > 0):
         raise ValueError("max_depth must be > 0")
-    _lib.check_tensor("codes", codes, torch.uint8, (None, None, None, 3), packed=2, disjoint=True)
-    dev = _on_context(ctx, "codes", codes)
-    N, H, W = non_empty("codes", codes, "pixel")
+    dev, N, H, W = frames_on_context(ctx, "codes", codes, ndim=None)
     w, h = size_arg(out_size, "out_size")
     s = stream_or_current(dev, stream)
     with torch.cuda.stream(s):
@@ -104,7 +109,7 @@ def focal_from_points(ctx, points, *, want_counts=False, stream=None):
         pitch, plane, stride = 4 * points.stride(2), 4 * points.stride(1), 4 * points.stride(0)
     else:
         raise ValueError(f"points must be [N, H, W, 3] or [N, 3, H, W], got shape {tuple(points.shape)}")
-    dev = _on_context(ctx, "points", points)
+    dev = on_context(ctx, "points", points)
     N, H, W = non_empty("points", points, "point", dims)
     s = stream_or_current(dev, stream)
     with torch.cuda.stream(s):
@@ -125,7 +130,7 @@ def lanczos_resize(ctx, images, out_size, *, form=0, stream=None):
     _lib.check_tensor("images", images, torch.uint8, ndim=(3, 4))
     ch = 1 if images.dim() == 3 else 3
     _lib.check_tensor("images", images, torch.uint8, (None, None, None) + ((3,) if ch == 3 else ()), packed=2 if ch == 3 else 1, disjoint=True)
-    dev = _on_context(ctx, "images", images)
+    dev = on_context(ctx, "images", images)
     N, H, W = non_empty("images", images, "pixel")
     w, h = size_arg(out_size, "out_size")
     s = stream_or_current(dev, stream)
@@ -141,9 +146,7 @@ def mask_model_input(ctx, frames, model_size, mean, std, *, bgr=False, stream=No
     """mdvt_mask_model_input on uint8 CUDA frames [N, H, W, 3] (rows and frames may be strided; B, G, R with bgr) -> float32
     [N, 3, h, w] at model_size = (w, h), planes R, G, B: rembg's normalize.  Only enqueues, on `stream`."""
     import torch
-    _lib.check_tensor("frames", frames, torch.uint8, (None, None, None, 3), packed=2, disjoint=True)
-    dev = _on_context(ctx, "frames", frames)
-    N, H, W = non_empty("frames", frames, "pixel")
+    dev, N, H, W = frames_on_context(ctx, "frames", frames, ndim=None)
     w, h = size_arg(model_size, "model_size")
     d3 = C.c_double * 3
     h_mean, h_std = d3(*(float(v) for v in mean)), d3(*(float(v) for v in std))
@@ -162,7 +165,7 @@ def mask_from_prediction(ctx, pred, out_size, *, channels=3, stream=None):
     if channels not in (1, 3):
         raise ValueError(f"channels must be 1 or 3, got {channels!r}")
     _lib.check_tensor("pred", pred, torch.float32, (None, None, None), packed=1, disjoint=True)
-    dev = _on_context(ctx, "pred", pred)
+    dev = on_context(ctx, "pred", pred)
     N, ph, pw = non_empty("pred", pred, "value")
     W, H = size_arg(out_size, "out_size")
     s = stream_or_current(dev, stream)
@@ -180,9 +183,7 @@ def bilinear_model_frames(ctx, frames, out_size=None, *, bgr=False, out=None, st
     planar tensor [N, 3, h, w] in R, G, B plane order at out_size = (w, h) (default: the frames' own size): v / 255 through torch's
     bilinear resize, unfused.  out: the tensor to fill (rows, planes and frames may be strided).  Only enqueues, on `stream`."""
     import torch
-    _lib.check_tensor("frames", frames, torch.uint8, (None, None, None, 3), packed=2, disjoint=True)
-    dev = _on_context(ctx, "frames", frames)
-    N, H, W = non_empty("frames", frames, "pixel")
+    dev, N, H, W = frames_on_context(ctx, "frames", frames, ndim=None)
     w, h = (W, H) if out_size is None else size_arg(out_size, "out_size")
     s = stream_or_current(dev, stream)
     if out is None:
@@ -203,7 +204,7 @@ def nearest_depth_codes(ctx, planes, mid_size, max_depth, out_size, *, scale=Non
     if not (float(max_depth) > 0):
         raise ValueError("max_depth must be > 0")
     _lib.check_tensor("planes", planes, torch.float32, ndim=3, packed=1, disjoint=True)
-    dev = _on_context(ctx, "planes", planes)
+    dev = on_context(ctx, "planes", planes)
     N, h, w = non_empty("planes", planes, "value")
     (mw, mh), (W, H) = (int(v) for v in mid_size), (int(v) for v in out_size)
     if min(mw, mh, W, H) < 1:
@@ -233,7 +234,7 @@ def ratio_median(ctx, cv, ref, mask=None, *, want_counts=False, out=None, stream
     Only enqueues, on `stream`."""
     import torch
     _lib.check_tensor("cv", cv, torch.float32, ndim=3, packed=1, disjoint=True)
-    dev = _on_context(ctx, "cv", cv)
+    dev = on_context(ctx, "cv", cv)
     N = int(cv.shape[0])
     _lib.check_tensor("ref", ref, torch.float32, (N, None, None), device=dev, packed=1, disjoint=True)
     if N < 1 or min(cv.shape[1:]) < 1 or min(ref.shape[1:]) < 1:
@@ -251,3 +252,28 @@ def ratio_median(ctx, cv, ref, mask=None, *, want_counts=False, out=None, stream
              int(ref.shape[2]), int(ref.shape[1]), ref.data_ptr(), 4 * ref.stride(1), 4 * ref.stride(0), *m,
              median.data_ptr(), counts.data_ptr() if want_counts else None, _lib.stream_arg(dev, s))
     return (median, counts) if want_counts else median
+
+
+# ---- include/mdvt_scene.h -----------------------------------------------------------------------------------------------------------
+
+def frame_sums(ctx, frames, prev=None, factor: int = 1, *, bgr: bool = False, stream=None):
+    """mdvt_scene_frame_sums on uint8 CUDA frames [n, H, W, 3] with packed pixels (rows and frames may be padded); prev: None or one
+    such frame [H, W, 3] on the same device -> the int64 CUDA tensor [pairs, 3] of sum |dH|, |dS|, |dV| (the sums are below 2^63),
+    pairs = n - 1 + (prev is not None).  Only enqueues, on `stream` (default: the current stream of the frames' device)."""
+    import torch
+    dev, n, H, W = frames_on_context(ctx, "frames", frames, "frame")
+    if prev is not None:
+        _lib.check_tensor("prev", prev, torch.uint8, (H, W, 3), ndim=3, device=dev, packed=2, disjoint=True)
+    pairs = n - 1 + (prev is not None)
+    if pairs < 1:
+        raise ValueError("one frame and no previous frame: no pair to compare")
+    factor = int(factor)
+    if factor < 1:
+        raise ValueError(f"factor must be >= 1, got {factor}")
+    s = stream_or_current(dev, stream)
+    with torch.cuda.stream(s):
+        sums = torch.empty((pairs, 3), dtype=torch.int64, device=dev)
+    ctx.call("mdvt_scene_frame_sums", W, H, n, frames.data_ptr(), frames.stride(1), frames.stride(0), 1 if bgr else 0,
+             prev.data_ptr() if prev is not None else None, prev.stride(0) if prev is not None else 0, factor, sums.data_ptr(),
+             _lib.stream_arg(dev, s))
+    return sums

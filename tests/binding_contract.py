@@ -25,7 +25,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # the modules whose wrappers the table covers (every module of the package that hands a tensor's address to the library)
 MODULES = ("stereo_rerender", "depth_frames_helper", "infill_common", "basic_nomal_infill", "stereo_dissoclusion_net_infill",
            "stereo_crafter_infill", "m2svid_infill", "infill_clip", "find_convergence_depth", "video_metric_convert", "view_depthfile",
-           "ffv1_device", "model_hop", "step_device", "geometry_device")
+           "ffv1_device", "model_hop", "step_device", "geometry_device", "megasam_device", "inspatio_device")
 
 SIZES = ((33, 5), (36, 6), (6, 6))          # W x H: odd and across a 32-pixel mask word; a multiple of 4 (vector paths); square
 N_FRAMES = 3
@@ -234,6 +234,8 @@ class Record:
     sizes: tuple = SIZES
     setup: Optional[Callable] = None          # env -> None: what the call needs beside tensors (packets, parameter records)
     entries: tuple = ()
+    min_frames: int = 1                       # the fewest frames the call takes (2: a pair of frames): the mid_frame layout's batch
+                                              # of one frame is not built for such a record
 
     def arg(self, name):
         return next(a for a in self.args if a.name == name)
@@ -522,6 +524,86 @@ def _grey(bits):
                   lambda e, a: {"out": mod("geometry_device").grey_batch(_ctx(e, True), a["depth"], max_depth=100.0, bits=bits)},
                   (G("depth", entry, 1, 2, 3, 0, R3), G("out", entry, 6, 7, 8, 0, lambda e: (2 if bits == 16 else 3) * e.W)))
 
+
+# ---- the scene, tracker and InSpatio wrappers.  Several of their entry points refuse the table's sizes, so these keep the three kinds
+# (odd across a 32-pixel word, a multiple of 4, square) at sizes of their own: an eye of 8 x 8 and more for the shift grid and the
+# blend; for cv2's area resize to 8 x 6 a frame no smaller than that on either axis whose two ratios are not both integers ----
+EYE_SIZES = ((33, 9), (36, 12), (8, 8))
+AREA_SIZES = ((33, 9), (36, 10), (10, 10))
+_K4 = lambda e: 4 * e.KW                     # noqa: E731
+_KROWS = lambda e: e.KH                      # noqa: E731
+
+
+def _frame_sums(with_prev):
+    """sums has a row per pair: N - 1, and one more with a previous frame (unbatched, of the frames' size, on their device)."""
+    entry = "mdvt_scene_frame_sums"
+    return Record(f"step_device.frame_sums[{'prev' if with_prev else 'no prev'}]", ("step_device.frame_sums",),
+                  (_frames_in(),) + ((_rgb("prev", batched=False),) if with_prev else ()),
+                  lambda e, a: {"sums": mod("step_device").frame_sums(_ctx(e), a["frames"], a.get("prev"))},
+                  (G("frames", entry, 3, 4, 5, 2, R3),) + ((G("prev", entry, 7, 8, row_bytes=R3),) if with_prev else ()) +
+                  (G("sums", entry, 10, row_bytes=lambda e: 24 * (e.N - 1 + with_prev), rows=ONE),), min_frames=2)
+
+
+def _tracker_in(fn, name, o, *extra):
+    """tracker_depth and tracker_mask: frames -> float32 planes at the crop (4 x 3) of the tracker's size (8 x 6); `o`: where the
+    output's pointer stands."""
+    entry = "mdvt_" + fn
+    return Record(f"megasam_device.{fn}", (f"megasam_device.{fn}",), (_frames_in(name),),
+                  lambda e, a: {"out": getattr(mod("megasam_device"), fn)(_ctx(e), a[name], *extra, (e.MW, e.MH), (e.KW, e.KH))},
+                  (G(name, entry, 3, 4, 5, 2, R3), G("out", entry, o, o + 1, o + 2, 2, _K4, _KROWS)))
+
+
+def _tracker_outputs(mode):
+    entry = "mdvt_tracker_outputs"
+    return Record(f"megasam_device.tracker_outputs[{'grey' if mode else 'depth'}]", ("megasam_device.tracker_outputs",),
+                  (_planes_in(leads=True), _out(hw=_ORG)),
+                  lambda e, a: {"out": mod("megasam_device").tracker_outputs(_ctx(e), a["planes"], mode, 4.0 if mode else 100.0, (e.OW, e.OH), out=a["out"])},
+                  (G("planes", entry, 4, 5, 6, 3, R4), G("out", entry, 10, 11, 12, 3, _O3, _OROWS)))
+
+
+def _shift_grid(path):
+    entry = "mdvt_masked_shift_grid"
+
+    def call(e, a):
+        shift, status, err = mod("inspatio_device").masked_shift_grid(_ctx(e), a["render"], a["infilled"], a["valid"], path=path)
+        return {"shift": shift, "status": status, "round_error": err}
+    return Record(f"inspatio_device.masked_shift_grid[{'direct' if path == 1 else 'transform'}]", ("inspatio_device.masked_shift_grid",),
+                  (_frames_in("render"), _rgb("infilled", expand=False), _plane("valid", expand=False)), call,
+                  (G("render", entry, 3, 4, 5, 2, R3), G("infilled", entry, 6, 7, 8, 2, R3), G("valid", entry, 9, 10, 11, 2, R1),
+                   G("shift", entry, 13, row_bytes=lambda e: 256 * e.N, rows=ONE), G("status", entry, 14, row_bytes=lambda e: 16 * e.N, rows=ONE),
+                   G("round_error", entry, 15, row_bytes=lambda e: 8, rows=ONE)), sizes=EYE_SIZES)
+
+
+def _inspatio_prepare(eye):
+    entry = "mdvt_inspatio_prepare_eye"
+    half = dict(offset=lambda e: eye * 3 * e.W, partial=True)
+
+    def call(e, a):
+        got = mod("inspatio_device").prepare_eye(_ctx(e), a["sbs_color"], a["sbs_mask"], eye, (e.MW, e.MH))
+        return dict(zip(("valid", "render", "model_valid", "model_render", "hole_counts"), got))
+    return Record(f"inspatio_device.prepare_eye[{eye}]", ("inspatio_device.prepare_eye",),
+                  (_rgb("sbs_color", wide=2, leads=True, expand=False), _rgb("sbs_mask", wide=2, expand=False)), call,
+                  (G("sbs_color", entry, 4, 5, 6, 2, R3, **half), G("sbs_mask", entry, 7, 8, 9, 2, R3, **half),
+                   G("valid", entry, 12, 13, 14, 2, R1), G("render", entry, 15, 16, 17, 2, R3),
+                   G("model_valid", entry, 18, 19, 20, 2, lambda e: e.MW, _MROWS), G("model_render", entry, 21, 22, 23, 2, _M3, _MROWS),
+                   G("hole_counts", entry, 24, row_bytes=_NVEC, rows=ONE)))
+
+
+def _inspatio_composite(eye, blend):
+    """The eye's half of `pasted` and, with `blend`, of `blended` is written."""
+    entry = "mdvt_inspatio_composite_eye"
+    half = dict(offset=lambda e: eye * 3 * e.W, partial=True)
+    sbs = ("sbs_color", "sbs_mask", "pasted") + (("blended",) if blend else ())
+
+    def call(e, a):
+        pasted, blended = mod("inspatio_device").composite_eye(_ctx(e), a["aligned"], a["sbs_color"], a["sbs_mask"], eye, a["pasted"], a.get("blended"))
+        return {"pasted": pasted, "blended": blended} if blend else {"pasted": pasted}
+    return Record(f"inspatio_device.composite_eye[{eye}, {'blended' if blend else 'pasted only'}]", ("inspatio_device.composite_eye",),
+                  (_frames_in("aligned"),) + tuple(_rgb(n, wide=2, expand=False) for n in sbs[:2]) + tuple(_out(n, wide=2, optional=False) for n in sbs[2:]),
+                  call, (G("aligned", entry, 4, 5, 6, 2, R3),) + tuple(G(n, entry, 7 + 3 * k, 8 + 3 * k, 9 + 3 * k, 2, R3, **half) for k, n in enumerate(sbs)),
+                  sizes=EYE_SIZES)
+
+
 RECORDS = (
     # ---- stereo_rerender: module functions ------------------------------------------------------------------------------------------
     Record("stereo_rerender.infill_using_normals", ("stereo_rerender.infill_using_normals",),
@@ -701,6 +783,27 @@ RECORDS = (
     Record("geometry_device.enqueue_export", ("geometry_device.enqueue_export",),
            (_rgb("depth", layout="contiguous", leads=True, fixed=True), _rgb("color", layout="contiguous")), _export, _export_io()),
     _grey(8), _grey(16),
+    # ---- step_device.frame_sums, megasam_device, inspatio_device: as step_device's (the context first, expand=False) ----------------
+    _frame_sums(False), _frame_sums(True),
+    # (the crop 4 x 3 is smaller than the tracker's size 8 x 6: a wrapper that dropped it would write 8 x 6)
+    Record("megasam_device.area_model_frames", ("megasam_device.area_model_frames",), (_frames_in(),),
+           lambda e, a: {"out": mod("megasam_device").area_model_frames(_ctx(e), a["frames"], (e.MW, e.MH), (e.KW, e.KH))},
+           (G("frames", "mdvt_area_model_frames", 3, 4, 5, 2, R3),
+            G("out", "mdvt_area_model_frames", 11, 12, 14, 2, lambda e: e.KW, _KROWS, plane=13, planes=3)), sizes=AREA_SIZES),
+    _tracker_in("tracker_depth", "codes", 12, 100.0), _tracker_in("tracker_mask", "masks", 11),
+    _tracker_outputs(0), _tracker_outputs(1),
+    _shift_grid(1), _shift_grid(2),
+    Record("inspatio_device.flow_warp", ("inspatio_device.flow_warp",),
+           (Arg("grids", "vec", "float32", layout="contiguous", shape=lambda e: (e.N, 4, 4, 2)),
+            Arg("has_grid", "vec", layout="contiguous", shape=lambda e: (e.N,)), _frames_in("infilled"), _out()),
+           lambda e, a: {"out": mod("inspatio_device").flow_warp(_ctx(e), a["grids"], a["has_grid"], a["infilled"], out=a["out"])},
+           (G("grids", "mdvt_flow_warp", 3, row_bytes=lambda e: 128 * e.N, rows=ONE), G("has_grid", "mdvt_flow_warp", 4, row_bytes=lambda e: e.N, rows=ONE),
+            G("infilled", "mdvt_flow_warp", 5, 6, 7, 2, R3), G("out", "mdvt_flow_warp", 8, 9, 10, 2, R3))),
+    _inspatio_prepare(0), _inspatio_prepare(1),
+    Record("inspatio_device.model_frames", ("inspatio_device.model_frames",), (_frames_in(),),
+           lambda e, a: {"out": mod("inspatio_device").model_frames(_ctx(e), a["frames"], (e.MW, e.MH))},
+           (G("frames", "mdvt_inspatio_model_frames", 3, 4, 5, 2, R3), G("out", "mdvt_inspatio_model_frames", 8, 9, 10, 2, _M3, _MROWS))),
+    _inspatio_composite(1, True), _inspatio_composite(0, False),
 )
 
 BY_NAME = {r.name: r for r in RECORDS}
@@ -887,7 +990,7 @@ def layouts_of(record):
             out.append(layout)
             continue
         for a in record.args:
-            dims = a.dims(Env(8, 4, 1 if layout == "mid_frame" else N_FRAMES))
+            dims = a.dims(Env(8, 4, max(record.min_frames, 1 if layout == "mid_frame" else N_FRAMES)))
             if Buffer._geometry(a, dims, layout)[4]:
                 out.append(layout)
                 break
@@ -913,7 +1016,7 @@ def make_env(record, W, H, layout, device=None):
         if key not in RENDERERS:
             RENDERERS[key] = mod("stereo_rerender").StereoRerenderer(W, H, **record.renderer)
         r = RENDERERS[key]
-    env = Env(W, H, 1 if layout == "mid_frame" else N_FRAMES, device, r)
+    env = Env(W, H, max(record.min_frames, 1 if layout == "mid_frame" else N_FRAMES), device, r)
     if record.setup:
         record.setup(env)
     return env

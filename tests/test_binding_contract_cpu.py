@@ -1,7 +1,10 @@
 """No GPU needed: the table of tests/binding_contract.py is in step with the package's sources -- a new wrapper that hands a tensor's
 address to the library needs a record before this passes -- and its extent checker catches the slips it is there to catch, on
 hand-made recordings over host tensors."""
+import glob
 import os
+import subprocess
+import sys
 
 import pytest
 
@@ -24,7 +27,7 @@ def _source(module):
 
 def test_every_site_that_takes_a_tensors_address_has_a_record():
     sites = bc.package_sites()
-    assert len(sites) >= 25 and "stereo_rerender.StereoRerenderer.prepare" in sites and "depth_frames_helper.swap_rb" in sites
+    assert len(sites) >= 50 and "stereo_rerender.StereoRerenderer.prepare" in sites and "depth_frames_helper.swap_rb" in sites
     covered = {s for r in bc.RECORDS for s in r.sites}
     missing = sorted(set(sites) - covered)
     assert not missing, f"functions that take a tensor's data_ptr() without a record in tests/binding_contract.py: {missing}"
@@ -44,6 +47,37 @@ def test_every_site_that_takes_a_tensors_address_has_a_record():
     assert not set(NO_TENSOR) & grouped
     names = [r.name for r in bc.RECORDS]
     assert len(set(names)) == len(names)
+
+
+def test_no_tool_outside_the_benchmarks_takes_a_tensors_address():
+    """The benchmarks call the raw C ABI next to their yardsticks; every other tool reaches the library through the package."""
+    tools = sorted(glob.glob(os.path.join(bc.REPO, "tools", "*.py")))
+    assert len(tools) >= 10
+    found = {}
+    for path in tools:
+        if not path.endswith("_bench.py"):
+            with open(path) as f:
+                found.update({s: os.path.basename(path) for s in bc.pointer_sites(f.read(), os.path.basename(path)[:-3])})
+    assert not found, (f"tools that take a tensor's data_ptr(): {found}.  A wrapper that hands a tensor's address to the library belongs in the "
+                       f"package (step_device.py, or a module of its step's own listed in binding_contract.MODULES) with a record in "
+                       f"tests/binding_contract.py; the tool imports it from there")
+
+
+def test_the_wrapper_modules_import_without_torch():
+    code = ("import sys; sys.path.insert(0, sys.argv[1]); from metric_depth_video_toolbox_amd import step_device, megasam_device, inspatio_device; "
+            "print('torch' in sys.modules)")
+    r = subprocess.run([sys.executable, "-c", code, bc.REPO], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.strip() == "False", r.stderr[-2000:]
+
+
+def test_a_record_of_frame_pairs_is_never_built_with_one_frame():
+    """min_frames: the mid_frame layout (a batch of one frame) is left to the arguments that have no frame dimension."""
+    assert "mid_frame" not in bc.layouts_of(bc.BY_NAME["step_device.frame_sums[no prev]"])
+    r = bc.BY_NAME["step_device.frame_sums[prev]"]
+    assert r.min_frames == 2 and "mid_frame" in bc.layouts_of(r)
+    assert bc.Buffer._geometry(r.arg("frames"), r.arg("frames").dims(bc.Env(8, 4, 2)), "mid_frame")[4] is False
+    assert bc.Buffer._geometry(r.arg("prev"), r.arg("prev").dims(bc.Env(8, 4, 2)), "mid_frame")[4] is True
+    assert all(x.min_frames == 1 for x in bc.RECORDS if "frame_sums" not in x.name)
 
 
 def test_the_site_parser_sees_methods_nested_helpers_and_conditional_names():

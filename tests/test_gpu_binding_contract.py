@@ -16,7 +16,11 @@ transposed view keeps its shape), 3 frames; the model-sized buffers of the adapt
 model-step wrappers of step_device.py take the same: every size the clip does not fix differs from W x H -- the model's input and
 PromptDA's prompt 8 x 6, MVSAnywhere's cost volume and its mask 4 x 3, the video a depth or a mask is resized to 9 x 7 -- and the
 planar tensors [N, 3, h, w] bring a third byte distance, the plane's.  geometry_device.py's wrappers read W x H from the context,
-so theirs is made for the frames' size.
+so theirs is made for the frames' size.  The scene, tracker and InSpatio wrappers (step_device.frame_sums, megasam_device.py,
+inspatio_device.py) take the same sizes, with these differences.  Passes (b) and (c) run the shift grid and InSpatio's compositing at
+33 x 9, 36 x 12 and 8 x 8 (their entry points refuse an eye below 8 x 8), and cv2's area resize to 8 x 6 at 33 x 9, 36 x 10 and
+10 x 10 (it refuses a frame smaller than 8 x 6 on an axis, and two integer ratios).  The tracker's inputs are cropped to 4 x 3 of its
+8 x 6, its outputs go to the video's 9 x 7.  frame_sums compares pairs: its records are never built with fewer than two frames.
 Every comparison is equality of bytes (floats: the same bits, or both NaN)."""
 import pytest
 

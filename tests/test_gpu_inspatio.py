@@ -2,7 +2,6 @@
 validity planes and the three outputs inside one arena filled with a pseudo-random poison (and, again, with its complement), of which
 only the outputs may change."""
 import os
-import sys
 
 import numpy as np
 import pytest
@@ -349,8 +348,7 @@ def test_the_smallest_eye_and_the_last_sizes_accepted(env):
 
 def test_the_wrapper_checks_its_tensors_and_enqueues(env):
     torch, L, ctx = env
-    sys.path.insert(0, os.path.join(REPO, "tools"))
-    import inspatio_device as idev
+    from metric_depth_video_toolbox_amd import inspatio_device as idev
     H, W = 33, 41
     R, I, V, want = _scene_and_reference(H, W)
     wide = torch.zeros((3, H, W + 7, 3), dtype=torch.uint8, device="cuda")

@@ -2,7 +2,6 @@
 flags, the infilled frames and the output inside one arena of pseudo-random poison (and, again, of its complement), of which only the
 first 3 * width bytes of the output's rows may change."""
 import os
-import sys
 
 import numpy as np
 import pytest
@@ -182,9 +181,7 @@ def test_the_wrapper_and_the_whole_alignment_of_a_moved_frame(env):
     """Shifts on the device, the clean-up on the host, the warp on the device: a frame that shows the render from three rows further
     down comes back as the render outside a margin of three rows."""
     torch, L, ctx = env
-    sys.path.insert(0, os.path.join(REPO, "tools"))
-    import inspatio_device as idev
-    from metric_depth_video_toolbox_amd import inspatio_world
+    from metric_depth_video_toolbox_amd import inspatio_device as idev, inspatio_world
     import test_inspatio_cpu as cpu
     R, I, V = cpu._shifted_scene(7)
     r, i, v = (torch.from_numpy(x[None]).cuda() for x in (R, I, V))

@@ -10,7 +10,6 @@ import importlib.util
 import json
 import os
 import shutil
-import sys
 
 import numpy as np
 import pytest
@@ -28,7 +27,6 @@ MAX_DEPTH, BATCH, XFOV = 20, 5, 60.0
 
 @pytest.fixture(scope="module")
 def tool():
-    sys.path.insert(0, os.path.join(REPO, "tools"))
     spec = importlib.util.spec_from_file_location("sam_track_video_tool", os.path.join(REPO, "tools", "sam_track_video.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)

@@ -33,7 +33,6 @@ def host():
 
 @pytest.fixture(scope="module")
 def tool():
-    sys.path.insert(0, os.path.join(REPO, "tools"))
     spec = importlib.util.spec_from_file_location("sam_track_video_tool", os.path.join(REPO, "tools", "sam_track_video.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)

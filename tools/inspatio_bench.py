@@ -28,7 +28,6 @@ import numpy as np
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
-sys.path.insert(0, os.path.join(REPO, "tools"))
 
 COPY = "device copy of the input bytes"
 TORCH = "torch.fft.rfft2 in float64 + round: the six sums of the interior cells"
@@ -123,8 +122,7 @@ def main():
     ap.add_argument("--json")
     args = ap.parse_args()
     import torch
-    import inspatio_device as idev
-    from metric_depth_video_toolbox_amd import _lib
+    from metric_depth_video_toolbox_amd import _lib, inspatio_device as idev
     ctx = _lib.Context(0, 16, 16)
     try:
         g = torch.Generator(device="cuda").manual_seed(26)

@@ -21,7 +21,7 @@ default, `inspatio_world`, wraps the InSpatio-World pipeline as the reference do
 lazily, fails with one line without it, and is UNTESTED (neither the checkout nor its weights are available to this project).
 
 Per chunk (225 frames, 6 kept: infill_clip's schedule, the pasted frames with their own masks) and eye, everything but the model on
-the device (include/mdvt_inspatio.h; wrappers: tools/inspatio_device.py): mdvt_inspatio_prepare_eye, the model skipped where the
+the device (include/mdvt_inspatio.h; wrappers: metric_depth_video_toolbox_amd/inspatio_device.py): mdvt_inspatio_prepare_eye, the model skipped where the
 chunk's eye has no hole (iwi:446, 452), its frames resized back (mdvt_inspatio_model_frames), mdvt_masked_shift_grid, the grid
 clean-up on the host (inspatio_world.flow_grids), mdvt_flow_warp, mdvt_inspatio_composite_eye.  Read-backs: the hole counts of both
 eyes once per chunk, then per eye with holes the shifts and status bytes; one upload per such eye: the float32 grids.
@@ -36,7 +36,6 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, HERE)
 
 from metric_depth_video_toolbox_amd import _lib, inspatio_world as iw                                  # noqa: E402
 from metric_depth_video_toolbox_amd.clip_io import ClipInputs                                          # noqa: E402
@@ -62,7 +61,7 @@ def deal_with_frame_chunk(keep_first_three, color, mask, org, keep_last_three, f
     without blending) from there to the last one it writes."""
     import numpy as np
     import torch
-    import inspatio_device as idev
+    from metric_depth_video_toolbox_amd import inspatio_device as idev
     dev = color.device
     ctx = _lib.shared_context(dev)
     T = int(color.shape[0])

@@ -30,7 +30,6 @@ import numpy as np
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
-sys.path.insert(0, os.path.join(REPO, "tools"))
 
 
 def _tool():
@@ -68,8 +67,7 @@ COPY = "device copy of the input bytes"
 def bench_calls(args):
     import torch
     import torch.nn.functional as nnf
-    import megasam_device as md
-    from metric_depth_video_toolbox_amd import _lib, step_device
+    from metric_depth_video_toolbox_amd import _lib, megasam_device as md, step_device
     ctx = _lib.Context(0, 16, 16)
     rows = []
 

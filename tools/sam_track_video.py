@@ -13,7 +13,7 @@ dumps give .npy frames.  INTEGRATION.md states the tracker's contract.
 The parser, the file names, the tracker's size, the intrinsics, the frames the reference's look-ahead loop hands over (frame_plan) and
 the pose conversion are host logic in metric_depth_video_toolbox_amd/sam_track.py; the opening of the clip with its checks, the
 context and the outputs are step_clip.py's and clip_io.py's.  Here is what touches the device.  Each decoded batch goes through
-mdvt_area_model_frames, mdvt_tracker_depth and mdvt_tracker_mask (tools/megasam_device.py) and is handed to the tracker frame by
+mdvt_area_model_frames, mdvt_tracker_depth and mdvt_tracker_mask (metric_depth_video_toolbox_amd/megasam_device.py) and is handed to the tracker frame by
 frame as views; after the tracker's global alignment its depth and motion planes go through mdvt_tracker_outputs to the writer or the
 device FFV1 encoder.  The frames stay on the device from decoder to writer; the clip's one read-back is the poses and the first
 frame's intrinsics."""
@@ -22,9 +22,8 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, HERE)
 
-from megasam_device import area_model_frames, tracker_depth, tracker_mask, tracker_outputs      # noqa: E402
+from metric_depth_video_toolbox_amd.megasam_device import area_model_frames, tracker_depth, tracker_mask, tracker_outputs      # noqa: E402
 
 
 def checked_results(got):

@@ -9,39 +9,16 @@ video as PySceneDetect's `<video stem>-Scenes.csv`.
 The detectors, the CSV and the parser are host logic in metric_depth_video_toolbox_amd/scene_detect.py (restated PySceneDetect
 0.6.x defaults: a decree, README); the opening of the clip with its checks and the context are step_clip.py's.  Here is what
 touches the device: per batch the decoded frames go through mdvt_scene_frame_sums (include/mdvt_scene.h) together with the last
-frame of the batch before, and 24 bytes per frame pair are read back.  The file is written under a temporary name and renamed."""
-import ctypes as C
+frame of the batch before, and 24 bytes per frame pair are read back.  frame_sums, the wrapper of that entry point, is
+metric_depth_video_toolbox_amd/step_device.py's; it stays reachable under this module's name.  The file is written under a temporary
+name and renamed."""
 import os
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 
-
-def frame_sums(ctx, frames, prev=None, factor: int = 1, *, bgr: bool = False, stream=None):
-    """The wrapper of mdvt_scene_frame_sums.  frames: uint8 CUDA [n, H, W, 3] with packed pixels (rows and frames may be padded);
-    prev: None or one such frame [H, W, 3] on the same device -> the int64 CUDA tensor [pairs, 3] of sum |dH|, |dS|, |dV| (the sums are
-    below 2^63), pairs = n - 1 + (prev is not None).  Only enqueues, on `stream` (default: the current stream of the frames' device)."""
-    import torch
-    from metric_depth_video_toolbox_amd import _lib, step_clip
-    _lib.check_tensor("frames", frames, torch.uint8, (None, None, None, 3), ndim=4, packed=2, disjoint=True)
-    n, H, W = step_clip.non_empty("frames", frames, "frame")
-    if prev is not None:
-        _lib.check_tensor("prev", prev, torch.uint8, (H, W, 3), ndim=3, device=frames, packed=2, disjoint=True)
-    pairs = n - 1 + (prev is not None)
-    if pairs < 1:
-        raise ValueError("one frame and no previous frame: no pair to compare")
-    factor = int(factor)
-    if factor < 1:
-        raise ValueError(f"factor must be >= 1, got {factor}")
-    dev = frames.device
-    s = step_clip.stream_or_current(dev, stream)
-    with torch.cuda.stream(s):
-        sums = torch.empty((pairs, 3), dtype=torch.int64, device=dev)
-    ctx.call("mdvt_scene_frame_sums", W, H, n, frames.data_ptr(), frames.stride(1), frames.stride(0), 1 if bgr else 0,
-             prev.data_ptr() if prev is not None else None, prev.stride(0) if prev is not None else 0, factor, sums.data_ptr(),
-             C.c_void_p(s.cuda_stream))
-    return sums
+from metric_depth_video_toolbox_amd.step_device import frame_sums      # noqa: E402
 
 
 def run_clip(args):
